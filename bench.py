@@ -25,11 +25,14 @@ Workloads (--workload):
               15-column table of the WHOLE run is all-gathered once per step.  "scaling": "strong".
 Weak scaling (configs1, dr12q-mix): every rank sweeps its own --spectra quasars.
 value = sample log-likelihood evaluations per second over all ranks.  Rank 0 prints ONE JSON line; it
-carries every rank's kernel / gather / step milliseconds and set-up seconds (`per_rank`).  At N = 1
-the configs1 line also carries riders measured AFTER the timed region and never part of `value`:
-config.dr12q_mix and config.k40 (one kernel-timed launch each), config.pcie_c (host arrays in, host
-arrays out through the one-shot C entry gpdla_process_batch: the PCIe-inclusive rate a C / MEX caller
-gets) and, with --pcie, the same through the Python surface.
+carries every rank's kernel / gather / step milliseconds and set-up seconds (`per_rank`).  A plain run
+sets up, warms up, times --steps steps and prints that line.  With --full, everything else is measured
+AFTER the timed region and is never part of `value`: at N = 1 the configs1 line carries config.dr12q_mix
+and config.k40 (one kernel-timed launch each), config.pcie_c (host arrays in, host arrays out through
+the one-shot C entry gpdla_process_batch: the PCIe-inclusive rate a C / MEX caller gets), with --pcie
+the same through the Python surface, and the CPU oracle's rate (cpu_baseline) with its parity check on
+the timed batch (parity); --contraction f32 adds its max-abs delta against fp64.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (dump_outputs).
 
 Environment: HSA_ENABLE_IPC_MODE_LEGACY=0 is set (if unset) before torch is imported, in both launch
 forms -- this pool's host driver only supports dmabuf IPC, and without it RCCL's intra-node
@@ -288,6 +291,55 @@ def job_cpus(world: int) -> int:
 
 
 SHARD_BATCH = 32768  # quasars per HBM-resident batch of the dr12q-shard workload
+DUMP_SEED = 20240601  # the row sample of --dump-outputs tables too large to write whole
+
+
+def dump_outputs(directory, cuts, batches, table, budget=56 << 20):
+    """--dump-outputs: what the last timed step computed, as a caller of the timed path receives it,
+    in float64 .npy files under `directory`: the per-quasar vectors of Batch.download (the variables
+    process_qsos.m:236-244 saves; `status` as float), sample_log_likelihoods_dla, and summary_table --
+    the 15-column posterior table the step ends with (all-gathered over the ranks when N > 1).  The
+    vectors and sample_log_likelihoods_dla are this rank's quasars.  A table too large for its share of
+    `budget` bytes is cut to a fixed seeded sample of rows; quasar_rows / sample_rows / table_rows hold
+    the row indices of what was written (all rows when nothing was cut)."""
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    written = 0
+
+    def save(name, a):
+        nonlocal written
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        np.save(os.path.join(directory, name + ".npy"), a)
+        written += a.nbytes
+
+    def rows(n, row_bytes, share):
+        if n * row_bytes <= share:
+            return np.arange(n)
+        return np.sort(rng.choice(n, max(1, int(share // row_bytes)), replace=False))
+
+    def pick(tensor, sel, b0, b1):  # the rows of `sel` that fall in [b0, b1), from a device tensor
+        local = sel[(sel >= b0) & (sel < b1)] - b0
+        return tensor[torch.as_tensor(local, device=tensor.device)].cpu().numpy()
+
+    nloc = cuts[-1][1] if cuts else 0
+    got = [bt.download(with_samples=False) for bt in batches]
+    vec = {name: np.concatenate([g[name] for g in got]) for name in got[0]} if got else {}
+    qrows = rows(nloc, 8 * sum(int(np.prod(v.shape[1:])) for v in vec.values()), budget // 4)
+    save("quasar_rows", qrows)
+    for name, v in vec.items():
+        save(name, v[qrows])
+    table_np = table.cpu().numpy() if table is not None else np.zeros((0, 15))
+    trows = rows(table_np.shape[0], 8 * table_np.shape[1], budget // 8)
+    save("table_rows", trows)
+    save("summary_table", table_np[trows])
+    S = batches[0].num_samples if batches else 0
+    srows = rows(nloc, 8 * max(S, 1), budget - written - 8 * nloc)
+    save("sample_rows", srows)
+    parts = [pick(bt.samples_tensor(), srows, b0, b1) for (b0, b1), bt in zip(cuts, batches)]
+    save("sample_log_likelihoods_dla", np.concatenate(parts) if parts else np.zeros((0, S)))
+    assert written <= 64e6, written
+    return written
 
 
 def main():
@@ -312,25 +364,34 @@ def main():
     ap.add_argument("--num-lines", type=int, default=3,
                     help="Lyman-series members in the Voigt profile (set_parameters.m:63: 3; voigt.c:16 allows 31); "
                          "a diagnostic: the headline is quoted at 3")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure and check everything that is not the headline: the "
+                         "riders below, the CPU oracle's rate and parity against it, and (f32) the delta vs f64")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float64, at most 64 MB; "
+                         "larger tables as a fixed seeded row sample)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU oracle leg")
     ap.add_argument("--no-mix-rider", action="store_true",
-                    help="configs1 at N = 1 also times ONE launch of the dr12q-mix shape after the timed "
+                    help="with --full, configs1 at N = 1 also times ONE launch of the dr12q-mix shape after the timed "
                          "region (config.dr12q_mix, never value), and one of 256 quasars at k = 40 (config.k40); "
                          "this skips both")
     ap.add_argument("--pcie", action="store_true",
                     help="also time the one-shot host-buffer entry point (H2D + sweep + D2H); "
-                         "reported as config.pcie_inclusive_evals_per_s, never as value")
-    ap.add_argument("--pcie-c", action="store_true", help=argparse.SUPPRESS)  # (kept for old command lines: now the default at N = 1)
+                         "reported as config.pcie_inclusive_evals_per_s, never as value; implies --full")
+    ap.add_argument("--pcie-c", action="store_true", help=argparse.SUPPRESS)  # (kept for old command lines: implies --full)
     ap.add_argument("--no-pcie-c", action="store_true",
-                    help="the N = 1 configs1 line also times gpdla_process_batch itself -- the one-shot C entry a MEX "
-                         "gateway binds -- on 2048 quasars handed over as CSR host arrays through ctypes, after the "
-                         "timed region (config.pcie_c, never value; about two seconds); this skips it")
+                    help="with --full, the N = 1 configs1 line also times gpdla_process_batch itself -- the one-shot C "
+                         "entry a MEX gateway binds -- on 2048 quasars handed over as CSR host arrays through ctypes, "
+                         "after the timed region (config.pcie_c, never value; about two seconds); this skips it")
     ap.add_argument("--timeout-min", type=float, default=10.0, help="process-group timeout (N > 1)")
     ap.add_argument("--launch-check", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
+    args.full = args.full or args.pcie or args.pcie_c  # legs of the full run: asking for one asks for it
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args.gpus, sys.argv[1:]))  # nothing above touched the GPU
     # this pool's host driver only supports dmabuf IPC (see the module docstring); set before torch /
@@ -421,6 +482,7 @@ def main():
     setup_s = time.perf_counter() - t_process
 
     gather_events = []
+    gathered = [None]  # the all-gathered table of the latest step (N > 1)
 
     def step():
         """One pass of the hot path over this rank's resident quasars + the gather of the table.
@@ -436,7 +498,7 @@ def main():
             if world > 1:
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record(stream)
-                gather_summaries(table if shard else batch.summary_tensor(), counts)
+                gathered[0] = gather_summaries(table if shard else batch.summary_tensor(), counts)
                 e1.record(stream)
                 gather_events.append((e0, e1))
         return ms
@@ -479,6 +541,11 @@ def main():
     flops = float(np.sum(algorithmic_flops(n_kept.astype(np.float64), args.k))) * args.samples
     achieved = flops / (sweep_ms * 1e-3) / 1e12 if sweep_ms > 0 else 0.0
     peak = FP64_MFMA_PEAK_TFLOPS if args.contraction == "f64" else FP32_MFMA_PEAK_TFLOPS
+
+    if rank == 0 and args.dump_outputs:
+        last_table = (gathered[0] if world > 1 else table if shard else
+                      batch.summary_tensor() if batch is not None else None)
+        dump_outputs(args.dump_outputs, cuts, batches, last_table)
 
     out = None
     if rank == 0:
@@ -535,7 +602,7 @@ def main():
         if rehearsal:
             out["rehearsal"] = True  # ranks time-slice ONE GPU over gloo: not a scaling point
             out["backend"] = "gloo"
-        if args.contraction == "f32":
+        if args.full and args.contraction == "f32":
             nchk = min(args.spectra, 4)
             lpc = (lp[0][:nchk], lp[1][:nchk])
             ref = gp.process_qsos(model, samples, spectra[:nchk], log_priors=lpc, device=local_rank)
@@ -565,14 +632,14 @@ def main():
                                                       f"{res_pc['sample_log_likelihoods_dla'].nbytes / 1e6:.0f} MB of "
                                                       "results out; upload / sweep / download pipelined)")
             out["config"]["pcie_inclusive_over_resident"] = out["config"]["pcie_inclusive_evals_per_s"] / value
-        if world == 1 and args.workload == "configs1" and (args.pcie_c or (not args.no_pcie_c and args.contraction == "f64"
-                                                                          and args.k <= 20 and not args.no_mix_rider)):
+        if args.full and world == 1 and args.workload == "configs1" and (
+                args.pcie_c or (not args.no_pcie_c and args.contraction == "f64" and args.k <= 20 and not args.no_mix_rider)):
             try:  # a rider: its failure must not cost the headline line
                 out["config"]["pcie_c"] = pcie_c_leg(model, samples, spectra, lp, params, local_rank, args.samples, value,
                                                      repeats=3 if args.pcie_c else 2)
             except Exception as e:  # noqa: BLE001
                 out["config"]["pcie_c"] = {"error": f"{type(e).__name__}: {e}"}
-        if (world == 1 and args.workload == "configs1" and args.contraction == "f64" and args.k <= 20
+        if (args.full and world == 1 and args.workload == "configs1" and args.contraction == "f64" and args.k <= 20
                 and not args.no_mix_rider):
             # the production shape beside the headline: ONE launch of 1000 quasars of the DR12Q length
             # mix (after a warm-up launch), timed by the same hipEvent pair; never `value`
@@ -616,7 +683,7 @@ def main():
                 "achieved_tflops": fl40 / (ms40 * 1e-3) / 1e12, "frac": fl40 / (ms40 * 1e-3) / 1e12 / peak}
             b40.close()
             ctx40.close()
-        if world == 1 and not args.no_cpu_baseline and not shard:
+        if args.full and world == 1 and not args.no_cpu_baseline and not shard:
             checked, out["cpu_baseline"] = cpu_baseline(model, samples, spectra)
             # the quasars the oracle has just swept (all S samples each), against the timed GPU batch:
             # the "max-abs delta" half of BASELINE.json's metric, measured on the bench workload itself

@@ -10,16 +10,10 @@ import pytest
 
 from gp_dla_detection_amd import hdf5, io
 
-MATLAB_FILE = None
-try:  # a genuine MATLAB 7.4 -v7.3 file that SciPy ships with its test data
-    import scipy.io.matlab
-    MATLAB_FILE = os.path.join(os.path.dirname(scipy.io.matlab.__file__), "tests", "data",
-                               "testhdf5_7.4_GLNX86.mat")
-except ImportError:  # pragma: no cover
-    pass
+# a genuine MATLAB 7.4 -v7.3 file: SciPy's test data (scipy/io/matlab/tests/data, BSD-3-Clause), stored here
+MATLAB_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "testhdf5_7.4_GLNX86.mat")
 
 
-@pytest.mark.skipif(not (MATLAB_FILE and os.path.exists(MATLAB_FILE)), reason="SciPy's MATLAB -v7.3 sample absent")
 def test_reads_a_file_written_by_matlab():
     """Bytes produced by MATLAB + libhdf5: user block 512, superblock 0, symbol-table root group,
     version-1 object header, version-2 contiguous layout, MATLAB_class attribute."""
@@ -293,7 +287,6 @@ def test_random_round_trips_hypothesis(tmp_path_factory):
     run()
 
 
-@pytest.mark.skipif(not (MATLAB_FILE and os.path.exists(MATLAB_FILE)), reason="SciPy's MATLAB -v7.3 sample absent")
 def test_native_cell_reader_on_a_file_written_by_matlab():
     """csrc/h5cells.c on bytes MATLAB wrote (version-1 object header, version-2 contiguous layout)."""
     lib = io._load_h5cells()
