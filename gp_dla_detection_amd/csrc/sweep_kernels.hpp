@@ -100,13 +100,23 @@ struct QuasarMeta {
   int64_t lam_off;   // first entry in the padded-wavelength pool
   int64_t rec_off;   // first K-step record in the record pool (records of a group of quasars share the
                      // pool: PrepareArgs::rec_off; without groups it is pix_off / 4)
-  // 0, or -inf when a kept pixel has noise variance +inf (a zero inverse variance the mask missed):
-  // log_mvnpdf_low_rank.m:30 then sums log(inf) into the log-determinant and every log-likelihood of
-  // the quasar is -inf.  The sweeps treat that pixel as neutral and add this to each result, so the
-  // K-loop's fast reciprocal never sees an infinite d (it would return NaN where exact division
-  // gives 0).
+  // What the kept pixels of noise variance above kNeutralNoiseVariance contribute, added to each
+  // result: the sweeps see such a pixel as a neutral row.  -inf when one has variance +inf (a zero
+  // inverse variance the mask missed): log_mvnpdf_low_rank.m:30 then sums log(inf) into the
+  // log-determinant and every log-likelihood of the quasar is -inf.  Otherwise the sum of their
+  // -log(nu)/2 (0 when there are none).  So the K-loop never sees a d above 1e100 + omega2 a^2: its
+  // fast reciprocals would return NaN for an infinite d (where exact division gives 0) and overflow
+  // or flush to 0 on products with a d above ~1e280, and its two-step log-determinant product would
+  // overflow for two such d in one lane.
   double ll_bias;
 };
+
+// A kept pixel of finite noise variance nu above this (and finite flux) is swept as a neutral row
+// (r = 0, d = 1, zero M row) and its -log(nu)/2 goes into QuasarMeta::ll_bias.  What the neutral row
+// drops from log_mvnpdf_low_rank.m -- r^2/d, log(d / nu) = log(1 + omega2 a^2 / nu), and the row's
+// M a M a' / d in B = I + M' D^-1 M -- is below 1e-39 in absolute value while |y|, |mu|, |M| and
+// omega2 stay below 1e30 (absorption a <= 1), against the pixel's own log(nu)/2 > 115.
+constexpr double kNeutralNoiseVariance = 1e100;
 
 struct PixelRow {  // one row of the per-pixel pool, on the unmasked-range grid
   double y, mu, omega2, nu;
@@ -146,6 +156,17 @@ struct PrepareArgs {
   double prev_tau_0, prev_beta;
 };
 
+__device__ __forceinline__ double block_reduce_sum(double v, double *sh) {  // (fixed order: deterministic)
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  __syncthreads();
+  if (lane == 0) sh[wave] = v;
+  __syncthreads();
+  double r = sh[0];
+  for (int w = 1; w < (int)(blockDim.x >> 6); ++w) r += sh[w];
+  return r;
+}
+
 __device__ __forceinline__ double block_reduce_minmax(double v, bool is_min, double *sh) {
   for (int o = 32; o > 0; o >>= 1) {
     double other = __shfl_xor(v, o);
@@ -179,6 +200,7 @@ __global__ __launch_bounds__(256) void k_prepare(PrepareArgs a) {
   double kept_min = INFINITY, kept_max = -INFINITY, un_min = INFINITY, un_max = -INFINITY;
   int kept_count = 0;
   int nv_flags = 0;  // 1: a kept pixel with noise variance +inf; 2: one with variance <= 0 or NaN
+  double huge_nv_ll = 0.0;  // -log(nu)/2 of the kept pixels of finite variance above kNeutralNoiseVariance
   for (int tile = 0; tile < npix; tile += 256) {
     const int i = tile + tid;
     double wl = 0.0, rest = 0.0;
@@ -259,15 +281,18 @@ __global__ __launch_bounds__(256) void k_prepare(PrepareArgs a) {
           row.omega2 = om * (mf * mf);                                                 // multi :293
         }
       }
-      // a kept pixel of infinite variance weighs nothing (1/d = 0) but log d = inf: it is swept as
-      // a neutral row and its effect re-enters through ll_bias (unless its flux is NaN, which the
-      // reference propagates into every result: then the row is left as it is)
-      const bool inf_nv = keep && row.nu == INFINITY && row.y == row.y;
-      if (inf_nv) row = PixelRow{0.0, 0.0, 0.0, 1.0};
+      // a kept pixel of huge or infinite variance weighs (next to) nothing but log d is large or
+      // inf: it is swept as a neutral row and its effect re-enters through ll_bias (unless its flux
+      // is NaN, which the reference propagates into every result: then the row is left as it is)
+      const bool huge_nv = keep && row.nu > kNeutralNoiseVariance && row.y == row.y;
+      if (huge_nv) {
+        if (row.nu != INFINITY) huge_nv_ll -= 0.5 * log(row.nu);
+        row = PixelRow{0.0, 0.0, 0.0, 1.0};
+      }
       pix[u] = row;
       for (int c = 0; c < k; ++c) {                                                    // :139
         const double m0 = a.model.M[lo + (int64_t)c * G], m1 = a.model.M[lo + 1 + (int64_t)c * G];
-        Mi[(int64_t)u * k + c] = (keep && !inf_nv) ? (m0 + (m1 - m0) * t) * mf : 0.0;  // multi :288
+        Mi[(int64_t)u * k + c] = (keep && !huge_nv) ? (m0 + (m1 - m0) * t) * mf : 0.0;  // multi :288
       }
     }
     __syncthreads();
@@ -286,6 +311,7 @@ __global__ __launch_bounds__(256) void k_prepare(PrepareArgs a) {
   kept_max = block_reduce_minmax(kept_max, false, s_red);
   un_min = block_reduce_minmax(un_min, true, s_red);
   un_max = block_reduce_minmax(un_max, false, s_red);
+  huge_nv_ll = block_reduce_sum(huge_nv_ll, s_red);
   nv_flags = __syncthreads_or(nv_flags & 1) | (__syncthreads_or(nv_flags & 2) ? 2 : 0);
   const int steps = (n_u + 3) >> 2;
   // pad rows up to 4*(steps+1): neutral pixels (the last 4 feed the neutral trailing record)
@@ -299,7 +325,7 @@ __global__ __launch_bounds__(256) void k_prepare(PrepareArgs a) {
     m.steps = steps;
     m.status = (n_kept > 0) ? ((nv_flags & 2) ? 3 : 0) : 1;
     m.rec_off = a.rec_off[q];
-    m.ll_bias = (nv_flags & 1) ? -INFINITY : 0.0;
+    m.ll_bias = (nv_flags & 1) ? -INFINITY : huge_nv_ll;
     if (n_kept > 0) {
       // set_parameters.m:65-73 on the kept-pixel wavelengths (process_qsos.m:159-160)
       m.max_z_dla = (kept_max / a.cfg.lya_wavelength - 1) - a.cfg.max_z_cut;
@@ -516,8 +542,9 @@ struct SweepArgs {
 };
 
 // 1/a to 2.2e-15 relative: v_rcp_f64 seed (measured 4.6e-8, tools/rcp_accuracy_probe.hip) + ONE
-// Newton step.  a must be finite, non-zero and normal (NaN otherwise): k_prepare keeps non-finite
-// and non-positive noise variances out of the sweeps (QuasarMeta::ll_bias, status 3).  A second step would make it correctly rounded at
+// Newton step.  a must be finite and normal, and so must 1/a (NaN for a = inf, 0 once 1/a is
+// subnormal): k_prepare keeps non-positive and NaN noise variances out of the sweeps (status 3) and
+// those above 1e100 out of the K-loop (QuasarMeta::ll_bias).  A second step would make it correctly rounded at
 // two more fp64 instructions per use -- two uses per K-step of the sweep, 4 % of its VALU work.
 // What 2e-15 costs: the optical depth moves by 2e-15 relative (absorption by <= 8e-16 absolute),
 // Sum r^2/d by <= 2e-15 |Sum r^2/d| ~ 1e-11..1e-10, log det B by <= k 2e-15: two orders below the
@@ -1214,8 +1241,9 @@ __device__ __forceinline__ double wing_sum3(double lamP, double msa, double msb,
 // folded into log_mvnpdf_low_rank.m:13-15; d is finite and positive, k_prepare sees to that) comes out
 // of the same v_rcp_f64 as the three lines' 1/s_j -- prefix products, one reciprocal of s_a s_b s_c d,
 // peeled: 9 multiplies and one fast_rcp instead of 7 multiplies and two (v_rcp_f64 issues in 17 cycles,
-// a multiply in 5.4: tools/valu_rate_probe.hip).  s_j in [2e-7, 2e9] and d in (0, 1e300): the product
-// stays normal.  Each quotient carries two or three more roundings than fast_rcp's 2.2e-15.
+// a multiply in 5.4: tools/valu_rate_probe.hip).  s_j in [2e-7, 2e9] and d in [1e-280, 1e100 + omega2 a^2]
+// (k_prepare sweeps a pixel of larger noise variance as a neutral row, kNeutralNoiseVariance): the
+// product and its reciprocal stay normal.  Each quotient carries two or three more roundings than fast_rcp's 2.2e-15.
 __device__ __forceinline__ double wing_sum3_rcp4(double lamP, double msa, double msb, double msc, double cs,
                                                  bool *near, double d, double *inv_d) {
   const double xa = fma(lamP, msa, -cs), xb = fma(lamP, msb, -cs), xc = fma(lamP, msc, -cs);

@@ -95,7 +95,9 @@ typedef struct {
   const int64_t *offsets;           /* [num_quasars + 1] into the four pixel arrays */
   const double *wavelengths;        /* observed, Angstrom */
   const double *flux;
-  const double *noise_variance;
+  const double *noise_variance;     /* of a kept pixel: > 0 (else status 3).  +inf gives -inf
+                                       log-likelihoods, as in the reference; a finite nu above 1e100
+                                       adds -log(nu)/2 outside the sweep, dropping terms below 1e-39 */
   const uint8_t *pixel_mask;        /* nonzero = masked */
   const double *z_qsos;             /* [num_quasars] */
   const double *log_priors_no_dla;  /* [num_quasars]  process_qsos.m:130-131 (host logic) */
@@ -166,7 +168,8 @@ typedef struct {
   double *p_no_dlas;                  /* [nq] */
   double *p_dlas;                     /* [nq] */
   int32_t *status;                    /* [nq] 0 ok, 1 = empty spectrum (multi: all_exceptions, :232),
-                                         3 = a kept pixel with noise variance <= 0 or NaN (skipped) */
+                                         3 = a kept pixel with noise variance <= 0 or NaN (skipped; any
+                                         other variance, huge or +inf, is computed as the reference does) */
   /* generate_ascii_catalog.m:73-80, found by the evidence kernel while it walks the table anyway:
    * [~, map_ind] = nanmax(sample_log_likelihoods_dla(i, :)) (1-based, first index on ties; 1 for an
    * all-NaN row, as MATLAB returns), map_z_dla = min_z + (max_z - min_z) * offset_samples(map_ind),

@@ -554,6 +554,76 @@ def test_noise_variance_guards(model20, oracle):
     assert np.all(np.isnan(out["sample_log_likelihoods_dla"][2])) and np.isnan(out["p_dlas"][2])
 
 
+HUGE_NV = (1e40, 1e100, 1e160, 1e200, 1e290, 1e300, 1e307)
+
+
+def huge_variance_batch(model, n=400, first_index=5000):
+    """One quasar per (variance, pattern): kept pixels of huge but finite noise variance, alone, in a
+    pair 4 apart (the same lane of consecutive K-steps) and in a run of 12, in the middle of the
+    Lyman-alpha forest (the middle of the z_DLA range), so that many samples put damping-wing
+    absorption on the pixel three K-steps ahead.  Then one quasar with NaN flux on such a pixel."""
+    spectra = []
+    patterns = ([0], [0, 4], list(range(12)))
+    for i, (nv, pat) in enumerate((nv, pat) for nv in HUGE_NV for pat in patterns):
+        sp = synthetic.make_spectrum(first_index + i, n, model)
+        sp["noise_variance"] = sp["noise_variance"].copy()
+        sp["noise_variance"][n // 2 + 2 + np.array(pat)] = nv  # (+2: the pixels before the modelled range)
+        spectra.append(sp)
+    bad = synthetic.make_spectrum(first_index + len(spectra), n, model)
+    bad["noise_variance"] = bad["noise_variance"].copy()
+    bad["flux"] = bad["flux"].copy()
+    bad["noise_variance"][n // 2 + 2: n // 2 + 6] = 1e300
+    bad["flux"][n // 2 + 3] = np.nan
+    return spectra, bad
+
+
+@pytest.mark.parametrize("k,num_lines", [(20, 3), (20, 1), (33, 3)])
+def test_huge_finite_noise_variances(oracle, k, num_lines):
+    """Kept pixels with noise variances up to 1e307: every log-likelihood matches the oracle at 1e-8
+    (k = 20, 3 lines: k_sweep_slim<3>, whose shared wing-tier reciprocal and two-step log-determinant
+    product would overflow on them in the K-loop; 1 line: k_sweep_slim<0>; k = 33:
+    k_sweep_split_slim).  k_prepare sweeps such a pixel as a neutral row and adds -log(nu)/2 to the
+    quasar's result; with NaN flux on it the quasar stays NaN, as the reference gives."""
+    from oracle.oracle import OracleParams
+    model = synthetic.make_model(k)
+    samples = synthetic.make_samples(200)
+    spectra, bad = huge_variance_batch(model)
+    out = gp.process_qsos(model, samples, spectra + [bad], log_priors=flat_priors(len(spectra) + 1),
+                          params=gp.Parameters(num_lines=num_lines))
+    assert (out["status"][:-1] == 0).all()
+    dev = []
+    for i, sp in enumerate(spectra):
+        ref = oracle.process_spectrum(model, samples["offset_samples"], samples["nhi_samples"], sp["wavelengths"],
+                                      sp["flux"], sp["noise_variance"], sp["pixel_mask"], sp["z_qso"],
+                                      params=OracleParams(num_lines=num_lines))
+        assert np.isfinite(ref["sample_log_likelihoods_dla"]).all()
+        d = max(float(np.abs(out["sample_log_likelihoods_dla"][i] - ref["sample_log_likelihoods_dla"]).max()),
+                abs(out["log_likelihoods_no_dla"][i] - ref["log_likelihood_no_dla"]),
+                abs(out["log_likelihoods_dla"][i] - ref["log_likelihood_dla"]))
+        dev.append(d if d == d else np.inf)
+    bad = [f"nu = {HUGE_NV[i // 3]:.0e} on {(1, 2, 12)[i % 3]} pixel(s): {d:.2e}"
+           for i, d in enumerate(dev) if not d < TOL]
+    assert not bad, "; ".join(bad)  # (every failing case)
+    assert np.isnan(out["sample_log_likelihoods_dla"][-1]).all() and np.isnan(out["log_likelihoods_no_dla"][-1])
+    print(f"huge noise variances (k = {k}, {num_lines} lines): worst |delta| = {max(dev):.2e}")
+
+
+def test_huge_finite_noise_variances_multi(oracle):
+    """The multi-DLA mean-flux driver (max_dlas = 2: k_sweep_multi_slim) on the same batch."""
+    from gp_dla_detection_amd.parameters import MultiParameters
+    from test_gpu_multi import compare, oracle_multi, priors
+    p = MultiParameters(max_dlas=2)
+    model = synthetic.make_model(20)
+    samples = synthetic.make_samples(200)
+    spectra, bad = huge_variance_batch(model)
+    batch = spectra + [bad]
+    out = gp.process_qsos_multiple_dlas_meanflux(model, samples, batch, priors(batch, p), params=p)
+    assert (out["status"][:-1] == 0).all()
+    for i, sp in enumerate(spectra):
+        compare(out, i, oracle_multi(oracle, model, samples, sp, out["base_sample_inds"][i], p), p)
+    assert np.isnan(out["sample_log_likelihoods_dla"][-1]).all() and np.isnan(out["log_likelihoods_no_dla"][-1])
+
+
 def test_randomised_shapes_vs_oracle(oracle):
     """Seeded fuzz over the sweep's shape space: rank 1..40 (all three kernel classes), 30..700
     pixels, 1..90 samples, 0..20 % masked, 1 / 3 / 5 lines -- every log-likelihood against the

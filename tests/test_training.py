@@ -2,7 +2,9 @@
 
 CPU: the oracle's gradient against central finite differences of its own value (the priors of
 objective.m:59-71 enter the gradient only, exactly as in the reference).  GPU: value and gradient
-against the oracle, and a short L-BFGS run that must decrease the objective."""
+against the oracle to 1e-9 relative per gradient block (assert_objective_close), from small ragged
+shapes up to the 4997 x 1217 training sets learn_qso_model uses, and a short L-BFGS run that must
+decrease the objective."""
 import numpy as np
 import pytest
 
@@ -19,6 +21,71 @@ def training_problem(nq=40, G=64, k=5, seed=0, missing=0.1):
     F[rng.uniform(size=F.shape) < missing] = np.nan
     F[3] = np.nan  # a quasar with no valid pixel contributes nothing
     return x, F, L1, NV
+
+
+def objective_deviation(f, g, f_ref, g_ref, G, k):
+    """Worst relative deviation of (f, g) from (f_ref, g_ref), block by block: the value; each of the
+    k columns of M, against that column's max |g_ref|; the log omega block, against its own max; each
+    of the three scalars, against its own |g_ref|.  (A single max over the whole gradient would let
+    the three scalars, ~1e4 times the log omega block at learning scale, set the scale for all.)
+    Returns {block name: deviation}; NaN anywhere gives inf."""
+    def rel(a, b):
+        d, s = np.abs(a - b).max(), np.abs(b).max()
+        if not np.isfinite(d):
+            return np.inf
+        return d / s if s > 0 else (0.0 if d == 0 else np.inf)
+    dev = {"f": rel(np.array([f]), np.array([f_ref]))}
+    for c in range(k):
+        dev[f"M[:, {c}]"] = rel(g[c * G:(c + 1) * G], g_ref[c * G:(c + 1) * G])
+    dev["log_omega"] = rel(g[k * G:(k + 1) * G], g_ref[k * G:(k + 1) * G])
+    for i, name in enumerate(("log_c0", "log_tau0", "log_beta")):
+        dev[name] = rel(g[(k + 1) * G + i:(k + 1) * G + i + 1], g_ref[(k + 1) * G + i:(k + 1) * G + i + 1])
+    return dev
+
+
+def assert_objective_close(f, g, f_ref, g_ref, G, k, rtol=1e-9, what=""):
+    """objective_deviation within rtol in every block; returns (worst deviation, its block)."""
+    assert g.shape == g_ref.shape == (G * (k + 1) + 3,)
+    dev = objective_deviation(f, g, f_ref, g_ref, G, k)
+    name = max(dev, key=dev.get)
+    bad = {b: v for b, v in dev.items() if not v < rtol}
+    assert not bad, (what, bad)
+    return dev[name], name
+
+
+# ---------------------------------------------------------------------------------------------
+# how the matrix-core objective splits its work (train_dims and the kernels' balanced splits,
+# gp_dla_detection_amd/csrc/gpdla.hip and training_mfma_kernels.hpp), restated so that a test can
+# show which paths a shape reaches
+# ---------------------------------------------------------------------------------------------
+
+TR_CHUNK, TR_BUILD_MAX_CHUNKS, TR_WIDE_PB = 4, 64, 2  # kTrChunk, kTrBuildMaxChunks, kTrWidePB
+
+
+def train_dims(nq, G, k):
+    NQ16, PG = -(-nq // 16), -(-G // 16)
+    H, H2, GS = (6, 24, 24) if k <= 20 else (3, 12, 24 * TR_WIDE_PB)
+    H = max(H, -(-PG // TR_BUILD_MAX_CHUNKS))
+    return dict(NQ16=NQ16, PG=PG, TQ=4 * NQ16, H=H, H2=H2, GS=(GS + 3) // 4 * 4)
+
+
+def train_reach(nq, G, k):
+    """Per-split work of each kernel: chunks of k_train_contract (quasar steps in chunks of 4) and of
+    k_train_build (16-pixel groups), quasar groups of k_train_core (k <= 20) / k_train_core_wide
+    (k > 20, four splits per block that iterate as often as the longest)."""
+    d = train_dims(nq, G, k)
+    bal = lambda n, parts: [(n * (h + 1)) // parts - (n * h) // parts for h in range(parts)]  # noqa: E731
+    contract = [-(-s // TR_CHUNK) for s in bal(d["TQ"], d["H2"])]
+    build = bal(d["PG"], d["H"])
+    groups = bal(d["NQ16"], d["GS"])
+    r = dict(d, contract_chunks=(min(contract), max(contract)), build_chunks=(min(build), max(build)))
+    if k <= 20:
+        r["core_groups"] = (min(groups), max(groups))
+    else:
+        blocks = [groups[b:b + 4] for b in range(0, d["GS"], 4)]
+        r["wide_iters"] = max(max(b) for b in blocks)
+        r["wide_uneven_blocks"] = sum(max(b) >= 2 and min(b) < max(b) for b in blocks)
+    return r
 
 
 def test_oracle_gradient_vs_finite_differences(oracle):
@@ -53,9 +120,7 @@ def test_gpu_objective_matches_oracle(oracle):
         x, F, L1, NV = training_problem(nq=nq, G=G, k=k, seed=k)
         f_ref, g_ref = oracle.objective(x, F, L1, NV)
         f, g = training.objective(x, F, L1, NV)
-        assert abs(f - f_ref) < 1e-9 * abs(f_ref), (f, f_ref)
-        scale = np.abs(g_ref).max()
-        assert np.abs(g - g_ref).max() < 1e-9 * scale, (np.abs(g - g_ref).max(), scale)
+        assert_objective_close(f, g, f_ref, g_ref, G, k, what=(nq, G, k))
 
 
 def _perturbed_start(x, G, k):
@@ -165,8 +230,7 @@ def test_gpu_objective_is_deterministic_and_matches_the_oracle_on_ragged_shapes(
         t.close()
         assert f1 == f2 and np.array_equal(g1, g2), (nq, G, k)  # (k > 20: slot-ordered sums, no atomics)
         f_ref, g_ref = oracle.objective(x, F, L1, NV)
-        assert abs(f1 - f_ref) < 1e-9 * abs(f_ref), (nq, G, k, f1, f_ref)
-        assert np.abs(g1 - g_ref).max() < 1e-9 * np.abs(g_ref).max(), (nq, G, k)
+        assert_objective_close(f1, g1, f_ref, g_ref, G, k, what=(nq, G, k))
 
 
 @pytest.mark.gpu
@@ -186,8 +250,7 @@ def test_gpu_training_handle_survives_rank_changes(oracle):
                                 rng.uniform(-3, -2, G), [np.log(0.1), np.log(0.0023), np.log(3.65)]])
             f, g = t.objective(x)
             f_ref, g_ref = oracle.objective(x, F, L1, NV)
-            assert abs(f - f_ref) < 1e-9 * abs(f_ref), k
-            assert np.abs(g - g_ref).max() < 1e-9 * np.abs(g_ref).max(), k
+            assert_objective_close(f, g, f_ref, g_ref, G, k, what=k)
     finally:
         t.close()
 
@@ -268,8 +331,7 @@ def test_gpu_lyseries_objective_matches_the_oracle(oracle):
                 f2, g2 = t.objective(x)
                 assert f == f2 and np.array_equal(g, g2)  # deterministic
                 f_ref, g_ref = oracle.objective_lyseries(x, F, L1, NV, nfl, wl, fs)
-                assert abs(f - f_ref) < 1e-9 * abs(f_ref), (nq, G, k, nfl, f, f_ref)
-                assert np.abs(g - g_ref).max() < 1e-9 * np.abs(g_ref).max(), (nq, G, k, nfl)
+                assert_objective_close(f, g, f_ref, g_ref, G, k, what=(nq, G, k, nfl))
                 assert abs(f - f0) > 1e-6 * abs(f0)  # the extra lines do something on this grid
             t.set_lyseries(0)
             f3, g3 = t.objective(x)
@@ -283,4 +345,191 @@ def test_gpu_lyseries_objective_matches_the_oracle(oracle):
     x, F, L1, NV = lyseries_problem()
     f, g = training.objective_lyseries(x, F, L1, NV, 6, wl, fs)
     f_ref, g_ref = oracle.objective_lyseries(x, F, L1, NV, 6, wl, fs)
-    assert abs(f - f_ref) < 1e-9 * abs(f_ref) and np.abs(g - g_ref).max() < 1e-9 * np.abs(g_ref).max()
+    assert_objective_close(f, g, f_ref, g_ref, 72, 5)
+
+
+# ---------------------------------------------------------------------------------------------
+# the objective at the size learn_qso_model trains at (~5000 quasars x 1217 rest pixels), where
+# every split of the matrix-core kernels runs several chunks / quasar groups
+# ---------------------------------------------------------------------------------------------
+
+LEARN_NQ, LEARN_G = 4997, 1217  # (not a multiple of 16 quasars: the last quasar group is padded)
+BOUNDARY_NQ = 853  # 54 quasar groups, the fewest with 3 chunks in every k_train_contract split at k <= 20
+# what each shape reaches (train_reach), asserted on the CPU by test_learning_scale_shapes_reach_the_split_paths;
+# per split: chunks of k_train_contract, quasar groups of k_train_core (k <= 20), iterations of k_train_core_wide
+# (k > 20) with the blocks whose four splits differ, split count H and chunks of k_train_build
+#   (nq, G, k)          contract  core    core_wide        build
+#   (4997, 1217, 20)    13-14     13-14   -                H = 6, 12-13
+#   (4997, 1217, 40)    26-27     -       7, 12 of 12      H = 3, 25-26
+#   (2000, 1217, 20)    5-6       5-6     -                H = 6, 12-13
+#   (2000, 1217, 33)    11        -       3, 12 of 12      H = 3, 25-26
+#   (853, 1217, 1/20)   3         2-3     -                H = 6, 12-13
+#   (853, 1217, 21/40)  5         -       2, 6 of 12       H = 3, 25-26
+#   (40, 6144, 20)      0-1       0-1     -                H = 6, 64 (the LDS omega2 table full)
+#   (40, 6145, 20)      0-1       0-1     -                H = 7 (raised), 55
+#   (40, 3072, 40)      1         -       1                H = 3, 64
+#   (40, 3073, 40)      1         -       1                H = 4 (raised), 48-49
+LEARNING_SCALE = ((LEARN_NQ, LEARN_G, 20), (LEARN_NQ, LEARN_G, 40))
+LYSERIES_SCALE = ((2000, LEARN_G, 20, 31), (2000, LEARN_G, 33, 6))
+RANK_BOUNDARIES = tuple((BOUNDARY_NQ, LEARN_G, k) for k in (1, 20, 21, 40))
+BUILD_BOUNDARIES = ((40, 6144, 20), (40, 6145, 20), (40, 3072, 40), (40, 3073, 40))
+
+
+def test_learning_scale_shapes_reach_the_split_paths():
+    """The shapes of the learning-scale GPU tests below really run what their table claims: at least
+    3 chunks per split of k_train_contract (the second LDS buffer, the prefetch of chunk c + 1 and the
+    refill after the barrier), at least 2 quasar groups per split of k_train_core, idle iterations
+    in k_train_core_wide (iters >= 2, the four splits of a block of different lengths), and the
+    build split count raised past the LDS table of k_train_build at G = 6145 / 3073."""
+    for (nq, G, k) in LEARNING_SCALE + tuple(s[:3] for s in LYSERIES_SCALE) + RANK_BOUNDARIES:
+        r = train_reach(nq, G, k)
+        assert r["contract_chunks"][0] >= 3 and r["build_chunks"][0] >= 3, (nq, G, k, r)
+        if k <= 20:
+            assert r["core_groups"][0] >= 2, (nq, G, k, r)
+        else:
+            assert r["wide_iters"] >= 2 and r["wide_uneven_blocks"] > 0, (nq, G, k, r)
+    assert train_reach(*LEARNING_SCALE[0])["core_groups"][0] >= 13
+    assert train_reach(*LEARNING_SCALE[1])["wide_iters"] == 7
+    h = [train_reach(*s) for s in BUILD_BOUNDARIES]
+    assert [r["H"] for r in h] == [6, 7, 3, 4]
+    assert h[0]["build_chunks"] == (64, 64) and h[2]["build_chunks"] == (64, 64)
+    assert max(r["build_chunks"][1] for r in h) <= TR_BUILD_MAX_CHUNKS
+    assert train_reach(BOUNDARY_NQ - 16, LEARN_G, 20)["contract_chunks"][0] == 2  # (one quasar group fewer: 2)
+
+
+def test_train_dims_mirror_follows_the_source():
+    """The constants train_dims / train_reach restate are still the ones the library is built with."""
+    import os
+    import re
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gp_dla_detection_amd", "csrc")
+    kern = open(os.path.join(csrc, "training_mfma_kernels.hpp")).read()
+    host = open(os.path.join(csrc, "gpdla.hip")).read()
+    assert re.search(r"constexpr int kTrChunk = %d;" % TR_CHUNK, kern)
+    assert re.search(r"constexpr int kTrBuildMaxChunks = %d;" % TR_BUILD_MAX_CHUNKS, kern)
+    assert re.search(r"#define TR_WIDE_PB %d\n" % TR_WIDE_PB, kern)
+    dims = host[host.index("TrainDims train_dims("):]
+    dims = dims[:dims.index("\n}\n")]
+    assigned = re.findall(r"d\.(H|H2|GS) = ([^;]+);", dims)
+    assert assigned[:6] == [("H", "6"), ("H2", "24"), ("GS", "24"), ("GS", "24 * kTrWidePB"), ("H", "3"), ("H2", "12")]
+    assert "(d.PG + kTrBuildMaxChunks - 1) / kTrBuildMaxChunks" in dims and "d.GS = (d.GS + 3) / 4 * 4;" in dims
+
+
+def with_edge_cases(F):
+    """The data edges a real training set has, on top of training_problem's all-NaN quasar 3: a
+    quasar with exactly one valid pixel, one whole 16-pixel group missing in one quasar, and a rest
+    pixel missing in every quasar."""
+    F = F.copy()
+    keep = F[5, 100]
+    F[5] = np.nan
+    F[5, 100] = 0.0 if np.isnan(keep) else keep
+    F[7, 160:176] = np.nan  # (pixel group 10: rows of the device copy start on 16-pixel boundaries)
+    F[:, 500] = np.nan
+    return F
+
+
+_scale_cache = {}
+
+
+def learning_problem(nq, G, k, seed):
+    key = (nq, G, k, seed)
+    if key not in _scale_cache:
+        x, F, L1, NV = training_problem(nq=nq, G=G, k=k, seed=seed)
+        _scale_cache[key] = (x, with_edge_cases(F), L1, NV)
+    return _scale_cache[key]
+
+
+def oracle_at(oracle, x, F, L1, NV, key):
+    """oracle.objective on all threads, once per key within the session."""
+    if key not in _scale_cache:
+        _scale_cache[key] = oracle.objective(x, F, L1, NV, num_threads=0)
+    return _scale_cache[key]
+
+
+def report(shape, f, g, f_ref, g_ref, G, k):
+    worst, block = assert_objective_close(f, g, f_ref, g_ref, G, k, what=shape)
+    print(f"training objective {shape}: worst per-block relative deviation {worst:.2e} ({block})")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", LEARNING_SCALE, ids=lambda s: "x".join(map(str, s)))
+def test_gpu_objective_at_learning_scale(oracle, shape):
+    """Value and gradient against the oracle, per block, at 4997 quasars x 1217 pixels with the data
+    edges of with_edge_cases; at k = 40 two evaluations are also bit for bit the same."""
+    from gp_dla_detection_amd import training
+    nq, G, k = shape
+    x, F, L1, NV = learning_problem(nq, G, k, seed=200 + k)
+    f_ref, g_ref = oracle_at(oracle, x, F, L1, NV, ("ref", nq, G, k, 200 + k))
+    t = training.TrainingSet(F, L1, NV)
+    try:
+        f, g = t.objective(x)
+        if k == 40:
+            f2, g2 = t.objective(x)
+            assert f == f2 and np.array_equal(g, g2)
+    finally:
+        t.close()
+    report(shape, f, g, f_ref, g_ref, G, k)
+
+
+@pytest.mark.gpu
+def test_gpu_training_handle_survives_rank_changes_at_learning_scale(oracle):
+    """One TrainingSet at 4997 x 1217 evaluated at k = 20, 40, 20: the workspace is rebuilt for each
+    rank class and the graph re-captured, and every evaluation matches the oracle per block."""
+    from gp_dla_detection_amd import training
+    nq, G = LEARN_NQ, LEARN_G
+    x40, F, L1, NV = learning_problem(nq, G, 40, seed=240)
+    x20 = np.concatenate([x40[:G * 20], x40[G * 40:]])  # the first 20 columns of M
+    ref40 = oracle_at(oracle, x40, F, L1, NV, ("ref", nq, G, 40, 240))
+    ref20 = oracle_at(oracle, x20, F, L1, NV, ("ref", nq, G, 20, 240))
+    t = training.TrainingSet(F, L1, NV)
+    try:
+        for k, x, ref in ((20, x20, ref20), (40, x40, ref40), (20, x20, ref20)):
+            f, g = t.objective(x)
+            assert_objective_close(f, g, *ref, G, k, what=k)
+    finally:
+        t.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", LYSERIES_SCALE, ids=lambda s: "x".join(map(str, s)))
+def test_gpu_lyseries_objective_at_learning_scale(oracle, shape):
+    """The Lyman-series objective (the LY = true build / core / core_wide kernels) at 2000 quasars,
+    with several chunks per split: 31 lines at k = 20 (the caller's table), 6 at k = 33 (the
+    library's)."""
+    from gp_dla_detection_amd import training
+    nq, G, k, nfl = shape
+    wl, fs = series_tables()
+    x, F, L1, NV = lyseries_problem(nq=nq, G=G, k=k, seed=300 + k)
+    f_ref, g_ref = oracle.objective_lyseries(x, F, L1, NV, nfl, wl, fs, num_threads=0)
+    t = training.TrainingSet(F, L1, NV)
+    try:
+        t.set_lyseries(nfl, *((wl, fs) if nfl == 31 else (None, None)))
+        f, g = t.objective(x)
+    finally:
+        t.close()
+    report(shape, f, g, f_ref, g_ref, G, k)
+
+
+@pytest.mark.gpu
+def test_gpu_objective_at_the_rank_class_boundaries(oracle):
+    """k = 1, 20 (the k <= 20 class: k_train_core) and 21, 40 (the k <= 40 class: k_train_core_wide,
+    four tile groups) with several chunks per split in every kernel."""
+    from gp_dla_detection_amd import training
+    for shape in RANK_BOUNDARIES:
+        nq, G, k = shape
+        x, F, L1, NV = training_problem(nq=nq, G=G, k=k, seed=400 + k)
+        f_ref, g_ref = oracle.objective(x, F, L1, NV, num_threads=0)
+        f, g = training.objective(x, F, L1, NV)
+        report(shape, f, g, f_ref, g_ref, G, k)
+
+
+@pytest.mark.gpu
+def test_gpu_objective_at_the_build_split_boundary(oracle):
+    """k_train_build keeps a split's omega2 table in LDS, 64 pixel groups at most: G = 6144 (k = 20)
+    and 3072 (k = 40) fill it exactly; one pixel more raises the split count H by one."""
+    from gp_dla_detection_amd import training
+    for shape in BUILD_BOUNDARIES:
+        nq, G, k = shape
+        x, F, L1, NV = training_problem(nq=nq, G=G, k=k, seed=500 + k)
+        f_ref, g_ref = oracle.objective(x, F, L1, NV, num_threads=0)
+        f, g = training.objective(x, F, L1, NV)
+        report(shape, f, g, f_ref, g_ref, G, k)
