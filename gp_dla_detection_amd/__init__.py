@@ -8,7 +8,8 @@ from .api import (Batch, Context, dla_existence_prior, dla_existence_prior_multi
                   log_mvnpdf_low_rank, prepare_prior, process_qsos,
                   process_qsos_multiple_dlas_meanflux, spectra_to_csr, voigt)
 from .parameters import MultiParameters, Parameters, kms_to_z
+from .training import learn_qso_model
 
 __all__ = ["Batch", "Context", "dla_existence_prior", "dla_existence_prior_multi",
            "log_mvnpdf_low_rank", "prepare_prior", "process_qsos", "process_qsos_multiple_dlas_meanflux",
-           "spectra_to_csr", "voigt", "Parameters", "MultiParameters", "kms_to_z"]
+           "spectra_to_csr", "voigt", "Parameters", "MultiParameters", "kms_to_z", "learn_qso_model"]

@@ -91,6 +91,12 @@ class Config(C.Structure):
                 ("pipeline_slots", C.c_int32), ("max_quasars_per_batch", C.c_int64)]
 
 
+class LearnConfig(C.Structure):
+    _fields_ = [("min_lambda", C.c_double), ("dlambda", C.c_double), ("num_rest_pixels", C.c_int64),
+                ("lya_wavelength", C.c_double), ("max_noise_variance", C.c_double),
+                ("prev_tau_0", C.c_double), ("prev_beta", C.c_double), ("num_forest_lines", C.c_int32)]
+
+
 class Results(C.Structure):
     _fields_ = [("min_z_dlas", _dp), ("max_z_dlas", _dp), ("log_likelihoods_no_dla", _dp),
                 ("sample_log_likelihoods_dla", _dp), ("log_likelihoods_dla", _dp),
@@ -159,6 +165,11 @@ SYMBOLS = [
     ("gpdla_training_objective", C.c_int, [C.c_void_p, _dp, C.c_int, _dp, _dp]),
     ("gpdla_training_set_lyseries", C.c_int, [C.c_void_p, C.c_int, _dp, _dp]),
     ("gpdla_training_destroy", None, [C.c_void_p]),
+    ("gpdla_training_create_from_spectra", C.c_int, [C.c_int, C.POINTER(Spectra), C.POINTER(LearnConfig),
+                                                     C.POINTER(C.c_void_p)]),
+    ("gpdla_training_column_stats", C.c_int, [C.c_void_p, _dp, _dp, _i64p]),
+    ("gpdla_training_pca_covariance", C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _i64p]),
+    ("gpdla_training_download", C.c_int, [C.c_void_p, _dp, _dp, _dp]),
     ("gpdla_debug_near_poly", C.c_int, [C.c_int, C.c_double, _dp, _dp]),
     ("gpdla_debug_prepared_rows", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, _dp, C.c_int64, _i64p]),
     ("gpdla_debug_philox4x32_10", None, [_u32p, _u32p, _u32p]),

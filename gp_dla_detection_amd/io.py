@@ -222,6 +222,45 @@ def load_learned_model(path: str) -> dict:
                 log_tau_0=float(_vec(m["log_tau_0"])[0]), log_beta=float(_vec(m["log_beta"])[0]))
 
 
+#: learn_qso_model.m:113-118 without its two MATLAB structs, in the reference's order
+LEARNED_MODEL_VARIABLES = ("training_release", "train_ind", "max_noise_variance", "rest_wavelengths", "mu",
+                           "initial_M", "initial_log_omega", "initial_log_c_0", "initial_tau_0", "initial_beta",
+                           "M", "log_omega", "log_c_0", "log_tau_0", "log_beta", "log_likelihood")
+
+
+def save_learned_model(path: str, model: dict, training_release: str | None = None, train_ind=None,
+                       compress: bool = False) -> None:
+    """learned_qso_model_*.mat as learn_qso_model.m:113-123 saves it (``-v7.3``): rest_wavelengths, mu,
+    log_omega and initial_log_omega as ROW vectors, M and initial_M as [G x k], the scalars as 1 x 1,
+    ``train_ind`` as a catalogue-length logical column and ``training_release`` as a string.  Every
+    variable of that list present in ``model`` (or passed here) is written, nothing else.
+    ``minFunc_options`` and ``minFunc_output`` are MATLAB structs, which this writer does not support:
+    they are left out (``model['fit']`` holds what minFunc_output reports)."""
+    extra = {}
+    if training_release is not None:
+        extra["training_release"] = str(training_release)
+    if train_ind is not None:
+        t = np.asarray(train_ind)
+        if t.dtype != bool:
+            raise TypeError("train_ind: a catalogue-length boolean mask")
+        extra["train_ind"] = t.reshape(-1, 1)
+    rows = ("rest_wavelengths", "mu", "log_omega", "initial_log_omega")
+    out = {}
+    for name in LEARNED_MODEL_VARIABLES:
+        if name in extra:
+            out[name] = extra[name]
+        elif name in model:
+            v = model[name]
+            if name in rows:
+                v = np.asarray(v, dtype=np.float64).reshape(1, -1)
+            elif name in ("M", "initial_M"):
+                v = np.asarray(v, dtype=np.float64)
+            else:
+                v = np.float64(v)
+            out[name] = v
+    savemat73(path, out, compress=compress)
+
+
 def load_dla_samples(path: str) -> dict:
     """Variables of process_qsos.m:38-40 (+ lls_nhi_samples when present, set_lls_parameters.m:63)."""
     m = _load_mat(path, ("offset_samples", "log_nhi_samples", "nhi_samples", "lls_nhi_samples",

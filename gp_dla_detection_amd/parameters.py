@@ -38,6 +38,11 @@ class Parameters:
     # HBM budget of a batch's per-K-step records; a larger batch is swept group by group through one
     # pool of this size (results do not depend on it); 0 = 16 GiB
     record_pool_bytes: int = 0
+    # learning the model (learn_qso_model.m): set_parameters.m:37-42
+    max_noise_variance: float = 1.0        # rest pixels with a noisier variance are dropped
+    initial_c_0: float = 0.1
+    initial_tau_0: float = 0.0023
+    initial_beta: float = 3.65
 
     def min_z_dla(self, wavelengths, z_qso):
         """set_parameters.m:70-73"""
@@ -51,6 +56,7 @@ class Parameters:
 
 @dataclass(frozen=True)
 class MultiParameters(Parameters):
+    max_noise_variance: float = 9.0            # set_parameters_multi.m:37
     max_dlas: int = 4                          # process_qsos_multiple_dlas_meanflux.m:32
     min_z_separation: float = kms_to_z(3000)   # :33
     prev_tau_0: float = 0.0023                 # :36

@@ -286,8 +286,7 @@ def write_file_set(directory: str, num_quasars: int = 24, num_samples: int = 256
     io.savemat73(paths["preloaded"], cells, compress=True)
     # learn_qso_model.m: rest_wavelengths, mu and log_omega are ROW vectors (read back as
     # f['mu'][:, 0], qso_loader.py:211-217), M is [G x k]
-    io.savemat73(paths["learned"], {k_: (np.asarray(v).reshape(1, -1) if np.ndim(v) == 1 else v)
-                                    for k_, v in model.items()}, compress=True)
+    io.save_learned_model(paths["learned"], model, compress=True)
     io.savemat73(paths["samples"], {k_: v.reshape(1, -1) for k_, v in samples.items()})
     test_ind = filter_flags == 0
     # snrs_qsos_*.mat is written for the SEARCHED quasars (calc_cddf.compute_all_snrs runs over the

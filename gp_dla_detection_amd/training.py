@@ -6,7 +6,11 @@ rest_noise_variances)`` returns ``(f, g)`` for ``x = [vec M; log omega; log c0; 
 :class:`TrainingSet` keeps the three [num_quasars x num_pixels] matrices resident in HBM so an
 L-BFGS driver (the reference uses the third-party minFunc, learn_qso_model.m:100-101) pays only for
 ``x`` and ``g`` per iteration; :func:`fit` is that driver, on :func:`minimize_lbfgs` (minFunc's
-default L-BFGS restated; numpy only).
+default L-BFGS restated; numpy only).  :func:`learn_qso_model` is learn_qso_model.m (and
+multi_dlas/learn_qso_model_meanflux.m) end to end: :meth:`TrainingSet.from_spectra` builds the three
+matrices on the GPU from the spectra (csrc/learn_kernels.hpp), the PCA covariance is formed there too,
+and ``fit`` starts on the data the kernels left in HBM.  ``python -m gp_dla_detection_amd.training``
+writes learned_qso_model_*.mat from preloaded_qsos.mat.
 """
 from __future__ import annotations
 
@@ -32,6 +36,70 @@ class TrainingSet:
         _lib.check(self.lib.gpdla_training_create(int(device), self.num_quasars, self.num_pixels,
                                                   F.ctypes.data_as(_dp), L.ctypes.data_as(_dp),
                                                   N.ctypes.data_as(_dp), C.byref(self._h)))
+
+    @classmethod
+    def from_spectra(cls, spectra, params=None, meanflux: bool = False, device: int = 0):
+        """The training set of learn_qso_model.m:37-67 (``meanflux``: learn_qso_model_meanflux.m:43-132)
+        made on the GPU from ``spectra``: the list of per-quasar dicts (wavelengths, flux,
+        noise_variance, pixel_mask, z_qso) or the CSR dict of ``PreloadedReader.read_csr`` /
+        ``api.spectra_to_csr``.  The flux stays uncentred until :meth:`column_stats`."""
+        from .api import spectra_to_csr
+        from .parameters import MultiParameters, Parameters
+        p = params or (MultiParameters() if meanflux else Parameters())
+        csr = spectra if isinstance(spectra, dict) else spectra_to_csr(list(spectra))
+        keep = dict(offsets=np.ascontiguousarray(csr["offsets"], dtype=np.int64),
+                    wavelengths=np.ascontiguousarray(csr["wavelengths"], dtype=np.float64),
+                    flux=np.ascontiguousarray(csr["flux"], dtype=np.float64),
+                    noise_variance=np.ascontiguousarray(csr["noise_variance"], dtype=np.float64),
+                    pixel_mask=np.ascontiguousarray(csr["pixel_mask"], dtype=np.uint8),
+                    z_qsos=np.ascontiguousarray(csr["z_qsos"], dtype=np.float64))
+        nq = keep["z_qsos"].size
+        if keep["offsets"].size != nq + 1:
+            raise ValueError(f"{nq} redshifts but {keep['offsets'].size} offsets")
+        sp = _lib.Spectra()
+        sp.num_quasars = nq
+        sp.offsets = keep["offsets"].ctypes.data_as(_lib._i64p)
+        for name in ("wavelengths", "flux", "noise_variance"):
+            setattr(sp, name, keep[name].ctypes.data_as(_dp))
+        sp.pixel_mask = keep["pixel_mask"].ctypes.data_as(_lib._u8p)
+        sp.z_qsos = keep["z_qsos"].ctypes.data_as(_dp)
+        cfg = learn_config(p, meanflux)
+        self = cls.__new__(cls)
+        self.lib = _lib.load()
+        self._h = C.c_void_p()
+        _lib.check(self.lib.gpdla_training_create_from_spectra(int(device), C.byref(sp), C.byref(cfg),
+                                                               C.byref(self._h)))
+        self.num_quasars, self.num_pixels = nq, int(cfg.num_rest_pixels)
+        return self
+
+    def column_stats(self):
+        """(mu, std, count): nanmean of the rest fluxes (learn_qso_model.m:70), which the resident flux
+        is then centred by (:71), nanstd of the centred flux (:87) and the finite entries per pixel.
+        The first call centres; later calls return the same numbers."""
+        G = self.num_pixels
+        mu, std, count = np.empty(G), np.empty(G), np.empty(G, dtype=np.int64)
+        _lib.check(self.lib.gpdla_training_column_stats(self._h, mu.ctypes.data_as(_dp), std.ctypes.data_as(_dp),
+                                                        count.ctypes.data_as(_lib._i64p)))
+        return mu, std, count
+
+    def pca_covariance(self, complete_rows: bool = False, with_count: bool = False):
+        """(cov, count or None, rows_used): the G x G matrix pca(centered_rest_fluxes, 'rows',
+        'pairwise' | 'complete') decomposes (csrc/learn_kernels.hpp)."""
+        G = self.num_pixels
+        cov = np.empty((G, G))
+        count = np.empty((G, G)) if with_count else None
+        rows = C.c_int64()
+        _lib.check(self.lib.gpdla_training_pca_covariance(
+            self._h, int(bool(complete_rows)), cov.ctypes.data_as(_dp),
+            None if count is None else count.ctypes.data_as(_dp), C.byref(rows)))
+        return cov, count, int(rows.value)
+
+    def download(self):
+        """(flux, lya_1pzs, noise): the resident matrices, [num_quasars, num_pixels] each."""
+        shape = (self.num_quasars, self.num_pixels)
+        out = [np.empty(shape, order="F") for _ in range(3)]
+        _lib.check(self.lib.gpdla_training_download(self._h, *(a.ctypes.data_as(_dp) for a in out)))
+        return tuple(out)
 
     def objective(self, x):
         """(f, g) of objective.m:12-75 at x."""
@@ -71,6 +139,25 @@ class TrainingSet:
             self.close()
         except Exception:
             pass
+
+
+def rest_grid_size(params) -> int:
+    """numel(min_lambda:dlambda:max_lambda) (learn_qso_model.m:29-30)."""
+    return int(round((params.max_lambda - params.min_lambda) / params.dlambda)) + 1
+
+
+def learn_config(params, meanflux: bool = False) -> "_lib.LearnConfig":
+    """gpdla_learn_config of ``params`` (set_parameters.m / set_parameters_multi.m)."""
+    cfg = _lib.LearnConfig()
+    cfg.min_lambda = params.min_lambda
+    cfg.dlambda = params.dlambda
+    cfg.num_rest_pixels = rest_grid_size(params)
+    cfg.lya_wavelength = params.lya_wavelength
+    cfg.max_noise_variance = params.max_noise_variance
+    cfg.prev_tau_0 = getattr(params, "prev_tau_0", 0.0023)
+    cfg.prev_beta = getattr(params, "prev_beta", 3.65)
+    cfg.num_forest_lines = getattr(params, "num_forest_lines", 31) if meanflux else 0
+    return cfg
 
 
 def objective(x, centered_rest_fluxes, lya_1pzs, rest_noise_variances, device: int = 0):
@@ -316,12 +403,18 @@ def fit(initial_x, centered_rest_fluxes, lya_1pzs, rest_noise_variances, max_ite
     reference's objective value (without the prior term) in either mode.  ``num_forest_lines > 1``:
     the mean-flux model's objective (multi_dlas/learn_qso_model_meanflux.m:140-147)."""
     t = TrainingSet(centered_rest_fluxes, lya_1pzs, rest_noise_variances, device)
-    if num_forest_lines > 1:
-        try:
+    try:
+        if num_forest_lines > 1:
             t.set_lyseries(num_forest_lines, all_transition_wavelengths, all_oscillator_strengths)
-        except BaseException:
-            t.close()
-            raise
+        return fit_training_set(t, initial_x, max_iter, max_fun_evals, prior_in_value)
+    finally:
+        t.close()
+
+
+def fit_training_set(t: TrainingSet, initial_x, max_iter: int = 2000, max_fun_evals: int = 4000,
+                     prior_in_value: bool = False):
+    """:func:`fit` on an existing handle (its objective as set: objective.m or, after
+    ``set_lyseries``, objective_lyseries.m).  Returns (x, f, FitResult)."""
 
     def safe(x):
         try:
@@ -334,11 +427,103 @@ def fit(initial_x, centered_rest_fluxes, lya_1pzs, rest_noise_variances, max_ite
             raise
         return (f + prior_value(x) if prior_in_value else f), g
 
+    res = minimize_lbfgs(safe, np.asarray(initial_x, dtype=np.float64), max_iter=max_iter,
+                         max_fun_evals=max_fun_evals)
+    if prior_in_value:
+        res.fun -= prior_value(res.x)
+    return res.x, res.fun, res
+
+
+def pca_initial_M(cov, k: int):
+    """(initial_M, latent) of learn_qso_model.m:75-84 from the covariance pca decomposes: the
+    eigenvalues in descending order, each eigenvector's sign set so that its element of largest
+    magnitude is positive (pca's convention), initial_M = coeff(:, 1:k) .* sqrt(latent(1:k))'.
+    Host ``numpy.linalg.eigh``, once per model.  Raises if one of the top k eigenvalues is not
+    positive (or the covariance is not finite)."""
+    cov = np.asarray(cov, dtype=np.float64)
+    if not np.all(np.isfinite(cov)):
+        raise ValueError("the PCA covariance is not finite (some pair of rest pixels shares fewer than two quasars)")
+    w, V = np.linalg.eigh(cov)
+    latent = w[::-1]
+    coeff = V[:, ::-1][:, :k]
+    if k > latent.size or not np.all(latent[:k] > 0.0):
+        raise ValueError(f"the top {k} eigenvalues of the PCA covariance are not all positive: {latent[:k]}")
+    big = np.abs(coeff).argmax(axis=0)
+    coeff = coeff * np.where(coeff[big, np.arange(k)] < 0.0, -1.0, 1.0)[None, :]
+    return np.asfortranarray(coeff * np.sqrt(latent[:k])[None, :]), latent
+
+
+def learn_qso_model(spectra, params=None, meanflux: bool = False, max_iter: int = 2000,
+                    max_fun_evals: int = 4000, device: int = 0, prior_in_value: bool = False) -> dict:
+    """learn_qso_model.m:27-118 (``meanflux``: multi_dlas/learn_qso_model_meanflux.m:27-179) on the
+    spectra of the training quasars (the ``train_ind`` subset, as :meth:`TrainingSet.from_spectra`
+    takes them).  Returns the variables the reference saves (everything but the minFunc structs) plus
+    ``fit`` (the :class:`FitResult`), ``latent`` and ``initial_x``; :func:`io.save_learned_model`
+    writes it and :func:`io.load_learned_model` / ``process_qsos`` read it back."""
+    from .parameters import MultiParameters, Parameters
+    p = params or (MultiParameters() if meanflux else Parameters())
+    k = int(p.k)
+    t = TrainingSet.from_spectra(spectra, p, meanflux, device)
     try:
-        res = minimize_lbfgs(safe, np.asarray(initial_x, dtype=np.float64), max_iter=max_iter,
-                             max_fun_evals=max_fun_evals)
-        if prior_in_value:
-            res.fun -= prior_value(res.x)
+        mu, std, count = t.column_stats()
+        thin = np.flatnonzero(count < 2)
+        if thin.size:
+            raise ValueError(f"rest pixels {thin.tolist()} have fewer than two finite training values")
+        cov, _, rows_used = t.pca_covariance(complete_rows=meanflux)
+        if meanflux and rows_used <= k:
+            raise ValueError(f"pca 'rows','complete': {rows_used} complete rows for k = {k} components")
+        initial_M, latent = pca_initial_M(cov, k)
+        initial_log_omega = np.log(std)
+        initial_log_c_0, initial_log_tau_0, initial_log_beta = (np.log(p.initial_c_0), np.log(p.initial_tau_0),
+                                                                np.log(p.initial_beta))
+        initial_x = np.concatenate([initial_M.ravel(order="F"), initial_log_omega,
+                                    [initial_log_c_0, initial_log_tau_0, initial_log_beta]])
+        if meanflux:
+            t.set_lyseries(int(getattr(p, "num_forest_lines", 31)))
+        x, f, res = fit_training_set(t, initial_x, max_iter, max_fun_evals, prior_in_value)
     finally:
         t.close()
-    return res.x, res.fun, res
+    G = mu.size
+    return dict(rest_wavelengths=p.min_lambda + p.dlambda * np.arange(G), mu=mu,
+                initial_M=initial_M, initial_log_omega=initial_log_omega, initial_log_c_0=float(initial_log_c_0),
+                initial_tau_0=float(p.initial_tau_0), initial_beta=float(p.initial_beta),
+                M=np.asfortranarray(x[:G * k].reshape(G, k, order="F")), log_omega=x[G * k:G * (k + 1)].copy(),
+                log_c_0=float(x[-3]), log_tau_0=float(x[-2]), log_beta=float(x[-1]), log_likelihood=float(f),
+                max_noise_variance=float(p.max_noise_variance), fit=res, latent=latent, initial_x=initial_x)
+
+
+def main(argv=None) -> int:
+    """learn_qso_model.m as a command: preloaded_qsos.mat + catalog.mat + a training mask ->
+    learned_qso_model_*.mat."""
+    import argparse
+
+    from . import io
+    from .parameters import MultiParameters, Parameters
+    ap = argparse.ArgumentParser(prog="python -m gp_dla_detection_amd.training", description=main.__doc__)
+    ap.add_argument("--preloaded", required=True, help="preloaded_qsos.mat (-v7.3)")
+    ap.add_argument("--catalog", required=True, help="catalog.mat (z_qsos)")
+    ap.add_argument("--train-ind", required=True,
+                    help=".npy: a catalogue-length boolean mask or 0-based indices of the training quasars")
+    ap.add_argument("--out", required=True, help="learned_qso_model_*.mat to write")
+    ap.add_argument("--meanflux", action="store_true", help="the mean-flux model (learn_qso_model_meanflux.m)")
+    ap.add_argument("--max-iter", type=int, default=2000)
+    ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--training-release", default="dr9")
+    a = ap.parse_args(argv)
+    z = io.load_catalog(a.catalog, names=("z_qsos",))["z_qsos"]
+    ind = np.load(a.train_ind)
+    idx = np.flatnonzero(ind) if ind.dtype == bool else np.asarray(ind, dtype=np.int64).reshape(-1)
+    mask = np.zeros(z.size, dtype=bool)
+    mask[idx] = True
+    csr = io.PreloadedReader(a.preloaded).read_csr(idx, z)
+    model = learn_qso_model(csr, MultiParameters() if a.meanflux else Parameters(), meanflux=a.meanflux,
+                            max_iter=a.max_iter, device=a.device)
+    io.save_learned_model(a.out, model, training_release=a.training_release, train_ind=mask)
+    res = model["fit"]
+    print(f"wrote {a.out}: {idx.size} quasars, k = {model['M'].shape[1]}, log_likelihood = "
+          f"{model['log_likelihood']:.6f}, {res.nit} iterations ({res.message})")
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

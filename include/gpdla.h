@@ -383,6 +383,47 @@ int gpdla_training_set_lyseries(gpdla_training *t, int num_forest_lines, const d
 void gpdla_training_destroy(gpdla_training *t);
 
 /* ---------------------------------------------------------------------------------------------
+ * Learning the model from spectra: learn_qso_model.m:27-87 (single-DLA model) and
+ * multi_dlas/learn_qso_model_meanflux.m:27-138 (mean-flux model) up to the PCA, on the GPU.  The
+ * handle's three training matrices are made in HBM from the spectra, never on the host.
+ * ------------------------------------------------------------------------------------------- */
+/* The set_parameters.m / set_parameters_multi.m values the learning reads. */
+typedef struct {
+  double min_lambda, dlambda;       /* rest grid min_lambda + p dlambda, p < num_rest_pixels (:33-35) */
+  int64_t num_rest_pixels;          /* G (1217 for the reference's grid) */
+  double lya_wavelength;            /* set_parameters.m:5 */
+  double max_noise_variance;        /* :37 (1; 9 for the mean-flux model) */
+  double prev_tau_0, prev_beta;     /* learn_qso_model_meanflux.m:102-103 (0.0023, 3.65) */
+  int32_t num_forest_lines;         /* <= 1: single-DLA model; 2..31: the mean-flux model over the
+                                       built-in Lyman-series table (set_parameters_multi.m:75-144) */
+} gpdla_learn_config;
+
+/* A training set made from spectra (learn_qso_model.m:37-67, or learn_qso_model_meanflux.m:43-132 with
+ * num_forest_lines > 1): each quasar interpolated onto the rest grid (NaN outside its range, NaN at
+ * masked pixels), noisy pixels (rest noise variance > max_noise_variance) removed, and -- mean-flux
+ * model -- flux and noise divided by the Lyman-series absorption exp(-tau) and exp(-tau)^2.  The
+ * flux is NOT yet centred: gpdla_training_column_stats does that.  The prior pointers of `spectra` are
+ * ignored.  gpdla_training_objective and gpdla_training_set_lyseries work on the result unchanged. */
+int gpdla_training_create_from_spectra(int device_id, const gpdla_spectra *spectra, const gpdla_learn_config *config,
+                                       gpdla_training **out);
+/* Of a handle made by gpdla_training_create_from_spectra: mu = nanmean(rest_fluxes) (:70), the
+ * centring of the resident flux in place (:71) and nanstd(centered_rest_fluxes) (:87, n - 1); count =
+ * finite entries per pixel.  The first call centres; later calls return the same numbers.  Each
+ * output [G] may be NULL. */
+int gpdla_training_column_stats(gpdla_training *t, double *mu, double *std, int64_t *count);
+/* The covariance pca(centered_rest_fluxes, 'rows', ...) decomposes: complete_rows = 0 for 'pairwise'
+ * (learn_qso_model.m:75-78: cov_ab = Sum_q x_qa x_qb / (N_ab - 1) over the quasars finite in both
+ * pixels), != 0 for 'complete' (learn_qso_model_meanflux.m:135-138: rows with any NaN dropped, the
+ * rest centred by their own column mean, X'X / (n_c - 1)).  cov and count (N_ab; may be NULL) are
+ * G x G, exactly symmetric; *rows_used (may be NULL): quasars with any finite pixel (pairwise) or the
+ * complete rows.  Runs gpdla_training_column_stats first if it has not run. */
+int gpdla_training_pca_covariance(gpdla_training *t, int complete_rows, double *cov, double *count,
+                                  int64_t *rows_used);
+/* The resident matrices, column-major [num_quasars x num_pixels] as MATLAB holds them (flux: centred
+ * once column_stats has run).  Any pointer may be NULL. */
+int gpdla_training_download(gpdla_training *t, double *flux, double *lya, double *noise);
+
+/* ---------------------------------------------------------------------------------------------
  * Diagnostics.  The sweep kernel evaluates the Voigt function within 30 Doppler widths of a line
  * centre from per-line piecewise polynomials of Re w(x + i y_line) (what voigt.c:288 gets from
  * libcerf's voigt()).  This returns the HOST evaluation of the table of Lyman line `line`
