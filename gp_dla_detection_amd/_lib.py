@@ -114,6 +114,25 @@ class ResultsMulti(C.Structure):
         ("base_sample_inds", _u32p), ("status", _i32p)]
 
 
+class BinRequest(C.Structure):
+    """gpdla_bin_request"""
+    _fields_ = [("quantity", C.c_int32), ("num_bins", C.c_int32), ("edges", _dp), ("z_lo", C.c_double),
+                ("z_hi", C.c_double), ("lnhi_lo", C.c_double), ("lnhi_hi", C.c_double), ("histogram", C.c_int32),
+                ("moment", C.c_int32), ("lowzcut", C.c_int32), ("p_thresh_sample", C.c_double),
+                ("p_switch", C.c_double)]
+
+
+class BinOutput(C.Structure):
+    """gpdla_bin_output"""
+    _fields_ = [("pois", _dp), ("mean", _dp), ("var", _dp), ("kept_count", _i32p), ("kept_bin", _i32p),
+                ("kept_p", _dp)]
+
+
+def ptr(a):
+    """double* of a C-contiguous float64 array."""
+    return a.ctypes.data_as(_dp)
+
+
 SUMMARY_COLS = 15  # GPDLA_SUMMARY_COLS
 
 
@@ -170,6 +189,9 @@ SYMBOLS = [
     ("gpdla_training_column_stats", C.c_int, [C.c_void_p, _dp, _dp, _i64p]),
     ("gpdla_training_pca_covariance", C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _i64p]),
     ("gpdla_training_download", C.c_int, [C.c_void_p, _dp, _dp, _dp]),
+    ("gpdla_stats_bin_posteriors", C.c_int, [C.c_int64, C.c_int64, _dp, C.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
+                                             C.c_int, C.POINTER(BinRequest), C.POINTER(BinOutput), C.c_int]),
+    ("gpdla_stats_poisson_binomial_cf", C.c_int, [C.c_int64, _i64p, _dp, _dp, _dp, C.c_int]),
     ("gpdla_debug_near_poly", C.c_int, [C.c_int, C.c_double, _dp, _dp]),
     ("gpdla_debug_prepared_rows", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, _dp, C.c_int64, _i64p]),
     ("gpdla_debug_philox4x32_10", None, [_u32p, _u32p, _u32p]),

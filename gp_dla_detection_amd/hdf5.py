@@ -583,13 +583,14 @@ class Dataset(_Node):
             out[sel] = block[tuple(slice(0, s.stop - s.start) for s in sel)]
         return out
 
-    def read_slab(self, lo: int, hi: int, axis1: tuple | None = None) -> np.ndarray:
+    def read_slab(self, lo: int, hi: int, axis1: tuple | None = None, axis2: tuple | None = None) -> np.ndarray:
         """Rows ``lo .. hi`` of the first (slowest) HDF5 dimension, touching only the data they need:
         a view of the memory map for contiguous data, the overlapping chunks for chunked data (the
         chunk index is walked once per dataset).  What a streamed copy of a table too large for
         memory is built from.  ``axis1 = (lo1, hi1)``: only that range of the SECOND dimension as
         well (a 3-D table whose first dimension is short -- ``[max_dlas, S, nq]`` -- is streamed by
-        (first index, range of the second) instead of by whole first-dimension rows)."""
+        (first index, range of the second) instead of by whole first-dimension rows).  ``axis2 =
+        (lo2, hi2)``: likewise for the THIRD dimension (a range of quasars of such a table)."""
         kind, where, cdims = self._layout_info()
         shape, dt = self.shape, self.dtype
         lo, hi = max(0, int(lo)), min(int(hi), shape[0] if shape else 0)
@@ -598,18 +599,27 @@ class Dataset(_Node):
             if len(shape) < 2:
                 raise HDF5Error("axis1 given for a dataset with fewer than two dimensions")
             lo1, hi1 = max(0, int(axis1[0])), min(int(axis1[1]), shape[1])
+        lo2, hi2 = 0, (shape[2] if len(shape) > 2 else 0)
+        if axis2 is not None:
+            if len(shape) < 3:
+                raise HDF5Error("axis2 given for a dataset with fewer than three dimensions")
+            lo2, hi2 = max(0, int(axis2[0])), min(int(axis2[1]), shape[2])
         if kind != "chunked":
             a = self.read(memmap=True)[lo:hi]
-            return a if axis1 is None else a[:, lo1:hi1]
+            a = a if axis1 is None else a[:, lo1:hi1]
+            return a if axis2 is None else a[:, :, lo2:hi2]
         if not hasattr(self, "_chunk_index"):
             self._chunk_index = []
             self._chunks(where, len(shape), self._chunk_index)
         second = (max(hi1 - lo1, 0),) if len(shape) > 1 else ()
-        out = np.zeros((max(hi - lo, 0),) + second + tuple(shape[2:]), dtype=dt)
+        third = (max(hi2 - lo2, 0),) if len(shape) > 2 else ()
+        out = np.zeros((max(hi - lo, 0),) + second + third + tuple(shape[3:]), dtype=dt)
         for offs, csize, cmask, caddr in self._chunk_index:
             if offs[0] >= hi or offs[0] + cdims[0] <= lo:
                 continue
             if len(shape) > 1 and (offs[1] >= hi1 or offs[1] + cdims[1] <= lo1):
+                continue
+            if len(shape) > 2 and (offs[2] >= hi2 or offs[2] + cdims[2] <= lo2):
                 continue
             raw = self._decode_chunk(self.file._bytes(caddr, csize), cmask)
             block = np.frombuffer(raw, dtype=dt, count=int(np.prod(cdims))).reshape(cdims)
@@ -620,7 +630,11 @@ class Dataset(_Node):
                 b0, b1 = max(offs[1], lo1), min(offs[1] + cdims[1], hi1, shape[1])
                 src.append(slice(b0 - offs[1], b1 - offs[1]))
                 dst.append(slice(b0 - lo1, b1 - lo1))
-            for o, c, s_ in zip(offs[2:], cdims[2:], shape[2:]):
+            if len(shape) > 2:
+                c0, c1 = max(offs[2], lo2), min(offs[2] + cdims[2], hi2, shape[2])
+                src.append(slice(c0 - offs[2], c1 - offs[2]))
+                dst.append(slice(c0 - lo2, c1 - lo2))
+            for o, c, s_ in zip(offs[3:], cdims[3:], shape[3:]):
                 stop = min(o + c, s_)
                 src.append(slice(0, stop - o))
                 dst.append(slice(o, stop))

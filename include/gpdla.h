@@ -452,6 +452,57 @@ void gpdla_debug_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uin
  * never a C++ exception (which would end MATLAB / Python).  Needs no GPU. */
 int gpdla_debug_throw(int kind);
 
+/* ---------------------------------------------------------------------------------------------
+ * CDDF statistics (CDDF_analysis/calc_cddf.py, class DLACatalogue).
+ *
+ * gpdla_stats_bin_posteriors: one pass over a block of selected spectra.  Row s of the sample
+ * table starts at sample_log_likelihoods + s * row_stride (S values); p = exp(sll - shift[s]) *
+ * p_dla[s] (shift = log_likelihoods_dla + log S, formed by the caller) and z = z_min[s] + (z_max[s]
+ * - z_min[s]) * offset, each operation rounded on its own.  Each request bins z or log10 N_HI:
+ *  - histogram = 0 (_split_distributions_single, :994-1034): samples with lnhi_lo < lnhi < lnhi_hi,
+ *    z_lo < z < upper (upper = min(upper_z[s], z_hi) with lowzcut, else z_hi) and p >
+ *    p_thresh_sample, in bin b when edges[b] < q < edges[b+1].  pois[s][b] sums those with p <
+ *    p_switch; the others are kept as (bin, p) pairs in sample order, at most
+ *    GPDLA_STATS_KEPT_CAPACITY per spectrum: kept_count[s] is the true number, and a spectrum above
+ *    the capacity makes the call return GPDLA_ERR_UNSUPPORTED naming it (the outputs are written).
+ *  - histogram != 0 (_get_z_nhi_hist, :1101-1125): the window without lowzcut and without a p cut,
+ *    np.histogram's bins ([a, b), the last closed), mean[s][b] = sum w p and var[s][b] = sum w^2 (1 - p)
+ *    p, w = 10^lnhi (moment != 0) or 1.  A NaN weight makes its bin and every later bin NaN, as
+ *    np.histogram's cumulative sums do.
+ * Every sum runs in sample order, compensated; outputs depend on their own row only.  Outputs are
+ * [num_spectra][num_bins] and [num_spectra][GPDLA_STATS_KEPT_CAPACITY] (unused slots: bin -1, p 0);
+ * pointers a request does not use may be NULL.  Edges must be finite and strictly increasing.
+ *
+ * gpdla_stats_poisson_binomial_cf: segment g holds p[offsets[g] .. offsets[g+1]) (N_g finite values
+ * >= 0; a kept probability may exceed 1 by rounding, which is accepted); for n = 0 .. (N_g+1)/2 it writes logsum = sum_j log|1 + p_j (e^{-2 pi i n/(N_g+1)} - 1)| and
+ * argsum = sum_j arg(...) (:1293-1295) at position n of the segment's block; the blocks follow one
+ * another, (N_g+1)/2 + 1 values each.  The pdf is irfft(exp(logsum + i argsum), N_g + 1).
+ * ------------------------------------------------------------------------------------------- */
+#define GPDLA_STATS_MAX_BINS 64
+#define GPDLA_STATS_MAX_REQUESTS 4
+#define GPDLA_STATS_KEPT_CAPACITY 8
+typedef struct {
+  int32_t quantity;       /* 0: z, 1: log10 N_HI */
+  int32_t num_bins;       /* 1 .. GPDLA_STATS_MAX_BINS */
+  const double *edges;    /* [num_bins + 1] */
+  double z_lo, z_hi, lnhi_lo, lnhi_hi;
+  int32_t histogram, moment, lowzcut;
+  double p_thresh_sample, p_switch;
+} gpdla_bin_request;
+typedef struct {
+  double *pois, *mean, *var;   /* [num_spectra][num_bins] */
+  int32_t *kept_count;         /* [num_spectra] */
+  int32_t *kept_bin;           /* [num_spectra][GPDLA_STATS_KEPT_CAPACITY] */
+  double *kept_p;
+} gpdla_bin_output;
+int gpdla_stats_bin_posteriors(int64_t num_spectra, int64_t num_samples, const double *sample_log_likelihoods,
+                               int64_t row_stride, const double *shift, const double *p_dla, const double *z_min,
+                               const double *z_max, const double *upper_z, const double *offset_samples,
+                               const double *log_nhi_samples, int num_requests, const gpdla_bin_request *requests,
+                               gpdla_bin_output *outputs, int device_id);
+int gpdla_stats_poisson_binomial_cf(int64_t num_segments, const int64_t *offsets, const double *p, double *logsum,
+                                    double *argsum, int device_id);
+
 #ifdef __cplusplus
 }
 #endif
