@@ -14,14 +14,13 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 #: the product library
 DEFAULT_LIB_PATH = os.path.join(CSRC, "libgpdla.so")
-# GPDLA_LIB_PATH: diagnostic override, read when the library is loaded (ablation builds made by
-# tools/ab_build.sh / tools/ablate.sh; libgpdla_legacy.so for the bit-identity tests)
-LIB_PATH = os.environ.get("GPDLA_LIB_PATH") or DEFAULT_LIB_PATH
 
 
 def lib_path() -> str:
     """The library load() opens: GPDLA_LIB_PATH if set (read at call time, so a child process may
-    set it after this module was imported), else the in-tree product library."""
+    set it after this module was imported), else the in-tree product library.  GPDLA_LIB_PATH is a
+    diagnostic override: ablation builds made by tools/ab_build.sh / tools/ablate.sh;
+    libgpdla_legacy.so for the bit-identity tests."""
     return os.environ.get("GPDLA_LIB_PATH") or DEFAULT_LIB_PATH
 
 # -no-hip-rt: libgpdla.so does NOT carry its own DT_NEEDED on libamdhip64.  A process must hold
@@ -33,7 +32,7 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-s
                "-std=c++17", "-no-hip-rt", "-Wno-inline-asm"]
 
 #: the second library: the same source with the superseded kernels and their environment switches
-#: compiled in (csrc/gpdla.hip, GPDLA_WITH_LEGACY).  Only bit-identity tests and A/B tools load it,
+#: compiled in (csrc/host_legacy.hpp, GPDLA_WITH_LEGACY).  Only bit-identity tests and A/B tools load it,
 #: through GPDLA_LIB_PATH; nothing in the package does.
 LEGACY_LIB_PATH = os.path.join(CSRC, "libgpdla_legacy.so")
 
@@ -201,39 +200,43 @@ SYMBOLS = [
 _lib = None
 
 
-def build(force: bool = False, verbose: bool = False) -> str:
-    """Compile csrc/gpdla.hip for gfx950 with hipcc (cross-compiles without a GPU)."""
+def host_sources() -> list:
+    """The host side of the library: csrc/gpdla.hip, the one translation unit, and the host_*.hpp
+    headers it includes (one per subsystem), in the order it includes them."""
+    import re
+    unit = os.path.join(CSRC, "gpdla.hip")
+    with open(unit) as f:
+        names = re.findall(r'^#include "(host_\w+\.hpp)"', f.read(), flags=re.M)
+    return [unit] + [os.path.join(CSRC, n) for n in names]
+
+
+def _build(out: str, extra_flags, force: bool, verbose: bool) -> str:
+    """hipcc of csrc/gpdla.hip into `out`, unless `out` is newer than every source."""
     import glob
-    srcs = (glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.hpp"))
+    srcs = (host_sources() + glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.hpp"))
             + glob.glob(os.path.join(_HERE, "..", "include", "*.h")))
-    if not force and os.path.exists(DEFAULT_LIB_PATH):
-        if all(os.path.getmtime(DEFAULT_LIB_PATH) >= os.path.getmtime(s) for s in srcs):
-            return DEFAULT_LIB_PATH
-    cmd = ["hipcc", *HIPCC_FLAGS, os.path.join(CSRC, "gpdla.hip"), "-o", DEFAULT_LIB_PATH]
+    if not force and os.path.exists(out):
+        if all(os.path.getmtime(out) >= os.path.getmtime(s) for s in srcs):
+            return out
+    cmd = ["hipcc", *HIPCC_FLAGS, *extra_flags, os.path.join(CSRC, "gpdla.hip"), "-o", out]
     res = subprocess.run(cmd, capture_output=True, text=True)
     if verbose or res.returncode:
         print(res.stdout, res.stderr)
     if res.returncode:
-        raise RuntimeError("hipcc failed building libgpdla.so:\n" + res.stderr)
-    return DEFAULT_LIB_PATH
+        raise RuntimeError(f"hipcc failed building {os.path.basename(out)}:\n" + res.stderr)
+    return out
+
+
+def build(force: bool = False, verbose: bool = False) -> str:
+    """Compile csrc/gpdla.hip for gfx950 with hipcc (cross-compiles without a GPU)."""
+    return _build(DEFAULT_LIB_PATH, [], force, verbose)
 
 
 def build_legacy(force: bool = False, verbose: bool = False) -> str:
-    """Compile libgpdla_legacy.so: csrc/gpdla.hip with -DGPDLA_WITH_LEGACY (the pre-expanded-record
-    sweeps, the round-1/-3 training kernels and the GPDLA_* environment switches that select them)."""
-    import glob
-    srcs = (glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.hpp"))
-            + glob.glob(os.path.join(_HERE, "..", "include", "*.h")))
-    if not force and os.path.exists(LEGACY_LIB_PATH):
-        if all(os.path.getmtime(LEGACY_LIB_PATH) >= os.path.getmtime(s) for s in srcs):
-            return LEGACY_LIB_PATH
-    cmd = ["hipcc", *HIPCC_FLAGS, "-DGPDLA_WITH_LEGACY", os.path.join(CSRC, "gpdla.hip"), "-o", LEGACY_LIB_PATH]
-    res = subprocess.run(cmd, capture_output=True, text=True)
-    if verbose or res.returncode:
-        print(res.stdout, res.stderr)
-    if res.returncode:
-        raise RuntimeError("hipcc failed building libgpdla_legacy.so:\n" + res.stderr)
-    return LEGACY_LIB_PATH
+    """Compile libgpdla_legacy.so: csrc/gpdla.hip with -DGPDLA_WITH_LEGACY, which turns the hooks of
+    csrc/host_legacy.hpp on (the pre-expanded-record sweeps, the round-1/-3 training kernels and the
+    GPDLA_* environment switches that select them)."""
+    return _build(LEGACY_LIB_PATH, ["-DGPDLA_WITH_LEGACY"], force, verbose)
 
 
 def _preload_hip_runtime():

@@ -148,7 +148,7 @@ struct PrepareArgs {
   PixelRow *pix;           // pool
   double *Mi;              // pool [row][k] interpolated (and zeroed for masked rows) M
   double *lam_pad;         // pool
-  const int64_t *rec_off;  // [nq] record-pool offsets planned by the host (gpdla.hip plan_records)
+  const int64_t *rec_off;  // [nq] record-pool offsets planned by the host (host_sweep.hpp plan_records)
   // multi-DLA driver only (process_qsos_multiple_dlas_meanflux.m:245-293): Lyman-series noise
   // scaling and mean-flux suppression of mu, M, omega2
   int32_t multi;
@@ -625,7 +625,7 @@ __device__ __forceinline__ void glds_wait() {
 // blocks.  Per chunk and wave that is two or three vector instructions where a loop over
 // (unit < units ? glds16 : skip) costs eight per block -- and non-arithmetic VALU instructions are
 // MFMA time in these kernels.  The copy always moves the whole chunk: a chunk that runs past a
-// quasar's last record reads the next quasar's records or the pool's padding (gpdla.hip allocates
+// quasar's last record reads the next quasar's records or the pool's padding (host_sweep.hpp allocates
 // kRecordPoolPad records behind the pool), which no K-step consumes.
 constexpr int kRecordPoolPad = 8;
 __device__ __forceinline__ void glds_quad(const double *gsrc, uint32_t lds, int count) {

@@ -203,14 +203,14 @@ def test_one_shot_entry_validates_before_it_touches_the_gpu(lib):
 
 def test_no_cpp_exception_crosses_the_boundary(lib):
     """An exception that reaches an extern "C" frame ends the host process (MATLAB through the MEX gateways
-    of integration/, Python through ctypes).  Every int-returning entry point of csrc/gpdla.hip is a
+    of integration/, Python through ctypes).  Every int-returning entry point of the host files is a
     function-try-block closed by the same handlers; the hook throws inside one."""
     assert lib.gpdla_debug_throw(0) == 0
     for kind, text in ((1, b"out of host memory"), (2, b"thrown on request"), (3, b"unexpected C++ exception")):
         assert lib.gpdla_debug_throw(kind) == _lib.ERR_HOST == -6
         assert text in lib.gpdla_last_error()
     # and every such entry point in the source is closed that way
-    src = open(os.path.join(ROOT, "gp_dla_detection_amd", "csrc", "gpdla.hip")).read()
+    src = "".join(open(path).read() for path in _lib.host_sources())
     blocks = re.findall(r'extern "C" \{(.*?)\}  // extern "C"', src, flags=re.S)
     defs = [m for b in blocks for m in re.findall(r"^int (gpdla_\w+)\([^;{]*?\)\s*(try )?\{", b, flags=re.M | re.S)]
     assert len(defs) >= 28

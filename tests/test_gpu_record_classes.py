@@ -2,7 +2,7 @@
 replace: k_sweep_slim vs k_sweep and k_sweep_multi_slim vs k_sweep_multi (k <= 20),
 k_sweep_split_slim vs k_sweep_split and k_sweep_multi_split (20 < k <= 40).  Same products, same MFMA sequence per
 column, same epilogue: every output must be bit-identical.  The superseded kernels are not in the
-product library: they live in libgpdla_legacy.so (csrc/gpdla.hip built with -DGPDLA_WITH_LEGACY,
+product library: they live in libgpdla_legacy.so (csrc/gpdla.hip built with -DGPDLA_WITH_LEGACY: csrc/host_legacy.hpp,
 __graft_entry__.build()), which a clean child process loads through GPDLA_LIB_PATH with the
 diagnostic switch GPDLA_EXPANDED_RECORDS=1 set (hot loops: process_qsos.m:185-199,
 process_qsos_multiple_dlas_meanflux.m:340-381)."""

@@ -20,8 +20,9 @@ def _model():
 
 
 def test_stride_formula_matches_the_library_source():
-    """The model restates multi_alloc's stride; hold it to the line in csrc/gpdla.hip."""
-    src = open(os.path.join(ROOT, "gp_dla_detection_amd", "csrc", "gpdla.hip")).read()
+    """The model restates multi_alloc's stride; hold it to the line in csrc/host_multi.hpp."""
+    from gp_dla_detection_amd import _lib
+    src = "".join(open(path).read() for path in _lib.host_sources())
     assert "const int64_t stride = ((4 * ((b->max_pix + 3) / 4) + 4 + 15) / 16) * 16;" in src
     assert "const size_t need = (size_t)nq_sub * 2 * S * stride;" in src
     kern = open(os.path.join(ROOT, "gp_dla_detection_amd", "csrc", "sweep_multi_slim_kernel.hpp")).read()

@@ -401,9 +401,10 @@ def test_train_dims_mirror_follows_the_source():
     """The constants train_dims / train_reach restate are still the ones the library is built with."""
     import os
     import re
-    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gp_dla_detection_amd", "csrc")
+    from gp_dla_detection_amd import _lib
+    csrc =os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gp_dla_detection_amd", "csrc")
     kern = open(os.path.join(csrc, "training_mfma_kernels.hpp")).read()
-    host = open(os.path.join(csrc, "gpdla.hip")).read()
+    host = "".join(open(path).read() for path in _lib.host_sources())
     assert re.search(r"constexpr int kTrChunk = %d;" % TR_CHUNK, kern)
     assert re.search(r"constexpr int kTrBuildMaxChunks = %d;" % TR_BUILD_MAX_CHUNKS, kern)
     assert re.search(r"#define TR_WIDE_PB %d\n" % TR_WIDE_PB, kern)

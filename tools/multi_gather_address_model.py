@@ -5,7 +5,7 @@ k_sweep_multi_slim<ND> / k_sweep_multi / k_sweep_multi_split read the per-quasar
 that k_profiles wrote:
 
     prof[((ql * 2 + kind) * S + i) * stride + p]          csrc/multi_kernels.hpp:37
-    stride = ceil16(4 * ceil(max_pix / 4) + 4)             csrc/gpdla.hip, multi_alloc
+    stride = ceil16(4 * ceil(max_pix / 4) + 4)             csrc/host_multi.hpp, multi_alloc
     allocation = nq_sub * 2 * S * stride doubles           (same place)
     steps(q) = ceil(n_u(q) / 4),  n_u <= the quasar's pixel count      csrc/sweep_kernels.hpp:285
     shipped gather index:  p = min(4 * (rn + kAhead) + jj, 4 * steps + jj),  rn < steps, jj < 4
@@ -28,7 +28,7 @@ K_AHEAD = 4
 
 
 def stride_of(max_pix: int, pad: int = 0) -> int:
-    """multi_alloc (csrc/gpdla.hip): doubles per profile row; `pad`: extra entries (the abandoned build's idea)."""
+    """multi_alloc (csrc/host_multi.hpp): doubles per profile row; `pad`: extra entries (the abandoned build's idea)."""
     return ((4 * ((max_pix + 3) // 4) + 4 + pad + 15) // 16) * 16
 
 
