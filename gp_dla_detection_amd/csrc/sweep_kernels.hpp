@@ -1480,7 +1480,8 @@ __global__ __launch_bounds__(WAVES * 64) void k_sweep(SweepArgs a) {
   const int64_t slot = slot0 + s;
   const bool is_sample = slot < a.S;
   const bool is_null = !is_sample;  // slot == S is the null model; slots beyond it are idle copies
-  const int32_t sample = is_sample ? a.perm[slot] : 0;
+  // (null-model and idle slots: the last sample in z order, see k_sweep_slim)
+  const int32_t sample = a.perm[is_sample ? slot : a.S - 1];
   // process_qsos.m:162-164
   const double z_dla = m.min_z_dla + (m.max_z_dla - m.min_z_dla) * a.offset_samples[sample];
   const double nhi = a.nhi_samples[sample];

@@ -198,7 +198,10 @@ __global__ __launch_bounds__(512) void k_sweep_slim(SweepArgs a) {
   const int64_t slot = slot0 + s;
   const bool is_sample = slot < a.S;
   const bool is_null = !is_sample;  // slot == S is the null model; slots beyond it are idle copies
-  const int32_t sample = is_sample ? a.perm[slot] : 0;
+  // the null-model and idle slots evaluate the LAST sample in z order (a wave that holds them next to real samples
+  // holds that one too, or one of equal z), never input sample 0: the accurate Voigt tier is taken by a whole wave
+  // when any lane asks for it, so which tier a sample gets must depend on the samples of its wave alone
+  const int32_t sample = a.perm[is_sample ? slot : a.S - 1];
   const double z_dla = m.min_z_dla + (m.max_z_dla - m.min_z_dla) * a.offset_samples[sample];  // process_qsos.m:162-164
   const double nhi = a.nhi_samples[sample];
   [[maybe_unused]] double mult_r[3];

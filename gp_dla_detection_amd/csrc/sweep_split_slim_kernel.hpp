@@ -223,7 +223,8 @@ __global__ __launch_bounds__(512) void k_sweep_split_slim(Args a) {
     }
   } else {
     L = LINES > 0 ? LINES : a.num_lines;
-    sample = is_sample ? a.perm[slot] : 0;
+    // (null-model and idle slots: the last sample in z order, see k_sweep_slim)
+    sample = a.perm[is_sample ? slot : a.S - 1];
     const double z_dla = m.min_z_dla + (m.max_z_dla - m.min_z_dla) * a.offset_samples[sample];  // :162-164
     const double nhi = a.nhi_samples[sample];
     if (LINES > 0) {
