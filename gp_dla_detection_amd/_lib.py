@@ -127,6 +127,24 @@ class BinOutput(C.Structure):
                 ("kept_p", _dp)]
 
 
+class ModelSpectraRequest(C.Structure):
+    """gpdla_model_spectra_request"""
+    _fields_ = [("num_selected", C.c_int64), ("selection", _i64p), ("absorber_offsets", _i64p), ("absorber_z", _dp),
+                ("absorber_nhi", _dp), ("weights_source", C.c_int32), ("sample_log_likelihoods", _dp),
+                ("sub_dla", C.c_int32), ("meanflux", C.c_int32), ("products", C.c_int32), ("capacity", C.c_int64)]
+
+
+class ModelSpectra(C.Structure):
+    """gpdla_model_spectra"""
+    _fields_ = [("offsets", _i64p), ("map_absorption", _dp), ("mean_absorption", _dp), ("var_absorption", _dp),
+                ("continuum", _dp), ("model_flux", _dp), ("status", _i32p)]
+
+
+SPECTRA_MAX_ABSORBERS = 8                                   # GPDLA_SPECTRA_MAX_ABSORBERS
+SPECTRA_MAP, SPECTRA_MOMENTS, SPECTRA_CONTINUUM = 1, 2, 4   # GPDLA_SPECTRA_* product bits
+SPECTRA_WEIGHTS_NONE, SPECTRA_WEIGHTS_RESIDENT, SPECTRA_WEIGHTS_HOST = 0, 1, 2
+
+
 def ptr(a):
     """double* of a C-contiguous float64 array."""
     return a.ctypes.data_as(_dp)
@@ -191,6 +209,13 @@ SYMBOLS = [
     ("gpdla_stats_bin_posteriors", C.c_int, [C.c_int64, C.c_int64, _dp, C.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
                                              C.c_int, C.POINTER(BinRequest), C.POINTER(BinOutput), C.c_int]),
     ("gpdla_stats_poisson_binomial_cf", C.c_int, [C.c_int64, _i64p, _dp, _dp, _dp, C.c_int]),
+    ("gpdla_model_spectra_validate", C.c_int, [C.POINTER(ModelSpectraRequest), C.c_int64, C.c_int64, C.c_int]),
+    ("gpdla_batch_unmasked_counts", C.c_int, [C.c_void_p, C.c_void_p, _i64p]),
+    ("gpdla_batch_model_spectra", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(ModelSpectraRequest),
+                                            C.POINTER(ModelSpectra)]),
+    ("gpdla_debug_profiles_ms", C.c_int, [C.c_void_p, C.c_void_p, _dp]),
+    ("gpdla_model_mean", C.c_int, [C.POINTER(Model), C.c_int64, _dp, _i64p, _dp, _dp, C.c_int, C.c_int, C.c_int,
+                                   C.c_double, C.c_double, _dp, C.c_int]),
     ("gpdla_debug_near_poly", C.c_int, [C.c_int, C.c_double, _dp, _dp]),
     ("gpdla_debug_prepared_rows", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, _dp, C.c_int64, _i64p]),
     ("gpdla_debug_philox4x32_10", None, [_u32p, _u32p, _u32p]),

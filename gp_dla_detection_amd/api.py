@@ -166,6 +166,7 @@ class Context:
         if stream is not None:
             self.set_stream(stream)
         self.num_samples = 0
+        self.has_lls_samples = False
         self.k = 0
 
     def set_stream(self, stream):
@@ -186,6 +187,7 @@ class Context:
         s = _samples_struct(samples, keep)
         _lib.check(self.lib.gpdla_context_set_samples(self._h, C.byref(s)))
         self.num_samples = int(s.num_dla_samples)
+        self.has_lls_samples = samples.get("lls_nhi_samples") is not None
 
     def set_timing(self, enabled: bool):
         _lib.check(self.lib.gpdla_context_set_timing(self._h, int(bool(enabled))))
@@ -319,6 +321,83 @@ class Batch:
         _lib.check(self.ctx.lib.gpdla_debug_prepared_rows(self.ctx._h, self._h, int(bool(multi)), int(quasar),
                                                           rows.ctypes.data_as(_dp), cap, C.byref(n)))
         return rows[: n.value].copy()
+
+    # ---- model spectra ----
+
+    def unmasked_counts(self) -> np.ndarray:
+        """n_u of every quasar: the stored pixels with rest wavelength in [min_lambda, max_lambda],
+        masked or not -- the grid the per-pixel outputs of :meth:`model_spectra` live on."""
+        n = np.zeros(self.num_quasars, dtype=np.int64)
+        _lib.check(self.ctx.lib.gpdla_batch_unmasked_counts(self.ctx._h, self._h, n.ctypes.data_as(C.POINTER(C.c_int64))))
+        return n
+
+    def model_spectra(self, selection=None, absorbers=None, weights=None, sub_dla: bool = False,
+                      meanflux: bool | None = None, products=("map", "moments", "continuum")) -> dict:
+        """What the fitted model looks like on the selected quasars (gpdla_batch_model_spectra), per
+        pixel of each quasar's unmasked-range grid.
+
+        ``selection``: quasar indices of the batch (default: all, in order).
+        ``absorbers``: ``(offsets [nsel + 1], z_dlas, log_nhis)`` in CSR form, one list per SELECTED quasar
+        (what :func:`map_absorbers` returns for the same quasars), at most 8 each; None: no absorbers.
+        ``weights``: ``"resident"`` -- the batch's own sample log-likelihoods after :meth:`process` /
+        :meth:`process_multi` (multi: model DLA(1), or the sub-DLA table with ``sub_dla``) -- or a
+        host array ``[nsel, S]`` of them (a processed file needs no second sweep); None: no moments.
+        ``meanflux``: prepared rows of the mean-flux model (default: on for a multi-DLA batch).
+        ``products``: any of ``"map"`` (``map_absorption``), ``"moments"`` (``mean_absorption``,
+        ``var_absorption``), ``"continuum"`` (``continuum``, ``model_flux``: the posterior mean of the
+        low-rank part of the GP under the listed absorbers -- the pixel-diagonal omega term predicts
+        nothing at an unmeasured pixel and is left out).
+        Returns ``offsets [nsel + 1]``, ``status [nsel]`` and the flat per-pixel arrays; quasar s of the
+        selection owns ``[offsets[s], offsets[s + 1])`` (:func:`split_cells` cuts them up)."""
+        lib = self.ctx.lib
+        sel = np.arange(self.num_quasars, dtype=np.int64) if selection is None else \
+            np.ascontiguousarray(selection, dtype=np.int64).reshape(-1)
+        nsel = sel.size
+        i64p = C.POINTER(C.c_int64)
+        rq = _lib.ModelSpectraRequest()
+        rq.num_selected = nsel
+        rq.selection = sel.ctypes.data_as(i64p)
+        keep = [sel]
+        if absorbers is not None:
+            a_off, a_z, a_ln = absorbers
+            a_off = np.ascontiguousarray(a_off, dtype=np.int64).reshape(-1)
+            if a_off.size != nsel + 1:
+                raise _lib.GpdlaError(-1, f"absorber offsets: {a_off.size} entries for {nsel} selected quasars")
+            a_z, a_n = _f64(a_z)[0].reshape(-1), 10.0 ** _f64(a_ln)[0].reshape(-1)
+            keep += [a_off, a_z, a_n]
+            rq.absorber_offsets, rq.absorber_z, rq.absorber_nhi = a_off.ctypes.data_as(i64p), a_z.ctypes.data_as(_dp), a_n.ctypes.data_as(_dp)
+        bits = {"map": _lib.SPECTRA_MAP, "moments": _lib.SPECTRA_MOMENTS, "continuum": _lib.SPECTRA_CONTINUUM}
+        products = [p for p in products if not (p == "moments" and weights is None)]
+        rq.products = int(sum(bits[p] for p in set(products)))
+        if isinstance(weights, str):
+            if weights != "resident":
+                raise ValueError("weights: 'resident', an array [nsel, S] or None")
+            rq.weights_source = _lib.SPECTRA_WEIGHTS_RESIDENT
+        elif weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float64)
+            if w.shape != (nsel, self.num_samples):
+                raise _lib.GpdlaError(-1, f"weights must be [nsel, S] = {(nsel, self.num_samples)}, got {w.shape}")
+            keep.append(w)
+            rq.weights_source, rq.sample_log_likelihoods = _lib.SPECTRA_WEIGHTS_HOST, w.ctypes.data_as(_dp)
+        rq.sub_dla = int(bool(sub_dla))
+        rq.meanflux = int(bool(self.max_dlas) if meanflux is None else bool(meanflux))
+        # refused requests never reach the device
+        _lib.check(lib.gpdla_model_spectra_validate(C.byref(rq), self.num_quasars, self.num_samples,
+                                                    int(self.ctx.has_lls_samples)))
+        total = int(self.unmasked_counts()[sel].sum())
+        rq.capacity = total
+        out = {"offsets": np.zeros(nsel + 1, dtype=np.int64), "status": np.zeros(nsel, dtype=np.int32)}
+        ms = _lib.ModelSpectra()
+        ms.offsets = out["offsets"].ctypes.data_as(i64p)
+        ms.status = out["status"].ctypes.data_as(C.POINTER(C.c_int32))
+        names = {"map": ("map_absorption",), "moments": ("mean_absorption", "var_absorption"),
+                 "continuum": ("continuum", "model_flux")}
+        for p in set(products):
+            for name in names[p]:
+                out[name] = np.empty(total)
+                setattr(ms, name, out[name].ctypes.data_as(_dp))
+        _lib.check(lib.gpdla_batch_model_spectra(self.ctx._h, self._h, C.byref(rq), C.byref(ms)))
+        return out
 
     def summary_tensor(self):
         """The per-quasar summary table as a zero-copy torch tensor on this GPU: [nq, 15] for a
@@ -767,4 +846,163 @@ def process_qsos_multiple_dlas_meanflux(model: dict, samples: dict, spectra, log
         out["log_priors_lls"][:] = lp_lls
         out["log_priors_dla"][:] = lp_dla
         out["all_exceptions"][:] = np.where(out["status"] == 1, 1.0, np.nan)  # multi :139, :232
+    return out
+
+
+# ----------------------------------------------------------------------------------------------
+# model spectra
+# ----------------------------------------------------------------------------------------------
+
+MODEL_SPECTRA_ARRAYS = ("map_absorption", "mean_absorption", "var_absorption", "continuum", "model_flux")
+
+
+def split_cells(flat, offsets) -> list:
+    """A flat CSR array as one view per quasar."""
+    o = np.asarray(offsets, dtype=np.int64)
+    return [flat[o[i]:o[i + 1]] for i in range(o.size - 1)]
+
+
+def map_absorbers(results: dict, sub_dla: bool = True):
+    """The absorbers of each quasar's most probable model, from the saved results, as the CSR triple
+    ``(offsets [nq + 1], z_dlas, log_nhis)`` that :meth:`Batch.model_spectra` and
+    :func:`dla_model_mean` take.
+
+    Multi-DLA results (``model_posteriors [nq, 1 + sub_dla + max_dlas]``, ``MAP_z_dlas`` /
+    ``MAP_log_nhis [nq, model, slot]``) follow the reference's QSOLoader: ``nth = argmax(model_posteriors)
+    - 1 - sub_dla`` (qso_loader.py:1695); ``nth >= 0`` selects slots ``0 .. nth`` of model ``nth``
+    (:285-301, :1698-1699).  ``sub_dla``: the posteriors carry a sub-DLA column after the null model
+    (the multi-DLA driver's always do); a sub-DLA or null winner has no absorbers.  Single-DLA results
+    (``model_posteriors [nq, 2]``) give ``MAP_z_dlas`` / ``MAP_log_nhis`` where p_dla wins (:1700-1704).
+    A quasar whose posteriors are all NaN has none; a NaN slot of a chosen model is dropped."""
+    mp = np.asarray(results["model_posteriors"], dtype=np.float64)
+    nq = mp.shape[0]
+    map_z = np.asarray(results["MAP_z_dlas"], dtype=np.float64)
+    map_n = np.asarray(results["MAP_log_nhis"], dtype=np.float64)
+    single = mp.shape[1] == 2 and map_z.ndim == 1
+    shift = 1 if single else 1 + int(bool(sub_dla))
+    z_out, n_out, offsets = [], [], np.zeros(nq + 1, dtype=np.int64)
+    for i in range(nq):
+        row = mp[i]
+        if not np.isnan(row).all():
+            nth = int(np.nanargmax(row)) - shift
+            if nth >= 0:
+                z, n = (map_z[i:i + 1], map_n[i:i + 1]) if single else (map_z[i, nth, :nth + 1], map_n[i, nth, :nth + 1])
+                ok = np.isfinite(z) & np.isfinite(n)
+                z_out.append(z[ok])
+                n_out.append(n[ok])
+        offsets[i + 1] = sum(a.size for a in z_out)
+    cat = lambda parts: np.concatenate(parts) if parts else np.zeros(0)  # noqa: E731
+    return offsets, cat(z_out), cat(n_out)
+
+
+def _take_absorbers(absorbers, idx):
+    """The CSR lists of quasars ``idx`` out of a CSR triple."""
+    off, z, n = absorbers
+    off = np.asarray(off, dtype=np.int64)
+    parts = [np.arange(off[i], off[i + 1]) for i in idx]
+    take = np.concatenate(parts) if parts else np.zeros(0, dtype=np.int64)
+    new = np.zeros(len(parts) + 1, dtype=np.int64)
+    np.cumsum([p.size for p in parts], out=new[1:])
+    return new, np.asarray(z, dtype=np.float64)[take], np.asarray(n, dtype=np.float64)[take]
+
+
+def model_spectra(model: dict, samples: dict, spectra, results: dict | None = None,
+                  params: Parameters | None = None, selection=None, absorbers="map", sub_dla: bool | None = None,
+                  moments_sub_dla: bool = False, products=("map", "moments", "continuum"), sample_rows=None,
+                  device: int = 0, max_quasars_per_batch: int | None = None) -> dict:
+    """Model spectra of the selected quasars of a processed run, batched like :func:`process_qsos`:
+    the selected spectra are uploaded block by block and nothing is swept again -- the posterior
+    weights come from the saved sample log-likelihoods.
+
+    ``spectra``: the list of per-quasar dicts the run processed; ``results``: what it returned (or
+    :func:`io.load_processed_qsos` of its file); ``params``: a :class:`MultiParameters` makes the
+    batches multi-DLA ones (mean-flux model).  ``selection``: indices into ``spectra`` (default all).
+    ``absorbers``: ``"map"`` (:func:`map_absorbers` of ``results``), a CSR triple over ALL quasars of
+    ``spectra``, or None.  ``sub_dla``: whether the posteriors carry a sub-DLA column (default: they do
+    for multi-DLA results).  Moments weight the DLA(1) table ``sample_log_likelihoods_dla`` (``[nq, S]``,
+    or ``[nq, max_dlas, S]``), or ``sample_log_likelihoods_lls`` with ``moments_sub_dla``;
+    ``sample_rows(idx) -> [len(idx), S]`` supplies the rows instead (a file streamed block by block).
+    Returns ``selection``, ``offsets``, ``status`` and the flat per-pixel arrays of
+    :meth:`Batch.model_spectra`, in selection order; results do not depend on the batching."""
+    p = params or Parameters()
+    multi = isinstance(p, MultiParameters)
+    spectra = list(spectra)
+    sel = np.arange(len(spectra), dtype=np.int64) if selection is None else np.asarray(selection, dtype=np.int64).reshape(-1)
+    products = tuple(products)
+    if isinstance(absorbers, str):
+        if absorbers != "map":
+            raise ValueError("absorbers: 'map', a CSR triple or None")
+        if results is None:
+            raise ValueError("absorbers='map' needs results")
+        absorbers = map_absorbers(results, sub_dla=multi if sub_dla is None else sub_dla)
+    if "moments" in products and sample_rows is None:
+        if results is None:
+            raise ValueError("moments need results or sample_rows")
+        table = np.asarray(results["sample_log_likelihoods_lls" if moments_sub_dla else "sample_log_likelihoods_dla"])
+        sample_rows = (lambda idx: table[idx]) if table.ndim == 2 else (lambda idx: table[idx, 0, :])
+    S = np.asarray(samples["offset_samples"]).size
+    longest = max([np.asarray(spectra[i]["wavelengths"]).size for i in sel], default=1)
+    per = int(max_quasars_per_batch or default_batch_size(sel.size, longest, np.asarray(model["M"]).shape[1], S, 1))
+    out = {"selection": sel, "offsets": np.zeros(sel.size + 1, dtype=np.int64), "status": np.zeros(sel.size, dtype=np.int32)}
+    parts = {}
+    if sel.size:
+        ctx = Context(device, p)
+        batch = None
+        try:
+            ctx.set_model(model)
+            ctx.set_samples(samples)
+            md = p.max_dlas if multi else 0
+            for lo, hi in batch_blocks(sel.size, per):
+                idx = sel[lo:hi]
+                n = idx.size
+                args = ([spectra[i] for i in idx], np.zeros(n), np.zeros((n, md)) if multi else np.zeros(n),
+                        np.zeros(n) if multi else None)
+                if batch is None:
+                    batch = ctx.upload(*args)
+                else:
+                    batch.reload(*args)
+                res = batch.model_spectra(absorbers=None if absorbers is None else _take_absorbers(absorbers, idx),
+                                          weights=np.asarray(sample_rows(idx), dtype=np.float64) if "moments" in products else None,
+                                          sub_dla=moments_sub_dla, products=products)
+                out["offsets"][lo + 1:hi + 1] = out["offsets"][lo] + res["offsets"][1:]
+                out["status"][lo:hi] = res["status"]
+                for name in MODEL_SPECTRA_ARRAYS:
+                    if name in res:
+                        parts.setdefault(name, []).append(res[name])
+        finally:
+            if batch is not None:
+                batch.close()
+            ctx.close()
+    for name, ps in parts.items():
+        out[name] = np.concatenate(ps)
+    return out
+
+
+def dla_model_mean(model: dict, z_qsos, absorbers=None, suppressed: bool = True, num_voigt_lines: int = 3,
+                   num_forest_lines: int = 31, prev_tau_0: float = 0.0023, prev_beta: float = 3.65,
+                   device: int = 0) -> np.ndarray:
+    """The reference's ``this_mu`` (QSOLoader.plot_this_mu, qso_loader.py:1685-1711) as data on the
+    model's rest grid: ``mu`` x (``suppressed``) ``total_scale_factor`` (:1777-1822) x the RAW Voigt
+    profiles of each quasar's absorbers at ``rest_wavelengths (1 + z_qso)``.  ``absorbers``: the CSR
+    triple ``(offsets [nq + 1], z_dlas, log_nhis)`` of :func:`map_absorbers`, or None.  Returns
+    ``[len(z_qsos), G]``."""
+    lib = _lib.load()
+    z, zp = _f64(np.atleast_1d(z_qsos))
+    keep = []
+    m = _lib.Model()
+    rw, rwp = _f64(model["rest_wavelengths"])
+    mu, mup = _f64(model["mu"])
+    m.num_rest_pixels, m.k, m.rest_wavelengths, m.mu = rw.size, 0, rwp, mup
+    offp = azp = anp = None
+    if absorbers is not None:
+        off = np.ascontiguousarray(absorbers[0], dtype=np.int64).reshape(-1)
+        if off.size != z.size + 1:
+            raise _lib.GpdlaError(-1, f"absorber offsets: {off.size} entries for {z.size} quasars")
+        az, an = _f64(absorbers[1])[0].reshape(-1), 10.0 ** _f64(absorbers[2])[0].reshape(-1)
+        keep += [off, az, an]
+        offp, azp, anp = off.ctypes.data_as(C.POINTER(C.c_int64)), az.ctypes.data_as(_dp), an.ctypes.data_as(_dp)
+    out = np.empty((z.size, rw.size))
+    _lib.check(lib.gpdla_model_mean(C.byref(m), z.size, zp, offp, azp, anp, int(num_voigt_lines), int(num_forest_lines),
+                                    int(bool(suppressed)), float(prev_tau_0), float(prev_beta),
+                                    out.ctypes.data_as(_dp), int(device)))
     return out

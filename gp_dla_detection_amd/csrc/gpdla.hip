@@ -32,6 +32,7 @@
 #include "sweep_split_slim_kernel.hpp"
 #include "learn_kernels.hpp"
 #include "stats_kernels.hpp"
+#include "spectra_kernels.hpp"
 #include "training_kernels.hpp"
 #include "training_mfma_kernels.hpp"
 
@@ -45,5 +46,6 @@ using namespace gpdla;
 #include "host_training.hpp"
 #include "host_learn.hpp"
 #include "host_stats.hpp"
+#include "host_spectra.hpp"
 // libgpdla_legacy.so (-DGPDLA_WITH_LEGACY): the superseded kernels and their environment switches
 #include "host_legacy.hpp"

@@ -77,6 +77,7 @@ struct gpdla_batch {
   // multi-DLA batch (uploaded with log_priors_lls): result tables, allocated by the first
   // gpdla_batch_process_multi and kept for the life of the batch
   int32_t md = 0;  // max_dlas the priors were uploaded for; 0 = single-DLA batch
+  bool processed = false;  // single-DLA batch: gpdla_batch_process has run on the current spectra
   struct MultiBuffers *mb = nullptr;
 };
 
@@ -418,6 +419,7 @@ int batch_fill(gpdla_context *c, gpdla_batch *b, const gpdla_spectra *sp, int md
   b->h_recs.resize((size_t)nq);
   for (int64_t q = 0; q < nq; ++q) b->h_recs[q] = (off[q + 1] - off[q] + 3) / 4 + 1;
   b->plan_budget = -1;  // the record plan is remade by the next process call
+  b->processed = false;
   if (b->md != md) {  // (reload with a different kind of batch)
     delete b->mb;
     b->mb = nullptr;

@@ -259,6 +259,7 @@ int gpdla_batch_process(gpdla_context *c, gpdla_batch *b) try {
   hipLaunchKernelGGL(k_evidence, dim3((unsigned)b->nq), dim3(256), 0, st, ea);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(b->ev_done, st));
+  b->processed = true;
   return GPDLA_OK;
 } GPDLA_NO_THROW
 

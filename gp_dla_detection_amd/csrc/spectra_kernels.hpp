@@ -1,0 +1,516 @@
+// spectra_kernels.hpp -- device side of the "model spectra" subsystem: what the
+// fitted model looks like on a spectrum, per pixel of the quasar's unmasked-range grid (the n_u
+// stored pixels with rest wavelength in [min_lambda, max_lambda], masked or not -- the grid
+// k_prepare lays out and the Voigt stage of every sweep walks).
+//
+//   k_spectra_map        process_qsos.m:187-190 (multi :342-351)  product of the instrument-broadened
+//                                                 Voigt profiles of a list of absorbers        (P1)
+//   k_spectra_weights    posterior weights of the S samples of a quasar from a row of sample
+//                        log-likelihoods: w_i = exp(l_i - max l) / Sum                           (P2)
+//   k_spectra_moments    Sum_i w_i (1 - a_i(p)) and Sum_i w_i (1 - a_i(p))^2 over 256 samples of a
+//                        quasar, a_i the broadened profile of sample i -- the hot kernel         (P2)
+//   k_spectra_combine    the chunks of k_spectra_moments in chunk order -> mean, variance        (P2)
+//   k_spectra_continuum  GP posterior mean of the low-rank continuum under a chosen absorption  (P3)
+//   k_spectra_model_mean qso_loader.py:1685-1711: mu x mean-flux suppression x raw profiles on the
+//                        model's rest grid                                                       (P4)
+//
+// Every sum runs in a fixed order and nothing is accumulated with atomics: outputs are bit-identical
+// from run to run and depend on their own quasar only.
+#pragma once
+#include "multi_kernels.hpp"
+
+namespace gpdla {
+
+constexpr int kSpectraMaxAbsorbers = 8;
+
+// voigt.c:278-291 at one wavelength, with the arithmetic of k_voigt_raw (gpdla_voigt's tiers).
+__device__ __forceinline__ double spectra_raw_at(double lambda, double z, double N, int num_lines) {
+  double total = 0.0;
+  for (int j = 0; j < num_lines; ++j) {
+    const double mult = g_lines.c / (g_lines.wavelength_cm[j] * (1 + z)) / 1e8;  // voigt.c:279
+    const double velocity = lambda * mult - g_lines.c;                           // voigt.c:287
+    const double v = rew_full(velocity * g_lines.inv_sqrt2_sigma, g_lines.y[j]) * g_lines.inv_sqrt2pi_sigma;
+    total += -g_lines.leading[j] * v;                                            // voigt.c:288
+  }
+  return exp(N * total);                                                         // voigt.c:291
+}
+
+// multi :267-285 at one observed wavelength (the arithmetic of k_prepare): exp(-Sum_l tau_l (1 + z_l)^beta)
+__device__ __forceinline__ double spectra_mean_flux(double wl, double z_qso, double lya_wavelength, double prev_tau_0,
+                                                    double prev_beta, int num_forest_lines) {
+  const double f_1 = g_lines.osc[0];
+  double total = 0.0;
+  for (int l = 0; l < num_forest_lines; ++l) {
+    const double wl_l = g_lines.wavelength_cm[l] * 1e8;
+    const double z_l = (wl - wl_l) / wl_l;                                       // multi :184-186
+    const double tau_l = prev_tau_0 * g_lines.osc[l] / f_1 * wl_l / lya_wavelength;
+    const double od = tau_l * pow(1 + z_l, prev_beta);                           // multi :275-276
+    if (l > 0 && z_l > z_qso) continue;                                          // multi :279-282
+    total += od;
+  }
+  return exp(-total);                                                            // multi :285
+}
+
+// ------------------------------------------------------------------------------------------
+// k_spectra_map: one block per selected quasar.  A tile of 250 output pixels needs 256 raw values;
+// each thread evaluates one, the block broadens (voigt.c:297-299, taps in ascending order like
+// k_voigt_broaden) and multiplies the absorbers in list order.  A quasar without a kept pixel has
+// no padded grid (k_prepare writes the six padding wavelengths only then): its row is NaN.
+// ------------------------------------------------------------------------------------------
+struct SpectraMapArgs {
+  const QuasarMeta *meta;
+  const double *lam_pad;
+  const int64_t *sel;       // [nsel] quasar of the batch
+  const int64_t *abs_off;   // [nsel + 1] into abs_z / abs_n, or nullptr: no absorbers anywhere
+  const double *abs_z, *abs_n;
+  const int64_t *out_off;   // [nsel + 1]
+  int32_t num_lines;
+  double *out;
+};
+
+constexpr int kMapTile = 250;
+
+__global__ __launch_bounds__(256) void k_spectra_map(SpectraMapArgs a) {
+  __shared__ double s_raw[256];
+  const int s = blockIdx.x, tid = threadIdx.x;
+  const QuasarMeta m = a.meta[a.sel[s]];
+  const double *lam = a.lam_pad + m.lam_off;
+  double *out = a.out + a.out_off[s];
+  const int64_t j0 = a.abs_off ? a.abs_off[s] : 0, j1 = a.abs_off ? a.abs_off[s + 1] : 0;
+  const int n_pad = m.n_u + 6;
+  for (int t0 = 0; t0 < m.n_u; t0 += kMapTile) {
+    double prod = 1.0;
+    for (int64_t j = j0; j < j1; ++j) {
+      const int P = t0 + tid;
+      if (P < n_pad) s_raw[tid] = spectra_raw_at(lam[P], a.abs_z[j], a.abs_n[j], a.num_lines);
+      __syncthreads();
+      if (tid < kMapTile && P < m.n_u) {
+        double acc = 0.0;
+        for (int kk = 0; kk < 7; ++kk) acc += s_raw[tid + kk] * g_lines.taps[kk];
+        prod = (j == j0) ? acc : prod * acc;
+      }
+      __syncthreads();
+    }
+    if (tid < kMapTile && t0 + tid < m.n_u) out[t0 + tid] = m.n_kept > 0 ? prod : NAN;
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// k_spectra_weights: one block per selected quasar.  Row s of sample log-likelihoods starts at
+// table + row_start[s].  w_i = exp(l_i - max l) / Sum_j exp(l_j - max l); a NaN l_i weighs 0.
+// flag[s] = 1 when no entry is above -inf (an all-NaN row, or a quasar whose log-likelihoods are all
+// -inf): its outputs are NaN.
+// ------------------------------------------------------------------------------------------
+struct SpectraWeightsArgs {
+  const double *table;
+  const int64_t *row_start;  // [nsel]
+  int64_t S;
+  double *w;                 // [nsel][S]
+  int32_t *flag;             // [nsel]
+};
+
+__global__ __launch_bounds__(256) void k_spectra_weights(SpectraWeightsArgs a) {
+  __shared__ double s_red[4];
+  const int s = blockIdx.x, tid = threadIdx.x;
+  const double *row = a.table + a.row_start[s];
+  double *w = a.w + (int64_t)s * a.S;
+  double mx = -INFINITY;
+  for (int64_t i = tid; i < a.S; i += 256) mx = fmax(mx, row[i]);  // (fmax returns the other operand for a NaN)
+  mx = block_reduce_minmax(mx, false, s_red);
+  const bool none = !(mx > -INFINITY) || mx == INFINITY;
+  double sum = 0.0;
+  for (int64_t i = tid; i < a.S; i += 256) {
+    const double l = row[i];
+    const double e = (l == l) ? exp(l - mx) : 0.0;
+    w[i] = e;
+    sum += e;
+  }
+  sum = block_reduce_sum(sum, s_red);
+  for (int64_t i = tid; i < a.S; i += 256) w[i] = none ? 0.0 : w[i] / sum;
+  if (tid == 0) a.flag[s] = none ? 1 : 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// k_spectra_moments: the Voigt stage of k_profiles -- one LANE per sample, 64 neighbours in z_DLA
+// per wave walking the padded pixels in lockstep, seven raw values in registers for the instrument
+// broadening, the accurate tier taken by whole waves -- with the store of the profile replaced by
+// its reduction.  A block is four waves = 256 consecutive samples (in z_DLA order) of one quasar.
+// Per tile of 16 pixels a wave transposes its 64 x 16 broadened values through LDS; lane (g, t) =
+// (lane >> 4, lane & 15) then adds rows 4 e + g, e = 0 .. 15, of pixel t in that order, the four g
+// are combined as (g0 + g1) + (g2 + g3), the four waves in wave order, and the block writes its
+// two partial sums per pixel.  What is summed is the absorbed fraction b = 1 - a, not a: where the
+// profiles are ~1 the moments then keep their relative accuracy.  No per-sample profile reaches HBM.
+// part[((sl * chunks + chunk) * 2 + moment) * stride + p]
+// ------------------------------------------------------------------------------------------
+struct SpectraMomentsArgs {
+  const QuasarMeta *meta;
+  const double *lam_pad;
+  const double *offset_samples, *nhi;  // nhi: nhi_samples, or lls_nhi_samples for the sub-DLA model
+  const int32_t *perm;
+  const int64_t *sel;   // [nsel]; this launch takes sel[s0 .. s0 + nsub)
+  const double *w;      // [nsel][S]
+  int64_t S;
+  int32_t num_lines;
+  int64_t s0;
+  int32_t chunks;       // ceil(S / 256): blocks per quasar
+  int64_t stride;       // >= n_u of every selected quasar
+  double *part;
+};
+
+constexpr int kMomWaves = 4;
+
+__global__ __launch_bounds__(kMomWaves * 64) void k_spectra_moments(SpectraMomentsArgs a) {
+  __shared__ double s_exp[kExpTab];
+  __shared__ double s_out[kMomWaves][64][kProfTile + 1];
+  __shared__ double s_w[kMomWaves][64];
+  __shared__ double s_part[2][kMomWaves][2][kProfTile];
+
+  for (int e = threadIdx.x; e < kExpTab; e += kMomWaves * 64) s_exp[e] = exp2((double)e * (1.0 / kExpTab));
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int64_t sl = blockIdx.x / a.chunks;       // selected quasar of this launch
+  const int chunk = blockIdx.x - sl * a.chunks;
+  const int64_t s = a.s0 + sl;
+  const QuasarMeta m = a.meta[a.sel[s]];
+  if (m.status != 0) return;  // (the whole block: no sample redshifts; k_spectra_combine writes NaN)
+  const int L = a.num_lines;
+  const int64_t pos = (int64_t)chunk * (kMomWaves * 64) + wave * 64 + lane;
+  const bool live = pos < a.S;
+  const int64_t i = a.perm[live ? pos : a.S - 1];
+  s_w[wave][lane] = live ? a.w[s * a.S + i] : 0.0;
+  __syncthreads();
+  const double z_dla = m.min_z_dla + (m.max_z_dla - m.min_z_dla) * a.offset_samples[i];
+  const double c_light = g_lines.c, inv_s = g_lines.inv_sqrt2_sigma;
+  double mult[3], ms[3];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    mult[j] = g_lines.c / (g_lines.wavelength_cm[j] * (1 + z_dla)) / 1e8;  // voigt.c:278-279
+    ms[j] = mult[j] * inv_s;
+  }
+  const double cs = c_light * inv_s;
+  const double inv_opz = 1.0 / (1 + z_dla);
+  const double nscale = -a.nhi[i] * g_lines.inv_sqrt2pi_sigma * kInvSqrtPi * kExpScale;
+  const double *lam = a.lam_pad + m.lam_off;
+  const int n_pad = m.n_u + 6;
+  const double t0 = g_lines.taps[0], t1 = g_lines.taps[1], t2 = g_lines.taps[2], t3 = g_lines.taps[3],
+               t4 = g_lines.taps[4], t5 = g_lines.taps[5], t6 = g_lines.taps[6];
+
+  auto raw = [&](int P) -> double {  // voigt.c:282-291 for this lane's sample at padded pixel P (as k_profiles)
+    const double lamP = lam[min(P, n_pad - 1)];  // wave-uniform address
+    double total;
+    bool near = false;
+    if (L == 3) total = wing_sum3(lamP, ms[0], ms[1], ms[2], cs, &near);
+    else total = wing_sum_runtime(lamP * inv_opz, cs, L, &near);
+    if (__any(near)) {  // accurate tier, wave-uniformly
+      if (L == 3) {
+        total = 0.0;
+        for (int j = 0; j < 3; ++j) {
+          const double ax = fabs((lamP * mult[j] - c_light) * inv_s);
+          total += ax < 30.0 ? 1.7724538509055159 * g_lines.leading[j] *
+                                   near_poly(g_lines.near_poly + j * kNearLineDoubles, ax)
+                             : g_lines.cwing[j] * wing_core(ax * ax, g_lines.y2[j]);
+        }
+      } else {
+        total = total_near_at(lamP, 1 + z_dla, L);
+      }
+    }
+    return exp_table_scaled(nscale * total, s_exp);
+  };
+
+  // the 16 weights of the rows this lane adds up (rows 4 e + g)
+  const int g = lane >> 4, tt = lane & 15;
+  double wr[16];
+#pragma unroll
+  for (int e = 0; e < 16; ++e) wr[e] = s_w[wave][4 * e + g];
+
+  double a0 = raw(0), a1 = raw(1), a2 = raw(2), a3 = raw(3), a4 = raw(4), a5 = raw(5), a6;
+  double *part = a.part + ((sl * a.chunks + chunk) * 2) * a.stride;
+  int buf = 0;
+  for (int p0 = 0; p0 < m.n_u; p0 += kProfTile, buf ^= 1) {
+#pragma unroll
+    for (int u = 0; u < kProfTile; ++u) {
+      a6 = raw(p0 + u + 6);
+      double acc = a0 * t0;  // voigt.c:297-299, taps in ascending order
+      acc = fma(a1, t1, acc);
+      acc = fma(a2, t2, acc);
+      acc = fma(a3, t3, acc);
+      acc = fma(a4, t4, acc);
+      acc = fma(a5, t5, acc);
+      acc = fma(a6, t6, acc);
+      s_out[wave][lane][u] = acc;
+      a0 = a1; a1 = a2; a2 = a3; a3 = a4; a4 = a5; a5 = a6;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    double m1 = 0.0, m2 = 0.0;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      const double b = 1.0 - s_out[wave][4 * e + g][tt];
+      const double t = wr[e] * b;
+      m1 += t;
+      m2 = fma(t, b, m2);
+    }
+    m1 += __shfl_xor(m1, 16);
+    m2 += __shfl_xor(m2, 16);
+    m1 += __shfl_xor(m1, 32);
+    m2 += __shfl_xor(m2, 32);
+    if (lane < kProfTile) {
+      s_part[buf][wave][0][lane] = m1;
+      s_part[buf][wave][1][lane] = m2;
+    }
+    // one barrier a tile: s_part is double-buffered (wave 0 reads buffer `buf` of tile t while the
+    // other waves can at most be writing buffer `buf ^ 1` of tile t + 1), and it also orders this
+    // wave's reads of s_out before its writes of the next tile
+    __syncthreads();
+    if (threadIdx.x < 2 * kProfTile) {
+      const int mom = threadIdx.x >> 4, t = threadIdx.x & 15;
+      double sum = s_part[buf][0][mom][t];
+#pragma unroll
+      for (int w = 1; w < kMomWaves; ++w) sum += s_part[buf][w][mom][t];
+      if (p0 + t < m.n_u) part[mom * a.stride + p0 + t] = sum;
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// k_spectra_combine: one block per selected quasar of a launch of k_spectra_moments; the chunks in
+// chunk order.  mean = 1 - Sum w b, var = Sum w b^2 - (Sum w b)^2 (never negative).
+// ------------------------------------------------------------------------------------------
+struct SpectraCombineArgs {
+  const QuasarMeta *meta;
+  const int64_t *sel;
+  const int32_t *flag;
+  const int64_t *out_off;
+  const double *part;
+  int64_t s0;
+  int32_t chunks;
+  int64_t stride;
+  double *mean, *var;
+};
+
+__global__ __launch_bounds__(256) void k_spectra_combine(SpectraCombineArgs a) {
+  const int64_t sl = blockIdx.x, s = a.s0 + sl;
+  const QuasarMeta m = a.meta[a.sel[s]];
+  const bool none = m.status != 0 || a.flag[s] != 0;
+  const double *part = a.part + (sl * a.chunks * 2) * a.stride;
+  double *mean = a.mean + a.out_off[s], *var = a.var + a.out_off[s];
+  for (int p = threadIdx.x; p < m.n_u; p += 256) {
+    double m1 = 0.0, m2 = 0.0;
+    if (!none)
+      for (int c = 0; c < a.chunks; ++c) {
+        m1 += part[(2 * c) * a.stride + p];
+        m2 += part[(2 * c + 1) * a.stride + p];
+      }
+    mean[p] = none ? NAN : 1.0 - m1;
+    var[p] = none ? NAN : fmax(m2 - m1 * m1, 0.0);
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// k_spectra_continuum: one block per selected quasar.  With the prepared rows of k_prepare (y, mu, M,
+// omega2, nu; a masked pixel is the neutral row y = mu = omega2 = 0, nu = 1, M = 0 and drops out of
+// every sum) and a = the absorption on the grid (nullptr: ones, the null model):
+//   d = a^2 omega2 + nu,  r = y - a mu,  B = I + M' diag(a^2 / d) M,  c = B^-1 M' (a r / d)
+// which is the posterior mean of the coefficients of the low-rank part of the covariance
+// (log_mvnpdf_low_rank.m's B and its right-hand side, solved instead of folded into the
+// likelihood).  continuum = mu + M c is evaluated at ALL n_u pixels -- a masked pixel's mu and M row
+// are interpolated here as k_prepare interpolates a kept one -- and model_flux = a continuum.  The
+// pixel-diagonal omega term has no posterior mean away from the pixel that measured it and is left
+// out.  B not positive definite: NaN rows and status 4.
+// ------------------------------------------------------------------------------------------
+struct SpectraContinuumArgs {
+  const QuasarMeta *meta;
+  const PixelRow *pix;
+  const double *Mi;
+  const double *lam_pad;
+  const double *z_qsos;
+  const int64_t *sel;
+  const int64_t *out_off;
+  const double *absorption;  // on the output layout, or nullptr
+  ModelDev model;
+  double lya_wavelength, prev_tau_0, prev_beta;
+  int32_t meanflux, num_forest_lines;
+  double *continuum, *model_flux;  // either may be nullptr
+  int32_t *status;                 // [nsel]
+};
+
+constexpr int kContTile = 128;
+
+__global__ __launch_bounds__(256) void k_spectra_continuum(SpectraContinuumArgs a) {
+  constexpr int kNb = GPDLA_MAX_K * (GPDLA_MAX_K + 1) / 2;
+  __shared__ double s_B[kNb + GPDLA_MAX_K];  // packed lower triangle of B, then v (then c)
+  __shared__ double s_wt[kContTile], s_ut[kContTile];
+  __shared__ double s_piv;
+  __shared__ int s_pd;
+  const int s = blockIdx.x, tid = threadIdx.x;
+  const int64_t q = a.sel[s];
+  const QuasarMeta m = a.meta[q];
+  const int k = a.model.k, G = a.model.G, nb = k * (k + 1) / 2;
+  const PixelRow *pix = a.pix + m.pix_off;
+  const double *Mi = a.Mi + m.pix_off * k;
+  const double *absn = a.absorption ? a.absorption + a.out_off[s] : nullptr;
+  double *cont = a.continuum ? a.continuum + a.out_off[s] : nullptr;
+  double *flux = a.model_flux ? a.model_flux + a.out_off[s] : nullptr;
+  if (m.status != 0) {  // no kept pixel, or a kept pixel of unusable noise variance: nothing to condition on
+    for (int p = tid; p < m.n_u; p += 256) {
+      if (cont) cont[p] = NAN;
+      if (flux) flux[p] = NAN;
+    }
+    if (tid == 0) a.status[s] = m.status;
+    return;
+  }
+  // the entries of [vech(B) | v] this thread accumulates (at most 4 for k = 40), as (i, j); j < 0: v_i
+  constexpr int kMine = (kNb + GPDLA_MAX_K + 255) / 256;
+  int ei[kMine], ej[kMine];
+  double acc[kMine];
+#pragma unroll
+  for (int t = 0; t < kMine; ++t) {
+    const int e = tid + 256 * t;
+    acc[t] = 0.0;
+    ei[t] = ej[t] = -1;
+    if (e < nb) {
+      int i = (int)((sqrt(8.0 * e + 1.0) - 1.0) * 0.5);
+      while ((i + 1) * (i + 2) / 2 <= e) ++i;
+      while (i * (i + 1) / 2 > e) --i;
+      ei[t] = i;
+      ej[t] = e - i * (i + 1) / 2;
+    } else if (e < nb + k) {
+      ei[t] = e - nb;
+    }
+  }
+  for (int p0 = 0; p0 < m.n_u; p0 += kContTile) {
+    if (tid < kContTile) {
+      const int p = p0 + tid;
+      double wt = 0.0, ut = 0.0;
+      if (p < m.n_u) {
+        const PixelRow row = pix[p];
+        const double ab = absn ? absn[p] : 1.0;
+        const double d = ab * ab * row.omega2 + row.nu;
+        const double r = row.y - ab * row.mu;
+        wt = ab * ab / d;
+        ut = ab * r / d;
+      }
+      s_wt[tid] = wt;
+      s_ut[tid] = ut;
+    }
+    __syncthreads();
+    const int np = min(kContTile, m.n_u - p0);
+#pragma unroll
+    for (int t = 0; t < kMine; ++t) {
+      if (ei[t] < 0) continue;
+      const double *Mp = Mi + (int64_t)p0 * k;
+      double sum = acc[t];
+      if (ej[t] >= 0)
+        for (int p = 0; p < np; ++p) sum = fma(Mp[p * k + ei[t]] * s_wt[p], Mp[p * k + ej[t]], sum);
+      else
+        for (int p = 0; p < np; ++p) sum = fma(Mp[p * k + ei[t]], s_ut[p], sum);
+      acc[t] = sum;
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int t = 0; t < kMine; ++t)
+    if (ei[t] >= 0) s_B[tid + 256 * t] = acc[t] + ((ej[t] == ei[t]) ? 1.0 : 0.0);
+  if (tid == 0) s_pd = 1;
+  __syncthreads();
+  // Cholesky of the packed lower triangle, column by column (as k_lowrank_single)
+  double *v = s_B + nb;
+  for (int j = 0; j < k; ++j) {
+    const int rj = j * (j + 1) / 2;
+    __syncthreads();
+    if (tid == 0) {
+      double sum = s_B[rj + j];
+      for (int mm = 0; mm < j; ++mm) sum = fma(-s_B[rj + mm], s_B[rj + mm], sum);
+      if (!(sum > 0.0)) s_pd = 0;
+      const double ljj = sqrt(sum);
+      s_B[rj + j] = ljj;
+      s_piv = ljj;
+    }
+    __syncthreads();
+    const double ljj = s_piv;
+    for (int i = j + 1 + tid; i < k; i += 256) {
+      const int ri = i * (i + 1) / 2;
+      double sum = s_B[ri + j];
+      for (int mm = 0; mm < j; ++mm) sum = fma(-s_B[ri + mm], s_B[rj + mm], sum);
+      s_B[ri + j] = sum / ljj;
+    }
+  }
+  __syncthreads();
+  if (tid == 0) {  // c = L'^-1 L^-1 v
+    for (int i = 0; i < k; ++i) {
+      const int ri = i * (i + 1) / 2;
+      double zi = v[i];
+      for (int mm = 0; mm < i; ++mm) zi = fma(-s_B[ri + mm], v[mm], zi);
+      v[i] = zi / s_B[ri + i];
+    }
+    for (int i = k - 1; i >= 0; --i) {
+      double ci = v[i];
+      for (int mm = i + 1; mm < k; ++mm) ci = fma(-s_B[mm * (mm + 1) / 2 + i], v[mm], ci);
+      v[i] = ci / s_B[i * (i + 1) / 2 + i];
+    }
+    a.status[s] = s_pd ? 0 : 4;
+  }
+  __syncthreads();
+  const bool pd = s_pd != 0;
+  // mu + M c on the whole grid: the interpolation of k_prepare (process_qsos.m:138-139, multi :287-288)
+  const double *lam = a.lam_pad + m.lam_off + 3;
+  const double z_qso = a.z_qsos[q];
+  for (int p = tid; p < m.n_u; p += 256) {
+    const double wl = lam[p];
+    const double rest = wl / (1 + z_qso);
+    int lo = 0, hi = G - 1;
+    if (rest >= a.model.rest[G - 1]) lo = G - 2;
+    else if (rest > a.model.rest[0]) {
+      while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (a.model.rest[mid] <= rest) lo = mid; else hi = mid;
+      }
+    }
+    const double t = (rest - a.model.rest[lo]) / (a.model.rest[lo + 1] - a.model.rest[lo]);
+    const double mf = a.meanflux ? spectra_mean_flux(wl, z_qso, a.lya_wavelength, a.prev_tau_0, a.prev_beta, a.num_forest_lines)
+                                 : 1.0;
+    double val = a.model.mu[lo] + (a.model.mu[lo + 1] - a.model.mu[lo]) * t;
+    if (a.meanflux) val = val * mf;
+    for (int c = 0; c < k; ++c) {
+      const double m0 = a.model.M[lo + (int64_t)c * G], m1 = a.model.M[lo + 1 + (int64_t)c * G];
+      val = fma((m0 + (m1 - m0) * t) * mf, v[c], val);
+    }
+    if (!pd) val = NAN;
+    if (cont) cont[p] = val;
+    if (flux) flux[p] = (absn ? absn[p] : 1.0) * val;
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// k_spectra_model_mean: qso_loader.py:1685-1711 as data.  Item it, grid point g:
+//   mu[g] x (suppressed: total_scale_factor at rest[g] (1 + z_qso), :1777-1822)
+//         x Prod_j raw profile of absorber j at rest[g] (1 + z_qso) (Voigt_absorption: no broadening),
+// multiplied in that order.
+// ------------------------------------------------------------------------------------------
+struct SpectraModelMeanArgs {
+  const double *rest, *mu;
+  int32_t G;
+  int64_t num_items;
+  const double *z_qsos;
+  const int64_t *abs_off;  // [num_items + 1]
+  const double *abs_z, *abs_n;
+  int32_t num_voigt_lines, num_forest_lines, suppressed;
+  double lya_wavelength, prev_tau_0, prev_beta;
+  double *out;  // [num_items][G]
+};
+
+__global__ __launch_bounds__(256) void k_spectra_model_mean(SpectraModelMeanArgs a) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= a.num_items * a.G) return;
+  const int64_t it = e / a.G;
+  const int g = (int)(e - it * a.G);
+  const double z_qso = a.z_qsos[it];
+  const double wl = a.rest[g] * (1 + z_qso);
+  double val = a.mu[g];
+  if (a.suppressed)
+    val = val * spectra_mean_flux(wl, z_qso, a.lya_wavelength, a.prev_tau_0, a.prev_beta, a.num_forest_lines);
+  for (int64_t j = a.abs_off[it]; j < a.abs_off[it + 1]; ++j)
+    val = val * spectra_raw_at(wl, a.abs_z[j], a.abs_n[j], a.num_voigt_lines);
+  a.out[e] = val;
+}
+
+}  // namespace gpdla

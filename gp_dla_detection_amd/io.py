@@ -700,6 +700,61 @@ def load_processed_qsos(path: str) -> dict:
 
 
 # ---------------------------------------------------------------------------------------------
+# model spectra
+# ---------------------------------------------------------------------------------------------
+
+MODEL_SPECTRA_CELLS = ("map_absorption", "mean_absorption", "var_absorption", "continuum", "model_flux")
+
+
+def save_model_spectra(path: str, spectra: dict, **run_metadata) -> None:
+    """What :func:`api.model_spectra` returns as a ``-v7.3`` file: ``quasar_ind`` (the selection, 1-based
+    like every MATLAB index), ``num_pixels`` and ``status`` as columns, the selected absorbers as the
+    cells ``map_z_dlas`` / ``map_log_nhis`` (when ``absorber_offsets``, ``absorber_z_dlas`` and
+    ``absorber_log_nhis`` are present), and each per-pixel product as a ragged N x 1 cell array with
+    one column vector per selected quasar (a quasar with no pixel in the modelled range holds an empty
+    one; an empty selection gives empty cells).  ``run_metadata``: scalars and strings, as given."""
+    off = np.asarray(spectra["offsets"], dtype=np.int64)
+    nsel = off.size - 1
+    w = _MatWriter(path)
+    try:
+        for k, v in run_metadata.items():
+            w.put(k, v)
+        w.put("quasar_ind", np.asarray(spectra.get("selection", np.arange(nsel)), dtype=np.float64) + 1)
+        w.put("num_pixels", np.diff(off).astype(np.float64))
+        w.put("status", np.asarray(spectra.get("status", np.zeros(nsel)), dtype=np.float64))
+        if "absorber_offsets" in spectra:
+            a = np.asarray(spectra["absorber_offsets"], dtype=np.int64)
+            for name, key in (("map_z_dlas", "absorber_z_dlas"), ("map_log_nhis", "absorber_log_nhis")):
+                v = np.asarray(spectra[key], dtype=np.float64)
+                w.put(name, [v[a[i]:a[i + 1]].reshape(-1, 1) for i in range(nsel)])
+        for name in MODEL_SPECTRA_CELLS:
+            if name in spectra:
+                v = np.asarray(spectra[name], dtype=np.float64)
+                w.put(name, [v[off[i]:off[i + 1]].reshape(-1, 1) for i in range(nsel)])
+    finally:
+        w.close()
+
+
+def load_model_spectra(path: str) -> dict:
+    """The reader of :func:`save_model_spectra`: ``selection`` (0-based), ``offsets``, ``status``, every
+    stored product as a LIST of per-quasar vectors, the absorbers as lists, the metadata as stored."""
+    m = loadmat73(path)
+    out = {}
+    for k, v in m.items():
+        if k == "quasar_ind":
+            out["selection"] = _vec(v).astype(np.int64) - 1
+        elif k == "num_pixels":
+            out["offsets"] = np.concatenate([[0], np.cumsum(_vec(v).astype(np.int64))])
+        elif k == "status":
+            out["status"] = _vec(v).astype(np.int32)
+        elif isinstance(v, list):
+            out[k] = [_vec(c) for c in v]
+        else:
+            out[k] = v
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
 # chunk files of a sharded run (CDDF_analysis/sbatch_reunion.py:13-63)
 # ---------------------------------------------------------------------------------------------
 

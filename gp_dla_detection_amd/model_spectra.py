@@ -1,0 +1,125 @@
+"""File-to-file model spectra:
+
+    python -m gp_dla_detection_amd.model_spectra --preloaded preloaded_qsos.mat --catalog catalog.mat \\
+        --model learned_qso_model.mat --samples dla_samples.mat --processed processed_qsos.mat \\
+        --p-dla 0.9 --out model_spectra.mat
+
+For the selected quasars of a processed run -- those with ``p_dla`` at or above a threshold, or an
+explicit list of positions within the run -- writes one ``-v7.3`` file with, per pixel of each
+quasar's unmasked-range grid: the absorption of the MAP absorbers of its most probable model, the
+posterior-weighted mean and variance of the sampled DLA profile, the GP continuum and the model
+flux (:func:`gp_dla_detection_amd.api.model_spectra`).  Nothing is swept again: the posterior weights
+are the rows of the processed file's sample table, streamed in blocks of selected quasars the way
+``cddf.from_processed_file`` reads them.
+
+The module shares its name with :func:`gp_dla_detection_amd.api.model_spectra`, so it is callable:
+``gp_dla_detection_amd.model_spectra(model, samples, spectra, results, ...)`` is that function.
+"""
+from __future__ import annotations
+
+import argparse
+import sys
+import types
+
+import numpy as np
+
+from . import api, hdf5, io
+from .parameters import MultiParameters, Parameters
+
+
+def sample_row_reader(processed: str, sub_dla: bool = False, span: int = 2048):
+    """``rows(idx) -> [len(idx), S]`` over the sample table of a processed file (stored ``[S, nq]``,
+    multi-DLA ``[max_dlas, S, nq]``: model DLA(1); ``sub_dla``: ``sample_log_likelihoods_lls``), one
+    read per run of selected quasars within ``span`` of its first.  ``idx`` ascending.  Returns
+    ``(rows, close)``."""
+    f = hdf5.File(processed)
+    ds = f["sample_log_likelihoods_lls" if sub_dla else "sample_log_likelihoods_dla"]
+    S = ds.shape[-2]
+
+    def rows(idx):
+        idx = np.asarray(idx, dtype=np.int64)
+        out = np.empty((idx.size, S))
+        i = 0
+        while i < idx.size:
+            lo = int(idx[i])
+            j = int(np.searchsorted(idx, lo + span))
+            hi = int(idx[j - 1]) + 1
+            slab = (ds.read_slab(0, S, axis1=(lo, hi)) if len(ds.shape) == 2
+                    else ds.read_slab(0, 1, axis1=(0, S), axis2=(lo, hi))[0])  # [S, hi - lo]
+            out[i:j] = slab[:, idx[i:j] - lo].T
+            i = j
+        return out
+    return rows, f.close
+
+
+def select(results: dict, p_dla: float | None, indices) -> np.ndarray:
+    """Positions within the run: an explicit (sorted, unique) list, or ``p_dlas >= p_dla``."""
+    if indices is not None:
+        return np.unique(np.asarray(indices, dtype=np.int64))
+    p = np.asarray(results["p_dlas"], dtype=np.float64).reshape(-1)
+    return np.flatnonzero(p >= (0.0 if p_dla is None else p_dla))
+
+
+def run(preloaded: str, catalog: str, model_file: str, samples_file: str, processed: str, out: str,
+        p_dla: float | None = None, indices=None, products=("map", "moments", "continuum"), multi: bool | None = None,
+        moments_sub_dla: bool = False, device: int = 0, max_quasars_per_batch: int | None = None) -> dict:
+    small = [k for k in ("model_posteriors", "p_dlas", "MAP_z_dlas", "MAP_log_nhis", "single_MAP_z_dlas",
+                         "single_MAP_log_nhis", "test_ind")]
+    results = io.loadmat73(processed, small)
+    results = {k[len("single_"):] if k.startswith("single_") else k: v for k, v in results.items()}
+    mp = np.asarray(results["model_posteriors"], dtype=np.float64)
+    is_multi = mp.shape[1] > 2 if multi is None else bool(multi)
+    for k in ("MAP_z_dlas", "MAP_log_nhis"):
+        v = np.asarray(results[k], dtype=np.float64)
+        results[k] = v.reshape(-1) if not is_multi else v  # MATLAB [nq x model x slot] is this package's order
+    results["p_dlas"] = np.asarray(results["p_dlas"], dtype=np.float64).reshape(-1)
+    sel = select(results, p_dla, indices)
+    z_qsos = np.asarray(io.load_catalog(catalog, ("z_qsos",))["z_qsos"], dtype=np.float64)
+    test_ind = np.asarray(results["test_ind"]).reshape(-1).astype(bool) if "test_ind" in results else None
+    run_pos = np.flatnonzero(test_ind) if test_ind is not None else np.arange(z_qsos.size)
+    spectra_sel = io.load_preloaded_qsos(preloaded, z_qsos, run_pos[sel])
+    absorbers = api.map_absorbers(results, sub_dla=is_multi)
+    absorbers_sel = api._take_absorbers(absorbers, sel)
+    model, samples = io.load_learned_model(model_file), io.load_dla_samples(samples_file)
+    rows, close = sample_row_reader(processed, sub_dla=moments_sub_dla)
+    try:  # the loaded list holds the selected quasars only: positions 0 .. len(sel) - 1 map to sel
+        res = api.model_spectra(model, samples, spectra_sel, None, params=MultiParameters() if is_multi else Parameters(),
+                                absorbers=absorbers_sel, moments_sub_dla=moments_sub_dla, products=products,
+                                sample_rows=lambda idx: rows(sel[idx]), device=device,
+                                max_quasars_per_batch=max_quasars_per_batch)
+    finally:
+        close()
+    res["selection"] = sel
+    res["absorber_offsets"], res["absorber_z_dlas"], res["absorber_log_nhis"] = absorbers_sel
+    io.save_model_spectra(out, res, processed_file=str(processed), multi_dla=np.float64(is_multi))
+    return res
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    for name in ("preloaded", "catalog", "model", "samples", "processed", "out"):
+        ap.add_argument(f"--{name}", required=True)
+    ap.add_argument("--p-dla", type=float, default=None, help="select quasars with p_dla at or above this")
+    ap.add_argument("--indices", type=str, default=None, help="comma-separated positions within the run (0-based)")
+    ap.add_argument("--products", type=str, default="map,moments,continuum")
+    ap.add_argument("--moments-sub-dla", action="store_true", help="weight the sub-DLA sample table")
+    ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--max-quasars-per-batch", type=int, default=None)
+    a = ap.parse_args(argv)
+    idx = None if a.indices is None else [int(x) for x in a.indices.split(",") if x]
+    res = run(a.preloaded, a.catalog, a.model, a.samples, a.processed, a.out, p_dla=a.p_dla, indices=idx,
+              products=tuple(a.products.split(",")), moments_sub_dla=a.moments_sub_dla, device=a.device,
+              max_quasars_per_batch=a.max_quasars_per_batch)
+    print(f"wrote {a.out}: {res['selection'].size} quasars, {int(res['offsets'][-1])} grid pixels")
+    return 0
+
+
+class _CallableModule(types.ModuleType):
+    def __call__(self, *args, **kwargs):
+        return api.model_spectra(*args, **kwargs)
+
+
+sys.modules[__name__].__class__ = _CallableModule
+
+if __name__ == "__main__":
+    raise SystemExit(main())

@@ -503,6 +503,107 @@ int gpdla_stats_bin_posteriors(int64_t num_spectra, int64_t num_samples, const d
 int gpdla_stats_poisson_binomial_cf(int64_t num_segments, const int64_t *offsets, const double *p, double *logsum,
                                     double *argsum, int device_id);
 
+/* ---------------------------------------------------------------------------------------------
+ * Model spectra: what the fitted model looks like on a spectrum -- the numbers
+ * behind the reference's QSOLoader.plot_this_mu (CDDF_analysis/qso_loader.py:1654-1774) and the
+ * per-pixel quantities a processed sample table stands for.
+ *
+ * Per-pixel outputs live on a quasar's UNMASKED-RANGE GRID: every stored pixel whose rest wavelength
+ * lies in [min_lambda, max_lambda] (process_qsos.m:104-108), masked or not, in stored order -- n_u
+ * pixels, the grid the Voigt stage of the sweeps runs on (padded by 3 pixels a side at
+ * pixel_spacing, :168-176).  Output arrays are CSR-style: offsets[num_selected + 1] (written by the
+ * call) and one value per grid pixel of each selected quasar, in selection order.
+ *
+ *  map_absorption   Prod_j of the instrument-broadened Voigt profiles of the quasar's listed absorbers
+ *                   (z_j, N_j) with the context's num_lines: the `absorption` vector of
+ *                   process_qsos.m:187-190 before the mask drop, multiplied over absorbers (multi
+ *                   :342-351).  Ones for an empty list; NaN for a quasar without a kept pixel (it has
+ *                   no padded grid).
+ *  mean_absorption, var_absorption
+ *                   posterior-weighted mean and variance, over all S samples, of the broadened profile
+ *                   of sample i: z_i = min_z_dla + (max_z_dla - min_z_dla) offset_i, N_i = nhi_samples[i]
+ *                   (sub_dla: lls_nhi_samples[i]), weights w_i = exp(l_i - max l) / Sum from a row l of
+ *                   sample log-likelihoods; a NaN l_i weighs 0, an all-NaN row gives NaN.  The row is
+ *                   the batch's resident table after gpdla_batch_process / gpdla_batch_process_multi
+ *                   (multi-DLA batch: model DLA(1), or the sub-DLA table with sub_dla), or row s of
+ *                   the caller's host table sample_log_likelihoods[num_selected][S] -- a processed file
+ *                   needs no second sweep.  Models with two or more absorbers are not averaged.
+ *  continuum, model_flux
+ *                   with a = map_absorption (ones for an empty list) and the prepared rows y, mu, M,
+ *                   omega2, nu of the kept pixels (meanflux != 0: with the Lyman-series suppression of
+ *                   multi :245-293): d = a^2 omega2 + nu, r = y - a mu, B = I + M' diag(a^2/d) M,
+ *                   c = B^-1 M' (a r / d); continuum = mu + M c at ALL n_u pixels (a masked pixel takes
+ *                   the same interpolated mu and M), model_flux = a continuum.  This is the posterior
+ *                   mean of the LOW-RANK part of the GP; the pixel-diagonal omega term predicts nothing
+ *                   at a pixel that was not measured and is left out.  B not positive definite: NaN
+ *                   rows and status 4 for that quasar, the call still returns GPDLA_OK.
+ *
+ * Sums run in a fixed order without atomics: outputs are bit-identical from run to run, for any
+ * selection order and any batching, and for the resident and the host form of the same table.
+ * The call returns when the outputs are in the caller's arrays.
+ * ------------------------------------------------------------------------------------------- */
+#define GPDLA_SPECTRA_MAX_ABSORBERS 8
+#define GPDLA_SPECTRA_MAP 1        /* products bit: map_absorption */
+#define GPDLA_SPECTRA_MOMENTS 2    /* mean_absorption and var_absorption */
+#define GPDLA_SPECTRA_CONTINUUM 4  /* continuum and model_flux */
+#define GPDLA_SPECTRA_WEIGHTS_NONE 0
+#define GPDLA_SPECTRA_WEIGHTS_RESIDENT 1
+#define GPDLA_SPECTRA_WEIGHTS_HOST 2
+typedef struct {
+  int64_t num_selected;
+  const int64_t *selection;          /* [num_selected] quasars of the batch; NULL = 0 .. num_selected-1 */
+  const int64_t *absorber_offsets;   /* [num_selected + 1] into absorber_z / absorber_nhi; NULL = no absorbers */
+  const double *absorber_z;
+  const double *absorber_nhi;        /* column densities (not their logarithms) */
+  int32_t weights_source;            /* GPDLA_SPECTRA_WEIGHTS_* */
+  const double *sample_log_likelihoods; /* [num_selected][S], GPDLA_SPECTRA_WEIGHTS_HOST */
+  int32_t sub_dla;                   /* != 0: lls_nhi_samples (and the resident sub-DLA table) */
+  int32_t meanflux;                  /* != 0: prepared rows of the mean-flux model (multi :245-293) */
+  int32_t products;                  /* GPDLA_SPECTRA_MAP | _MOMENTS | _CONTINUUM */
+  int64_t capacity;                  /* entries of each per-pixel output array */
+} gpdla_model_spectra_request;
+typedef struct {
+  int64_t *offsets;                  /* [num_selected + 1]; required */
+  double *map_absorption, *mean_absorption, *var_absorption, *continuum, *model_flux; /* any may be NULL */
+  int32_t *status;                   /* [num_selected] or NULL: the quasar's sweep status (0, 1, 3), or 4 = B not
+                                        positive definite (continuum) */
+} gpdla_model_spectra;
+
+/* The checks gpdla_batch_model_spectra makes before its first device call, for a batch of num_quasars
+ * quasars and S = num_samples: more than GPDLA_SPECTRA_MAX_ABSORBERS absorbers for a quasar or
+ * decreasing absorber_offsets, a selection index outside the batch, moments without a weights source
+ * (or a host source without a table), sub_dla without lls_nhi_samples, no product or an unknown one.
+ * Returns GPDLA_OK or GPDLA_ERR_INVALID_ARGUMENT.  Needs no GPU. */
+int gpdla_model_spectra_validate(const gpdla_model_spectra_request *request, int64_t num_quasars,
+                                 int64_t num_samples, int has_lls_nhi_samples);
+/* n_u of every quasar of the batch (runs the preparation kernel; synchronises): the sizes a caller
+ * allocates the outputs of gpdla_batch_model_spectra from. */
+int gpdla_batch_unmasked_counts(gpdla_context *ctx, gpdla_batch *batch, int64_t *n_u);
+int gpdla_batch_model_spectra(gpdla_context *ctx, gpdla_batch *batch, const gpdla_model_spectra_request *request,
+                              gpdla_model_spectra *out);
+
+/* With gpdla_context_set_timing enabled, gpdla_context_last_sweep_ms reports the k_spectra_moments +
+ * k_spectra_combine launches of the most recent gpdla_batch_model_spectra call that computed moments.
+ *
+ * Measuring aid for tools/bench_model_spectra.py: runs the preparation kernel and then k_profiles ALONE
+ * over every quasar of a multi-DLA batch (the Voigt stage of the multi-DLA driver: the same line sums,
+ * 2 S n values stored instead of reduced) and returns the k_profiles launches' duration from device
+ * events.  The batch's results are untouched; the context's profile table is overwritten. */
+int gpdla_debug_profiles_ms(gpdla_context *ctx, gpdla_batch *batch, double *ms_out);
+
+/* The reference's `this_mu` (qso_loader.py:1685-1711) as data, on the model's rest grid: for item i,
+ * out[i][g] = mu[g] x (suppressed != 0: QSOLoader.total_scale_factor(prev_tau_0, prev_beta, z_qsos[i],
+ * rest_wavelengths, num_forest_lines)[g], :1777-1822) x Prod_j Voigt_absorption(rest_wavelengths (1 +
+ * z_qsos[i]), absorber_nhi[j], absorber_z[j], num_voigt_lines)[g] -- RAW profiles, no instrument
+ * broadening -- over the item's absorbers j in absorber_offsets[i] .. absorber_offsets[i+1] (at most
+ * GPDLA_SPECTRA_MAX_ABSORBERS; absorber_offsets NULL = none).  Only num_rest_pixels, rest_wavelengths
+ * and mu of `model` are read.  Line counts in [1, 31].  Invalid arguments are refused before any device
+ * call. */
+int gpdla_model_mean(const gpdla_model *model, int64_t num_items, const double *z_qsos,
+                     const int64_t *absorber_offsets, const double *absorber_z, const double *absorber_nhi,
+                     int num_voigt_lines, int num_forest_lines, int suppressed, double prev_tau_0,
+                     double prev_beta, double *out, int device_id);
+
 #ifdef __cplusplus
 }
 #endif
