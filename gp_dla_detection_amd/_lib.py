@@ -140,6 +140,19 @@ class ModelSpectra(C.Structure):
                 ("continuum", _dp), ("model_flux", _dp), ("status", _i32p)]
 
 
+class MockRequest(C.Structure):
+    """gpdla_mock_request"""
+    _fields_ = [("seed", C.c_uint64), ("absorber_offsets", _i64p), ("absorber_z", _dp), ("absorber_nhi", _dp),
+                ("meanflux", C.c_int32), ("write_resident", C.c_int32), ("capacity_stored", C.c_int64),
+                ("capacity_grid", C.c_int64)]
+
+
+class MockSpectra(C.Structure):
+    """gpdla_mock_spectra"""
+    _fields_ = [("flux", _dp), ("grid_offsets", _i64p), ("absorption", _dp), ("continuum", _dp), ("sigma", _dp),
+                ("latents", _dp), ("status", _i32p)]
+
+
 SPECTRA_MAX_ABSORBERS = 8                                   # GPDLA_SPECTRA_MAX_ABSORBERS
 SPECTRA_MAP, SPECTRA_MOMENTS, SPECTRA_CONTINUUM = 1, 2, 4   # GPDLA_SPECTRA_* product bits
 SPECTRA_WEIGHTS_NONE, SPECTRA_WEIGHTS_RESIDENT, SPECTRA_WEIGHTS_HOST = 0, 1, 2
@@ -216,6 +229,8 @@ SYMBOLS = [
     ("gpdla_debug_profiles_ms", C.c_int, [C.c_void_p, C.c_void_p, _dp]),
     ("gpdla_model_mean", C.c_int, [C.POINTER(Model), C.c_int64, _dp, _i64p, _dp, _dp, C.c_int, C.c_int, C.c_int,
                                    C.c_double, C.c_double, _dp, C.c_int]),
+    ("gpdla_mock_validate", C.c_int, [C.POINTER(MockRequest), C.c_int64]),
+    ("gpdla_batch_draw_mocks", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(MockRequest), C.POINTER(MockSpectra)]),
     ("gpdla_debug_near_poly", C.c_int, [C.c_int, C.c_double, _dp, _dp]),
     ("gpdla_debug_prepared_rows", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, _dp, C.c_int64, _i64p]),
     ("gpdla_debug_philox4x32_10", None, [_u32p, _u32p, _u32p]),

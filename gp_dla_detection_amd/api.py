@@ -246,6 +246,7 @@ class Batch:
         ctx = self.ctx
         csr = spectra if isinstance(spectra, dict) else spectra_to_csr(spectra)
         self.num_quasars = csr["z_qsos"].size
+        self.num_pixels = int(csr["offsets"][-1] - csr["offsets"][0])
         self.num_samples = ctx.num_samples
         self.max_dlas = int(getattr(ctx.params, "max_dlas", 0)) if log_priors_lls is not None else 0
         keep = []
@@ -397,6 +398,66 @@ class Batch:
                 out[name] = np.empty(total)
                 setattr(ms, name, out[name].ctypes.data_as(_dp))
         _lib.check(lib.gpdla_batch_model_spectra(self.ctx._h, self._h, C.byref(rq), C.byref(ms)))
+        return out
+
+    # ---- mock spectra ----
+
+    MOCK_COMPONENTS = ("absorption", "continuum", "sigma", "latents")
+
+    def draw_mocks(self, absorbers=None, seed: int | None = None, meanflux: bool | None = None,
+                   write_resident: bool = True, components=()) -> dict:
+        """One draw per quasar from the model the sweeps evaluate (gpdla_batch_draw_mocks):
+        ``flux = a (mu + M z) + sqrt(a^2 omega2 + nu) eps`` on the kept pixels of each quasar's
+        unmasked-range grid, with the prepared rows of this batch, its stored noise variance and the
+        instrument-broadened absorption ``a`` of the listed absorbers.
+
+        ``absorbers``: ``(offsets [nq + 1], z_dlas, log_nhis)`` in CSR form over the quasars of the batch
+        (what :func:`gp_dla_detection_amd.mocks.draw_truth` returns), at most 8 each; None: none.
+        ``seed``: 64-bit seed of the Philox streams (default: the context's ``rng_seed``); the key also
+        carries ``first_quasar_index + q``, so a quasar's draw does not depend on its batch.
+        ``meanflux``: rows of the mean-flux model (default: on for a multi-DLA batch).
+        ``write_resident``: the batch's resident flux becomes the draw, and the next :meth:`process` /
+        :meth:`process_multi` sweeps it without another upload.
+        ``components``: any of ``"absorption"``, ``"continuum"``, ``"sigma"`` (flat, per grid pixel, with
+        ``grid_offsets``) and ``"latents"`` (``[nq, k]``).
+        Returns ``flux`` (flat, upload layout: masked pixels of the grid are NaN, stored pixels outside
+        the modelled range keep the uploaded flux), ``status`` and the requested components."""
+        lib = self.ctx.lib
+        nq = self.num_quasars
+        unknown = set(components) - set(self.MOCK_COMPONENTS)
+        if unknown:
+            raise ValueError(f"components: any of {self.MOCK_COMPONENTS}, got {sorted(unknown)}")
+        i64p = C.POINTER(C.c_int64)
+        rq = _lib.MockRequest()
+        rq.seed = int(getattr(self.ctx.params, "rng_seed", 0x9E3779B97F4A7C15) if seed is None else seed) & (2 ** 64 - 1)
+        keep = []
+        if absorbers is not None:
+            a_off, a_z, a_ln = absorbers
+            a_off = np.ascontiguousarray(a_off, dtype=np.int64).reshape(-1)
+            if a_off.size != nq + 1:
+                raise _lib.GpdlaError(-1, f"absorber offsets: {a_off.size} entries for {nq} quasars")
+            a_z, a_n = _f64(a_z)[0].reshape(-1), 10.0 ** _f64(a_ln)[0].reshape(-1)
+            keep += [a_off, a_z, a_n]
+            rq.absorber_offsets, rq.absorber_z, rq.absorber_nhi = a_off.ctypes.data_as(i64p), a_z.ctypes.data_as(_dp), a_n.ctypes.data_as(_dp)
+        rq.meanflux = int(bool(self.max_dlas) if meanflux is None else bool(meanflux))
+        rq.write_resident = int(bool(write_resident))
+        _lib.check(lib.gpdla_mock_validate(C.byref(rq), nq))  # refused requests never reach the device
+        grid = set(components) & {"absorption", "continuum", "sigma"}
+        total = int(self.unmasked_counts().sum()) if grid else 0
+        rq.capacity_stored, rq.capacity_grid = self.num_pixels, total
+        out = {"flux": np.empty(self.num_pixels), "status": np.zeros(nq, dtype=np.int32),
+               "grid_offsets": np.zeros(nq + 1, dtype=np.int64)}
+        ms = _lib.MockSpectra()
+        ms.flux = out["flux"].ctypes.data_as(_dp)
+        ms.grid_offsets = out["grid_offsets"].ctypes.data_as(i64p)
+        ms.status = out["status"].ctypes.data_as(C.POINTER(C.c_int32))
+        for name in grid:
+            out[name] = np.empty(total)
+            setattr(ms, name, out[name].ctypes.data_as(_dp))
+        if "latents" in components:
+            out["latents"] = np.empty((nq, self.ctx.k))
+            ms.latents = out["latents"].ctypes.data_as(_dp)
+        _lib.check(lib.gpdla_batch_draw_mocks(self.ctx._h, self._h, C.byref(rq), C.byref(ms)))
         return out
 
     def summary_tensor(self):
@@ -975,6 +1036,69 @@ def model_spectra(model: dict, samples: dict, spectra, results: dict | None = No
             ctx.close()
     for name, ps in parts.items():
         out[name] = np.concatenate(ps)
+    return out
+
+
+# ----------------------------------------------------------------------------------------------
+# mock spectra
+# ----------------------------------------------------------------------------------------------
+
+def draw_mock_spectra(model: dict, samples: dict, templates, truth=None, params: Parameters | None = None,
+                      seed: int | None = None, first_quasar_index: int = 0, components=(), device: int = 0,
+                      max_quasars_per_batch: int | None = None) -> dict:
+    """Mock spectra of many quasars, drawn on the GPU from the model the sweeps evaluate
+    (:meth:`Batch.draw_mocks`), batched like :func:`process_qsos`.
+
+    ``templates``: list of per-quasar dicts (``wavelengths, flux, noise_variance, pixel_mask, z_qso``):
+    the wavelength grids, noise variances and masks of the mocks; a template's flux survives only
+    where the model says nothing (outside the modelled rest range, or a quasar the sweep would skip).
+    ``truth``: CSR triple ``(offsets [nq + 1], z_dlas, log_nhis)`` over ALL templates
+    (:func:`gp_dla_detection_amd.mocks.draw_truth`), or None.  ``params``: a :class:`MultiParameters`
+    draws from the mean-flux model.  The Philox key of template i carries ``first_quasar_index + i``
+    whatever the batching, so any ``max_quasars_per_batch`` gives the same spectra.
+    Returns ``flux`` (list of per-quasar arrays), ``status``, and per requested component a list of
+    per-quasar arrays (``latents``: ``[nq, k]``)."""
+    p = params or Parameters()
+    multi = isinstance(p, MultiParameters)
+    templates = list(templates)
+    nq = len(templates)
+    S = np.asarray(samples["offset_samples"]).size
+    k = np.asarray(model["M"]).shape[1]
+    longest = max([np.asarray(t["wavelengths"]).size for t in templates], default=1)
+    per = int(max_quasars_per_batch or default_batch_size(nq, longest, k, S, 1))
+    out = {"flux": [], "status": np.zeros(nq, dtype=np.int32)}
+    for name in components:
+        out[name] = np.empty((nq, k)) if name == "latents" else []
+    if nq:
+        ctx = Context(device, p)
+        batch = None
+        try:
+            ctx.set_model(model)
+            ctx.set_samples(samples)
+            md = p.max_dlas if multi else 0
+            for lo, hi in batch_blocks(nq, per):
+                n = hi - lo
+                args = (templates[lo:hi], np.zeros(n), np.zeros((n, md)) if multi else np.zeros(n),
+                        np.zeros(n) if multi else None)
+                if batch is None:
+                    batch = ctx.upload(*args)
+                else:
+                    batch.reload(*args)
+                ctx.set_first_quasar_index(first_quasar_index + lo)
+                res = batch.draw_mocks(absorbers=None if truth is None else _take_absorbers(truth, range(lo, hi)),
+                                       seed=seed, write_resident=False, components=components)
+                sizes = np.array([np.asarray(t["wavelengths"]).size for t in templates[lo:hi]], dtype=np.int64)
+                out["flux"] += split_cells(res["flux"], np.concatenate([[0], np.cumsum(sizes)]))
+                out["status"][lo:hi] = res["status"]
+                for name in components:
+                    if name == "latents":
+                        out[name][lo:hi] = res[name]
+                    else:
+                        out[name] += split_cells(res[name], res["grid_offsets"])
+        finally:
+            if batch is not None:
+                batch.close()
+            ctx.close()
     return out
 
 

@@ -33,6 +33,7 @@
 #include "learn_kernels.hpp"
 #include "stats_kernels.hpp"
 #include "spectra_kernels.hpp"
+#include "mock_kernels.hpp"
 #include "training_kernels.hpp"
 #include "training_mfma_kernels.hpp"
 
@@ -47,5 +48,6 @@ using namespace gpdla;
 #include "host_learn.hpp"
 #include "host_stats.hpp"
 #include "host_spectra.hpp"
+#include "host_mock.hpp"
 // libgpdla_legacy.so (-DGPDLA_WITH_LEGACY): the superseded kernels and their environment switches
 #include "host_legacy.hpp"

@@ -604,6 +604,55 @@ int gpdla_model_mean(const gpdla_model *model, int64_t num_items, const double *
                      int num_voigt_lines, int num_forest_lines, int suppressed, double prev_tau_0,
                      double prev_beta, double *out, int device_id);
 
+/* ---------------------------------------------------------------------------------------------
+ * Mock spectra: one draw per quasar of a resident batch from the distribution
+ * whose likelihood the sweeps evaluate (process_qsos.m:190-198),
+ *     flux ~ N(a mu, A (M M' + diag omega2) A + diag nu),   A = diag a,
+ * on the KEPT pixels of the quasar's unmasked-range grid: a = the instrument-broadened product of the
+ * listed absorbers (what gpdla_batch_model_spectra returns as map_absorption; ones for an empty
+ * list), mu, M, omega2 = the rows the preparation kernel hands the sweep (meanflux != 0: the
+ * Lyman-series rows of multi :245-293), nu = the stored noise variance.
+ *     z     in R^k  standard normal, one vector per quasar            (stream 0, index i = 0 .. k-1)
+ *     eps_j         standard normal per STORED pixel position j       (stream 1, index j)
+ *     continuum_p = mu_p + M_p. z;  sigma_p = sqrt(a_p^2 omega2_p + nu_p);  flux_p = a_p continuum_p + sigma_p eps_p
+ * Normals: Philox4x32-10, counter (lo32(index), hi32(index), stream, 1) -- the multi-DLA resampling
+ * uses counter word 3 = 0, so the streams are disjoint under one seed -- and key
+ * (seed ^ qid, (seed >> 32) ^ (qid >> 32) ^ 0x5851F42D), qid = first_quasar_index + q.  From the four
+ * output words m1 = (out0 >> 5) 2^26 + (out1 >> 6), m2 likewise from out2, out3; u1 = (m1 + 1) 2^-53,
+ * u2 = m2 2^-53, n = sqrt(-2 ln u1) cos(2 pi u2): one normal per call, |n| <= 8.58.  eps is indexed by
+ * the stored position, so a quasar's draw depends neither on its mask nor on the batching.
+ * Pixels that are not drawn: a stored pixel outside [min_lambda, max_lambda] keeps the uploaded flux
+ * (masked or not: the model says nothing there); a masked pixel inside gets NaN (flux, continuum,
+ * sigma); a quasar of status != 0 keeps its flux, reports its status, and has NaN continuum, sigma
+ * and latents.  A kept pixel the sweep sees as a neutral row (noise variance above 1e100) is drawn as
+ * pure noise of its stored variance.  Nothing is accumulated with atomics and every sum runs in a
+ * fixed order: outputs are bit-identical from run to run.
+ * With write_resident != 0 the batch's resident flux becomes the draw: a following
+ * gpdla_batch_process / gpdla_batch_process_multi sweeps it without the flux visiting the host.
+ * The call returns when the outputs are in the caller's arrays.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct {
+  uint64_t seed;
+  const int64_t *absorber_offsets;   /* [num_quasars + 1] or NULL: no absorbers */
+  const double *absorber_z, *absorber_nhi;   /* <= GPDLA_SPECTRA_MAX_ABSORBERS per quasar; N, not log N */
+  int32_t meanflux;                  /* rows of the mean-flux model */
+  int32_t write_resident;            /* != 0: the batch's resident flux is replaced by the draw */
+  int64_t capacity_stored, capacity_grid;   /* entries of flux; of each per-grid-pixel array */
+} gpdla_mock_request;
+typedef struct {
+  double *flux;                      /* [stored pixels of the batch], upload layout; may be NULL */
+  int64_t *grid_offsets;             /* [num_quasars + 1]; required */
+  double *absorption, *continuum, *sigma;   /* per grid pixel; any may be NULL */
+  double *latents;                   /* [num_quasars][k] or NULL */
+  int32_t *status;                   /* [num_quasars] or NULL: the quasar's sweep status (0, 1, 3) */
+} gpdla_mock_spectra;
+/* The checks gpdla_batch_draw_mocks makes before its first device call: more than
+ * GPDLA_SPECTRA_MAX_ABSORBERS absorbers for a quasar, decreasing absorber_offsets, a NaN redshift, a
+ * column density that is NaN or not positive, a negative capacity.  Needs no GPU. */
+int gpdla_mock_validate(const gpdla_mock_request *request, int64_t num_quasars);
+int gpdla_batch_draw_mocks(gpdla_context *ctx, gpdla_batch *batch, const gpdla_mock_request *request,
+                           gpdla_mock_spectra *out);
+
 #ifdef __cplusplus
 }
 #endif
