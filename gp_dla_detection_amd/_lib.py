@@ -222,6 +222,11 @@ SYMBOLS = [
     ("gpdla_stats_bin_posteriors", C.c_int, [C.c_int64, C.c_int64, _dp, C.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
                                              C.c_int, C.POINTER(BinRequest), C.POINTER(BinOutput), C.c_int]),
     ("gpdla_stats_poisson_binomial_cf", C.c_int, [C.c_int64, _i64p, _dp, _dp, _dp, C.c_int]),
+    ("gpdla_stats_sightline_snrs", C.c_int, [C.c_int64, _i64p, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int]),
+    ("gpdla_stats_path_lengths", C.c_int, [C.c_int64, _dp, _dp, C.c_int, _dp, C.c_int, C.c_double, C.c_double, _dp,
+                                           C.c_int]),
+    ("gpdla_stats_bootstrap_sums", C.c_int, [C.c_int64, C.c_int, _dp, _i32p, C.c_uint64, C.c_int64, C.c_int64, _dp,
+                                             C.c_int]),
     ("gpdla_model_spectra_validate", C.c_int, [C.POINTER(ModelSpectraRequest), C.c_int64, C.c_int64, C.c_int]),
     ("gpdla_batch_unmasked_counts", C.c_int, [C.c_void_p, C.c_void_p, _i64p]),
     ("gpdla_batch_model_spectra", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(ModelSpectraRequest),

@@ -13,6 +13,12 @@ Only DLA(1) enters: the reference's DLA(k >= 2) branch (:922-94
 for every sample, so it never passes ``p_thresh_sample``.
 
     python -m gp_dla_detection_amd.cddf PROCESSED SAMPLES [--snrs F] [--z-min 2 --z-max 4 ...] [--json OUT]
+                                        [--sample-errors R [--seed N]]
+
+``--snrs`` takes the table ``python -m gp_dla_detection_amd.snrs`` writes.  ``--sample-errors`` adds the
+stratified bootstrap over sightlines (DLAStatistics.sample_errors): sample-variance
+percentiles of dN/dX, Omega_DLA and f(N_HI), the sightline draws and their sums on the GPU
+(k_path_lengths, k_bootstrap_sums).
 """
 from __future__ import annotations
 
@@ -401,6 +407,183 @@ def poisson_binomial_cf(segments, device=0):
 
 
 # ---------------------------------------------------------------------------------------------
+# path length per sightline and bin, and the stratified bootstrap
+# ---------------------------------------------------------------------------------------------
+
+BOOTSTRAP_MAX_COLUMNS = 256   # GPDLA_BOOTSTRAP_MAX_COLUMNS
+PATH_PANEL = 0.25             # widest quadrature panel in z (kPathPanel)
+#: the positive nodes of the 8-point Gauss-Legendre rule and their weights (kGaussX, kGaussW)
+GAUSS_NODES = (0.1834346424956498, 0.525532409916329, 0.7966664774136267, 0.9602898564975363)
+GAUSS_WEIGHTS = (0.362683783378362, 0.31370664587788727, 0.22238103445337448, 0.10122853629037626)
+
+
+def gauss_legendre_path(z_lo, z_hi, omega_m=0.279):
+    """The integral of dX_dz over [z_lo, z_hi] by the rule k_path_lengths uses, on the host: 8
+    nodes on each of ceil((z_hi - z_lo) / 0.25) equal panels."""
+    width = z_hi - z_lo
+    panels = max(int(math.ceil(width / PATH_PANEL)), 1)
+    half = width / (2.0 * panels)
+    terms = []
+    for p in range(panels):
+        mid = z_lo + (2.0 * p + 1.0) * half
+        for x, w in zip(GAUSS_NODES, GAUSS_WEIGHTS):
+            terms.append(w * (dX_dz(mid - half * x, omega_m) + dX_dz(mid + half * x, omega_m)))
+    return half * math.fsum(terms)
+
+
+def _check_edges(edges):
+    e = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+    if not 2 <= e.size <= MAX_BINS + 1:
+        raise ValueError(f"{e.size - 1} bins; a request takes 1 to {MAX_BINS}")
+    if not np.all(np.isfinite(e)) or not np.all(np.diff(e) > 0):
+        raise ValueError("bin edges must be finite and strictly increasing")
+    if not e[0] > -1 or e[-1] - e[0] > 1000:
+        raise ValueError("bin edges must lie above z = -1 and span at most 1000")
+    return e
+
+
+def path_length_matrix(min_z_dlas, max_z_dlas, snrs, edges, *, snr_thresh=-2, lowzcut=False, proximity_zone=0.1,
+                       omega_m=0.279, device=0):
+    """(rows, dX): for the sightlines over the SNR cut (``rows``: their indices), the absorption
+    path of each inside each bin [edges[b], edges[b + 1]] -- the terms path_length adds up, by
+    k_path_lengths.  A sightline that does not reach into a bin has exactly 0 there."""
+    from . import _lib
+    e = _check_edges(edges)
+    if not (math.isfinite(proximity_zone) and 0 < omega_m <= 1):
+        raise ValueError("need a finite proximity zone and 0 < omega_m <= 1")
+    n = len(min_z_dlas)
+    rows = np.flatnonzero((np.asarray(snrs, dtype=np.float64).reshape(-1) > snr_thresh)[:n])
+    lo = np.ascontiguousarray(np.asarray(min_z_dlas, dtype=np.float64).reshape(-1)[rows])
+    hi = np.ascontiguousarray(np.asarray(max_z_dlas, dtype=np.float64).reshape(-1)[rows])
+    end = np.maximum(np.minimum(hi, hi - proximity_zone), lo) if lowzcut else hi
+    if np.any(end - lo < 0):
+        raise ValueError("a search range ends below its start")
+    dX = np.zeros((rows.size, e.size - 1))
+    if rows.size:
+        _lib.check(_lib.load().gpdla_stats_path_lengths(rows.size, _lib.ptr(lo), _lib.ptr(hi), e.size - 1, _lib.ptr(e),
+                                                        int(bool(lowzcut)), float(proximity_zone), float(omega_m),
+                                                        _lib.ptr(dX), int(device)))
+    return rows, dX
+
+
+def bootstrap_strata(max_z_dlas, min_count=10, num_strata=9):
+    """A stratum label per sightline (dense, from 0, rising with max_z_dla) for the bootstrap.
+    As the reference's resample (:299-310): ``num_strata`` equal-width strata in max_z_dla between
+    two ends that are pulled in from the extremes in steps of 0.2 until the sightlines beyond each
+    end number at least ``min_count``; the end strata are extended to cover everything.  Unlike
+    the reference, a stratum still under ``min_count`` is merged into its lower neighbour (the
+    lowest into the one above), and every loop is bounded: all-equal redshifts, fewer than
+    2 x min_count sightlines or ends that cross give one stratum."""
+    z = np.asarray(max_z_dlas, dtype=np.float64).reshape(-1)
+    if np.any(np.isnan(z)):
+        raise ValueError("max_z_dlas must not be NaN")
+    if min_count < 1 or num_strata < 1:
+        raise ValueError("min_count and num_strata must be >= 1")
+    label = np.zeros(z.size, dtype=np.int32)
+    if z.size < 2 * min_count or num_strata == 1:
+        return label
+    z_lo, z_hi = float(z.min()), float(z.max())
+    if not (math.isfinite(z_lo) and math.isfinite(z_hi)) or z_lo == z_hi:
+        return label
+    steps = int(math.ceil((z_hi - z_lo) / 0.2)) + 1
+    top = next((z_hi - 0.2 * k for k in range(1, steps + 1) if np.count_nonzero(z > z_hi - 0.2 * k) >= min_count), z_lo)
+    bottom = next((z_lo + 0.2 * k for k in range(1, steps + 1) if np.count_nonzero(z <= z_lo + 0.2 * k) >= min_count), z_hi)
+    if not bottom < top:
+        return label
+    inner = np.linspace(bottom, top, num_strata + 1)[1:-1]         # the end strata reach to -inf / +inf
+    raw = np.searchsorted(inner, z, side="left")                    # inner[s-1] < z <= inner[s]
+    counts = np.bincount(raw, minlength=num_strata)
+    group = np.arange(num_strata)
+    for b in range(num_strata - 1, 0, -1):                          # small strata join the one below
+        if counts[b] < min_count:
+            counts[b - 1] += counts[b]
+            counts[b] = 0
+            group[group == b] = b - 1
+    if counts[0] < min_count:                                       # the lowest joins the next one that is left
+        up = np.flatnonzero(counts[1:] > 0)
+        if up.size:
+            group[group == 0] = 1 + int(up[0])
+    _, dense = np.unique(group, return_inverse=True)
+    return dense[raw].astype(np.int32)
+
+
+def _check_seed(seed):
+    """The bootstrap's seed as an int in [0, 2^64); NaN, fractions and other types are ValueErrors."""
+    if isinstance(seed, (float, np.floating)):
+        if not (math.isfinite(seed) and float(seed).is_integer()):
+            raise ValueError(f"seed must be an integer, not {seed!r}")
+        seed = int(seed)
+    try:
+        seed = int(np.asarray(seed).astype(object).item()) if not isinstance(seed, int) else seed
+    except (TypeError, ValueError):
+        raise ValueError(f"seed must be an integer, not {seed!r}") from None
+    if isinstance(seed, bool) or not 0 <= seed < 2 ** 64:
+        raise ValueError("seed must lie in [0, 2^64)")
+    return seed
+
+
+def bootstrap_sums(V, stratum, replicates, seed, *, first_replicate=0, path_columns=None, device=0):
+    """k_bootstrap_sums: for replicates first_replicate .. first_replicate + replicates - 1, the
+    column sums of ``V`` [N, C] over the rows each replicate draws.  ``stratum``: one label per row,
+    non-decreasing (rows sorted by stratum); position j of a stratum of m rows starting at row f
+    draws row f + ((w * m) >> 32), w the first word of Philox4x32-10 at counter (lo32(j), hi32(j),
+    r, 2) keyed by the seed.  ``path_columns``: columns that must be finite (the dX ones).
+    Returns [replicates, C]; a replicate's sums do not depend on how a run is split into calls."""
+    from . import _lib
+    V = np.ascontiguousarray(V, dtype=np.float64)
+    if V.ndim != 2 or V.shape[0] < 1 or not 1 <= V.shape[1] <= BOOTSTRAP_MAX_COLUMNS:
+        raise ValueError(f"V must be [N >= 1, 1 .. {BOOTSTRAP_MAX_COLUMNS}]")
+    lab = np.asarray(stratum)
+    if lab.shape != (V.shape[0],) or not np.issubdtype(lab.dtype, np.integer):
+        raise ValueError("stratum needs one integer label per row of V")
+    if lab.min() < 0 or np.any(np.diff(lab) < 0):
+        raise ValueError("rows must be sorted by stratum, labels >= 0")
+    seed = _check_seed(seed)
+    if isinstance(replicates, (float, np.floating)) and not float(replicates).is_integer():
+        raise ValueError("replicates must be an integer")
+    replicates, first_replicate = int(replicates), int(first_replicate)
+    if replicates < 1:
+        raise ValueError("replicates must be >= 1")
+    if first_replicate < 0 or first_replicate + replicates > 2 ** 32:
+        raise ValueError("replicate indices must lie in [0, 2^32)")
+    if path_columns is not None and not np.all(np.isfinite(V[:, path_columns])):
+        raise ValueError("the path-length columns of V must be finite")
+    lab = np.ascontiguousarray(lab, dtype=np.int32)
+    out = np.zeros((replicates, V.shape[1]))
+    _lib.check(_lib.load().gpdla_stats_bootstrap_sums(V.shape[0], V.shape[1], _lib.ptr(V), lab.ctypes.data_as(_lib._i32p),
+                                                      seed, first_replicate, replicates, _lib.ptr(out), int(device)))
+    return out
+
+
+def expected_counts(partials, nbins):
+    """[n, nbins]: each spectrum's expected number of absorbers per bin from the partials of a
+    strict request -- its Poisson sum plus its directly kept probabilities, scattered to their bins."""
+    out = np.array(partials["pois"], dtype=np.float64).reshape(-1, nbins)
+    count = np.asarray(partials["count"])
+    if np.any(count > KEPT_CAPACITY):
+        s = int(np.flatnonzero(count > KEPT_CAPACITY)[0])
+        raise KeptCapacityError(s, int(count[s]))
+    kb, kp = np.asarray(partials["kept_bin"]), np.asarray(partials["kept_p"])
+    for s in np.flatnonzero(count):
+        for i in range(int(count[s])):
+            out[s, int(kb[s, i])] += kp[s, i]
+    return out
+
+
+def sample_percentiles(replicates):
+    """(median, [84th, 16th], [97.5th, 2.5th]) over the finite replicates of each column, shaped
+    like the reference's dndx_sample / dndx_68_sample / dndx_95_sample (:338-344).  A column with no
+    finite replicate gives NaN."""
+    r = np.asarray(replicates, dtype=np.float64)
+    r = np.where(np.isfinite(r), r, np.nan)
+    import warnings
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)
+        q = np.nanpercentile(r, [50., 84., 16., 97.5, 2.5], axis=0)
+    return q[0], q[1:3], q[3:5]
+
+
+# ---------------------------------------------------------------------------------------------
 # the user-facing object
 # ---------------------------------------------------------------------------------------------
 
@@ -572,6 +755,72 @@ class DLAStatistics:
                     omega_dla=self.omega_dla(z_min, z_max, hubble))
 
 
+    def sample_errors(self, z_min=2, z_max=4, replicates=1000, seed=0x9E3779B97F4A7C15, hubble=0.7, lnhi_nbins=30,
+                      min_count=10, num_strata=9, replicates_per_call=None):
+        """Sample-variance errors of dN/dX, Omega_DLA and f(N_HI) from a stratified bootstrap over
+        the sightlines above the SNR cut: sightlines are resampled with
+        replacement inside strata of max_z_dla (bootstrap_strata), every stratum keeping its size.
+        Replicate statistics: sum of expected counts / sum dX per z bin; omega_dla_from's conversion
+        of sum of N_HI moments / sum dX; sum of expected counts / sum dX / dN per column-density
+        bin.  z bins without path in the data are dropped, as line_density drops them; a replicate
+        that draws no path into a bin is left out of that bin's percentiles.
+
+        Returns a dict: ``z_centres``, ``lnhi_centres``; for name in dndx / omega / cddf:
+        ``<name>_sample`` (median), ``<name>_68_sample`` ([84th, 16th] percentiles, shape [2, bins]),
+        ``<name>_95_sample`` ([97.5th, 2.5th]), ``<name>_replicates`` ([replicates, bins]) and
+        ``<name>_point`` (the same statistic of the data itself); ``strata`` (sizes); ``seed``."""
+        seed = _check_seed(seed)
+        if int(replicates) != replicates or replicates < 1:
+            raise ValueError("replicates must be an integer >= 1")
+        replicates = int(replicates)
+        line, col = self._line_request(z_min, z_max), self._cddf_request(z_min, z_max, lnhi_nbins, 20., 23.)
+        om = omega_dla_request(z_min, z_max, bins_per_z=self.bins_per_z)
+        p_line, p_col, p_om = self.partials([line, col, om])
+        zb, nb_edges = np.asarray(line.edges), np.asarray(col.edges)
+        nz, nn = zb.size - 1, nb_edges.size - 1
+        rows, dX = path_length_matrix(self.z_min, self.z_max, self.snrs, zb, snr_thresh=self.snr_thresh,
+                                      lowzcut=self.lowzcut, proximity_zone=self.proximity_zone, device=self.device)
+        _, dX_all = path_length_matrix(self.z_min, self.z_max, self.snrs, [float(z_min), float(z_max)],
+                                       snr_thresh=self.snr_thresh, lowzcut=self.lowzcut,
+                                       proximity_zone=self.proximity_zone, device=self.device)
+        if rows.size == 0:
+            raise ValueError("no sightline is above the SNR cut")
+        V = np.zeros((rows.size, 3 * nz + nn + 1))
+        at = np.searchsorted(rows, self.selected)               # selected spectra are all over the cut
+        V[at, :nz] = expected_counts(p_line, nz)
+        V[at, nz:nz + nn] = expected_counts(p_col, nn)
+        V[at, nz + nn:2 * nz + nn] = np.asarray(p_om["mean"]).reshape(-1, nz)
+        V[:, 2 * nz + nn:3 * nz + nn] = dX
+        V[:, -1] = dX_all[:, 0]
+        path_cols = slice(2 * nz + nn, 3 * nz + nn + 1)
+        label = bootstrap_strata(self.z_max[rows], min_count, num_strata)
+        order = np.argsort(label, kind="stable")
+        Vs, ls = np.ascontiguousarray(V[order]), label[order]
+        step = replicates if replicates_per_call is None else max(int(replicates_per_call), 1)
+        sums = np.concatenate([bootstrap_sums(Vs, ls, min(step, replicates - r0), seed, first_replicate=r0,
+                                              path_columns=path_cols, device=self.device)
+                               for r0 in range(0, replicates, step)])
+        point = np.array([math.fsum(V[:, c]) for c in range(V.shape[1])])[None, :]
+        live = point[0, 2 * nz + nn:3 * nz + nn] > 0
+        width = np.power(10., nb_edges[1:]) - np.power(10., nb_edges[:-1])
+        per_atom = PROTON_MASS * (H100 * hubble) / LIGHT / critical_density()
+
+        def ratios(t):
+            with np.errstate(divide="ignore", invalid="ignore"):
+                path = t[:, 2 * nz + nn:3 * nz + nn][:, live]
+                return dict(dndx=t[:, :nz][:, live] / path, omega=per_atom * t[:, nz + nn:2 * nz + nn][:, live] / path,
+                            cddf=t[:, nz:nz + nn] / t[:, -1:] / width[None, :])
+
+        rep, pt = ratios(sums), ratios(point)
+        out = dict(z_centres=_centres(zb)[live], lnhi_centres=_centres(nb_edges), seed=seed, replicates=replicates,
+                   strata=np.bincount(label))
+        for name in ("dndx", "omega", "cddf"):
+            med, r68, r95 = sample_percentiles(rep[name])
+            out.update({f"{name}_sample": med, f"{name}_68_sample": r68, f"{name}_95_sample": r95,
+                        f"{name}_replicates": rep[name], f"{name}_point": pt[name][0]})
+        return out
+
+
 def _jsonable(x):
     if isinstance(x, (tuple, list)):
         return [_jsonable(v) for v in x]
@@ -598,6 +847,9 @@ def main(argv=None):
     ap.add_argument("--block-size", type=int, default=2048)
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--json", help="output file (default: stdout)")
+    ap.add_argument("--sample-errors", type=int, metavar="R",
+                    help="add bootstrap sample errors from R replicates (keys sample_errors_*)")
+    ap.add_argument("--seed", type=int, default=None, help="seed of the bootstrap")
     a = ap.parse_args(argv)
     from . import io
     snrs = a.snrs
@@ -609,6 +861,11 @@ def main(argv=None):
                                            lowzcut=a.lowzcut, block_size=a.block_size, device=a.device)
     try:
         out = {k: _jsonable(v) for k, v in st.statistics(a.z_min, a.z_max, a.lnhi_nbins).items()}
+        if a.sample_errors is not None:
+            kw = {} if a.seed is None else dict(seed=a.seed)
+            err = st.sample_errors(a.z_min, a.z_max, replicates=a.sample_errors, lnhi_nbins=a.lnhi_nbins, **kw)
+            out.update({f"sample_errors_{k}": (v if isinstance(v, int) else _jsonable(v)) for k, v in err.items()
+                        if not k.endswith("_replicates")})
     finally:
         st.close()
     text = json.dumps(out)

@@ -1,9 +1,11 @@
-// host_stats.hpp -- the CDDF statistics (stats_kernels.hpp)
+// host_stats.hpp -- the CDDF statistics (stats_kernels.hpp), the sightline S/N table,
+// the path-length matrix and the stratified bootstrap
 #pragma once
 
 static_assert(GPDLA_STATS_MAX_BINS == gpdla::kStatsMaxBins && GPDLA_STATS_MAX_REQUESTS == gpdla::kStatsMaxRequests &&
                   GPDLA_STATS_KEPT_CAPACITY == gpdla::kStatsKept,
               "gpdla.h and stats_kernels.hpp disagree");
+static_assert(GPDLA_BOOTSTRAP_MAX_COLUMNS == gpdla::kBootMaxColumns, "gpdla.h and stats_kernels.hpp disagree");
 
 extern "C" {
 
@@ -178,6 +180,125 @@ int gpdla_stats_poisson_binomial_cf(int64_t num_segments, const int64_t *offsets
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpy(logsum, d_ls, M * sizeof(double), hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(argsum, d_as, M * sizeof(double), hipMemcpyDeviceToHost));
+  return GPDLA_OK;
+} GPDLA_NO_THROW
+
+int gpdla_stats_sightline_snrs(int64_t num_sightlines, const int64_t *offsets, const double *wavelengths,
+                               const double *flux, const double *noise_variance, const double *max_z_dlas,
+                               const double *normalizers, double *snrs, int device_id) try {
+  using namespace gpdla;
+  if (num_sightlines < 0 || (num_sightlines > 0 && (!offsets || !max_z_dlas || !snrs)))
+    return fail(GPDLA_ERR_INVALID_ARGUMENT, "null argument or negative sightline count");
+  if (num_sightlines == 0) return GPDLA_OK;
+  if (num_sightlines > 2147483647LL) return fail(GPDLA_ERR_UNSUPPORTED, "more than 2^31 - 1 sightlines in one call");
+  const int64_t n = num_sightlines;
+  if (offsets[0] != 0) return fail(GPDLA_ERR_INVALID_ARGUMENT, "offsets[0] must be 0");
+  for (int64_t i = 0; i < n; ++i) {
+    if (offsets[i + 1] < offsets[i]) return fail(GPDLA_ERR_INVALID_ARGUMENT, "offsets must be non-decreasing (sightline %lld)", (long long)i);
+    if (offsets[i + 1] - offsets[i] > 2147483647LL) return fail(GPDLA_ERR_UNSUPPORTED, "sightline %lld has more than 2^31 - 1 pixels", (long long)i);
+  }
+  const int64_t total = offsets[n];
+  if (total > 0 && (!wavelengths || !flux || !noise_variance)) return fail(GPDLA_ERR_INVALID_ARGUMENT, "null pixel arrays");
+  int rc = select_device(device_id);
+  if (rc) return rc;
+  DeviceTemps tmp;
+  int64_t *d_off;
+  double *d_pix, *d_z, *d_nm = nullptr, *d_out;
+  if ((rc = tmp.alloc(&d_off, (size_t)n + 1)) || (rc = tmp.alloc(&d_pix, (size_t)3 * total)) || (rc = tmp.alloc(&d_z, (size_t)n)) ||
+      (rc = tmp.alloc(&d_out, (size_t)n)) || (normalizers && (rc = tmp.alloc(&d_nm, (size_t)n))))
+    return rc;
+  HIP_TRY(hipMemcpy(d_off, offsets, (n + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+  if (total > 0) {
+    HIP_TRY(hipMemcpy(d_pix, wavelengths, total * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_pix + total, flux, total * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_pix + 2 * total, noise_variance, total * sizeof(double), hipMemcpyHostToDevice));
+  }
+  HIP_TRY(hipMemcpy(d_z, max_z_dlas, n * sizeof(double), hipMemcpyHostToDevice));
+  if (normalizers) HIP_TRY(hipMemcpy(d_nm, normalizers, n * sizeof(double), hipMemcpyHostToDevice));
+  SnrArgs a{d_off, d_pix, d_pix + total, d_pix + 2 * total, d_z, d_nm, d_out};
+  hipLaunchKernelGGL(k_sightline_snr, dim3((unsigned)n), dim3(256), 0, 0, a);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(snrs, d_out, n * sizeof(double), hipMemcpyDeviceToHost));
+  return GPDLA_OK;
+} GPDLA_NO_THROW
+
+int gpdla_stats_path_lengths(int64_t num_sightlines, const double *min_z_dlas, const double *max_z_dlas,
+                             int num_bins, const double *edges, int lowzcut, double proximity_zone, double omega_m,
+                             double *dX, int device_id) try {
+  using namespace gpdla;
+  if (num_sightlines < 0 || (num_sightlines > 0 && (!min_z_dlas || !max_z_dlas || !dX)))
+    return fail(GPDLA_ERR_INVALID_ARGUMENT, "null argument or negative sightline count");
+  if (num_bins < 1 || num_bins > kStatsMaxBins || !edges)
+    return fail(GPDLA_ERR_INVALID_ARGUMENT, "%d bins; a request takes 1 to %d", num_bins, kStatsMaxBins);
+  for (int b = 0; b <= num_bins; ++b)
+    if (!std::isfinite(edges[b]) || (b > 0 && !(edges[b] > edges[b - 1])))
+      return fail(GPDLA_ERR_INVALID_ARGUMENT, "edges must be finite and strictly increasing");
+  if (!(edges[0] > -1.0) || edges[num_bins] - edges[0] > 1000.0)
+    return fail(GPDLA_ERR_INVALID_ARGUMENT, "edges must lie above z = -1 and span at most 1000");
+  if (!std::isfinite(proximity_zone) || !(omega_m > 0.0 && omega_m <= 1.0))
+    return fail(GPDLA_ERR_INVALID_ARGUMENT, "need a finite proximity zone and 0 < omega_m <= 1");
+  for (int64_t i = 0; i < num_sightlines; ++i) {
+    const double lo = min_z_dlas[i];
+    double hi = max_z_dlas[i];
+    if (lowzcut) hi = std::fmax(std::fmin(hi, hi - proximity_zone), lo);
+    if (hi - lo < 0) return fail(GPDLA_ERR_INVALID_ARGUMENT, "the search range of sightline %lld ends below its start", (long long)i);
+  }
+  if (num_sightlines == 0) return GPDLA_OK;
+  const int64_t n = num_sightlines, cells = n * num_bins;
+  if ((cells + 255) / 256 > 2147483647LL) return fail(GPDLA_ERR_UNSUPPORTED, "too many sightlines for one launch");
+  int rc = select_device(device_id);
+  if (rc) return rc;
+  DeviceTemps tmp;
+  double *d_z, *d_e, *d_out;
+  if ((rc = tmp.alloc(&d_z, (size_t)2 * n)) || (rc = tmp.alloc(&d_e, (size_t)num_bins + 1)) || (rc = tmp.alloc(&d_out, (size_t)cells)))
+    return rc;
+  HIP_TRY(hipMemcpy(d_z, min_z_dlas, n * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_z + n, max_z_dlas, n * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_e, edges, (num_bins + 1) * sizeof(double), hipMemcpyHostToDevice));
+  PathArgs a{n, num_bins, lowzcut != 0, d_z, d_z + n, d_e, proximity_zone, omega_m, d_out};
+  hipLaunchKernelGGL(k_path_lengths, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, 0, a);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(dX, d_out, cells * sizeof(double), hipMemcpyDeviceToHost));
+  return GPDLA_OK;
+} GPDLA_NO_THROW
+
+int gpdla_stats_bootstrap_sums(int64_t num_rows, int num_columns, const double *V, const int32_t *stratum,
+                               uint64_t seed, int64_t first_replicate, int64_t num_replicates, double *sums,
+                               int device_id) try {
+  using namespace gpdla;
+  if (num_rows < 1 || !V || !stratum || !sums) return fail(GPDLA_ERR_INVALID_ARGUMENT, "need num_rows >= 1 and non-null arrays");
+  if (num_columns < 1 || num_columns > kBootMaxColumns)
+    return fail(GPDLA_ERR_INVALID_ARGUMENT, "%d columns; the matrix takes 1 to %d", num_columns, kBootMaxColumns);
+  if (num_replicates < 1 || first_replicate < 0 || first_replicate + num_replicates > 4294967296LL)
+    return fail(GPDLA_ERR_INVALID_ARGUMENT, "need num_replicates >= 1 and replicate indices in [0, 2^32)");
+  if (num_rows > 2147483647LL || num_replicates > 2147483647LL)
+    return fail(GPDLA_ERR_UNSUPPORTED, "more than 2^31 - 1 rows or replicates in one call");
+  const int64_t n = num_rows;
+  std::vector<int32_t> first(n), size(n);
+  if (stratum[0] < 0) return fail(GPDLA_ERR_INVALID_ARGUMENT, "stratum labels must be >= 0");
+  for (int64_t i = 0, start = 0; i < n; ++i) {   // rows come sorted by stratum
+    if (i > 0 && stratum[i] < stratum[i - 1]) return fail(GPDLA_ERR_INVALID_ARGUMENT, "rows must be sorted by stratum (row %lld)", (long long)i);
+    if (i > 0 && stratum[i] != stratum[i - 1]) start = i;
+    first[i] = (int32_t)start;
+  }
+  for (int64_t i = n - 1, end = n; i >= 0; --i) {
+    size[i] = (int32_t)(end - first[i]);
+    if (first[i] == i) end = i;
+  }
+  int rc = select_device(device_id);
+  if (rc) return rc;
+  DeviceTemps tmp;
+  double *d_V, *d_out;
+  int32_t *d_fs;
+  const size_t cells = (size_t)n * num_columns, outs = (size_t)num_replicates * num_columns;
+  if ((rc = tmp.alloc(&d_V, cells)) || (rc = tmp.alloc(&d_fs, (size_t)2 * n)) || (rc = tmp.alloc(&d_out, outs))) return rc;
+  HIP_TRY(hipMemcpy(d_V, V, cells * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_fs, first.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_fs + n, size.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
+  BootArgs a{n, num_columns, d_V, d_fs, d_fs + n, (uint32_t)seed, (uint32_t)(seed >> 32), first_replicate, d_out};
+  hipLaunchKernelGGL(k_bootstrap_sums, dim3((unsigned)num_replicates), dim3(256), 0, 0, a);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(sums, d_out, outs * sizeof(double), hipMemcpyDeviceToHost));
   return GPDLA_OK;
 } GPDLA_NO_THROW
 

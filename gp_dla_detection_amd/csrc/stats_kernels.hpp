@@ -177,4 +177,242 @@ __global__ __launch_bounds__(256) void k_poisson_binomial_cf(StatsCfArgs a) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Sightline S/N, path-length matrix and the stratified bootstrap.
+//
+//   k_sightline_snr    one block per sightline of a ragged CSR set: the pixels redward of
+//                      1215.67 (1 + max_z_dla), sqrt(noise_variance) / |floored flux| of each,
+//                      their median as NumPy takes it, snr = 1 / median (find_snr as executed,
+//                      calc_cddf.py:1167-1185).  The selected values are compacted into LDS in
+//                      pixel order and the two middle ones found by rank (ties broken by
+//                      position), in tiles when more qualify than one tile holds.
+//   k_path_lengths     one thread per (sightline, bin): Gauss-Legendre (8 nodes on panels no wider
+//                      than 0.25 in z) of (1+z)^2 / sqrt(Om (1+z)^3 + 1 - Om) over the overlap of
+//                      the sightline's search range with the bin (cddf.path_length's rules)
+//   k_bootstrap_sums   one block per replicate: column sums of V[N][C] over the rows the replicate
+//                      draws (Philox4x32-10, counter (lo32(j), hi32(j), r, 2)); a lane owns columns,
+//                      a wave a fixed stride of positions, the four waves combine in a fixed tree
+//
+// No atomics anywhere; every output is bit-identical run to run, and a replicate's sums do not
+// depend on which launch computed it.
+// ---------------------------------------------------------------------------------------------
+
+constexpr int kSnrTile = 2048;          // selected values held in LDS per step (16 KiB a buffer)
+constexpr int kPathOrder = 8;           // Gauss-Legendre nodes per panel
+constexpr double kPathPanel = 0.25;     // widest panel in z
+constexpr int kBootMaxColumns = 256;    // columns of V: 64 lanes x kBootTiles
+constexpr int kBootTiles = kBootMaxColumns / 64;
+
+struct SnrArgs {
+  const int64_t *offsets;                 // [n + 1]
+  const double *wavelengths, *flux, *noise_variance;
+  const double *max_z;                    // [n]
+  const double *normalizers;              // [n] or null
+  double *snr;                            // [n]
+};
+
+// sqrt(nv) / |flux with the floor of find_snr|, each operation rounded once
+__device__ inline double snr_value(double f, double nv, bool has_norm, double nm) {
+  if (has_norm) {
+    if (f / nm < 0.1) f = nm * 0.1;
+  } else if (f < 0.1) {
+    f = 0.1;
+  }
+  return sqrt(nv) / fabs(f);
+}
+
+// Compacts, in pixel order, the selected values whose compaction index lies in [start, start +
+// kSnrTile) into buf; returns the number of selected pixels and whether any value is NaN.
+__device__ inline int snr_stage(const SnrArgs &a, int64_t p0, int np, double thresh, bool has_norm, double nm,
+                                int start, double *buf, int *wave_tot, bool *any_nan) {
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  int base = 0;
+  bool nan_here = false;
+  for (int t0 = 0; t0 < np; t0 += 256) {
+    const int j = t0 + tid;
+    bool sel = false;
+    double v = 0.0;
+    if (j < np && a.wavelengths[p0 + j] > thresh) {
+      sel = true;
+      v = snr_value(a.flux[p0 + j], a.noise_variance[p0 + j], has_norm, nm);
+      nan_here |= v != v;
+    }
+    const unsigned long long m = __ballot(sel);
+    const int before = __popcll(m & ((1ull << lane) - 1ull));
+    if (lane == 0) wave_tot[wave] = __popcll(m);
+    __syncthreads();
+    int off = base;
+    for (int w = 0; w < wave; ++w) off += wave_tot[w];
+    const int total = wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
+    const int pos = off + before - start;
+    if (sel && pos >= 0 && pos < kSnrTile) buf[pos] = v;
+    base += total;
+    __syncthreads();
+  }
+  *any_nan = __syncthreads_or(nan_here) != 0;
+  return base;
+}
+
+__global__ __launch_bounds__(256) void k_sightline_snr(SnrArgs a) {
+  __shared__ double cand[kSnrTile], other[kSnrTile];
+  __shared__ double mid[2];
+  __shared__ int wave_tot[4];
+  const int64_t s = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int64_t p0 = a.offsets[s];
+  const int np = (int)(a.offsets[s + 1] - p0);
+  const bool has_norm = a.normalizers != nullptr;
+  const double nm = has_norm ? a.normalizers[s] : 1.0;
+  const double thresh = 1215.67 * (1.0 + a.max_z[s]);   // NaN max_z: no pixel passes
+  const double nan = __builtin_nan("");
+  bool any_nan;
+  const int m = snr_stage(a, p0, np, thresh, has_norm, nm, 0, cand, wave_tot, &any_nan);
+  if (m == 0 || any_nan) {   // block-uniform; NaN is settled before any ordering
+    if (tid == 0) a.snr[s] = nan;
+    return;
+  }
+  const int k_lo = (m - 1) / 2, k_hi = m / 2;
+  constexpr int kPer = kSnrTile / 256;
+  for (int c0 = 0; c0 < m; c0 += kSnrTile) {
+    if (c0 > 0) snr_stage(a, p0, np, thresh, has_norm, nm, c0, cand, wave_tot, &any_nan);
+    const int nc = (m - c0 < kSnrTile) ? (m - c0) : kSnrTile;
+    int rank[kPer];
+    double mine[kPer];
+#pragma unroll
+    for (int q = 0; q < kPer; ++q) {
+      rank[q] = 0;
+      mine[q] = (tid + 256 * q < nc) ? cand[tid + 256 * q] : 0.0;
+    }
+    for (int b0 = 0; b0 < m; b0 += kSnrTile) {
+      const double *src = cand;
+      if (m > kSnrTile) {   // more than one tile: the values compared against are staged apart
+        snr_stage(a, p0, np, thresh, has_norm, nm, b0, other, wave_tot, &any_nan);
+        src = other;
+      }
+      const int nb = (m - b0 < kSnrTile) ? (m - b0) : kSnrTile;
+#pragma unroll
+      for (int q = 0; q < kPer; ++q) {
+        const int i = tid + 256 * q;
+        if (i >= nc) continue;
+        const double x = mine[q];
+        const int gi = c0 + i;
+        int r = 0;
+        for (int j = 0; j < nb; ++j) {
+          const double y = src[j];
+          r += (y < x || (y == x && b0 + j < gi)) ? 1 : 0;
+        }
+        rank[q] += r;
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < kPer; ++q) {
+      if (tid + 256 * q >= nc) continue;
+      if (rank[q] == k_lo) mid[0] = mine[q];
+      if (rank[q] == k_hi) mid[1] = mine[q];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    const double med = (k_lo == k_hi) ? mid[0] : (mid[0] + mid[1]) / 2.0;   // np.median: mean of the middle two
+    a.snr[s] = 1.0 / med;
+  }
+}
+
+struct PathArgs {
+  int64_t n;
+  int32_t nb, lowzcut;
+  const double *z_min, *z_max;   // [n]
+  const double *edges;           // [nb + 1]
+  double proximity_zone, omega_m;
+  double *dX;                    // [n][nb]
+};
+
+__device__ __constant__ const double kGaussX[kPathOrder / 2] = {0.1834346424956498, 0.525532409916329,
+                                                                0.7966664774136267, 0.9602898564975363};
+__device__ __constant__ const double kGaussW[kPathOrder / 2] = {0.362683783378362, 0.31370664587788727,
+                                                                0.22238103445337448, 0.10122853629037626};
+
+__device__ inline double dX_dz(double z, double om) {
+  const double x = 1.0 + z;
+  return x * x / sqrt(om * (x * x * x) + (1.0 - om));
+}
+
+__global__ __launch_bounds__(256) void k_path_lengths(PathArgs a) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= a.n * a.nb) return;
+  const int64_t i = t / a.nb;
+  const int b = (int)(t - i * a.nb);
+  const double lo = a.z_min[i];
+  double hi = a.z_max[i];
+  if (a.lowzcut) hi = fmax(fmin(hi, hi - a.proximity_zone), lo);
+  const double e_lo = a.edges[b], e_hi = a.edges[b + 1];
+  double out = 0.0;
+  if (lo < e_hi && hi > e_lo) {   // `inside`; NaN ends fail it
+    const double za = fmax(e_lo, lo), zb = fmin(e_hi, hi);
+    const double width = zb - za;
+    int panels = (int)ceil(width / kPathPanel);
+    if (panels < 1) panels = 1;
+    const double half = width / (2.0 * panels);
+    CompSum acc;
+    for (int p = 0; p < panels; ++p) {
+      const double mid = za + (2.0 * p + 1.0) * half;
+      for (int k = 0; k < kPathOrder / 2; ++k) {
+        const double d = half * kGaussX[k];
+        acc.add(kGaussW[k] * (dX_dz(mid - d, a.omega_m) + dX_dz(mid + d, a.omega_m)));
+      }
+    }
+    out = half * acc.value();
+  }
+  a.dX[t] = out;
+}
+
+struct BootArgs {
+  int64_t n;                      // rows of V, sorted by stratum
+  int32_t C;                      // columns, <= kBootMaxColumns
+  const double *V;                // [n][C]
+  const int32_t *first, *size;    // [n] first row and size of the stratum of position j
+  uint32_t key0, key1;
+  int64_t r0;                     // replicate index of block 0
+  double *out;                    // [gridDim.x][C]
+};
+
+__global__ __launch_bounds__(256) void k_bootstrap_sums(BootArgs a) {
+  __shared__ double ss[4][kBootMaxColumns], sc[4][kBootMaxColumns];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const uint32_t r = (uint32_t)(a.r0 + blockIdx.x);
+  CompSum acc[kBootTiles];
+  for (int64_t base = (int64_t)wave * 64; base < a.n; base += 256) {
+    const int64_t j = base + lane;
+    int row = 0;
+    if (j < a.n) {   // this lane draws position j; the wave then reads the 64 drawn rows one by one
+      uint32_t w[4];
+      philox4x32_10((uint32_t)j, (uint32_t)((uint64_t)j >> 32), r, 2u, a.key0, a.key1, w);
+      row = a.first[j] + (int)(((uint64_t)w[0] * (uint64_t)(uint32_t)a.size[j]) >> 32);
+    }
+    const int cnt = (a.n - base < 64) ? (int)(a.n - base) : 64;
+#pragma unroll 4
+    for (int q = 0; q < cnt; ++q) {
+      const double *v = a.V + (int64_t)__shfl(row, q) * a.C;   // adjacent lanes, adjacent columns
+#pragma unroll
+      for (int t = 0; t < kBootTiles; ++t)
+        if (lane + 64 * t < a.C) acc[t].add(v[lane + 64 * t]);
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < kBootTiles; ++t) {
+    ss[wave][lane + 64 * t] = acc[t].s;
+    sc[wave][lane + 64 * t] = acc[t].c;
+  }
+  __syncthreads();
+  for (int c = tid; c < a.C; c += 256) {   // (w0 + w1) + (w2 + w3)
+    CompSum lo, hi;
+    lo.s = ss[0][c]; lo.c = sc[0][c];
+    lo.add(ss[1][c]); lo.c += sc[1][c];
+    hi.s = ss[2][c]; hi.c = sc[2][c];
+    hi.add(ss[3][c]); hi.c += sc[3][c];
+    lo.add(hi.s); lo.c += hi.c;
+    a.out[(int64_t)blockIdx.x * a.C + c] = lo.value();
+  }
+}
+
 }  // namespace gpdla

@@ -504,6 +504,43 @@ int gpdla_stats_poisson_binomial_cf(int64_t num_segments, const int64_t *offsets
                                     double *argsum, int device_id);
 
 /* ---------------------------------------------------------------------------------------------
+ * Sightline S/N, path length per sightline and bin, stratified bootstrap.  Additive:
+ * GPDLA_ABI_VERSION is unchanged.
+ *
+ * gpdla_stats_sightline_snrs: find_snr of calc_cddf.py:1167-1185 as it executes, on ragged CSR
+ * spectra (sightline i holds pixels offsets[i] .. offsets[i+1]).  The pixels with wavelength >
+ * 1215.67 * (1 + max_z_dlas[i]) are taken, masked or not; flux with flux / normalizers[i] < 0.1
+ * becomes normalizers[i] * 0.1 (normalizers == NULL: flux < 0.1 becomes 0.1); snrs[i] = 1 /
+ * median(sqrt(noise_variance) / |flux|), the median as NumPy takes it: NaN if any selected value is
+ * NaN or none is selected (a NaN max_z_dla selects none), the mean of the middle two for an even
+ * count.  Any number of selected pixels is handled.
+ *
+ * gpdla_stats_path_lengths: dX[i][b] = integral of (1+z)^2 / sqrt(omega_m (1+z)^3 + 1 - omega_m) over
+ * the overlap of [min_z_dlas[i], hi_i] with [edges[b], edges[b+1]]; hi_i = max_z_dlas[i], or with
+ * lowzcut max(min(hi, hi - proximity_zone), min_z_dlas[i]).  A sightline with min >= edges[b+1] or
+ * hi <= edges[b] (or a NaN end) gets exactly 0.  8-node Gauss-Legendre on panels no wider than 0.25.
+ * A search range that ends below its start is GPDLA_ERR_INVALID_ARGUMENT.  1 .. GPDLA_STATS_MAX_BINS bins.
+ *
+ * gpdla_stats_bootstrap_sums: V is [num_rows][num_columns] (1 .. GPDLA_BOOTSTRAP_MAX_COLUMNS columns),
+ * its rows sorted by stratum[] (non-decreasing labels >= 0).  For replicate r = first_replicate ..
+ * first_replicate + num_replicates - 1, position j (0 .. num_rows - 1, in a stratum that starts at
+ * row f and holds m rows) draws row f + ((uint64) w * m >> 32), w the first word of Philox4x32-10 at
+ * counter (lo32(j), hi32(j), r, 2) under key (lo32(seed), hi32(seed)); sums[r - first_replicate][c]
+ * is the compensated sum of V[row][c] over the positions in a fixed order.  A replicate's sums do
+ * not depend on first_replicate / num_replicates of the call that computed it.
+ * ------------------------------------------------------------------------------------------- */
+#define GPDLA_BOOTSTRAP_MAX_COLUMNS 256
+int gpdla_stats_sightline_snrs(int64_t num_sightlines, const int64_t *offsets, const double *wavelengths,
+                               const double *flux, const double *noise_variance, const double *max_z_dlas,
+                               const double *normalizers, double *snrs, int device_id);
+int gpdla_stats_path_lengths(int64_t num_sightlines, const double *min_z_dlas, const double *max_z_dlas,
+                             int num_bins, const double *edges, int lowzcut, double proximity_zone, double omega_m,
+                             double *dX, int device_id);
+int gpdla_stats_bootstrap_sums(int64_t num_rows, int num_columns, const double *V, const int32_t *stratum,
+                               uint64_t seed, int64_t first_replicate, int64_t num_replicates, double *sums,
+                               int device_id);
+
+/* ---------------------------------------------------------------------------------------------
  * Model spectra: what the fitted model looks like on a spectrum -- the numbers
  * behind the reference's QSOLoader.plot_this_mu (CDDF_analysis/qso_loader.py:1654-1774) and the
  * per-pixel quantities a processed sample table stands for.
