@@ -1244,6 +1244,8 @@ __device__ __forceinline__ double wing_sum3(double lamP, double msa, double msb,
 // a multiply in 5.4: tools/valu_rate_probe.hip).  s_j in [2e-7, 2e9] and d in [1e-280, 1e100 + omega2 a^2]
 // (k_prepare sweeps a pixel of larger noise variance as a neutral row, kNeutralNoiseVariance): the
 // product and its reciprocal stay normal.  Each quotient carries two or three more roundings than fast_rcp's 2.2e-15.
+// (sweep_slim_kernel.hpp spells the same operations as two halves, wing3_front + wing3_back_rcp4: the record classes
+// are bit-identical only while both stay in step -- change them together.)
 __device__ __forceinline__ double wing_sum3_rcp4(double lamP, double msa, double msb, double msc, double cs,
                                                  bool *near, double d, double *inv_d) {
   const double xa = fma(lamP, msa, -cs), xb = fma(lamP, msb, -cs), xc = fma(lamP, msc, -cs);
@@ -1312,6 +1314,7 @@ __device__ __forceinline__ ExpState exp_table_begin_scaled(double t, const doubl
   e.r = t - nf;
   return e;
 }
+// (sweep_slim_kernel.hpp has this function as two halves, exp_series_scaled + exp_finish_scaled: change them together.)
 __device__ __forceinline__ double exp_table_end_scaled(const ExpState &e) {
   // (ln2/64)^k / k!
   constexpr double L = 0.010830424696249145;

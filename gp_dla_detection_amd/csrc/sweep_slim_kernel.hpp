@@ -131,6 +131,49 @@ __device__ __forceinline__ ExpState exp_ring_begin_scaled(double t, const double
   return e;
 }
 
+// exp_table_end_scaled in two pieces, so that arithmetic which does not need the table entry can stand
+// between its request and its first use: the series in the reduced argument (no LDS data) ...
+__device__ __forceinline__ double exp_series_scaled(const ExpState &e) {
+  constexpr double L = 0.010830424696249145;  // (ln2/64)^k / k!, as in exp_table_end_scaled
+  constexpr double c1 = L, c2 = L * L / 2, c3 = L * L * L / 6, c4 = L * L * L * L / 24, c5 = L * L * L * L * L / 120;
+  double p;
+  const double c4v = c4;
+  asm("v_fma_f64 %0, %1, %2, %3" : "=v"(p) : "s"(c5), "v"(e.r), "v"(c4v));
+  asm("v_fma_f64 %0, %1, %2, %3" : "=v"(p) : "v"(p), "v"(e.r), "s"(c3));
+  asm("v_fma_f64 %0, %1, %2, %3" : "=v"(p) : "v"(p), "v"(e.r), "s"(c2));
+  asm("v_fma_f64 %0, %1, %2, %3" : "=v"(p) : "v"(p), "v"(e.r), "s"(c1));
+  return fma(p, e.r, 1.0);
+}
+// ... and the table entry times the series, scaled
+__device__ __forceinline__ double exp_finish_scaled(const ExpState &e, double p) { return ldexp(e.tabv * p, e.ni >> 6); }
+
+// wing_sum3_rcp4 in two pieces (the same operations on the same operands): the part that needs the
+// wavelength alone -- velocities, s_j, the near vote, the prefix products -- and the part that takes d.
+struct WingFront {
+  double sa, sb, sc, pab, pabc;
+};
+__device__ __forceinline__ WingFront wing3_front(double lamP, double msa, double msb, double msc, double cs, bool *near) {
+  WingFront f;
+  const double xa = fma(lamP, msa, -cs), xb = fma(lamP, msb, -cs), xc = fma(lamP, msc, -cs);
+  f.sa = fma(xa, xa, g_lines.y2[0]), f.sb = fma(xb, xb, g_lines.y2[1]), f.sc = fma(xc, xc, g_lines.y2[2]);
+  *near = min(min(hi_word(f.sa), hi_word(f.sb)), hi_word(f.sc)) < 0x408C2000u;
+  f.pab = f.sa * f.sb, f.pabc = f.pab * f.sc;
+  return f;
+}
+__device__ __forceinline__ double wing3_back_rcp4(const WingFront &f, double d, double *inv_d) {
+  const double rinv = fast_rcp(f.pabc * d);
+  *inv_d = rinv * f.pabc;
+  const double r3 = rinv * d;
+  const double rc = r3 * f.pab, r2 = r3 * f.sc;
+  const double ra = r2 * f.sb, rb = r2 * f.sa;
+  double ta = ra * kE5 + kE4, tb = rb * kE5 + kE4, tc = rc * kE5 + kE4;
+  ta = fma(ta, ra, kE3); tb = fma(tb, rb, kE3); tc = fma(tc, rc, kE3);
+  ta = fma(ta, ra, g_lines.t2[0]); tb = fma(tb, rb, g_lines.t2[1]); tc = fma(tc, rc, g_lines.t2[2]);
+  ta = fma(ta, ra, kE1); tb = fma(tb, rb, kE1); tc = fma(tc, rc, kE1);
+  ta = fma(ta, ra, 1.0); tb = fma(tb, rb, 1.0); tc = fma(tc, rc, 1.0);
+  return fma(g_lines.cwing[2], rc * tc, fma(g_lines.cwing[1], rb * tb, g_lines.cwing[0] * (ra * ta)));
+}
+
 // Epilogue pass of the slim sweep: factor_pass of sweep_kernels.hpp with the spill scattered
 // through the column map (tile, column) -> packed-triangle position.
 __device__ __forceinline__ double slim_factor_pass(const d4 (&acc)[14], const double (&xw)[kXW],
@@ -340,8 +383,21 @@ __global__ __launch_bounds__(512) void k_sweep_slim(SweepArgs a) {
   // barrier.  Measured against the alternatives on one box (tools/ab.sh, ms per launch): this
   // 149.6; three tiles per K-step over five K-steps 150.1; products stored before the burst 152.0;
   // without the explicit lgkmcnt(0) at the top of a K-step 153.1; pre-expanded records (k_sweep) 149.5.
+  //
+  // LDS latency.  Inside a chunk the ring taps and the pixel row of K-step tt + 1 are requested in K-step tt's MFMA
+  // burst, after its 11th MFMA (most B fragments are dead by then and three MFMAs, >= 190 cycles, still cover the
+  // round trip), carried in n0..n6 / n01, n23 as lam_next is, and consumed behind the lgkmcnt(0) at the top of the
+  // next K-step.  The reads stand behind this step's ring write: lanes jj = 2, 3 of step tt + 1 read what step tt
+  // writes.  A read for a step that does not exist (rn + 1 == m.steps) fetches valid LDS and is dropped.  K-step 0
+  // of a chunk has its row in the other parity's raw buffer, complete only behind the chunk barrier: it requests
+  // wavelength, taps and row itself and runs the part of the wing tier that needs the wavelength alone in front of
+  // their first use.  The exp table entry is covered by the series and the weights.  Measurements and the variants
+  // that lost: LABBOOK, "Taps and row under the MFMA burst".
   for (int c = 0; c < nchunks; ++c) {
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // (nothing of ours is in flight: see k_sweep)
+    // vmcnt(0): nothing of ours is in flight (see k_sweep).  lgkmcnt(0): no LDS request is open behind the chunk
+    // barrier either, but the compiler cannot know that no scalar load of the prologue is (they return out of order),
+    // and would make K-step 0's first use of LDS data wait for ALL of that step's requests
+    __builtin_amdgcn_s_waitcnt(0x0070);
     if (c + 1 < nchunks) issue_chunk(c + 1);
     const int par = (c & 1) * kSlimBlock;
     const double *tbuf = pinned(tb0 + par);
@@ -349,6 +405,8 @@ __global__ __launch_bounds__(512) void k_sweep_slim(SweepArgs a) {
     const double *ubuf = pinned(ub0 + par);
     double *xdst = pinned(xd0 + (kSlimBlock - par));
     double lam_next = 0.0;
+    double n0 = 0.0, n1 = 0.0, n2 = 0.0, n3 = 0.0, n4 = 0.0, n5 = 0.0, n6 = 0.0;  // taps of the next K-step
+    double2 n01 = {0.0, 0.0}, n23 = {0.0, 0.0};                                    // its pixel row
 #pragma unroll
     for (int tt = 0; tt < CH; ++tt) {
       const int rn = c * CH + tt;
@@ -360,14 +418,26 @@ __global__ __launch_bounds__(512) void k_sweep_slim(SweepArgs a) {
         const double *mine = mine0 + (size_t)tt * kSlimRec;
         const int slot_p = (4 * tt) & 15;
         const int slot_w = (slot_p + 12) & 15;
-        if (tt > 0) __builtin_amdgcn_s_waitcnt(0xC07F);  // lam_next (requested before the last burst) is here
+        if (tt > 0) __builtin_amdgcn_s_waitcnt(0xC07F);  // what the last burst requested (lam_next, taps, row) is here
         const double lamP = tt == 0 ? mine[10] : lam_next;
-        const double *g = my_ring + slot_p;
-        const double g0 = g[0], g1 = g[1], g2 = g[2], g3 = g[3], g4 = g[4], g5 = g[5], g6 = g[6];
-        const double2 p01 = *reinterpret_cast<const double2 *>(mine);
-        const double2 p23 = *reinterpret_cast<const double2 *>(mine + 2);
+        double g0 = n0, g1 = n1, g2 = n2, g3 = n3, g4 = n4, g5 = n5, g6 = n6;
+        double2 p01 = n01, p23 = n23;
+        if (tt == 0) {
+          const double *g = my_ring + slot_p;
+          g0 = g[0], g1 = g[1], g2 = g[2], g3 = g[3], g4 = g[4], g5 = g[5], g6 = g[6];
+          p01 = *reinterpret_cast<const double2 *>(mine);
+          p23 = *reinterpret_cast<const double2 *>(mine + 2);
+        }
         const double py = p01.x, pmu = p01.y, pom = p23.x, pnu = p23.y;
         __builtin_amdgcn_sched_barrier(0);
+        [[maybe_unused]] WingFront wf;
+        [[maybe_unused]] bool near = false;
+        if constexpr (LINES == 3) {
+          if (tt == 0) {  // needs the wavelength (requested first) only: runs while taps and row arrive
+            wf = wing3_front(lamP, ms_r[0], ms_r[1], ms_r[2], cs, &near);
+            __builtin_amdgcn_sched_barrier(0);
+          }
+        }
         // (2) instrument broadening for pixel 4 rn + jj: voigt.c:297-299 (symmetric taps).  In front of (1)
         // since round 5: the three-line wing tier takes this pixel's d along and returns 1/d from the same
         // v_rcp_f64 as its own three quotients (wing_sum3_rcp4): 151.06 -> 150.21 ms on one box
@@ -386,8 +456,8 @@ __global__ __launch_bounds__(512) void k_sweep_slim(SweepArgs a) {
         // (1) raw profile three K-steps ahead: voigt.c:282-292
         double total;
         if constexpr (LINES == 3) {
-          bool near;
-          total = wing_sum3_rcp4(lamP, ms_r[0], ms_r[1], ms_r[2], cs, &near, d, &inv_d);
+          if (tt > 0) wf = wing3_front(lamP, ms_r[0], ms_r[1], ms_r[2], cs, &near);
+          total = wing3_back_rcp4(wf, d, &inv_d);
 #ifndef SLIM_EXP_NONEAR  // (ablation, results wrong by construction: what the accurate tier costs)
           if (__builtin_expect(__any(near), 0)) total = total_near<3>(lamP, mult_r[0], mult_r[1], mult_r[2], nullptr, 3);
 #endif
@@ -402,10 +472,9 @@ __global__ __launch_bounds__(512) void k_sweep_slim(SweepArgs a) {
         for (int cc = 0; cc < kSlimTilesW; ++cc) bop[cc] = tl[cc * 64];
         bop[13] = ubuf[(size_t)tt * kSlimRec];  // m[0..15] of the 4 pixels in lane order: the u tile
         __builtin_amdgcn_sched_barrier(0);
-        const double raw = exp_table_end_scaled(es);
-        my_ring[slot_w] = raw;
-        my_ring[slot_w + 16] = raw;
-        // (3) weights: process_qsos.m:192-198 folded into log_mvnpdf_low_rank.m:11-15
+        const double pser = exp_series_scaled(es);
+        // (3) weights: process_qsos.m:192-198 folded into log_mvnpdf_low_rank.m:11-15.  Between the exp series and
+        // its multiply by the table entry, which was requested just before the B fragments.
         const double r = fma(-absorb, pmu, py);
         const double w = a2 * inv_d;
         const double ri = r * inv_d;
@@ -416,26 +485,42 @@ __global__ __launch_bounds__(512) void k_sweep_slim(SweepArgs a) {
           dexp += __builtin_amdgcn_frexp_exp(dprod);
           dprod = __builtin_amdgcn_frexp_mant(dprod);
         }
+        __builtin_amdgcn_sched_barrier(0);
+        const double raw = exp_finish_scaled(es, pser);
+        my_ring[slot_w] = raw;
+        my_ring[slot_w + 16] = raw;
         Operands x;
         if (tt < kXS) expand_load(kT0[tt < kXS ? tt : 0], kT1[tt < kXS ? tt : 0], x);
         if (tt + 1 < CH) lam_next = mine[kSlimRec + 10];
         __builtin_amdgcn_sched_barrier(0);
-        // (4) rank-4 update of [B | v] on the matrix cores
+        // (4) rank-4 update of [B | v] on the matrix cores, in two parts with the next K-step's requests between them
+        constexpr int kSplit = 11;
+        // vech columns 208, 209 and m columns 16..19 of this lane's pixel
+        const double2 xp = *reinterpret_cast<const double2 *>(mine + 8);
+        const double2 u01 = *reinterpret_cast<const double2 *>(mine + 4);
+        const double2 u23 = *reinterpret_cast<const double2 *>(mine + 6);
 #pragma unroll
-        for (int cc = 0; cc < 14; ++cc)
+        for (int cc = 0; cc < kSplit; ++cc)
           acc[cc] = __builtin_amdgcn_mfma_f64_16x16x4f64(cc < kSlimTilesW ? w : u, bop[cc], acc[cc], 0, 0, 0);
-        {  // vech columns 208, 209 and m columns 16..19 of this lane's pixel: 6 FMAs
-          const double2 xp = *reinterpret_cast<const double2 *>(mine + 8);
-          const double2 u01 = *reinterpret_cast<const double2 *>(mine + 4);
-          const double2 u23 = *reinterpret_cast<const double2 *>(mine + 6);
-          xw[0] = fma(w, xp.x, xw[0]);
-          xw[1] = fma(w, xp.y, xw[1]);
-          xu[0] = fma(u, u01.x, xu[0]);
-          xu[1] = fma(u, u01.y, xu[1]);
-          xu[2] = fma(u, u23.x, xu[2]);
-          xu[3] = fma(u, u23.y, xu[3]);
-        }
         if (tt < kXS) expand_store(xdst, kT0[tt < kXS ? tt : 0], kT1[tt < kXS ? tt : 0], x);
+        if (tt + 1 < CH) {
+          __builtin_amdgcn_sched_barrier(0);
+          const double *g = my_ring + ((4 * (tt + 1)) & 15);
+          n0 = g[0], n1 = g[1], n2 = g[2], n3 = g[3], n4 = g[4], n5 = g[5], n6 = g[6];
+          n01 = *reinterpret_cast<const double2 *>(mine + kSlimRec);
+          n23 = *reinterpret_cast<const double2 *>(mine + kSlimRec + 2);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+#pragma unroll
+        for (int cc = kSplit; cc < 14; ++cc)
+          acc[cc] = __builtin_amdgcn_mfma_f64_16x16x4f64(cc < kSlimTilesW ? w : u, bop[cc], acc[cc], 0, 0, 0);
+        // the 6 FMAs of the off-matrix columns
+        xw[0] = fma(w, xp.x, xw[0]);
+        xw[1] = fma(w, xp.y, xw[1]);
+        xu[0] = fma(u, u01.x, xu[0]);
+        xu[1] = fma(u, u01.y, xu[1]);
+        xu[2] = fma(u, u23.x, xu[2]);
+        xu[3] = fma(u, u23.y, xu[3]);
       }
     }
     glds_wait();      // the prefetched raw chunk and this wave's next rows have landed ...
