@@ -153,6 +153,18 @@ class MockSpectra(C.Structure):
                 ("latents", _dp), ("status", _i32p)]
 
 
+class NhiPrior(C.Structure):
+    """gpdla_nhi_prior"""
+    _fields_ = [("coeff", C.c_double * 3), ("centre", C.c_double), ("alpha", C.c_double), ("uniform_min", C.c_double),
+                ("uniform_max", C.c_double), ("lower", C.c_double), ("flat_below", C.c_double), ("Z", C.c_double)]
+
+
+class SampleDraw(C.Structure):
+    """gpdla_sample_draw"""
+    _fields_ = [("offset", _dp), ("log_nhi", _dp), ("nhi", _dp), ("lls_offset", _dp), ("lls_log_nhi", _dp),
+                ("lls_nhi", _dp)]
+
+
 SPECTRA_MAX_ABSORBERS = 8                                   # GPDLA_SPECTRA_MAX_ABSORBERS
 SPECTRA_MAP, SPECTRA_MOMENTS, SPECTRA_CONTINUUM = 1, 2, 4   # GPDLA_SPECTRA_* product bits
 SPECTRA_WEIGHTS_NONE, SPECTRA_WEIGHTS_RESIDENT, SPECTRA_WEIGHTS_HOST = 0, 1, 2
@@ -236,6 +248,13 @@ SYMBOLS = [
                                    C.c_double, C.c_double, _dp, C.c_int]),
     ("gpdla_mock_validate", C.c_int, [C.POINTER(MockRequest), C.c_int64]),
     ("gpdla_batch_draw_mocks", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(MockRequest), C.POINTER(MockSpectra)]),
+    ("gpdla_samples_kde", C.c_int, [C.c_int64, _dp, C.c_int64, _dp, C.c_double, _dp, _dp, C.c_int]),
+    ("gpdla_samples_fit_prior", C.c_int, [C.c_int64, _dp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
+                                          C.c_double, C.c_double, C.c_double, C.POINTER(NhiPrior), C.c_int]),
+    ("gpdla_samples_prior_eval", C.c_int, [C.POINTER(NhiPrior), C.c_int64, _dp, _dp, _dp, C.c_int]),
+    ("gpdla_samples_halton", C.c_int, [C.c_int64, C.c_int64, C.c_int, _i32p, _dp, C.c_int]),
+    ("gpdla_samples_draw", C.c_int, [C.POINTER(NhiPrior), C.c_int64, C.c_int64, _dp, C.c_int, C.c_double, C.c_double,
+                                     C.POINTER(SampleDraw), C.c_int]),
     ("gpdla_debug_near_poly", C.c_int, [C.c_int, C.c_double, _dp, _dp]),
     ("gpdla_debug_prepared_rows", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, _dp, C.c_int64, _i64p]),
     ("gpdla_debug_philox4x32_10", None, [_u32p, _u32p, _u32p]),

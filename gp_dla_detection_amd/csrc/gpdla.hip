@@ -34,6 +34,7 @@
 #include "stats_kernels.hpp"
 #include "spectra_kernels.hpp"
 #include "mock_kernels.hpp"
+#include "sample_kernels.hpp"
 #include "training_kernels.hpp"
 #include "training_mfma_kernels.hpp"
 
@@ -49,5 +50,6 @@ using namespace gpdla;
 #include "host_stats.hpp"
 #include "host_spectra.hpp"
 #include "host_mock.hpp"
+#include "host_samples.hpp"
 // libgpdla_legacy.so (-DGPDLA_WITH_LEGACY): the superseded kernels and their environment switches
 #include "host_legacy.hpp"

@@ -272,6 +272,35 @@ def load_dla_samples(path: str) -> dict:
     return out
 
 
+#: generate_dla_samples.m:59-61 + set_lls_parameters.m:59-71, in the reference's order
+DLA_SAMPLE_VECTORS = ("offset_samples", "log_nhi_samples", "nhi_samples", "lls_log_nhi_samples", "lls_nhi_samples")
+DLA_SAMPLE_SCALARS = ("uniform_min_log_nhi", "uniform_max_log_nhi", "fit_min_log_nhi", "fit_max_log_nhi", "alpha",
+                      "Z_lls", "Z_dla")
+
+
+def save_dla_samples(path: str, samples: dict) -> None:
+    """dla_samples.mat as generate_dla_samples.m:59-63 saves it (``-v7.3``): the sample vectors as ROW
+    vectors (stored [S x 1]: the reference's DLACatalogue reads ``f['log_nhi_samples'][:, 0]``), the
+    scalars as 1 x 1.  Of the names above, those present in ``samples`` are written, nothing else."""
+    out = {}
+    for name in DLA_SAMPLE_SCALARS[:5] + DLA_SAMPLE_VECTORS + DLA_SAMPLE_SCALARS[5:]:
+        if name in samples:
+            out[name] = (np.asarray(samples[name], dtype=np.float64).reshape(1, -1) if name in DLA_SAMPLE_VECTORS
+                         else np.float64(samples[name]))
+    missing = [n for n in DLA_SAMPLE_VECTORS[:3] if n not in out]
+    if missing:
+        raise KeyError(f"samples lack {missing}")
+    savemat73(path, out)
+
+
+def load_sample_normalisers(path: str):
+    """``(Z_lls, Z_dla)`` of set_lls_parameters.m:70-71 when the samples file carries both, else None."""
+    m = _load_mat(path, ("Z_lls", "Z_dla"))
+    if "Z_lls" not in m or "Z_dla" not in m:
+        return None
+    return float(_vec(m["Z_lls"])[0]), float(_vec(m["Z_dla"])[0])
+
+
 def load_catalog(path: str, names=("z_qsos", "thing_ids", "plates", "mjds", "fiber_ids", "snrs",
                                    "filter_flags", "los_inds", "dla_inds")) -> dict:
     """catalog.mat (build_catalogs.m:86-91): the per-quasar columns as flat vectors.  ``los_inds`` /

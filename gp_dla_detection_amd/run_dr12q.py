@@ -108,7 +108,8 @@ def run(preloaded_file: str, catalog_file: str, learned_file: str, samples_file:
     """One rank of the sharded file-to-file run (see the module docstring).
 
     ``prior_catalog``: ``{"z_qsos", "dla_ind"}`` of the training release (``api.prepare_prior``);
-    multi-DLA runs also need ``Z_lls`` / ``Z_dla`` (set_lls_parameters.m:59-71).
+    multi-DLA runs also need ``Z_lls`` / ``Z_dla`` (set_lls_parameters.m:59-71): given here, or -- when
+    neither is -- read from a samples file that carries both (``samples.generate_dla_samples(lls=True)``).
     Host memory is bounded by ONE batch: each batch's results are downloaded into a page-locked
     staging buffer, its per-sample tables are handed to the chunk writer from there, and only the
     per-quasar variables (a few hundred bytes per quasar) are kept for the end of the file -- the
@@ -156,10 +157,13 @@ def run(preloaded_file: str, catalog_file: str, learned_file: str, samples_file:
             nloc = hi - lo
             z_sel = z_all[sel]
             if multi:
-                if Z_lls is None or Z_dla is None:
+                zl, zd = Z_lls, Z_dla
+                if zl is None and zd is None:   # neither given: the samples file may carry them (samples.py)
+                    zl, zd = io.load_sample_normalisers(samples_file) or (None, None)
+                if zl is None or zd is None:
                     raise ValueError("a multi-DLA run needs Z_lls and Z_dla (set_lls_parameters.m:59-71)")
                 lp_no, lp_lls, lp_dla = dla_existence_prior_multi(prior_catalog["z_qsos"], prior_catalog["dla_ind"],
-                                                                  z_sel[lo:hi], Z_lls, Z_dla, p)
+                                                                  z_sel[lo:hi], zl, zd, p)
                 ncol = _lib.summary_cols_multi(md)
             else:
                 lp_no, lp_dla = dla_existence_prior(prior_catalog["z_qsos"], prior_catalog["dla_ind"], z_sel[lo:hi], p)
@@ -290,8 +294,9 @@ def main(argv=None):
     ap.add_argument("--out", required=True, help="output directory for the chunk files")
     ap.add_argument("--name", default="dr12q", help="test_set_name")
     ap.add_argument("--multi", action="store_true", help="multi-DLA driver (process_qsos_multiple_dlas_meanflux)")
-    ap.add_argument("--z-lls", type=float, default=None)
-    ap.add_argument("--z-dla", type=float, default=None)
+    ap.add_argument("--z-lls", type=float, default=None,
+                    help="Z_lls of set_lls_parameters.m (default, with --z-dla also absent: the samples file's)")
+    ap.add_argument("--z-dla", type=float, default=None, help="Z_dla, likewise")
     ap.add_argument("--max-dlas", type=int, default=4)
     ap.add_argument("--batch", type=int, default=None, help="quasars per HBM-resident batch")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL)")

@@ -690,6 +690,73 @@ int gpdla_mock_validate(const gpdla_mock_request *request, int64_t num_quasars);
 int gpdla_batch_draw_mocks(gpdla_context *ctx, gpdla_batch *batch, const gpdla_mock_request *request,
                            gpdla_mock_spectra *out);
 
+/* ---------------------------------------------------------------------------------------------
+ * DLA parameter samples and LLS normalisers: what generate_dla_samples.m,
+ * multi_dlas/generate_dla_samples_multi.m and multi_dlas/set_lls_parameters.m compute from the
+ * catalogue's log10 N_HI values.  Additive: GPDLA_ABI_VERSION is unchanged.  Every pointer is the
+ * caller's, in host memory; arguments are checked before the GPU is touched.
+ *
+ * gpdla_samples_kde: density[g] = 1 / (N h) Sum_j phi((points[g] - values[j]) / h), phi the standard
+ * normal density, no boundary correction (ksdensity's defaults).  bandwidth > 0 is used as given;
+ * bandwidth == 0 takes h = sig (4 / (3 N))^(1/5), sig = median(|v - median(v)|) / 0.6745, and
+ * sig == 0 is GPDLA_ERR_INVALID_ARGUMENT.  *bandwidth_used (optional) receives h.  N >= 2, any
+ * num_points >= 0.  The sums run in a fixed order: the result depends on the inputs only.
+ *
+ * gpdla_nhi_prior: p(t) = alpha g(t) / Z + (1 - alpha) U[uniform_min, uniform_max](t) on
+ * [lower, GPDLA_SAMPLES_UPPER], log g(t) = coeff[0] + coeff[1] s + coeff[2] s^2 with s = t - centre;
+ * with a finite flat_below, g(t) = g(flat_below) for t < flat_below (NaN: no such break);
+ * Z = integral of g over [lower, GPDLA_SAMPLES_UPPER]; F(x) = integral of p over [lower, x].
+ *
+ * gpdla_samples_fit_prior: the KDE of `values` on GPDLA_SAMPLES_FIT_POINTS equally spaced points of
+ * [fit_min, fit_max] (bandwidth as above), the least-squares quadratic through its logarithm (about
+ * centre = (fit_min + fit_max) / 2, by orthogonal polynomials), and Z.  The other fields of *prior are
+ * copied from the arguments.  A KDE that underflows to 0 on the grid is GPDLA_ERR_INVALID_ARGUMENT.
+ *
+ * gpdla_samples_prior_eval: pdf[i] = p(x[i]) and cdf[i] = F(x[i]) (either may be NULL); F is 0 at and
+ * below lower and F(GPDLA_SAMPLES_UPPER) at and above the upper limit.
+ *
+ * gpdla_samples_halton: out[i][d] = Sum_j pi_b(d_j) b^-(j+1) for b = bases[d] (2 .. GPDLA_HALTON_MAX_BASE,
+ * at most GPDLA_HALTON_MAX_DIMS of them), d_j the base-b digits of index first_index + i, pi_b the
+ * reverse-radix ("RR2") permutation: the ceil(log2 b)-bit bit reversals of 0, 1, 2, ... in order,
+ * those >= b dropped.  Each value is the correctly rounded quotient of two exact integers.  Index 0
+ * is the origin.  first_index >= 0 and first_index + num <= 2^32.
+ *
+ * gpdla_samples_draw: sample i (index first_index + i) takes the points of bases 2, 3, 5 -- or row i
+ * of `sequence` ([num][sequence_dims], sequence_dims 2 or 3, values in [0, 1]) -- as (u1, u2, u3):
+ * offset = u1, log_nhi = F^-1(u2) (u2 == 0: lower exactly; u2 >= F(upper): the upper limit; else
+ * |F(x) - u2| <= 1e-13 or x bracketed to one ulp), nhi = 10^log_nhi, and when out->lls_nhi is given
+ * lls_offset = u3, lls_log_nhi = lls_lower + (lls_upper - lls_lower) u3, lls_nhi = 10^lls_log_nhi.
+ * ------------------------------------------------------------------------------------------- */
+#define GPDLA_SAMPLES_UPPER 25.0
+#define GPDLA_SAMPLES_FIT_POINTS 1000
+#define GPDLA_HALTON_MAX_DIMS 8
+#define GPDLA_HALTON_MAX_BASE 64
+typedef struct {
+  double coeff[3];                   /* log g about `centre`: constant, linear, quadratic */
+  double centre;
+  double alpha;                      /* in [0, 1] */
+  double uniform_min, uniform_max;
+  double lower;                      /* F(lower) = 0 */
+  double flat_below;                 /* NaN: none */
+  double Z;
+} gpdla_nhi_prior;
+typedef struct {
+  double *offset, *log_nhi, *nhi;               /* [num]; required */
+  double *lls_offset, *lls_log_nhi, *lls_nhi;   /* [num]; all three or none */
+} gpdla_sample_draw;
+int gpdla_samples_kde(int64_t num_values, const double *values, int64_t num_points, const double *points,
+                      double bandwidth, double *density, double *bandwidth_used, int device_id);
+int gpdla_samples_fit_prior(int64_t num_values, const double *values, double fit_min, double fit_max, double alpha,
+                            double uniform_min, double uniform_max, double lower, double flat_below,
+                            double bandwidth, gpdla_nhi_prior *prior, int device_id);
+int gpdla_samples_prior_eval(const gpdla_nhi_prior *prior, int64_t num_points, const double *x, double *pdf,
+                             double *cdf, int device_id);
+int gpdla_samples_halton(int64_t first_index, int64_t num, int num_bases, const int32_t *bases, double *out,
+                         int device_id);
+int gpdla_samples_draw(const gpdla_nhi_prior *prior, int64_t first_index, int64_t num, const double *sequence,
+                       int sequence_dims, double lls_lower, double lls_upper, gpdla_sample_draw *out,
+                       int device_id);
+
 #ifdef __cplusplus
 }
 #endif
