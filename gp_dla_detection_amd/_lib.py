@@ -41,6 +41,7 @@ _i64p = C.POINTER(C.c_int64)
 _i32p = C.POINTER(C.c_int32)
 _u8p = C.POINTER(C.c_uint8)
 _u32p = C.POINTER(C.c_uint32)
+_f32p = C.POINTER(C.c_float)
 
 
 # gpdla_status (include/gpdla.h)
@@ -165,6 +166,13 @@ class SampleDraw(C.Structure):
                 ("lls_nhi", _dp)]
 
 
+class PreloadConfig(C.Structure):
+    """gpdla_preload_config"""
+    _fields_ = [("loading_min_lambda", C.c_double), ("loading_max_lambda", C.c_double),
+                ("normalization_min_lambda", C.c_double), ("normalization_max_lambda", C.c_double),
+                ("min_lambda", C.c_double), ("max_lambda", C.c_double), ("min_num_pixels", C.c_int64)]
+
+
 SPECTRA_MAX_ABSORBERS = 8                                   # GPDLA_SPECTRA_MAX_ABSORBERS
 SPECTRA_MAP, SPECTRA_MOMENTS, SPECTRA_CONTINUUM = 1, 2, 4   # GPDLA_SPECTRA_* product bits
 SPECTRA_WEIGHTS_NONE, SPECTRA_WEIGHTS_RESIDENT, SPECTRA_WEIGHTS_HOST = 0, 1, 2
@@ -255,6 +263,8 @@ SYMBOLS = [
     ("gpdla_samples_halton", C.c_int, [C.c_int64, C.c_int64, C.c_int, _i32p, _dp, C.c_int]),
     ("gpdla_samples_draw", C.c_int, [C.POINTER(NhiPrior), C.c_int64, C.c_int64, _dp, C.c_int, C.c_double, C.c_double,
                                      C.POINTER(SampleDraw), C.c_int]),
+    ("gpdla_preload_spectra", C.c_int, [C.c_int64, _i64p, _f32p, _f32p, _f32p, _i32p, _dp, _u8p, C.POINTER(PreloadConfig),
+                                        _i64p, _dp, _dp, _dp, _u8p, _dp, C.c_int]),
     ("gpdla_debug_near_poly", C.c_int, [C.c_int, C.c_double, _dp, _dp]),
     ("gpdla_debug_prepared_rows", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, _dp, C.c_int64, _i64p]),
     ("gpdla_debug_philox4x32_10", None, [_u32p, _u32p, _u32p]),

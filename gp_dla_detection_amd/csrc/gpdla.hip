@@ -35,6 +35,7 @@
 #include "spectra_kernels.hpp"
 #include "mock_kernels.hpp"
 #include "sample_kernels.hpp"
+#include "preload_kernels.hpp"
 #include "training_kernels.hpp"
 #include "training_mfma_kernels.hpp"
 
@@ -51,5 +52,6 @@ using namespace gpdla;
 #include "host_spectra.hpp"
 #include "host_mock.hpp"
 #include "host_samples.hpp"
+#include "host_preload.hpp"
 // libgpdla_legacy.so (-DGPDLA_WITH_LEGACY): the superseded kernels and their environment switches
 #include "host_legacy.hpp"

@@ -389,6 +389,45 @@ def _load_h5cells():
     return _h5cells or None
 
 
+_FITSSPEC_SRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "fitsspec.c")
+_FITSSPEC_LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libgpdla_fitsspec.so")
+_fitsspec = None
+
+
+def build_fitsspec(force: bool = False) -> str:
+    """gcc -O2 -fopenmp csrc/fitsspec.c -> csrc/libgpdla_fitsspec.so (host code: no GPU involved)."""
+    import subprocess
+    if force or not os.path.exists(_FITSSPEC_LIB) or os.path.getmtime(_FITSSPEC_LIB) < os.path.getmtime(_FITSSPEC_SRC):
+        tmp = f"{_FITSSPEC_LIB}.{os.getpid()}.tmp"  # published atomically, as build_h5cells does
+        try:
+            subprocess.check_call(["gcc", "-O2", "-fPIC", "-shared", "-fopenmp", "-Wall", _FITSSPEC_SRC, "-o", tmp],
+                                  stderr=subprocess.DEVNULL if not force else None)
+            os.replace(tmp, _FITSSPEC_LIB)
+        finally:
+            if os.path.exists(tmp):
+                os.remove(tmp)
+    return _FITSSPEC_LIB
+
+
+def _load_fitsspec():
+    """The native spec-file reader, or None when it cannot be built / loaded: fits.read_spec_files then
+    reads every file with the Python reader -- same arrays, slower."""
+    global _fitsspec
+    if _fitsspec is None:
+        import ctypes as C
+        try:
+            lib = C.CDLL(_FITSSPEC_LIB if os.path.exists(_FITSSPEC_LIB) else build_fitsspec())
+            lib.gpdla_fitsspec_sizes.restype = C.c_int
+            lib.gpdla_fitsspec_sizes.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p,
+                                                 C.c_int, C.c_int]
+            lib.gpdla_fitsspec_read.restype = C.c_int
+            lib.gpdla_fitsspec_read.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 7 + [C.c_char_p, C.c_int, C.c_int]
+            _fitsspec = lib
+        except Exception:  # (a missing compiler must not stop a run: the Python reader is complete)
+            _fitsspec = False
+    return _fitsspec or None
+
+
 class PreloadedReader:
     """Random access to the ragged cell arrays of a ``-v7.3`` preloaded_qsos.mat (preload_qsos.m:64-79):
     the file is opened once, the four reference tables are read, and a rank then dereferences only
@@ -509,6 +548,76 @@ class PreloadedReader:
 
     def __exit__(self, *exc):
         self.close()
+
+
+#: preload_qsos.m:73-77: the five scalars, then the four cell arrays and all_normalizers
+PRELOADED_SCALARS = ("loading_min_lambda", "loading_max_lambda", "normalization_min_lambda",
+                     "normalization_max_lambda", "min_num_pixels")
+
+
+class PreloadedStreamWriter:
+    """preloaded_qsos.mat (preload_qsos.m:73-79, ``-v7.3``) for spectra that arrive block by block: every
+    block's cells are written when :meth:`append` gets them -- column vectors, ``all_pixel_mask`` logical,
+    a quasar without pixels as the 0 x 0 empty ``cell(n, 1)`` leaves -- and :meth:`finish` writes the four
+    N x 1 cell arrays that point at them, ``all_normalizers`` and the five scalars."""
+
+    def __init__(self, path: str, params=None, compress: bool = False):
+        from .parameters import Parameters
+        self.params = params or Parameters()
+        self.compress = compress
+        self.w = _MatWriter(path)
+        self.w.w.create_group("#refs#")
+        self._cells = {k: [] for k in PreloadedReader.KEYS}
+        self._norm = []
+
+    def append(self, block: dict) -> None:
+        """One block in the shape ``preload.preload_csr`` returns (offsets, wavelengths, flux,
+        noise_variance, pixel_mask, all_normalizers)."""
+        off = np.asarray(block["offsets"], dtype=np.int64)
+        for key, name, dt in zip(PreloadedReader.KEYS, ("wavelengths", "flux", "noise_variance", "pixel_mask"),
+                                 (np.float64, np.float64, np.float64, bool)):
+            flat = np.asarray(block[name]).astype(dt, copy=False)
+            for i in range(off.size - 1):
+                v = flat[off[i]:off[i + 1]]
+                self.w._refs += 1
+                self._cells[key].append(self.w.put(f"#refs#/{self.w._refs:08d}",
+                                                   v.reshape(-1, 1) if v.size else np.zeros((0, 0), dtype=dt), self.compress))
+        self._norm.append(np.asarray(block["all_normalizers"], dtype=np.float64).reshape(-1))
+
+    def finish(self) -> None:
+        try:
+            p = self.params
+            for k in PRELOADED_SCALARS:
+                self.w.put(k, np.float64(getattr(p, k)))
+            for key, refs in self._cells.items():
+                if not refs:
+                    self.w.w.create_dataset(key, np.array([0, 0], dtype=np.uint64),
+                                            attrs={"MATLAB_class": "cell", "MATLAB_empty": np.int32(1)})
+                    continue
+                arr = np.empty((1, len(refs)), dtype=object)  # an N x 1 cell, dimensions reversed
+                arr[0, :] = refs
+                self.w.w.create_dataset(key, arr, attrs={"MATLAB_class": "cell"})
+            self.w.put("all_normalizers", np.concatenate(self._norm) if self._norm else np.zeros((0, 1)))
+        finally:
+            self.w.close()
+
+    def abort(self) -> None:
+        try:
+            self.w.close()
+        except Exception:
+            pass
+
+
+def save_preloaded_qsos(path: str, blocks, params=None, compress: bool = False) -> None:
+    """preloaded_qsos.mat from one block (a dict) or an iterable of blocks, streamed block by block."""
+    w = PreloadedStreamWriter(path, params, compress)
+    try:
+        for b in ([blocks] if isinstance(blocks, dict) else blocks):
+            w.append(b)
+    except BaseException:
+        w.abort()
+        raise
+    w.finish()
 
 
 # ---------------------------------------------------------------------------------------------

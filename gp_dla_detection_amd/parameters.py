@@ -43,6 +43,21 @@ class Parameters:
     initial_c_0: float = 0.1
     initial_tau_0: float = 0.0023
     initial_beta: float = 3.65
+    # preloading the spectra (preload_qsos.m): set_parameters.m:21-30
+    loading_min_lambda: float = 910.0            # :21  rest range kept in preloaded_qsos.mat
+    loading_max_lambda: float = 1217.0           # :22
+    min_num_pixels: int = 200                    # :26  fewer unmasked pixels in the modelled range: flag bit 3
+    normalization_min_lambda: float = 1310.0     # :29  rest range whose median flux normalises a spectrum
+    normalization_max_lambda: float = 1325.0     # :30
+
+    def __post_init__(self):
+        if not (self.loading_min_lambda <= self.min_lambda <= self.max_lambda <= self.loading_max_lambda):
+            raise ValueError(f"the loading range [{self.loading_min_lambda}, {self.loading_max_lambda}] must contain "
+                             f"the modelling range [{self.min_lambda}, {self.max_lambda}]")
+        if not self.normalization_min_lambda <= self.normalization_max_lambda:
+            raise ValueError("normalization_min_lambda exceeds normalization_max_lambda")
+        if self.min_num_pixels < 0:
+            raise ValueError("min_num_pixels is negative")
 
     def min_z_dla(self, wavelengths, z_qso):
         """set_parameters.m:70-73"""

@@ -304,3 +304,59 @@ def write_file_set(directory: str, num_quasars: int = 24, num_samples: int = 256
             f.write("%d\n" % cat["thing_ids"][i])
     return dict(paths=paths, model=model, samples=samples, spectra=spectra, catalog=cat, prior=prior,
                 test_ind=test_ind, Z_lls=0.31, Z_dla=0.69)
+
+
+def make_raw_spectra(num: int, first_index: int = 0, seed: int = 4321) -> list:
+    """``num`` quasars as an SDSS spec file holds them: the whole BOSS grid, float32 ``flux`` (in
+    10^-17 erg/s/cm^2/A: a smooth continuum of a random amplitude, Lyman-alpha forest blueward of the
+    emission line, noise), float32 ``loglam`` and ``ivar``, int32 ``and_mask``.  5 % of the pixels are bad:
+    half through ``ivar`` = 0, half through the BRIGHTSKY bit (bit 23) of ``and_mask``; other mask bits
+    are scattered over good pixels."""
+    z = sample_dr12q_redshifts(first_index + num, seed)[first_index:]
+    out = []
+    for i in range(num):
+        rng = np.random.default_rng(SPECTRUM_SEED0 + 15485863 * 1000 + first_index + i)
+        loglam = (BOSS_LOGLAM0 + 1e-4 * np.arange(BOSS_NPIX)).astype(np.float32)
+        rest = 10.0 ** loglam.astype(np.float64) / (1 + z[i])
+        amp = float(rng.uniform(1.0, 30.0))
+        cont = amp * (rest / 1300.0) ** -1.5 * (1 + 0.8 * np.exp(-0.5 * ((rest - 1215.67) / 12.0) ** 2))
+        cont = np.where(rest < 1215.67, cont * np.exp(-0.0023 * (1 + 10.0 ** loglam / 1215.67 - 1) ** 3.65), cont)
+        sigma = amp * 10.0 ** rng.uniform(-1.5, -0.5, size=BOSS_NPIX)
+        flux = (cont + sigma * rng.standard_normal(BOSS_NPIX)).astype(np.float32)
+        ivar = (1.0 / sigma ** 2).astype(np.float32)
+        and_mask = np.where(rng.uniform(size=BOSS_NPIX) < 0.02, 1 << rng.integers(16, 23, size=BOSS_NPIX), 0).astype(np.int32)
+        u = rng.uniform(size=BOSS_NPIX)
+        ivar[u < 0.025] = 0.0
+        and_mask[(u >= 0.025) & (u < 0.05)] |= 1 << 23
+        out.append(dict(loglam=loglam, flux=flux, ivar=ivar, and_mask=and_mask, z_qso=float(z[i])))
+    return out
+
+
+def write_spec_files(directory: str, spectra, catalog: dict) -> list:
+    """The raw side of a synthetic set (:func:`make_raw_spectra`) as SDSS spec files under
+    ``directory``: ``PLATE/spec-PLATE-MJD-FIBER.fits`` from the catalogue's ``plates`` / ``mjds`` /
+    ``fiber_ids``, HDU 1 with the eight float32 / int32 columns of a real "lite" file (flux, loglam,
+    ivar, and_mask, or_mask, wdisp, sky, model) and a second table HDU after it, as the real files
+    carry.  Returns the paths."""
+    import os
+
+    from . import fits
+    from .preload import spec_filename
+    paths = []
+    for i, s in enumerate(spectra):
+        path = spec_filename(directory, catalog["plates"][i], catalog["mjds"][i], catalog["fiber_ids"][i])
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        n = np.asarray(s["flux"]).size
+        f32 = lambda a: np.asarray(a, dtype=np.float32)
+        coadd = [("flux", f32(s["flux"])), ("loglam", f32(s["loglam"])), ("ivar", f32(s["ivar"])),
+                 ("and_mask", np.asarray(s["and_mask"], dtype=np.int32)),
+                 ("or_mask", np.asarray(s["and_mask"], dtype=np.int32) | 1), ("wdisp", np.full(n, 1.1, np.float32)),
+                 ("sky", np.full(n, 3.0, np.float32)), ("model", f32(s["flux"]) * np.float32(0.5))]
+        spall = [("PLATE", np.array([catalog["plates"][i]], dtype=np.int32)), ("MJD", np.array([catalog["mjds"][i]], dtype=np.int32)),
+                 ("FIBERID", np.array([catalog["fiber_ids"][i]], dtype=np.int32)), ("Z", np.array([s.get("z_qso", 0.0)])),
+                 ("CLASS", np.array([b"QSO"]))]
+        fits.write_bintable(path, [coadd, spall], primary_cards=[("PLATEID", int(catalog["plates"][i])),
+                                                                 ("MJD", int(catalog["mjds"][i])),
+                                                                 ("FIBERID", int(catalog["fiber_ids"][i]))])
+        paths.append(path)
+    return paths

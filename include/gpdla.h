@@ -757,6 +757,40 @@ int gpdla_samples_draw(const gpdla_nhi_prior *prior, int64_t first_index, int64_
                        int sequence_dims, double lls_lower, double lls_upper, gpdla_sample_draw *out,
                        int device_id);
 
+/* ---------------------------------------------------------------------------------------------
+ * Preloading spectra: the columns of SDSS spec files -> the normalised, truncated
+ * spectra of preloaded_qsos.mat, as read_spec.m:27-38 and preload_qsos.m:26-67 compute them.
+ * Additive: GPDLA_ABI_VERSION is unchanged.
+ *
+ * Input: a raw CSR set (quasar i holds pixels offsets[i] .. offsets[i+1]) of the float32 columns
+ * flux, loglam, ivar and the int32 column and_mask, one redshift per quasar, and filter_flags[]
+ * (in/out).  A quasar whose flag is not 0 on entry is not looked at.  For the others, per pixel in
+ * fp64: wavelength = 10^loglam, noise_variance = 1 / ivar, pixel_mask = (ivar == 0) | bit 23 of
+ * and_mask (0-based; MATLAB's bitget(and_mask, 24)), rest = wavelength / (1 + z).  normalizers[i] =
+ * the median of the non-NaN flux of the unmasked pixels with rest in [normalization_min_lambda,
+ * normalization_max_lambda] (mean of the middle two for an even count); none: filter_flags[i] |= 4.
+ * Fewer than min_num_pixels unmasked pixels with rest in [min_lambda, max_lambda]: filter_flags[i]
+ * |= 8.  A quasar flagged on entry or here keeps no pixel and normaliser 0.  Otherwise the pixels
+ * with rest in [loading_min_lambda, loading_max_lambda], masked or not, plus the nearest unmasked
+ * pixel below the first and above the last of them (where one exists) are kept in pixel order, with
+ * flux / normaliser and noise_variance / normaliser^2.
+ *
+ * Output: CSR (out_offsets[num_quasars + 1]) wavelengths, flux, noise_variance, pixel_mask; the
+ * caller sizes these four by the INPUT pixel count offsets[num_quasars].  Bit-identical run to run
+ * and independent of how a set is split into calls.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct {
+  double loading_min_lambda, loading_max_lambda;             /* set_parameters.m:21-22 */
+  double normalization_min_lambda, normalization_max_lambda; /* :29-30 */
+  double min_lambda, max_lambda;                             /* :33-34 */
+  int64_t min_num_pixels;                                    /* :26 */
+} gpdla_preload_config;
+int gpdla_preload_spectra(int64_t num_quasars, const int64_t *offsets, const float *flux, const float *loglam,
+                          const float *ivar, const int32_t *and_mask, const double *z_qsos, uint8_t *filter_flags,
+                          const gpdla_preload_config *config, int64_t *out_offsets, double *wavelengths,
+                          double *out_flux, double *noise_variance, uint8_t *pixel_mask, double *normalizers,
+                          int device_id);
+
 #ifdef __cplusplus
 }
 #endif
