@@ -173,6 +173,21 @@ class PreloadConfig(C.Structure):
                 ("min_lambda", C.c_double), ("max_lambda", C.c_double), ("min_num_pixels", C.c_int64)]
 
 
+class SummaryRequest(C.Structure):
+    """gpdla_summary_request"""
+    _fields_ = [("num_models", C.c_int32), ("num_probabilities", C.c_int32), ("probabilities", C.c_double * 8),
+                ("num_thresholds", C.c_int32), ("thresholds", C.c_double * 4)]
+
+
+class ParameterSummaries(C.Structure):
+    """gpdla_parameter_summaries"""
+    _fields_ = [("mean_z", _dp), ("std_z", _dp), ("mean_log_nhi", _dp), ("std_log_nhi", _dp), ("cov", _dp),
+                ("quantiles_z", _dp), ("quantiles_log_nhi", _dp), ("exceedance", _dp), ("effective_samples", _dp),
+                ("status", _i32p)]
+
+
+POSTERIOR_MAX_MODELS, POSTERIOR_MAX_PROBABILITIES, POSTERIOR_MAX_THRESHOLDS = 4, 8, 4   # GPDLA_POSTERIOR_MAX_*
+POSTERIOR_UNUSABLE, POSTERIOR_NAN_RANGE = 1, 2                                          # status bits
 SPECTRA_MAX_ABSORBERS = 8                                   # GPDLA_SPECTRA_MAX_ABSORBERS
 SPECTRA_MAP, SPECTRA_MOMENTS, SPECTRA_CONTINUUM = 1, 2, 4   # GPDLA_SPECTRA_* product bits
 SPECTRA_WEIGHTS_NONE, SPECTRA_WEIGHTS_RESIDENT, SPECTRA_WEIGHTS_HOST = 0, 1, 2
@@ -265,6 +280,11 @@ SYMBOLS = [
                                      C.POINTER(SampleDraw), C.c_int]),
     ("gpdla_preload_spectra", C.c_int, [C.c_int64, _i64p, _f32p, _f32p, _f32p, _i32p, _dp, _u8p, C.POINTER(PreloadConfig),
                                         _i64p, _dp, _dp, _dp, _u8p, _dp, C.c_int]),
+    ("gpdla_stats_parameter_summaries", C.c_int, [C.c_int64, C.c_int64, _dp, C.c_int64, _u32p, _dp, _dp, _dp, _dp,
+                                                  C.POINTER(SummaryRequest), C.POINTER(ParameterSummaries), C.c_int]),
+    ("gpdla_batch_parameter_summaries", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _i64p, C.c_int64,
+                                                  C.POINTER(SummaryRequest), C.POINTER(ParameterSummaries)]),
+    ("gpdla_debug_last_summaries_ms", C.c_double, []),
     ("gpdla_debug_near_poly", C.c_int, [C.c_int, C.c_double, _dp, _dp]),
     ("gpdla_debug_prepared_rows", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, _dp, C.c_int64, _i64p]),
     ("gpdla_debug_philox4x32_10", None, [_u32p, _u32p, _u32p]),

@@ -188,6 +188,9 @@ class Context:
         _lib.check(self.lib.gpdla_context_set_samples(self._h, C.byref(s)))
         self.num_samples = int(s.num_dla_samples)
         self.has_lls_samples = samples.get("lls_nhi_samples") is not None
+        # scales of log N for Batch.parameter_summaries' correlation floor (DLA table, sub-DLA table)
+        self._log_nhi_scale = [float(np.max(np.abs(samples["log_nhi_samples"]))) if samples.get("log_nhi_samples") is not None else np.nan,
+                               float(np.max(np.abs(np.log10(samples["lls_nhi_samples"])))) if self.has_lls_samples else np.nan]
 
     def set_timing(self, enabled: bool):
         _lib.check(self.lib.gpdla_context_set_timing(self._h, int(bool(enabled))))
@@ -398,6 +401,33 @@ class Batch:
                 out[name] = np.empty(total)
                 setattr(ms, name, out[name].ctypes.data_as(_dp))
         _lib.check(lib.gpdla_batch_model_spectra(self.ctx._h, self._h, C.byref(rq), C.byref(ms)))
+        return out
+
+    # ---- parameter summaries ----
+
+    def parameter_summaries(self, selection=None, multi: bool = False, sub_dla: bool = False, probabilities=None,
+                            thresholds=None, num_models: int | None = None) -> dict:
+        """Credible intervals and moments of the absorber parameters of the selected quasars from the
+        batch's RESIDENT sample tables (gpdla_batch_parameter_summaries) after :meth:`process`
+        (``multi=False``) or :meth:`process_multi` (``multi=True``: all ``max_dlas`` models, slots
+        gathered through the resident ``base_sample_inds``; ``sub_dla``: the sub-DLA table with the LLS
+        column densities, one model).  No second sweep and no download of the table.  Returns what
+        :func:`posteriors.parameter_summaries` returns, plus ``selection``."""
+        from . import posteriors
+        p, t = posteriors.check_request(posteriors.DEFAULT_PROBABILITIES if probabilities is None else probabilities,
+                                        posteriors.DEFAULT_THRESHOLDS if thresholds is None else thresholds)
+        sel = np.arange(self.num_quasars, dtype=np.int64) if selection is None else \
+            np.ascontiguousarray(selection, dtype=np.int64).reshape(-1)
+        md = int(num_models) if num_models is not None else (self.max_dlas if (multi and not sub_dla) else 1)
+        out, ps = posteriors._outputs(sel.size, md, len(p), len(t))
+        rq = posteriors._request(md, p, t)
+        _lib.check(self.ctx.lib.gpdla_batch_parameter_summaries(
+            self.ctx._h, self._h, int(bool(multi)), int(bool(sub_dla)), sel.ctypes.data_as(C.POINTER(C.c_int64)),
+            sel.size, C.byref(rq), C.byref(ps)))
+        res = self.download_multi(with_samples=False) if self.max_dlas else self.download(with_samples=False)
+        z_min, z_max = res["min_z_dlas"][sel], res["max_z_dlas"][sel]
+        out = posteriors.finish(out, z_min, z_max, self.ctx._log_nhi_scale[int(bool(sub_dla))], p, t)
+        out["selection"] = sel
         return out
 
     # ---- mock spectra (DESIGN.md 4.13) ----

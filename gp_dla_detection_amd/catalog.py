@@ -160,6 +160,48 @@ def generate_json_catalogue(results: dict, quasar_info: dict, outfile: str | Non
     return out
 
 
+def generate_json_catalogue_with_intervals(results: dict, quasar_info: dict, summaries: dict,
+                                           outfile: str | None = None, sub_dla: bool = True,
+                                           occams_razor: float = 10000.0, drop_nan: bool = True) -> list:
+    """:func:`generate_json_catalogue` plus what :mod:`posteriors` knows about each listed absorber.
+    ``summaries``: the dict of ``posteriors.parameter_summaries`` / ``from_processed_file`` /
+    ``Batch.parameter_summaries`` over all models of the run; its rows are the searched quasars, or
+    those of its ``selection``.  Each entry of ``dlas`` (the absorbers of the most probable model)
+    gains ``log_nhi_mean``, ``log_nhi_std``, ``z_dla_mean``, ``z_dla_std``, the quantiles as
+    ``log_nhi_q<p>`` / ``z_dla_q<p>`` and ``p_log_nhi_ge_<t>``; each record gains ``effective_samples``
+    of that model (null when the record lists no DLA or the quasar has no summaries).  NaN values are
+    written as JSON's NaN, as the reference's json.dump does.  With the added keys removed the output
+    equals :func:`generate_json_catalogue`'s."""
+    from .posteriors import quantile_key, threshold_key
+    out = generate_json_catalogue(results, quasar_info, None, sub_dla, occams_razor, drop_nan)
+    _, _, keep = loader_view(results, quasar_info, sub_dla, occams_razor, drop_nan)
+    nq = np.asarray(results["model_posteriors"]).shape[0]
+    sel = np.asarray(summaries.get("selection", np.arange(np.asarray(summaries["status"]).shape[0])), dtype=np.int64)
+    row_of = np.full(nq, -1, dtype=np.int64)
+    row_of[sel] = np.arange(sel.size)
+    probs, thr = np.asarray(summaries["probabilities"]), np.asarray(summaries["thresholds"])
+    for spec, i in zip(out, keep):
+        r, n = int(row_of[i]), spec["num_dlas"]
+        has = r >= 0 and 1 <= n <= np.asarray(summaries["status"]).shape[1]
+        spec["effective_samples"] = _py(summaries["effective_samples"][r, n - 1]) if has else None
+        for j, dla in enumerate(spec["dlas"]):
+            if not has:
+                continue
+            at = (r, n - 1, j)
+            dla["log_nhi_mean"], dla["log_nhi_std"] = _py(summaries["mean_log_nhi"][at]), _py(summaries["std_log_nhi"][at])
+            dla["z_dla_mean"], dla["z_dla_std"] = _py(summaries["mean_z"][at]), _py(summaries["std_z"][at])
+            for q, p in enumerate(probs):
+                dla[quantile_key("log_nhi", p)] = _py(summaries["quantiles_log_nhi"][at + (q,)])
+                dla[quantile_key("z_dla", p)] = _py(summaries["quantiles_z"][at + (q,)])
+            for k, t in enumerate(thr):
+                dla[threshold_key(t)] = _py(summaries["exceedance"][at + (k,)])
+    if outfile is not None:
+        import json
+        with open(outfile, "w") as f:
+            json.dump(out, f, indent=2)
+    return out
+
+
 def generate_sub_dla_catalogue(results: dict, quasar_info: dict, outfile: str | None = None,
                                sub_dla: bool = True, occams_razor: float = 10000.0,
                                drop_nan: bool = True) -> list:

@@ -36,6 +36,7 @@
 #include "mock_kernels.hpp"
 #include "sample_kernels.hpp"
 #include "preload_kernels.hpp"
+#include "posterior_kernels.hpp"
 #include "training_kernels.hpp"
 #include "training_mfma_kernels.hpp"
 
@@ -53,5 +54,6 @@ using namespace gpdla;
 #include "host_mock.hpp"
 #include "host_samples.hpp"
 #include "host_preload.hpp"
+#include "host_posterior.hpp"
 // libgpdla_legacy.so (-DGPDLA_WITH_LEGACY): the superseded kernels and their environment switches
 #include "host_legacy.hpp"

@@ -893,6 +893,53 @@ def load_model_spectra(path: str) -> dict:
 
 
 # ---------------------------------------------------------------------------------------------
+# parameter summaries
+# ---------------------------------------------------------------------------------------------
+
+PARAMETER_SUMMARY_FIELDS = ("mean_z", "std_z", "mean_log_nhi", "std_log_nhi", "cov", "correlation", "quantiles_z",
+                            "quantiles_log_nhi", "exceedance", "effective_samples")
+
+
+def save_parameter_summaries(path: str, summaries: dict, **run_metadata) -> None:
+    """What :mod:`posteriors` returns as a ``-v7.3`` file: ``quasar_ind`` (the selection, 1-based like
+    every MATLAB index), ``probabilities`` and ``thresholds`` as columns, ``status`` and
+    ``effective_samples`` [n x models], every other field as MATLAB sees this package's array --
+    [n x model x slot], the quantiles [n x model x slot x probability], the exceedance [n x model x
+    slot x threshold].  ``run_metadata``: scalars and strings, as given."""
+    n = np.asarray(summaries["status"]).shape[0]
+    w = _MatWriter(path)
+    try:
+        for k, v in run_metadata.items():
+            w.put(k, v)
+        w.put("quasar_ind", np.asarray(summaries.get("selection", np.arange(n)), dtype=np.float64).reshape(-1, 1) + 1)
+        w.put("probabilities", np.asarray(summaries["probabilities"], dtype=np.float64).reshape(-1, 1))
+        w.put("thresholds", np.asarray(summaries["thresholds"], dtype=np.float64).reshape(-1, 1))
+        w.put("status", np.asarray(summaries["status"], dtype=np.float64))
+        for k in PARAMETER_SUMMARY_FIELDS:
+            if k in summaries:
+                w.put(k, np.asarray(summaries[k], dtype=np.float64))
+    finally:
+        w.close()
+
+
+def load_parameter_summaries(path: str) -> dict:
+    """The reader of :func:`save_parameter_summaries`: this package's shapes again, ``selection``
+    0-based, ``status`` int32."""
+    m = loadmat73(path)
+    out = {}
+    for k, v in m.items():
+        if k == "quasar_ind":
+            out["selection"] = _vec(v).astype(np.int64) - 1
+        elif k in ("probabilities", "thresholds"):
+            out[k] = _vec(v).astype(np.float64)
+        elif k == "status":
+            out[k] = np.asarray(v).astype(np.int32)
+        else:
+            out[k] = v
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
 # chunk files of a sharded run (CDDF_analysis/sbatch_reunion.py:13-63)
 # ---------------------------------------------------------------------------------------------
 

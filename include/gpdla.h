@@ -791,6 +791,80 @@ int gpdla_preload_spectra(int64_t num_quasars, const int64_t *offsets, const flo
                           double *out_flux, double *noise_variance, uint8_t *pixel_mask, double *normalizers,
                           int device_id);
 
+/* ---------------------------------------------------------------------------------------------
+ * Credible intervals and moments of the absorber parameters.  Additive:
+ * GPDLA_ABI_VERSION is unchanged.
+ *
+ * A row of S sample log-likelihoods l_i of model m (m absorbers, m = 1 .. num_models) is a weighted
+ * sample of the posterior of the parameters of its m absorbers ("slots").
+ *  - weights: a sample of model m whose slot 2 .. m holds base index 0 (never drawn), or one above S,
+ *    counts as l_i = NaN.  w_i = exp(l_i - max l) over the non-NaN entries; NaN and -inf weigh 0.  No
+ *    finite entry, or a maximum of +inf: every output of that (row, model) is NaN and status bit 1 is
+ *    set.  T = Sum w_i.  A sample of weight 0 does not exist for anything below.
+ *  - slot values: slot 1 of sample i has the parameters of sample i, slot j >= 2 those of sample
+ *    base_sample_inds[row][j - 2][i] - 1 (1-based, multi :347, :441): log N = log_nhi_samples[b],
+ *    z = min_z + (max_z - min_z) offset_samples[b], each operation rounded on its own.  A NaN min_z or
+ *    max_z makes the z outputs (mean_z, std_z, cov, quantiles_z) of the row NaN and sets status bit 2.
+ *  - per slot: mean = Sum w v / T; var = Sum w (v - mean)^2 / T about the computed mean, std =
+ *    sqrt(var); cov(z, log N) likewise; exceedance[t] = Sum over log N_i >= thresholds[t] of w_i / T.
+ *  - per model: effective_samples = T^2 / Sum w^2.
+ *  - quantiles: with F(v) = Sum over v_i <= v of w_i, the smallest sample value v* (of a sample of
+ *    positive weight) with F(v*) >= p T.  No interpolation: the answer is bitwise one of the slot's
+ *    values.  F is summed in a fixed order of its own, so where p T lies within rounding of a step of
+ *    F the neighbouring value may be named.
+ * Probabilities: 0 .. GPDLA_POSTERIOR_MAX_PROBABILITIES of them, each in (0, 1), strictly increasing.
+ * Thresholds: 0 .. GPDLA_POSTERIOR_MAX_THRESHOLDS, not NaN.  Checked before the device is touched.
+ *
+ * Outputs are [n][num_models][num_models] in (model, slot) order per field -- quantiles with a
+ * trailing [num_probabilities], exceedance with a trailing [num_thresholds] -- NaN where slot > model;
+ * effective_samples and status are [n][num_models].  Any output pointer may be NULL.
+ *
+ * Every sum runs in a fixed order without atomics: an output depends on its own row only, is
+ * bit-identical from run to run, for any selection and order, and for the host and the resident form
+ * of the same table.
+ *
+ * gpdla_stats_parameter_summaries: host tables.  Row r, model m starts at sample_log_likelihoods +
+ * r * row_stride + (m - 1) * num_samples (row_stride >= num_models * num_samples);
+ * base_sample_inds is [num_rows][num_models - 1][num_samples], NULL exactly when num_models == 1.
+ *
+ * gpdla_batch_parameter_summaries: the same kernel on the batch's resident tables after
+ * gpdla_batch_process (multi == 0) / gpdla_batch_process_multi (multi != 0: num_models must be the
+ * batch's max_dlas); no second sweep, no download of the table.  sub_dla != 0 (multi-DLA batch,
+ * num_models 1): the sub-DLA table with log10 of lls_nhi_samples as a one-model, one-slot problem.
+ * selection: quasars of the batch, NULL = 0 .. num_selected - 1.
+ * ------------------------------------------------------------------------------------------- */
+#define GPDLA_POSTERIOR_MAX_MODELS 4
+#define GPDLA_POSTERIOR_MAX_PROBABILITIES 8
+#define GPDLA_POSTERIOR_MAX_THRESHOLDS 4
+#define GPDLA_POSTERIOR_UNUSABLE 1   /* status bit 1 */
+#define GPDLA_POSTERIOR_NAN_RANGE 2  /* status bit 2 */
+typedef struct {
+  int32_t num_models;                /* 1 .. GPDLA_POSTERIOR_MAX_MODELS */
+  int32_t num_probabilities;
+  double probabilities[GPDLA_POSTERIOR_MAX_PROBABILITIES];
+  int32_t num_thresholds;
+  double thresholds[GPDLA_POSTERIOR_MAX_THRESHOLDS];
+} gpdla_summary_request;
+typedef struct {
+  double *mean_z, *std_z, *mean_log_nhi, *std_log_nhi, *cov;   /* [n][md][md] */
+  double *quantiles_z, *quantiles_log_nhi;                     /* [n][md][md][num_probabilities] */
+  double *exceedance;                                          /* [n][md][md][num_thresholds] */
+  double *effective_samples;                                   /* [n][md] */
+  int32_t *status;                                             /* [n][md] */
+} gpdla_parameter_summaries;
+int gpdla_stats_parameter_summaries(int64_t num_rows, int64_t num_samples, const double *sample_log_likelihoods,
+                                    int64_t row_stride, const uint32_t *base_sample_inds, const double *min_z_dlas,
+                                    const double *max_z_dlas, const double *offset_samples,
+                                    const double *log_nhi_samples, const gpdla_summary_request *request,
+                                    gpdla_parameter_summaries *outputs, int device_id);
+int gpdla_batch_parameter_summaries(gpdla_context *ctx, gpdla_batch *batch, int multi, int sub_dla,
+                                    const int64_t *selection, int64_t num_selected,
+                                    const gpdla_summary_request *request, gpdla_parameter_summaries *outputs);
+/* Measuring aid for tools/bench_posteriors.py: the duration of the k_parameter_summaries launch of the
+ * calling thread's most recent successful call of either function above, from device events (-1 before
+ * the first). */
+double gpdla_debug_last_summaries_ms(void);
+
 #ifdef __cplusplus
 }
 #endif
