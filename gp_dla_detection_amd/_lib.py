@@ -186,6 +186,19 @@ class ParameterSummaries(C.Structure):
                 ("status", _i32p)]
 
 
+class RefineRequest(C.Structure):
+    """gpdla_refine_request"""
+    _fields_ = [("levels", C.c_int32), ("delta", C.c_double), ("pad", C.c_double)]
+
+
+class RefinedResults(C.Structure):
+    """gpdla_refined_results"""
+    _fields_ = [("levels", C.c_int32), ("num_points", C.c_int64)] + [(n, _dp) for n in ("boxes", "sample_log_likelihoods_refined", "sample_log_posteriors_refined",
+                                   "log_likelihoods_dla_refined", "log_posteriors_dla_refined", "MAP_z_dlas_refined",
+                                   "MAP_log_nhis_refined", "MAP_inds_refined")] + [("status", _i32p)]
+
+
+REFINE_MAX_LEVELS, REFINE_UNUSABLE, REFINE_NOT_REFINED = 4, 1, -1   # GPDLA_REFINE_*
 POSTERIOR_MAX_MODELS, POSTERIOR_MAX_PROBABILITIES, POSTERIOR_MAX_THRESHOLDS = 4, 8, 4   # GPDLA_POSTERIOR_MAX_*
 POSTERIOR_UNUSABLE, POSTERIOR_NAN_RANGE = 1, 2                                          # status bits
 SPECTRA_MAX_ABSORBERS = 8                                   # GPDLA_SPECTRA_MAX_ABSORBERS
@@ -285,6 +298,14 @@ SYMBOLS = [
     ("gpdla_batch_parameter_summaries", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _i64p, C.c_int64,
                                                   C.POINTER(SummaryRequest), C.POINTER(ParameterSummaries)]),
     ("gpdla_debug_last_summaries_ms", C.c_double, []),
+    ("gpdla_refine_validate", C.c_int, [C.POINTER(RefineRequest), C.POINTER(NhiPrior), C.c_int64, _dp, _dp]),
+    ("gpdla_context_set_refine_points", C.c_int, [C.c_void_p, C.c_int64, _dp, _dp]),
+    ("gpdla_batch_refine", C.c_int, [C.c_void_p, C.c_void_p, _i64p, C.c_int64, C.POINTER(RefineRequest),
+                                     C.POINTER(NhiPrior)]),
+    ("gpdla_batch_download_refined", C.c_int, [C.c_void_p, C.c_void_p, _i64p, C.c_int64, C.POINTER(RefinedResults)]),
+    ("gpdla_batch_refined_summaries", C.c_int, [C.c_void_p, C.c_void_p, _i64p, C.c_int64, C.POINTER(SummaryRequest),
+                                                C.POINTER(ParameterSummaries)]),
+    ("gpdla_debug_last_refine_ms", C.c_double, []),
     ("gpdla_debug_near_poly", C.c_int, [C.c_int, C.c_double, _dp, _dp]),
     ("gpdla_debug_prepared_rows", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, _dp, C.c_int64, _i64p]),
     ("gpdla_debug_philox4x32_10", None, [_u32p, _u32p, _u32p]),

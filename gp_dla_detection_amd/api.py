@@ -168,6 +168,7 @@ class Context:
         self.num_samples = 0
         self.has_lls_samples = False
         self.k = 0
+        self.refine_points = None
 
     def set_stream(self, stream):
         """``stream``: a raw hipStream_t (int) or a torch.cuda.Stream."""
@@ -191,6 +192,20 @@ class Context:
         # scales of log N for Batch.parameter_summaries' correlation floor (DLA table, sub-DLA table)
         self._log_nhi_scale = [float(np.max(np.abs(samples["log_nhi_samples"]))) if samples.get("log_nhi_samples") is not None else np.nan,
                                float(np.max(np.abs(np.log10(samples["lls_nhi_samples"])))) if self.has_lls_samples else np.nan]
+
+    def set_refine_points(self, u=None, v=None, num: int | None = None):
+        """The unit-square point set of :meth:`Batch.refine` (gpdla_context_set_refine_points): ``u`` and
+        ``v`` in [0, 1), any number of them.  Without arguments: ``num`` (default: the number of DLA samples)
+        RR2-scrambled Halton points of bases 2 and 3 from index 1 (:func:`refine.default_points`)."""
+        from . import refine
+        if u is None:
+            u, v = refine.default_points(int(num) if num is not None else self.num_samples, self.device)
+        u = np.ascontiguousarray(u, dtype=np.float64).reshape(-1)
+        v = np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
+        if u.size != v.size:
+            raise ValueError(f"{u.size} u for {v.size} v")
+        _lib.check(self.lib.gpdla_context_set_refine_points(self._h, u.size, _lib.ptr(u), _lib.ptr(v)))
+        self.refine_points = (u.copy(), v.copy())
 
     def set_timing(self, enabled: bool):
         _lib.check(self.lib.gpdla_context_set_timing(self._h, int(bool(enabled))))
@@ -237,6 +252,7 @@ class Batch:
     def __init__(self, ctx: Context, spectra, log_priors_no_dla, log_priors_dla, log_priors_lls=None):
         self.ctx = ctx
         self._h = C.c_void_p()
+        self._refined = None   # (levels, refine points) of the last refine() of the current spectra
         self._fill(spectra, log_priors_no_dla, log_priors_dla, log_priors_lls)
 
     def reload(self, spectra, log_priors_no_dla, log_priors_dla, log_priors_lls=None):
@@ -247,6 +263,7 @@ class Batch:
 
     def _fill(self, spectra, log_priors_no_dla, log_priors_dla, log_priors_lls):
         ctx = self.ctx
+        self._refined = None
         csr = spectra if isinstance(spectra, dict) else spectra_to_csr(spectra)
         self.num_quasars = csr["z_qsos"].size
         self.num_pixels = int(csr["offsets"][-1] - csr["offsets"][0])
@@ -403,21 +420,84 @@ class Batch:
         _lib.check(lib.gpdla_batch_model_spectra(self.ctx._h, self._h, C.byref(rq), C.byref(ms)))
         return out
 
+    # ---- refined posteriors ----
+
+    def _selection(self, selection):
+        return np.arange(self.num_quasars, dtype=np.int64) if selection is None else \
+            np.ascontiguousarray(selection, dtype=np.int64).reshape(-1)
+
+    def refine(self, selection=None, levels: int = 2, delta: float = 12.5, pad: float = 2.0, prior=None,
+               with_samples: bool = True, download: bool = True) -> dict | None:
+        """Zoom boxes of (z_DLA, log N_HI) around the posterior mass of the selected quasars, re-swept on
+        the context's refine points (gpdla_batch_refine, after :meth:`process`; the definitions are in
+        include/gpdla.h).  ``prior``: a :class:`samples.NhiPrior` (None: uniform over the range of the log N
+        samples).  Returns ``selection``, ``boxes`` [n, levels, 4] as (z_lo, z_hi, n_lo, n_hi),
+        ``log_likelihoods_dla_refined``, ``log_posteriors_dla_refined``, ``MAP_z_dlas_refined``,
+        ``MAP_log_nhis_refined``, ``MAP_inds_refined`` (1-based), ``status`` and, ``with_samples``, the last
+        level's ``sample_log_likelihoods_refined`` and ``sample_log_posteriors_refined`` [n, S'].  The
+        batch's own results are not touched.  ``download=False``: only launch (asynchronous on the context's
+        stream) and return None; :meth:`download_refined` fetches the results."""
+        from . import refine as _refine
+        if self.ctx.refine_points is None:
+            self.ctx.set_refine_points()
+        sel = self._selection(selection)
+        rq = _refine.request(levels, delta, pad)
+        ps = C.byref(prior._s) if prior is not None else None
+        _lib.check(self.ctx.lib.gpdla_batch_refine(self.ctx._h, self._h, sel.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                   sel.size, C.byref(rq), ps))
+        self._refined = (int(levels), int(self.ctx.refine_points[0].size))
+        return self.download_refined(sel, None, with_samples) if download else None
+
+    def download_refined(self, selection=None, levels: int | None = None, with_samples: bool = True) -> dict:
+        """The resident results of the last :meth:`refine` for quasars of its selection
+        (gpdla_batch_download_refined).  The arrays are sized by what that call was made with -- its levels
+        and the point set of that time, which the batch remembers; ``levels``, if given, must agree.  The
+        library checks the sizes again and refuses a mismatch."""
+        from . import refine as _refine
+        if self._refined is None:
+            raise _lib.GpdlaError(_lib.ERR_INVALID_ARGUMENT, "the batch has not been refined")
+        last_levels, num_points = self._refined
+        if levels is not None and int(levels) != last_levels:
+            raise ValueError(f"levels = {levels}, but the batch was refined with {last_levels} levels")
+        sel = self._selection(selection)
+        out = _refine.empty_results(sel.size, last_levels, num_points, with_samples)
+        r = _lib.RefinedResults()
+        r.levels, r.num_points = last_levels, num_points
+        for name in out:
+            setattr(r, name, out[name].ctypes.data_as(C.POINTER(C.c_int32 if name == "status" else C.c_double)))
+        _lib.check(self.ctx.lib.gpdla_batch_download_refined(self.ctx._h, self._h, sel.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                             sel.size, C.byref(r)))
+        out["selection"] = sel
+        return out
+
     # ---- parameter summaries (DESIGN.md 4.17) ----
 
     def parameter_summaries(self, selection=None, multi: bool = False, sub_dla: bool = False, probabilities=None,
-                            thresholds=None, num_models: int | None = None) -> dict:
+                            thresholds=None, num_models: int | None = None, refined: bool = False) -> dict:
         """Credible intervals and moments of the absorber parameters of the selected quasars from the
         batch's RESIDENT sample tables (gpdla_batch_parameter_summaries) after :meth:`process`
         (``multi=False``) or :meth:`process_multi` (``multi=True``: all ``max_dlas`` models, slots
         gathered through the resident ``base_sample_inds``; ``sub_dla``: the sub-DLA table with the LLS
         column densities, one model).  No second sweep and no download of the table.  Returns what
-        :func:`posteriors.parameter_summaries` returns, plus ``selection``."""
+        :func:`posteriors.parameter_summaries` returns, plus ``selection``.  ``refined``: the summaries of
+        the last level of :meth:`refine` instead -- the resident lambda table as weights over the points of
+        each quasar's own box (gpdla_batch_refined_summaries), in the same units."""
         from . import posteriors
         p, t = posteriors.check_request(posteriors.DEFAULT_PROBABILITIES if probabilities is None else probabilities,
                                         posteriors.DEFAULT_THRESHOLDS if thresholds is None else thresholds)
         sel = np.arange(self.num_quasars, dtype=np.int64) if selection is None else \
             np.ascontiguousarray(selection, dtype=np.int64).reshape(-1)
+        if refined:
+            if multi or sub_dla or num_models not in (None, 1):
+                raise ValueError("refined=True: the refined table holds one single-DLA model (no multi, sub_dla or num_models)")
+            out, ps = posteriors._outputs(sel.size, 1, len(p), len(t))
+            rq = posteriors._request(1, p, t)
+            _lib.check(self.ctx.lib.gpdla_batch_refined_summaries(
+                self.ctx._h, self._h, sel.ctypes.data_as(C.POINTER(C.c_int64)), sel.size, C.byref(rq), C.byref(ps)))
+            last = self.download_refined(sel, None, with_samples=False)["boxes"][:, -1]   # the z range the rows were summarised on
+            out = posteriors.finish(out, last[:, 0], last[:, 1], self.ctx._log_nhi_scale[0], p, t)
+            out["selection"] = sel
+            return out
         md = int(num_models) if num_models is not None else (self.max_dlas if (multi and not sub_dla) else 1)
         out, ps = posteriors._outputs(sel.size, md, len(p), len(t))
         rq = posteriors._request(md, p, t)
@@ -853,6 +933,13 @@ def process_qsos(model: dict, samples: dict, spectra, prior_catalog: dict | None
     out["prior_z_qso_increase"] = p.prior_z_qso_increase
     out["max_z_cut"] = p.max_z_cut
     return out
+
+
+def refine_absorbers(model: dict, samples: dict, spectra, results: dict, p_dla_threshold: float = 0.9, **kw) -> dict:
+    """Refine the absorber posteriors of the quasars of ``spectra`` whose ``results["p_dlas"]`` reach
+    ``p_dla_threshold``: :func:`refine.refine_absorbers`, which documents the keywords."""
+    from . import refine
+    return refine.refine_absorbers(model, samples, spectra, results, p_dla_threshold, **kw)
 
 
 # ----------------------------------------------------------------------------------------------

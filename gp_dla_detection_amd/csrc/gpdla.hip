@@ -37,6 +37,7 @@
 #include "sample_kernels.hpp"
 #include "preload_kernels.hpp"
 #include "posterior_kernels.hpp"
+#include "refine_kernels.hpp"
 #include "training_kernels.hpp"
 #include "training_mfma_kernels.hpp"
 
@@ -55,5 +56,6 @@ using namespace gpdla;
 #include "host_samples.hpp"
 #include "host_preload.hpp"
 #include "host_posterior.hpp"
+#include "host_refine.hpp"
 // libgpdla_legacy.so (-DGPDLA_WITH_LEGACY): the superseded kernels and their environment switches
 #include "host_legacy.hpp"

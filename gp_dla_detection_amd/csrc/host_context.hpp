@@ -21,6 +21,16 @@ struct gpdla_context {
   int64_t S = 0;
   double *d_offset = nullptr, *d_nhi = nullptr, *d_log_nhi = nullptr, *d_lls_nhi = nullptr;
   int32_t *d_perm = nullptr;
+  // the refine pass (host_refine.hpp): the range of the log N table, the table itself where the samples
+  // came without one (log10 of nhi_samples, taken by the host), and the unit-square point set with the
+  // order of u (the boxed sweep's perm) and the stable ranks of u and v (the refined summaries)
+  double log_nhi_lo = NAN, log_nhi_hi = NAN;
+  double *d_log_nhi_derived = nullptr;
+  int64_t Sr = 0;
+  double *d_ru = nullptr, *d_rv = nullptr;
+  int32_t *d_rperm = nullptr;
+  std::vector<double> h_ru, h_rv;
+  int64_t refine_points_gen = 0;  // counts gpdla_context_set_refine_points calls: a refined batch remembers its set
   gpdla_config cfg{};
   // timing
   bool timing = false;
@@ -79,6 +89,31 @@ struct gpdla_batch {
   int32_t md = 0;  // max_dlas the priors were uploaded for; 0 = single-DLA batch
   bool processed = false;  // single-DLA batch: gpdla_batch_process has run on the current spectra
   struct MultiBuffers *mb = nullptr;
+  struct RefineBuffers *rf = nullptr;  // the refine pass's tables, allocated by the first gpdla_batch_refine
+};
+
+// What gpdla_batch_refine keeps per batch (host_refine.hpp): tables indexed by the batch's quasar, kept
+// across reloads while they suffice.
+struct RefineBuffers {
+  void *arena = nullptr;
+  size_t cap_bytes = 0;
+  int64_t nq = 0, Sr = 0;              // what the arena is laid out for
+  double *box = nullptr;               // [nq][kRefineBoxStride]
+  QuasarMeta *rmeta = nullptr;         // [nq]
+  double *ell = nullptr, *lam = nullptr;  // [nq][Sr] the last level's l' and lambda
+  double *ll_scratch = nullptr;        // [nq] the boxed sweep's null-model row
+  double *terms = nullptr;             // [nq][kRefineTerms][2]
+  double *scal = nullptr;              // [nq][kRefineScalars]
+  int32_t *status = nullptr;           // [nq]
+  int32_t *rows = nullptr;             // [nq] the selected quasars in dealing order
+  std::vector<int32_t> h_rows;         // source of the asynchronous copy into `rows`
+  hipEvent_t ev_rows = nullptr;        // behind that copy: h_rows may be rewritten once it has run
+  int32_t levels = 0;                  // of the last call; 0: none since the last (re)load
+  int64_t points_gen = 0;              // gpdla_context::refine_points_gen of the last call
+  ~RefineBuffers() {
+    if (ev_rows) (void)hipEventDestroy(ev_rows);
+    if (arena) (void)hipFree(arena);
+  }
 };
 
 struct MultiBuffers {
@@ -184,6 +219,10 @@ void gpdla_context_destroy(gpdla_context *c) {
   dev_free(c->d_log_nhi);
   dev_free(c->d_lls_nhi);
   dev_free(c->d_perm);
+  dev_free(c->d_log_nhi_derived);
+  dev_free(c->d_ru);
+  dev_free(c->d_rv);
+  dev_free(c->d_rperm);
   dev_free(c->d_prof);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -275,7 +314,8 @@ int gpdla_context_set_samples(gpdla_context *c, const gpdla_samples *s) try {
   dev_free(c->d_log_nhi);
   dev_free(c->d_lls_nhi);
   dev_free(c->d_perm);
-  c->d_log_nhi = c->d_lls_nhi = nullptr;
+  dev_free(c->d_log_nhi_derived);
+  c->d_log_nhi = c->d_lls_nhi = c->d_log_nhi_derived = nullptr;
   const size_t S = (size_t)s->num_dla_samples;
   // visit samples in ascending z_DLA order: z = min + (max - min) * offset is monotone in offset
   // for every quasar, so one permutation serves the whole run
@@ -290,6 +330,20 @@ int gpdla_context_set_samples(gpdla_context *c, const gpdla_samples *s) try {
   if (s->log_nhi_samples && (rc = upload(&c->d_log_nhi, s->log_nhi_samples, S, c->stream))) return rc;
   if (s->lls_nhi_samples && (rc = upload(&c->d_lls_nhi, s->lls_nhi_samples, S, c->stream))) return rc;
   if ((rc = upload(&c->d_perm, perm.data(), S, c->stream))) return rc;
+  // (for the refine pass) the range of log N; without a log table, log10 of nhi_samples as the table
+  std::vector<double> derived;
+  const double *ln = s->log_nhi_samples;
+  if (!ln) {
+    derived.resize(S);
+    for (size_t i = 0; i < S; ++i) derived[i] = std::log10(s->nhi_samples[i]);
+    ln = derived.data();
+    if ((rc = upload(&c->d_log_nhi_derived, ln, S, c->stream))) return rc;
+  }
+  c->log_nhi_lo = c->log_nhi_hi = ln[0];
+  for (size_t i = 1; i < S; ++i) {
+    c->log_nhi_lo = ln[i] < c->log_nhi_lo ? ln[i] : c->log_nhi_lo;
+    c->log_nhi_hi = ln[i] > c->log_nhi_hi ? ln[i] : c->log_nhi_hi;
+  }
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->S = (int64_t)S;
   c->has_samples = true;
@@ -336,6 +390,7 @@ void gpdla_batch_destroy(gpdla_batch *b) {
   dev_free(b->arena);
   dev_free(b->d_records);
   delete b->mb;
+  delete b->rf;
   delete b;
 }
 
@@ -420,6 +475,7 @@ int batch_fill(gpdla_context *c, gpdla_batch *b, const gpdla_spectra *sp, int md
   for (int64_t q = 0; q < nq; ++q) b->h_recs[q] = (off[q + 1] - off[q] + 3) / 4 + 1;
   b->plan_budget = -1;  // the record plan is remade by the next process call
   b->processed = false;
+  if (b->rf) b->rf->levels = 0;  // (the tables are kept; their contents belong to the previous spectra)
   if (b->md != md) {  // (reload with a different kind of batch)
     delete b->mb;
     b->mb = nullptr;

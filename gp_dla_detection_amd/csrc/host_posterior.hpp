@@ -56,11 +56,13 @@ int stable_ranks(const double *v, int64_t S, const char *name, std::vector<int32
 }
 
 // The kernel over n rows of a device table.  row_start / base_start: element offsets of each row's
-// first model / first base row; offsets, lnhi, z_min, z_max: host arrays.
+// first model / first base row; offsets, lnhi, z_min, z_max: host arrays.  n_lo / n_hi (host, [n], optional): the
+// per-row affine reading of lnhi (PosteriorArgs::n_lo).
 int run_parameter_summaries(int64_t n, int64_t S, const double *d_sll, const std::vector<int64_t> &row_start,
                             const uint32_t *d_base, const std::vector<int64_t> &base_start, const double *z_min,
                             const double *z_max, const double *offsets, const double *lnhi,
-                            const gpdla_summary_request &rq, const gpdla_parameter_summaries &out, hipStream_t st) {
+                            const gpdla_summary_request &rq, const gpdla_parameter_summaries &out, hipStream_t st,
+                            const double *n_lo = nullptr, const double *n_hi = nullptr) {
   const int md = rq.num_models, Q = rq.num_probabilities, nt = rq.num_thresholds;
   if (n * md > 2147483647LL) return fail(GPDLA_ERR_UNSUPPORTED, "more than 2^31 - 1 (row, model) pairs in one call");
   std::vector<int32_t> rank_off, inv_off, rank_n, inv_n;
@@ -77,7 +79,7 @@ int run_parameter_summaries(int64_t n, int64_t S, const double *d_sll, const std
   double *d_out = nullptr, *d_vec = nullptr, *d_smp = nullptr;
   int32_t *d_status = nullptr, *d_rank = nullptr;
   int64_t *d_start = nullptr;
-  if ((rc = tmp.alloc(&d_out, n_dbl)) || (rc = tmp.alloc(&d_status, models)) || (rc = tmp.alloc(&d_vec, (size_t)2 * n)) ||
+  if ((rc = tmp.alloc(&d_out, n_dbl)) || (rc = tmp.alloc(&d_status, models)) || (rc = tmp.alloc(&d_vec, (size_t)4 * n)) ||
       (rc = tmp.alloc(&d_smp, (size_t)2 * S)) || (rc = tmp.alloc(&d_rank, (size_t)4 * S)) ||
       (rc = tmp.alloc(&d_start, (size_t)2 * n)))
     return rc;
@@ -91,6 +93,7 @@ int run_parameter_summaries(int64_t n, int64_t S, const double *d_sll, const std
       (rc = put(d_rank + 3 * S, inv_n.data(), (size_t)S)) || (rc = put(d_start, row_start.data(), (size_t)n)))
     return rc;
   if (md > 1 && (rc = put(d_start + n, base_start.data(), (size_t)n))) return rc;
+  if (n_lo && ((rc = put(d_vec + 2 * n, n_lo, (size_t)n)) || (rc = put(d_vec + 3 * n, n_hi, (size_t)n)))) return rc;
   HIP_TRY(hipMemsetAsync(d_out, 0xFF, n_dbl * sizeof(double), st));  // NaN: slot > model, unusable models
   HIP_TRY(hipMemsetAsync(d_status, 0, models * sizeof(int32_t), st));
   PosteriorArgs a{};
@@ -106,6 +109,8 @@ int run_parameter_summaries(int64_t n, int64_t S, const double *d_sll, const std
   a.base_start = md > 1 ? d_start + n : nullptr;
   a.z_min = d_vec;
   a.z_max = d_vec + n;
+  a.n_lo = n_lo ? d_vec + 2 * n : nullptr;
+  a.n_hi = n_lo ? d_vec + 3 * n : nullptr;
   a.offsets = d_smp;
   a.lnhi = d_smp + S;
   a.rank_off = d_rank;

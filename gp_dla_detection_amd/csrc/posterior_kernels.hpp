@@ -56,7 +56,13 @@ struct PosteriorArgs {
   double *exceed;                   // [n][md][md][nt]
   double *ess;                      // [n][md]
   int32_t *status;                  // [n][md]  1: no usable sample, 2: NaN search range
+  // optional affine reading of lnhi per row (the refined tables of DESIGN.md 4.18, whose lnhi holds unit
+  // coordinates): log N = n_lo[r] + (n_hi[r] - n_lo[r]) lnhi[i], in the moments, against the thresholds and in
+  // the quantiles.  Null: lnhi is log N itself.
+  const double *n_lo, *n_hi;        // [n] or null
 };
+
+__device__ inline double post_log_n(bool mapped, double lo, double width, double v) { return mapped ? lo + width * v : v; }
 
 // Sum over the block, the same bits in every thread: butterfly inside each wave, then the four wave
 // totals as (w0 + w1) + (w2 + w3).
@@ -130,6 +136,8 @@ __global__ __launch_bounds__(256) void k_parameter_summaries(PosteriorArgs a) {
   const double dz = zmax - zmin;
   const bool z_ok = zmin == zmin && zmax == zmax;
   const bool rev = dz < 0.0;                              // z falls with the offset: ranks run backwards
+  const bool mapped = a.n_lo != nullptr;
+  const double nlo = mapped ? a.n_lo[r] : 0.0, nw = mapped ? a.n_hi[r] - a.n_lo[r] : 1.0;
   const int64_t om = r * a.md + (m - 1);                  // [n][md]
   const double nan = __builtin_nan("");
 
@@ -169,7 +177,7 @@ __global__ __launch_bounds__(256) void k_parameter_summaries(PosteriorArgs a) {
     for (int64_t i = tid; i < S; i += 256) {
       const double w = post_weight(post_ll(row, brow, m, S, i), mx);
       const int64_t b = post_base(brow, j, S, i);
-      const double z = zmin + dz * a.offsets[b], ln = a.lnhi[b];
+      const double z = zmin + dz * a.offsets[b], ln = post_log_n(mapped, nlo, nw, a.lnhi[b]);
       if (w > 0.0) {                                      // a sample of weight 0 does not exist
         if (z_ok) sz.add(w * z);
         sn.add(w * ln);
@@ -191,7 +199,7 @@ __global__ __launch_bounds__(256) void k_parameter_summaries(PosteriorArgs a) {
     for (int64_t i = tid; i < S; i += 256) {
       const double w = post_weight(post_ll(row, brow, m, S, i), mx);
       const int64_t b = post_base(brow, j, S, i);
-      const double z = zmin + dz * a.offsets[b], ln = a.lnhi[b];
+      const double z = zmin + dz * a.offsets[b], ln = post_log_n(mapped, nlo, nw, a.lnhi[b]);
       if (w > 0.0) {
         const double dn = ln - mn;
         vn.add(w * (dn * dn));
@@ -306,7 +314,7 @@ __global__ __launch_bounds__(256) void k_parameter_summaries(PosteriorArgs a) {
           if (q >= a.Q || ans < 0) continue;
           double v;
           if (qy) {
-            v = a.lnhi[a.inv_n[ans]];
+            v = post_log_n(mapped, nlo, nw, a.lnhi[a.inv_n[ans]]);
           } else {
             const int64_t rk = rev ? (S - 1) - ans : ans;
             v = zmin + dz * a.offsets[a.inv_off[rk]];

@@ -541,6 +541,18 @@ struct SweepArgs {
   double *ll_no_dla;              // [nq]      process_qsos.m:149
 };
 
+// The boxed sweeps of the refine pass (refine_kernels.hpp): SweepArgs plus the box of
+// (z_DLA, log10 N_HI) of the level being swept, quasar q's at box + q * kRefineBoxStride as
+// (z_lo, z_hi, n_lo, n_hi).  The unboxed sweeps take plain SweepArgs: their kernel arguments do not change.
+constexpr int kRefineMaxLevels = 4;
+constexpr int kRefineBoxStride = 4 * kRefineMaxLevels;   // doubles per quasar: [level][4]
+struct BoxedSweepArgs : SweepArgs {
+  const double *box;
+};
+// quasar q's box (the first overload is only ever named in a discarded branch of an unboxed sweep)
+__device__ __forceinline__ const double *sweep_box(const SweepArgs &, int64_t) { return nullptr; }
+__device__ __forceinline__ const double *sweep_box(const BoxedSweepArgs &a, int64_t q) { return a.box + q * kRefineBoxStride; }
+
 // 1/a to 2.2e-15 relative: v_rcp_f64 seed (measured 4.6e-8, tools/rcp_accuracy_probe.hip) + ONE
 // Newton step.  a must be finite and normal, and so must 1/a (NaN for a = inf, 0 once 1/a is
 // subnormal): k_prepare keeps non-positive and NaN noise variances out of the sweeps (status 3) and

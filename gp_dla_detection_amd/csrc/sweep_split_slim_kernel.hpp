@@ -151,6 +151,7 @@ __host__ __device__ constexpr size_t sweep_split_slim_lds_doubles(bool multi) {
 // LINES: number of Lyman lines when known at compile time (0: read at run time); single-DLA only.
 // ND == 0: the single-DLA sweep (Args = SweepArgs); ND >= 1: the multi-DLA sweep of a model whose
 // samples multiply ND profiles (Args = SweepMultiArgs; mode 0, the sub-DLA pass, has ND = 1).
+// Args = BoxedSweepArgs (ND == 0): the boxed sweep of the refine pass, see k_sweep_slim_boxed.
 template <int LINES, int ND, typename Args>
 __global__ __launch_bounds__(512) void k_sweep_split_slim(Args a) {
   extern __shared__ double smem[];
@@ -226,7 +227,11 @@ __global__ __launch_bounds__(512) void k_sweep_split_slim(Args a) {
     // (null-model and idle slots: the last sample in z order, see k_sweep_slim)
     sample = a.perm[is_sample ? slot : a.S - 1];
     const double z_dla = m.min_z_dla + (m.max_z_dla - m.min_z_dla) * a.offset_samples[sample];  // :162-164
-    const double nhi = a.nhi_samples[sample];
+    double nhi = a.nhi_samples[sample];
+    if constexpr (std::is_same_v<Args, BoxedSweepArgs>) {  // the refine pass: nhi_samples holds unit coordinates
+      const double *box = sweep_box(a, q);
+      nhi = exp10(box[2] + (box[3] - box[2]) * nhi);
+    }
     if (LINES > 0) {
 #pragma unroll
       for (int j = 0; j < LINES; ++j) mult_r[j] = g_lines.c / (g_lines.wavelength_cm[j] * (1 + z_dla)) / 1e8;  // voigt.c:278-279

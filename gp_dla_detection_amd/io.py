@@ -940,6 +940,61 @@ def load_parameter_summaries(path: str) -> dict:
 
 
 # ---------------------------------------------------------------------------------------------
+# refined absorber posteriors
+# ---------------------------------------------------------------------------------------------
+
+def save_refined_results(path: str, refined: dict, **run_metadata) -> None:
+    """What :meth:`api.Batch.refine` / :func:`refine.refine_absorbers` return as a ``-v7.3`` file:
+    ``quasar_ind`` (the selection, 1-based), the per-quasar scalars as columns, ``boxes`` [n x level x 4],
+    ``status``, the two sample tables when present, and the refined parameter summaries (the dict under
+    ``summaries``) with a ``summary_`` prefix.  ``run_metadata``: scalars and strings, as given."""
+    from . import refine as _refine
+    n = np.asarray(refined["status"]).shape[0]
+    w = _MatWriter(path)
+    try:
+        for k, v in run_metadata.items():
+            w.put(k, v)
+        w.put("quasar_ind", np.asarray(refined.get("selection", np.arange(n)), dtype=np.float64).reshape(-1, 1) + 1)
+        w.put("status", np.asarray(refined["status"], dtype=np.float64).reshape(-1, 1))
+        w.put("boxes", np.asarray(refined["boxes"], dtype=np.float64))
+        for k in _refine.SCALARS:
+            w.put(k, np.asarray(refined[k], dtype=np.float64).reshape(-1, 1))
+        for k in _refine.TABLES:
+            if k in refined:
+                w.put(k, np.asarray(refined[k], dtype=np.float64))
+        for k, v in (refined.get("summaries") or {}).items():
+            if k != "selection":
+                w.put("summary_" + k, np.asarray(v, dtype=np.float64))
+    finally:
+        w.close()
+
+
+def load_refined_results(path: str) -> dict:
+    """The reader of :func:`save_refined_results`: this package's shapes again, ``selection`` 0-based,
+    ``status`` int32, the summaries under ``summaries``."""
+    from . import refine as _refine
+    m = loadmat73(path)
+    out, summ = {}, {}
+    for k, v in m.items():
+        if k == "quasar_ind":
+            out["selection"] = _vec(v).astype(np.int64) - 1
+        elif k == "status":
+            out[k] = _vec(v).astype(np.int32)
+        elif k in _refine.SCALARS:
+            out[k] = _vec(v).astype(np.float64)
+        elif k.startswith("summary_"):
+            k = k[len("summary_"):]
+            summ[k] = _vec(v).astype(np.float64) if k in ("probabilities", "thresholds") else \
+                np.asarray(v).astype(np.int32) if k == "status" else v
+        else:
+            out[k] = v
+    if summ:
+        summ["selection"] = out["selection"]
+        out["summaries"] = summ
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
 # chunk files of a sharded run (CDDF_analysis/sbatch_reunion.py:13-63)
 # ---------------------------------------------------------------------------------------------
 

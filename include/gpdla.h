@@ -865,6 +865,100 @@ int gpdla_batch_parameter_summaries(gpdla_context *ctx, gpdla_batch *batch, int 
  * the first). */
 double gpdla_debug_last_summaries_ms(void);
 
+/* ---------------------------------------------------------------------------------------------
+ * Refined absorber posteriors: per-quasar zoom boxes of (z_DLA, log10 N_HI) around the
+ * posterior mass of a processed single-DLA batch, re-swept on a shared unit-square point set.  Additive:
+ * GPDLA_ABI_VERSION is unchanged.  fp64, k <= 40, single-DLA batches; anything else is
+ * GPDLA_ERR_UNSUPPORTED.  Nothing of this exists in the reference.
+ *
+ * Every operation is rounded on its own; every reduction runs in a fixed order without atomics; a
+ * quasar's results depend on that quasar only: bit-identical from run to run and for any selection, order
+ * and record grouping.  tests/refine_restatement.py states the same in NumPy.
+ *
+ * Inputs per selected quasar: its first-pass row l_i, i < S, with z_i = min_z + (max_z - min_z)
+ * offset_samples[i] and n_i = log_nhi_samples[i] (log10 of nhi_samples[i], taken by the host, where the
+ * samples came without that table); [N_lo, N_hi] = the range of the whole log N table; the request's
+ * delta > 0, pad >= 0 and levels L in 1 .. GPDLA_REFINE_MAX_LEVELS; the context's point set (u_j, v_j) in
+ * [0, 1)^2, j < S' (S' need not equal S); optionally a gpdla_nhi_prior p_N (NULL: p_N = 1 / (N_hi - N_lo),
+ * its logarithm -log(N_hi - N_lo) taken by the host).
+ *
+ * Unusable rows: quasar status != 0, no finite l_i, a maximum of +inf, a NaN min_z or max_z, or max_z <
+ * min_z; at a later level, no finite lambda_j or a maximum of +inf.  Every output of such a row is NaN
+ * (boxes of the levels reached before are kept), its refine status has bit 1 (GPDLA_REFINE_UNUSABLE) set,
+ * and it is not swept (again).  A quasar outside the last call's selection has status
+ * GPDLA_REFINE_NOT_REFINED and NaN outputs.
+ *
+ * Box of level 1 from (l_i, z_i, n_i) with parent P = (min_z, max_z, N_lo, N_hi) and s = sqrt(S); box of
+ * level l + 1 from (lambda_j, z'_j, n'_j) of level l with P = box l and s = sqrt(S'):
+ *   A = {i : l_i >= max l - delta} (NaN never qualifies; the maximum skips NaN),
+ *   z_lo = max(P.z_lo, min_A z - pad (P.z_hi - P.z_lo) / s),  z_hi = min(P.z_hi, max_A z + pad (P.z_hi - P.z_lo) / s),
+ *   n_lo = max(P.n_lo, min_A n - pad (P.n_hi - P.n_lo) / s),  n_hi = min(P.n_hi, max_A n + pad (P.n_hi - P.n_lo) / s).
+ * A zero-width box is legal.
+ *
+ * Samples of level l: z'_j = z_lo + (z_hi - z_lo) u_j, n'_j = n_lo + (n_hi - n_lo) v_j, N'_j = exp10(n'_j),
+ * l'_j = the sweep's log-likelihood at (z'_j, N'_j), lambda_j = l'_j + log p_N(n'_j).
+ *
+ * Refined evidence: with V_l = (z_hi - z_lo) / (max_z - min_z) of box l (1 where max_z == min_z) and
+ * W_l = n_hi - n_lo, Z_ref = Sum_{t = 0 .. L} exp(m_t) s_t with
+ *   t = 0:           m = max l_i,              s = (Sum over i outside box 1 of exp(l_i - m)) / S,
+ *   t = 1 .. L - 1:  m = max lambda_j (level t), s = (V_t W_t) ((Sum over j outside box t + 1 of exp(lambda_j - m)) / S'),
+ *   t = L:           m = max lambda_j (level L), s = (V_L W_L) ((Sum over all j of exp(lambda_j - m)) / S'),
+ * "outside" meaning z or n strictly beyond an edge and NaN contributing 0; the terms are added in this
+ * order as exp(m_t - M) s_t with the one shift M = max m_t, and log_likelihoods_dla_refined = M + log of
+ * that sum; log_posteriors_dla_refined adds the batch's log_priors_dla.  The batch's own results and model
+ * posteriors are not touched.
+ *
+ * Refined MAP: the first j of largest lambda_j at level L: MAP_z_dlas_refined = z'_j, MAP_log_nhis_refined
+ * = n'_j, MAP_inds_refined = j + 1.
+ *
+ * gpdla_refine_validate: the checks of a request, a prior (may be NULL) and a point set (num_points == 0
+ * with NULL u, v: not checked) that the calls below make before they touch the device.  Needs no GPU.
+ * gpdla_context_set_refine_points: copies the point set; u and v finite in [0, 1), 1 <= num_points <= 2^30.
+ * gpdla_batch_refine: asynchronous on the context's stream, after gpdla_batch_process of the same
+ * spectra.  selection: quasars of the batch (NULL: 0 .. num_selected - 1), duplicates allowed.  Record
+ * groups (cfg.record_pool_bytes) are honoured as by the first pass; changing that setting between the
+ * two is GPDLA_ERR_INVALID_ARGUMENT.  The tables are allocated on first use and kept across reloads.
+ * Resident afterwards: the boxes of every level, the last level's l' and lambda, the scalars above.
+ * gpdla_batch_download_refined: rows of the given quasars; boxes is [n][levels of the last call][4] as
+ * (z_lo, z_hi, n_lo, n_hi); the two tables are [n][S'].  Any output pointer may be NULL.  results->levels and
+ * results->num_points state what the arrays were sized for; a value that differs from the last gpdla_batch_refine's
+ * levels / S' is GPDLA_ERR_INVALID_ARGUMENT and nothing is written.
+ * gpdla_batch_refined_summaries: gpdla_parameter_summaries (num_models = 1) of the resident lambda table
+ * as weights over (z'_j, n'_j) of the last level: same definitions, outputs [n][1][1]...  Refused
+ * (GPDLA_ERR_INVALID_ARGUMENT) once gpdla_context_set_refine_points has been called again after the refine.
+ * ------------------------------------------------------------------------------------------- */
+#define GPDLA_REFINE_MAX_LEVELS 4
+#define GPDLA_REFINE_UNUSABLE 1        /* status bit 1 */
+#define GPDLA_REFINE_NOT_REFINED (-1)  /* status of a quasar outside the last call's selection */
+typedef struct {
+  int32_t levels;                    /* 1 .. GPDLA_REFINE_MAX_LEVELS */
+  double delta;                      /* > 0: samples within delta of the maximum span the box */
+  double pad;                        /* >= 0: in units of (parent width) / sqrt(samples) */
+} gpdla_refine_request;
+typedef struct {
+  int32_t levels;                               /* what the caller sized boxes for: must equal the last call's levels */
+  int64_t num_points;                           /* what the caller sized the two tables for: must equal S' */
+  double *boxes;                                /* [n][levels][4] */
+  double *sample_log_likelihoods_refined;       /* [n][S'] l' of the last level */
+  double *sample_log_posteriors_refined;        /* [n][S'] lambda of the last level */
+  double *log_likelihoods_dla_refined, *log_posteriors_dla_refined;        /* [n] */
+  double *MAP_z_dlas_refined, *MAP_log_nhis_refined, *MAP_inds_refined;    /* [n] */
+  int32_t *status;                              /* [n] */
+} gpdla_refined_results;
+int gpdla_refine_validate(const gpdla_refine_request *request, const gpdla_nhi_prior *prior, int64_t num_points,
+                          const double *u, const double *v);
+int gpdla_context_set_refine_points(gpdla_context *ctx, int64_t num_points, const double *u, const double *v);
+int gpdla_batch_refine(gpdla_context *ctx, gpdla_batch *batch, const int64_t *selection, int64_t num_selected,
+                       const gpdla_refine_request *request, const gpdla_nhi_prior *prior);
+int gpdla_batch_download_refined(gpdla_context *ctx, gpdla_batch *batch, const int64_t *selection,
+                                 int64_t num_selected, gpdla_refined_results *results);
+int gpdla_batch_refined_summaries(gpdla_context *ctx, gpdla_batch *batch, const int64_t *selection,
+                                  int64_t num_selected, const gpdla_summary_request *request,
+                                  gpdla_parameter_summaries *outputs);
+/* Measuring aid for tools/bench_refine.py: device time of the calling thread's most recent gpdla_batch_refine
+ * made with the context's timing on (all groups and levels; -1 before the first). */
+double gpdla_debug_last_refine_ms(void);
+
 #ifdef __cplusplus
 }
 #endif
