@@ -20,6 +20,7 @@ PyTorch-ROCm tensors are staging only; all arithmetic happens in the HIP kernels
 from __future__ import annotations
 
 import ctypes as C
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -27,11 +28,27 @@ from . import _lib
 from .parameters import MultiParameters, Parameters
 
 _dp = C.POINTER(C.c_double)
+_i64p = C.POINTER(C.c_int64)
+_i32p = C.POINTER(C.c_int32)
 
 
 def _f64(a):
     a = np.ascontiguousarray(a, dtype=np.float64)
     return a, a.ctypes.data_as(_dp)
+
+
+def _absorber_fields(rq, absorbers, n: int, keep: list, what: str):
+    """Absorber lists ``(offsets [n + 1], z_dlas, log_nhis)`` in CSR form (or None) into the absorber_* fields of
+    a request; the arrays the fields point at are appended to ``keep``."""
+    if absorbers is None:
+        return
+    a_off, a_z, a_ln = absorbers
+    a_off = np.ascontiguousarray(a_off, dtype=np.int64).reshape(-1)
+    if a_off.size != n + 1:
+        raise _lib.GpdlaError(-1, f"absorber offsets: {a_off.size} entries for {n} {what}")
+    a_z, a_n = _f64(a_z)[0].reshape(-1), 10.0 ** _f64(a_ln)[0].reshape(-1)
+    keep += [a_off, a_z, a_n]
+    rq.absorber_offsets, rq.absorber_z, rq.absorber_nhi = a_off.ctypes.data_as(_i64p), a_z.ctypes.data_as(_dp), a_n.ctypes.data_as(_dp)
 
 
 def _config(params: Parameters) -> _lib.Config:
@@ -349,7 +366,7 @@ class Batch:
         """n_u of every quasar: the stored pixels with rest wavelength in [min_lambda, max_lambda],
         masked or not -- the grid the per-pixel outputs of :meth:`model_spectra` live on."""
         n = np.zeros(self.num_quasars, dtype=np.int64)
-        _lib.check(self.ctx.lib.gpdla_batch_unmasked_counts(self.ctx._h, self._h, n.ctypes.data_as(C.POINTER(C.c_int64))))
+        _lib.check(self.ctx.lib.gpdla_batch_unmasked_counts(self.ctx._h, self._h, n.ctypes.data_as(_i64p)))
         return n
 
     def model_spectra(self, selection=None, absorbers=None, weights=None, sub_dla: bool = False,
@@ -371,22 +388,13 @@ class Batch:
         Returns ``offsets [nsel + 1]``, ``status [nsel]`` and the flat per-pixel arrays; quasar s of the
         selection owns ``[offsets[s], offsets[s + 1])`` (:func:`split_cells` cuts them up)."""
         lib = self.ctx.lib
-        sel = np.arange(self.num_quasars, dtype=np.int64) if selection is None else \
-            np.ascontiguousarray(selection, dtype=np.int64).reshape(-1)
+        sel = self._selection(selection)
         nsel = sel.size
-        i64p = C.POINTER(C.c_int64)
         rq = _lib.ModelSpectraRequest()
         rq.num_selected = nsel
-        rq.selection = sel.ctypes.data_as(i64p)
+        rq.selection = sel.ctypes.data_as(_i64p)
         keep = [sel]
-        if absorbers is not None:
-            a_off, a_z, a_ln = absorbers
-            a_off = np.ascontiguousarray(a_off, dtype=np.int64).reshape(-1)
-            if a_off.size != nsel + 1:
-                raise _lib.GpdlaError(-1, f"absorber offsets: {a_off.size} entries for {nsel} selected quasars")
-            a_z, a_n = _f64(a_z)[0].reshape(-1), 10.0 ** _f64(a_ln)[0].reshape(-1)
-            keep += [a_off, a_z, a_n]
-            rq.absorber_offsets, rq.absorber_z, rq.absorber_nhi = a_off.ctypes.data_as(i64p), a_z.ctypes.data_as(_dp), a_n.ctypes.data_as(_dp)
+        _absorber_fields(rq, absorbers, nsel, keep, "selected quasars")
         bits = {"map": _lib.SPECTRA_MAP, "moments": _lib.SPECTRA_MOMENTS, "continuum": _lib.SPECTRA_CONTINUUM}
         products = [p for p in products if not (p == "moments" and weights is None)]
         rq.products = int(sum(bits[p] for p in set(products)))
@@ -409,8 +417,8 @@ class Batch:
         rq.capacity = total
         out = {"offsets": np.zeros(nsel + 1, dtype=np.int64), "status": np.zeros(nsel, dtype=np.int32)}
         ms = _lib.ModelSpectra()
-        ms.offsets = out["offsets"].ctypes.data_as(i64p)
-        ms.status = out["status"].ctypes.data_as(C.POINTER(C.c_int32))
+        ms.offsets = out["offsets"].ctypes.data_as(_i64p)
+        ms.status = out["status"].ctypes.data_as(_i32p)
         names = {"map": ("map_absorption",), "moments": ("mean_absorption", "var_absorption"),
                  "continuum": ("continuum", "model_flux")}
         for p in set(products):
@@ -443,7 +451,7 @@ class Batch:
         sel = self._selection(selection)
         rq = _refine.request(levels, delta, pad)
         ps = C.byref(prior._s) if prior is not None else None
-        _lib.check(self.ctx.lib.gpdla_batch_refine(self.ctx._h, self._h, sel.ctypes.data_as(C.POINTER(C.c_int64)),
+        _lib.check(self.ctx.lib.gpdla_batch_refine(self.ctx._h, self._h, sel.ctypes.data_as(_i64p),
                                                    sel.size, C.byref(rq), ps))
         self._refined = (int(levels), int(self.ctx.refine_points[0].size))
         return self.download_refined(sel, None, with_samples) if download else None
@@ -464,8 +472,8 @@ class Batch:
         r = _lib.RefinedResults()
         r.levels, r.num_points = last_levels, num_points
         for name in out:
-            setattr(r, name, out[name].ctypes.data_as(C.POINTER(C.c_int32 if name == "status" else C.c_double)))
-        _lib.check(self.ctx.lib.gpdla_batch_download_refined(self.ctx._h, self._h, sel.ctypes.data_as(C.POINTER(C.c_int64)),
+            setattr(r, name, out[name].ctypes.data_as(_i32p if name == "status" else _dp))
+        _lib.check(self.ctx.lib.gpdla_batch_download_refined(self.ctx._h, self._h, sel.ctypes.data_as(_i64p),
                                                              sel.size, C.byref(r)))
         out["selection"] = sel
         return out
@@ -485,15 +493,14 @@ class Batch:
         from . import posteriors
         p, t = posteriors.check_request(posteriors.DEFAULT_PROBABILITIES if probabilities is None else probabilities,
                                         posteriors.DEFAULT_THRESHOLDS if thresholds is None else thresholds)
-        sel = np.arange(self.num_quasars, dtype=np.int64) if selection is None else \
-            np.ascontiguousarray(selection, dtype=np.int64).reshape(-1)
+        sel = self._selection(selection)
         if refined:
             if multi or sub_dla or num_models not in (None, 1):
                 raise ValueError("refined=True: the refined table holds one single-DLA model (no multi, sub_dla or num_models)")
             out, ps = posteriors._outputs(sel.size, 1, len(p), len(t))
             rq = posteriors._request(1, p, t)
             _lib.check(self.ctx.lib.gpdla_batch_refined_summaries(
-                self.ctx._h, self._h, sel.ctypes.data_as(C.POINTER(C.c_int64)), sel.size, C.byref(rq), C.byref(ps)))
+                self.ctx._h, self._h, sel.ctypes.data_as(_i64p), sel.size, C.byref(rq), C.byref(ps)))
             last = self.download_refined(sel, None, with_samples=False)["boxes"][:, -1]   # the z range the rows were summarised on
             out = posteriors.finish(out, last[:, 0], last[:, 1], self.ctx._log_nhi_scale[0], p, t)
             out["selection"] = sel
@@ -502,7 +509,7 @@ class Batch:
         out, ps = posteriors._outputs(sel.size, md, len(p), len(t))
         rq = posteriors._request(md, p, t)
         _lib.check(self.ctx.lib.gpdla_batch_parameter_summaries(
-            self.ctx._h, self._h, int(bool(multi)), int(bool(sub_dla)), sel.ctypes.data_as(C.POINTER(C.c_int64)),
+            self.ctx._h, self._h, int(bool(multi)), int(bool(sub_dla)), sel.ctypes.data_as(_i64p),
             sel.size, C.byref(rq), C.byref(ps)))
         res = self.download_multi(with_samples=False) if self.max_dlas else self.download(with_samples=False)
         z_min, z_max = res["min_z_dlas"][sel], res["max_z_dlas"][sel]
@@ -537,18 +544,10 @@ class Batch:
         unknown = set(components) - set(self.MOCK_COMPONENTS)
         if unknown:
             raise ValueError(f"components: any of {self.MOCK_COMPONENTS}, got {sorted(unknown)}")
-        i64p = C.POINTER(C.c_int64)
         rq = _lib.MockRequest()
         rq.seed = int(getattr(self.ctx.params, "rng_seed", 0x9E3779B97F4A7C15) if seed is None else seed) & (2 ** 64 - 1)
         keep = []
-        if absorbers is not None:
-            a_off, a_z, a_ln = absorbers
-            a_off = np.ascontiguousarray(a_off, dtype=np.int64).reshape(-1)
-            if a_off.size != nq + 1:
-                raise _lib.GpdlaError(-1, f"absorber offsets: {a_off.size} entries for {nq} quasars")
-            a_z, a_n = _f64(a_z)[0].reshape(-1), 10.0 ** _f64(a_ln)[0].reshape(-1)
-            keep += [a_off, a_z, a_n]
-            rq.absorber_offsets, rq.absorber_z, rq.absorber_nhi = a_off.ctypes.data_as(i64p), a_z.ctypes.data_as(_dp), a_n.ctypes.data_as(_dp)
+        _absorber_fields(rq, absorbers, nq, keep, "quasars")
         rq.meanflux = int(bool(self.max_dlas) if meanflux is None else bool(meanflux))
         rq.write_resident = int(bool(write_resident))
         _lib.check(lib.gpdla_mock_validate(C.byref(rq), nq))  # refused requests never reach the device
@@ -559,8 +558,8 @@ class Batch:
                "grid_offsets": np.zeros(nq + 1, dtype=np.int64)}
         ms = _lib.MockSpectra()
         ms.flux = out["flux"].ctypes.data_as(_dp)
-        ms.grid_offsets = out["grid_offsets"].ctypes.data_as(i64p)
-        ms.status = out["status"].ctypes.data_as(C.POINTER(C.c_int32))
+        ms.grid_offsets = out["grid_offsets"].ctypes.data_as(_i64p)
+        ms.status = out["status"].ctypes.data_as(_i32p)
         for name in grid:
             out[name] = np.empty(total)
             setattr(ms, name, out[name].ctypes.data_as(_dp))
@@ -866,7 +865,7 @@ def _cells_struct(spectra, lp_no, lp_dla, lp_lls, keep: list) -> "_lib.SpectraCe
         a = np.ascontiguousarray(a, dtype=np.float64)
         keep.append(a)
         return a.ctypes.data_as(_dp)
-    return _lib.SpectraCells(n, npix.ctypes.data_as(C.POINTER(C.c_int64)), ptrs[0].ctypes.data, ptrs[1].ctypes.data,
+    return _lib.SpectraCells(n, npix.ctypes.data_as(_i64p), ptrs[0].ctypes.data, ptrs[1].ctypes.data,
                              ptrs[2].ctypes.data, ptrs[3].ctypes.data, z.ctypes.data_as(_dp), dptr(lp_no), dptr(lp_dla),
                              None if lp_lls is None else dptr(lp_lls))
 
@@ -1234,16 +1233,11 @@ def dla_model_mean(model: dict, z_qsos, absorbers=None, suppressed: bool = True,
     rw, rwp = _f64(model["rest_wavelengths"])
     mu, mup = _f64(model["mu"])
     m.num_rest_pixels, m.k, m.rest_wavelengths, m.mu = rw.size, 0, rwp, mup
-    offp = azp = anp = None
-    if absorbers is not None:
-        off = np.ascontiguousarray(absorbers[0], dtype=np.int64).reshape(-1)
-        if off.size != z.size + 1:
-            raise _lib.GpdlaError(-1, f"absorber offsets: {off.size} entries for {z.size} quasars")
-        az, an = _f64(absorbers[1])[0].reshape(-1), 10.0 ** _f64(absorbers[2])[0].reshape(-1)
-        keep += [off, az, an]
-        offp, azp, anp = off.ctypes.data_as(C.POINTER(C.c_int64)), az.ctypes.data_as(_dp), an.ctypes.data_as(_dp)
+    a = SimpleNamespace(absorber_offsets=None, absorber_z=None, absorber_nhi=None)
+    _absorber_fields(a, absorbers, z.size, keep, "quasars")
     out = np.empty((z.size, rw.size))
-    _lib.check(lib.gpdla_model_mean(C.byref(m), z.size, zp, offp, azp, anp, int(num_voigt_lines), int(num_forest_lines),
+    _lib.check(lib.gpdla_model_mean(C.byref(m), z.size, zp, a.absorber_offsets, a.absorber_z, a.absorber_nhi,
+                                    int(num_voigt_lines), int(num_forest_lines),
                                     int(bool(suppressed)), float(prev_tau_0), float(prev_beta),
                                     out.ctypes.data_as(_dp), int(device)))
     return out

@@ -47,6 +47,7 @@ using namespace gpdla;
 #include "host_context.hpp"
 #include "host_sweep.hpp"
 #include "host_multi.hpp"
+#include "host_consumers.hpp"
 #include "host_pipeline.hpp"
 #include "host_training.hpp"
 #include "host_learn.hpp"

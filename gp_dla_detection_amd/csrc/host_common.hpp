@@ -159,6 +159,42 @@ struct DeviceTemps {
   }
 };
 
+// The device temporaries of one call and its asynchronous copies on one stream.  Declared AFTER every
+// host buffer those copies read or write (StreamDrain's rule): on every exit path the stream is
+// drained first, then the temporaries are freed, and only then do those host buffers go.
+struct Staging {
+  hipStream_t st;
+  DeviceTemps tmp;
+  explicit Staging(hipStream_t stream) : st(stream) {}
+  ~Staging() { (void)hipStreamSynchronize(st); }
+  template <typename T>  // allocate, then host -> device
+  int put(T **dst, const T *src, size_t count) {
+    int rc = tmp.alloc(dst, count);
+    if (rc) return rc;
+    if (count) HIP_TRY(hipMemcpyAsync(*dst, src, count * sizeof(T), hipMemcpyHostToDevice, st));
+    return GPDLA_OK;
+  }
+  template <typename T>  // device -> host, where the caller asked for the array
+  int fetch(T *host, const T *dev, size_t count) {
+    if (host && count) HIP_TRY(hipMemcpyAsync(host, dev, count * sizeof(T), hipMemcpyDeviceToHost, st));
+    return GPDLA_OK;
+  }
+};
+
+// Two timing events of one call, destroyed on every exit path.
+struct EventPair {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  int create() {
+    HIP_TRY(hipEventCreate(&e0));
+    HIP_TRY(hipEventCreate(&e1));
+    return GPDLA_OK;
+  }
+  ~EventPair() {
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+  }
+};
+
 // -DONESHOT_EXP_TIMING (diagnostic build, profiles/r05_one_shot_timing.txt): where a one-shot call
 // spends what the sweeps do not, on stderr.  The code that reports is compiled in every build and
 // does nothing in the normal one.

@@ -147,6 +147,24 @@ struct MultiBuffers {
   }
 };
 
+namespace {
+
+// The timed region of gpdla_context_last_sweep_ms (gpdla_context_set_timing): around the kernels of the
+// context's most recent sweep, moments or mock-draw call on `st`.
+int begin_timing(gpdla_context *c, hipStream_t st) {
+  if (c->timing) HIP_TRY(hipEventRecord(c->ev0, st));
+  return GPDLA_OK;
+}
+
+int end_timing(gpdla_context *c, hipStream_t st) {
+  if (!c->timing) return GPDLA_OK;
+  HIP_TRY(hipEventRecord(c->ev1, st));
+  c->have_timing = true;
+  return GPDLA_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 void gpdla_default_config(gpdla_config *cfg) {

@@ -31,12 +31,8 @@ int gpdla_mock_validate(const gpdla_mock_request *rq, int64_t num_quasars) try {
 } GPDLA_NO_THROW
 
 int gpdla_batch_draw_mocks(gpdla_context *c, gpdla_batch *b, const gpdla_mock_request *rq, gpdla_mock_spectra *out) try {
-  if (!c || !b || b->ctx != c || !rq || !out || !out->grid_offsets)
-    return fail(GPDLA_ERR_INVALID_ARGUMENT, "null/mismatched argument");
-  int rc = validate_mock(rq, b->nq);
-  if (rc) return rc;
-  if (b->S != c->S || b->k != c->model.k)
-    return fail(GPDLA_ERR_INVALID_ARGUMENT, "model/samples changed after the batch was uploaded");
+  int rc = check_batch_pair(c, b, rq && out && out->grid_offsets);
+  if (rc || (rc = validate_mock(rq, b->nq)) || (rc = check_unchanged(c, b, true))) return rc;
   if (b->k > GPDLA_MAX_K) return fail(GPDLA_ERR_UNSUPPORTED, "k = %d above %d", b->k, GPDLA_MAX_K);
   if (out->flux && rq->capacity_stored < b->total_pix)
     return fail(GPDLA_ERR_INVALID_ARGUMENT, "the batch stores %lld pixels, capacity_stored is %lld", (long long)b->total_pix,
@@ -47,7 +43,7 @@ int gpdla_batch_draw_mocks(gpdla_context *c, gpdla_batch *b, const gpdla_mock_re
   std::vector<QuasarMeta> meta;
   if ((rc = spectra_prepare(c, b, rq->meanflux != 0, meta))) return rc;
 
-  std::vector<int64_t> sel((size_t)nq), off((size_t)nq + 1, 0), abs_off;
+  std::vector<int64_t> sel((size_t)nq), off((size_t)nq + 1, 0);
   std::vector<int32_t> status((size_t)nq);
   for (int64_t q = 0; q < nq; ++q) {
     sel[(size_t)q] = q;
@@ -62,55 +58,28 @@ int gpdla_batch_draw_mocks(gpdla_context *c, gpdla_batch *b, const gpdla_mock_re
   if (out->status) std::memcpy(out->status, status.data(), (size_t)nq * sizeof(int32_t));
   if (nq == 0) return GPDLA_OK;
 
-  DeviceTemps tmp;
-  StreamDrain drain{st};  // drained before the temporaries and the host vectors above go
-  int64_t *d_sel = nullptr, *d_off = nullptr, *d_abs_off = nullptr;
-  double *d_abs_z = nullptr, *d_abs_n = nullptr;
-  auto put = [&](auto **dst, const auto *src, size_t count) -> int {
-    int r = tmp.alloc(dst, count);
-    if (r) return r;
-    if (count) HIP_TRY(hipMemcpyAsync(*dst, src, count * sizeof(**dst), hipMemcpyHostToDevice, st));
-    return GPDLA_OK;
-  };
-  if ((rc = put(&d_off, off.data(), (size_t)nq + 1))) return rc;
-  const bool have_abs = rq->absorber_offsets && rq->absorber_offsets[nq] > rq->absorber_offsets[0];
+  AbsorberLists lists;
+  Staging sg(st);
+  int64_t *d_sel = nullptr, *d_off = nullptr;
+  if ((rc = sg.put(&d_off, off.data(), (size_t)nq + 1))) return rc;
+  if ((rc = lists.upload(sg, nq, rq->absorber_offsets, rq->absorber_z, rq->absorber_nhi))) return rc;
   const size_t tot = (size_t)total, npx = (size_t)b->total_pix;
 
   // a: k_spectra_map over the whole batch (skipped when it would be all ones and nobody asked for it)
   double *d_abs = nullptr;
-  if (have_abs || out->absorption) {
-    if ((rc = put(&d_sel, sel.data(), (size_t)nq))) return rc;
-    if (have_abs) {
-      const int64_t a0 = rq->absorber_offsets[0], na = rq->absorber_offsets[nq] - a0;
-      abs_off.resize((size_t)nq + 1);
-      for (int64_t q = 0; q <= nq; ++q) abs_off[(size_t)q] = rq->absorber_offsets[q] - a0;
-      if ((rc = put(&d_abs_off, abs_off.data(), (size_t)nq + 1))) return rc;
-      if ((rc = put(&d_abs_z, rq->absorber_z + a0, (size_t)na))) return rc;
-      if ((rc = put(&d_abs_n, rq->absorber_nhi + a0, (size_t)na))) return rc;
-    }
-    if ((rc = tmp.alloc(&d_abs, tot))) return rc;
-    SpectraMapArgs ma;
-    ma.meta = b->d_meta;
-    ma.lam_pad = b->d_lam;
-    ma.sel = d_sel;
-    ma.abs_off = d_abs_off;
-    ma.abs_z = d_abs_z;
-    ma.abs_n = d_abs_n;
-    ma.out_off = d_off;
-    ma.num_lines = c->cfg.num_lines;
-    ma.out = d_abs;
-    hipLaunchKernelGGL(k_spectra_map, dim3((unsigned)nq), dim3(256), 0, st, ma);
-    HIP_TRY(hipGetLastError());
+  if (lists.have_abs || out->absorption) {
+    if ((rc = sg.put(&d_sel, sel.data(), (size_t)nq)) || (rc = sg.tmp.alloc(&d_abs, tot))) return rc;
+    if ((rc = launch_spectra_map(c, b, nq, d_sel, d_off, lists, d_abs, st))) return rc;
   }
 
   double *d_flux = b->d_flux, *d_cont = nullptr, *d_sig = nullptr, *d_lat = nullptr;
   if (!rq->write_resident) {  // the draw is in place: on a copy of the resident flux
-    if ((rc = tmp.alloc(&d_flux, npx))) return rc;
+    if ((rc = sg.tmp.alloc(&d_flux, npx))) return rc;
     if (npx) HIP_TRY(hipMemcpyAsync(d_flux, b->d_flux, npx * sizeof(double), hipMemcpyDeviceToDevice, st));
   }
-  if (out->continuum && (rc = tmp.alloc(&d_cont, tot))) return rc;
-  if (out->sigma && (rc = tmp.alloc(&d_sig, tot))) return rc;
-  if (out->latents && (rc = tmp.alloc(&d_lat, (size_t)nq * (size_t)b->k))) return rc;
+  if (out->continuum && (rc = sg.tmp.alloc(&d_cont, tot))) return rc;
+  if (out->sigma && (rc = sg.tmp.alloc(&d_sig, tot))) return rc;
+  if (out->latents && (rc = sg.tmp.alloc(&d_lat, (size_t)nq * (size_t)b->k))) return rc;
   MockDrawArgs da;
   da.meta = b->d_meta;
   da.pix = b->d_pix;
@@ -126,7 +95,7 @@ int gpdla_batch_draw_mocks(gpdla_context *c, gpdla_batch *b, const gpdla_mock_re
   da.seed = rq->seed;
   da.first_quasar_index = c->cfg.first_quasar_index;
   da.grid_off = d_off;
-  da.absorption = have_abs ? d_abs : nullptr;
+  da.absorption = lists.have_abs ? d_abs : nullptr;
   da.flux = d_flux;
   da.continuum = d_cont;
   da.sigma = d_sig;
@@ -135,20 +104,13 @@ int gpdla_batch_draw_mocks(gpdla_context *c, gpdla_batch *b, const gpdla_mock_re
     b->processed = false;
     if (b->mb) b->mb->processed = false;
   }
-  if (c->timing) HIP_TRY(hipEventRecord(c->ev0, st));
+  if ((rc = begin_timing(c, st))) return rc;
   hipLaunchKernelGGL(k_mock_draw, dim3((unsigned)nq), dim3(256), 0, st, da);
   HIP_TRY(hipGetLastError());
-  if (c->timing) {
-    HIP_TRY(hipEventRecord(c->ev1, st));
-    c->have_timing = true;
-  }
-  auto fetch = [&](double *host, const double *dev, size_t count) -> int {
-    if (host && count) HIP_TRY(hipMemcpyAsync(host, dev, count * sizeof(double), hipMemcpyDeviceToHost, st));
-    return GPDLA_OK;
-  };
-  if ((rc = fetch(out->flux, d_flux, npx)) || (rc = fetch(out->absorption, d_abs, tot)) ||
-      (rc = fetch(out->continuum, d_cont, tot)) || (rc = fetch(out->sigma, d_sig, tot)) ||
-      (rc = fetch(out->latents, d_lat, (size_t)nq * (size_t)b->k)))
+  if ((rc = end_timing(c, st))) return rc;
+  if ((rc = sg.fetch(out->flux, d_flux, npx)) || (rc = sg.fetch(out->absorption, d_abs, tot)) ||
+      (rc = sg.fetch(out->continuum, d_cont, tot)) || (rc = sg.fetch(out->sigma, d_sig, tot)) ||
+      (rc = sg.fetch(out->latents, d_lat, (size_t)nq * (size_t)b->k)))
     return rc;
   HIP_TRY(hipStreamSynchronize(st));
   return GPDLA_OK;

@@ -106,7 +106,7 @@ int gpdla_batch_process_multi(gpdla_context *c, gpdla_batch *b, const uint32_t *
   int rc = multi_alloc(b);
   if (rc) return rc;
   MultiBuffers &mb = *b->mb;
-  if (c->timing) HIP_TRY(hipEventRecord(c->ev0, st));
+  if ((rc = begin_timing(c, st))) return rc;
   // (the multi-DLA sweeps walk the batch in profile-table sub-batches of their own: all records
   // are built up front, one group)
   const RecordClass cls = legacy_record_class(b->k, b->k <= 20 ? kRecSlim20 : kRecSlim40);
@@ -239,10 +239,7 @@ int gpdla_batch_process_multi(gpdla_context *c, gpdla_batch *b, const uint32_t *
   pp.summary = mb.summary;
   hipLaunchKernelGGL(k_multi_posteriors, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, pp);
   HIP_TRY(hipGetLastError());
-  if (c->timing) {
-    HIP_TRY(hipEventRecord(c->ev1, st));
-    c->have_timing = true;
-  }
+  if ((rc = end_timing(c, st))) return rc;
   HIP_TRY(hipEventRecord(b->ev_done, st));
   mb.processed = true;
   return GPDLA_OK;

@@ -14,14 +14,6 @@ namespace {
 // (gpdla_debug_last_summaries_ms; tools/bench_posteriors.py)
 thread_local double t_summaries_ms = -1.0;
 
-struct EventPair {
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  ~EventPair() {
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-  }
-};
-
 int validate_summary_request(const gpdla_summary_request *rq) {
   if (!rq) return fail(GPDLA_ERR_INVALID_ARGUMENT, "null request");
   if (rq->num_models < 1 || rq->num_models > GPDLA_POSTERIOR_MAX_MODELS)
@@ -74,16 +66,15 @@ int run_parameter_summaries(int64_t n, int64_t S, const double *d_sll, const std
   const size_t n_dbl = 5 * cells + 2 * cells * (size_t)Q + cells * (size_t)nt + models;
   std::vector<double> h_out(n_dbl);
   std::vector<int32_t> h_status(models);
-  DeviceTemps tmp;
-  StreamDrain drain{st};  // drained before the temporaries and the host vectors above go
+  Staging sg(st);
   double *d_out = nullptr, *d_vec = nullptr, *d_smp = nullptr;
   int32_t *d_status = nullptr, *d_rank = nullptr;
   int64_t *d_start = nullptr;
-  if ((rc = tmp.alloc(&d_out, n_dbl)) || (rc = tmp.alloc(&d_status, models)) || (rc = tmp.alloc(&d_vec, (size_t)4 * n)) ||
-      (rc = tmp.alloc(&d_smp, (size_t)2 * S)) || (rc = tmp.alloc(&d_rank, (size_t)4 * S)) ||
-      (rc = tmp.alloc(&d_start, (size_t)2 * n)))
+  if ((rc = sg.tmp.alloc(&d_out, n_dbl)) || (rc = sg.tmp.alloc(&d_status, models)) || (rc = sg.tmp.alloc(&d_vec, (size_t)4 * n)) ||
+      (rc = sg.tmp.alloc(&d_smp, (size_t)2 * S)) || (rc = sg.tmp.alloc(&d_rank, (size_t)4 * S)) ||
+      (rc = sg.tmp.alloc(&d_start, (size_t)2 * n)))
     return rc;
-  auto put = [&](auto *dst, const auto *src, size_t count) -> int {
+  auto put = [&](auto *dst, const auto *src, size_t count) -> int {  // into a carved block: no allocation
     if (count) HIP_TRY(hipMemcpyAsync(dst, src, count * sizeof(*dst), hipMemcpyHostToDevice, st));
     return GPDLA_OK;
   };
@@ -130,14 +121,12 @@ int run_parameter_summaries(int64_t n, int64_t S, const double *d_sll, const std
   a.ess = carve(models);
   a.status = d_status;
   EventPair ev;
-  HIP_TRY(hipEventCreate(&ev.e0));
-  HIP_TRY(hipEventCreate(&ev.e1));
+  if ((rc = ev.create())) return rc;
   HIP_TRY(hipEventRecord(ev.e0, st));
   hipLaunchKernelGGL(k_parameter_summaries, dim3((unsigned)(n * md)), dim3(256), 0, st, a);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(ev.e1, st));
-  HIP_TRY(hipMemcpyAsync(h_out.data(), d_out, n_dbl * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(h_status.data(), d_status, models * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  if ((rc = sg.fetch(h_out.data(), d_out, n_dbl)) || (rc = sg.fetch(h_status.data(), d_status, models))) return rc;
   HIP_TRY(hipStreamSynchronize(st));
   float ms = -1.f;
   HIP_TRY(hipEventElapsedTime(&ms, ev.e0, ev.e1));
@@ -213,27 +202,18 @@ int gpdla_batch_parameter_summaries(gpdla_context *c, gpdla_batch *b, int multi,
                                     int64_t num_selected, const gpdla_summary_request *request,
                                     gpdla_parameter_summaries *outputs) try {
   using namespace gpdla;
-  if (!c || !b || b->ctx != c || !outputs) return fail(GPDLA_ERR_INVALID_ARGUMENT, "null/mismatched argument");
-  int rc = validate_summary_request(request);
-  if (rc) return rc;
+  int rc = check_batch_pair(c, b, outputs != nullptr);
+  if (rc || (rc = validate_summary_request(request))) return rc;
   const int64_t nsel = num_selected, S = b->S;
   const int md = request->num_models;
-  if (nsel < 0 || (!selection && nsel > b->nq))
-    return fail(GPDLA_ERR_INVALID_ARGUMENT, "num_selected = %lld outside [0, %lld]", (long long)nsel, (long long)b->nq);
-  if (selection)
-    for (int64_t s = 0; s < nsel; ++s)
-      if (selection[s] < 0 || selection[s] >= b->nq)
-        return fail(GPDLA_ERR_INVALID_ARGUMENT, "selection[%lld] = %lld outside the batch of %lld quasars", (long long)s,
-                    (long long)selection[s], (long long)b->nq);
+  if ((rc = check_selection(b->nq, selection, nsel))) return rc;
   if ((multi != 0) != (b->md != 0))
     return fail(GPDLA_ERR_INVALID_ARGUMENT, b->md ? "a multi-DLA batch: pass multi != 0" : "a single-DLA batch: pass multi = 0");
   if (sub_dla && !multi) return fail(GPDLA_ERR_INVALID_ARGUMENT, "sub_dla needs a multi-DLA batch");
   if (sub_dla ? md != 1 : (multi ? md > b->md : md != 1))
     return fail(GPDLA_ERR_INVALID_ARGUMENT, "num_models = %d does not fit the batch (sub_dla and single-DLA: 1; multi: up to %d)",
                 md, (int)b->md);
-  if (b->md ? (!b->mb || !b->mb->processed) : !b->processed)
-    return fail(GPDLA_ERR_INVALID_ARGUMENT, "the batch has not been processed");
-  if (b->S != c->S) return fail(GPDLA_ERR_INVALID_ARGUMENT, "samples changed after the batch was uploaded");
+  if ((rc = check_processed(b)) || (rc = check_unchanged(c, b, false))) return rc;
   if (!c->d_log_nhi || (sub_dla && !c->d_lls_nhi))
     return fail(GPDLA_ERR_INVALID_ARGUMENT, "the context's samples lack log_nhi_samples / lls_nhi_samples");
   if (S > (1LL << 30)) return fail(GPDLA_ERR_UNSUPPORTED, "more than 2^30 samples");
@@ -253,16 +233,15 @@ int gpdla_batch_parameter_summaries(gpdla_context *c, gpdla_batch *b, int multi,
   }
   if (sub_dla)
     for (auto &v : lnhi) v = std::log10(v);
-  const int64_t row_w = b->md ? (sub_dla ? S : (int64_t)b->md * S) : S;
+  const SampleTable t = resident_samples(b, sub_dla != 0);
   for (int64_t s = 0; s < nsel; ++s) {
     const int64_t q = selection ? selection[s] : s;
     z_min[(size_t)s] = meta[(size_t)q].min_z_dla;
     z_max[(size_t)s] = meta[(size_t)q].max_z_dla;
-    row_start[(size_t)s] = q * row_w;
+    row_start[(size_t)s] = q * t.width;
     base_start[(size_t)s] = b->md ? q * (int64_t)(b->md - 1) * S : 0;
   }
-  const double *table = b->md ? (sub_dla ? b->mb->sll_lls : b->mb->sll_dla) : b->d_sample_ll;
-  return run_parameter_summaries(nsel, S, table, row_start, b->md ? b->mb->base : nullptr, base_start, z_min.data(),
+  return run_parameter_summaries(nsel, S, t.table, row_start, b->md ? b->mb->base : nullptr, base_start, z_min.data(),
                                  z_max.data(), offsets.data(), lnhi.data(), *request, *outputs, st);
 } GPDLA_NO_THROW
 

@@ -31,17 +31,6 @@ int validate_refine_points(int64_t n, const double *u, const double *v) {
   return GPDLA_OK;
 }
 
-int validate_refine_selection(const gpdla_batch *b, const int64_t *selection, int64_t nsel) {
-  if (nsel < 0 || (!selection && nsel > b->nq))
-    return fail(GPDLA_ERR_INVALID_ARGUMENT, "num_selected = %lld outside [0, %lld]", (long long)nsel, (long long)b->nq);
-  if (selection)
-    for (int64_t s = 0; s < nsel; ++s)
-      if (selection[s] < 0 || selection[s] >= b->nq)
-        return fail(GPDLA_ERR_INVALID_ARGUMENT, "selection[%lld] = %lld outside the batch of %lld quasars", (long long)s,
-                    (long long)selection[s], (long long)b->nq);
-  return GPDLA_OK;
-}
-
 // The tables of RefineBuffers in one allocation, each 256-byte aligned (batch_layout's scheme)
 size_t refine_layout(RefineBuffers *rf, char *base, size_t nq, size_t Sr) {
   size_t at = 0;
@@ -96,7 +85,8 @@ int launch_boxed_sweep(gpdla_context *c, gpdla_batch *b, RecordClass cls, int64_
 
 // what the refined entry points ask of a batch
 int check_refinable(gpdla_context *c, gpdla_batch *b) {
-  if (!c || !b || b->ctx != c) return fail(GPDLA_ERR_INVALID_ARGUMENT, "null/mismatched context or batch");
+  int rc = check_batch_pair(c, b);
+  if (rc) return rc;
   if (b->md) return fail(GPDLA_ERR_UNSUPPORTED, "the refine pass serves single-DLA batches only");
   if (c->cfg.contraction_precision == 1) return fail(GPDLA_ERR_UNSUPPORTED, "the refine pass is fp64 only (contraction_precision = 1)");
   if (b->k > 40) return fail(GPDLA_ERR_UNSUPPORTED, "k = %d: the refine pass serves k <= 40", b->k);
@@ -146,9 +136,8 @@ int gpdla_batch_refine(gpdla_context *c, gpdla_batch *b, const int64_t *selectio
   int rc = check_refinable(c, b);
   if (rc) return rc;
   if ((rc = validate_refine_request(request, prior))) return rc;
-  if ((rc = validate_refine_selection(b, selection, num_selected))) return rc;
-  if (!b->processed) return fail(GPDLA_ERR_INVALID_ARGUMENT, "the batch has not been processed");
-  if (b->S != c->S || b->k != c->model.k) return fail(GPDLA_ERR_INVALID_ARGUMENT, "model/samples changed after the batch was uploaded");
+  if ((rc = check_selection(b->nq, selection, num_selected))) return rc;
+  if ((rc = check_processed(b)) || (rc = check_unchanged(c, b, true))) return rc;
   if (c->Sr < 1) return fail(GPDLA_ERR_INVALID_ARGUMENT, "no refine points: call gpdla_context_set_refine_points");
   if (!(c->log_nhi_lo < c->log_nhi_hi) || !std::isfinite(c->log_nhi_lo) || !std::isfinite(c->log_nhi_hi))
     return fail(GPDLA_ERR_INVALID_ARGUMENT, "the log N table spans [%g, %g]: the refine pass needs a finite range of positive width",
@@ -240,8 +229,7 @@ int gpdla_batch_refine(gpdla_context *c, gpdla_batch *b, const int64_t *selectio
   // (the timed region spans every group and level, as gpdla_context_last_sweep_ms does for the first pass)
   EventPair ev;
   if (c->timing) {
-    HIP_TRY(hipEventCreate(&ev.e0));
-    HIP_TRY(hipEventCreate(&ev.e1));
+    if ((rc = ev.create())) return rc;
     HIP_TRY(hipEventRecord(ev.e0, st));
   }
   for (size_t g = 0; g < b->groups.size(); ++g) {
@@ -286,7 +274,7 @@ int gpdla_batch_download_refined(gpdla_context *c, gpdla_batch *b, const int64_t
   int rc = check_refinable(c, b);
   if (rc) return rc;
   if (!r) return fail(GPDLA_ERR_INVALID_ARGUMENT, "null results");
-  if ((rc = validate_refine_selection(b, selection, num_selected))) return rc;
+  if ((rc = check_selection(b->nq, selection, num_selected))) return rc;
   RefineBuffers *rf = b->rf;
   if (!rf || rf->levels < 1 || rf->nq != b->nq) return fail(GPDLA_ERR_INVALID_ARGUMENT, "the batch has not been refined");
   // the caller states what its arrays were sized for: a mismatch would write past them
@@ -334,7 +322,7 @@ int gpdla_batch_refined_summaries(gpdla_context *c, gpdla_batch *b, const int64_
   if (!outputs) return fail(GPDLA_ERR_INVALID_ARGUMENT, "null outputs");
   if ((rc = validate_summary_request(request))) return rc;
   if (request->num_models != 1) return fail(GPDLA_ERR_INVALID_ARGUMENT, "num_models = %d: the refined table holds one model", request->num_models);
-  if ((rc = validate_refine_selection(b, selection, num_selected))) return rc;
+  if ((rc = check_selection(b->nq, selection, num_selected))) return rc;
   RefineBuffers *rf = b->rf;
   if (!rf || rf->levels < 1 || rf->nq != b->nq) return fail(GPDLA_ERR_INVALID_ARGUMENT, "the batch has not been refined");
   if (rf->Sr != c->Sr || rf->points_gen != c->refine_points_gen)

@@ -25,18 +25,12 @@ int validate_absorbers(int64_t n, const int64_t *off, const double *z, const dou
 
 int validate_model_spectra(const gpdla_model_spectra_request *rq, int64_t nq, int64_t S, bool has_lls) {
   if (!rq) return fail(GPDLA_ERR_INVALID_ARGUMENT, "null request");
-  if (rq->num_selected < 0 || (!rq->selection && rq->num_selected > nq))
-    return fail(GPDLA_ERR_INVALID_ARGUMENT, "num_selected = %lld outside [0, %lld]", (long long)rq->num_selected, (long long)nq);
-  if (rq->selection)
-    for (int64_t s = 0; s < rq->num_selected; ++s)
-      if (rq->selection[s] < 0 || rq->selection[s] >= nq)
-        return fail(GPDLA_ERR_INVALID_ARGUMENT, "selection[%lld] = %lld outside the batch of %lld quasars", (long long)s,
-                    (long long)rq->selection[s], (long long)nq);
+  int rc = check_selection(nq, rq->selection, rq->num_selected);
+  if (rc) return rc;
   const int known = GPDLA_SPECTRA_MAP | GPDLA_SPECTRA_MOMENTS | GPDLA_SPECTRA_CONTINUUM;
   if (!rq->products || (rq->products & ~known))
     return fail(GPDLA_ERR_INVALID_ARGUMENT, "products = %d: a non-empty set of GPDLA_SPECTRA_MAP | _MOMENTS | _CONTINUUM", rq->products);
-  int rc = validate_absorbers(rq->num_selected, rq->absorber_offsets, rq->absorber_z, rq->absorber_nhi);
-  if (rc) return rc;
+  if ((rc = validate_absorbers(rq->num_selected, rq->absorber_offsets, rq->absorber_z, rq->absorber_nhi))) return rc;
   if (rq->products & GPDLA_SPECTRA_MOMENTS) {
     if (rq->weights_source != GPDLA_SPECTRA_WEIGHTS_RESIDENT && rq->weights_source != GPDLA_SPECTRA_WEIGHTS_HOST)
       return fail(GPDLA_ERR_INVALID_ARGUMENT, "mean / var absorption need a weights source (resident table or host table)");
@@ -76,32 +70,23 @@ int gpdla_model_spectra_validate(const gpdla_model_spectra_request *rq, int64_t 
 } GPDLA_NO_THROW
 
 int gpdla_batch_unmasked_counts(gpdla_context *c, gpdla_batch *b, int64_t *n_u) try {
-  if (!c || !b || b->ctx != c || !n_u) return fail(GPDLA_ERR_INVALID_ARGUMENT, "null/mismatched argument");
-  if (b->S != c->S || b->k != c->model.k)
-    return fail(GPDLA_ERR_INVALID_ARGUMENT, "model/samples changed after the batch was uploaded");
+  int rc = check_batch_pair(c, b, n_u != nullptr);
+  if (rc || (rc = check_unchanged(c, b, true))) return rc;
   HIP_TRY(hipSetDevice(c->device_id));
   std::vector<QuasarMeta> meta;
-  int rc = spectra_prepare(c, b, b->md != 0, meta);
-  if (rc) return rc;
+  if ((rc = spectra_prepare(c, b, b->md != 0, meta))) return rc;
   for (int64_t q = 0; q < b->nq; ++q) n_u[q] = meta[(size_t)q].n_u;
   return GPDLA_OK;
 } GPDLA_NO_THROW
 
 int gpdla_batch_model_spectra(gpdla_context *c, gpdla_batch *b, const gpdla_model_spectra_request *rq,
                               gpdla_model_spectra *out) try {
-  if (!c || !b || b->ctx != c || !rq || !out || !out->offsets)
-    return fail(GPDLA_ERR_INVALID_ARGUMENT, "null/mismatched argument");
-  int rc = validate_model_spectra(rq, b->nq, b->S, c->d_lls_nhi != nullptr);
-  if (rc) return rc;
-  if (b->S != c->S || b->k != c->model.k)
-    return fail(GPDLA_ERR_INVALID_ARGUMENT, "model/samples changed after the batch was uploaded");
+  int rc = check_batch_pair(c, b, rq && out && out->offsets);
+  if (rc || (rc = validate_model_spectra(rq, b->nq, b->S, c->d_lls_nhi != nullptr)) || (rc = check_unchanged(c, b, true))) return rc;
   const bool want_map = (rq->products & GPDLA_SPECTRA_MAP) && out->map_absorption;
   const bool want_mom = (rq->products & GPDLA_SPECTRA_MOMENTS) && (out->mean_absorption || out->var_absorption);
   const bool want_cont = (rq->products & GPDLA_SPECTRA_CONTINUUM) && (out->continuum || out->model_flux);
-  if (want_mom && rq->weights_source == GPDLA_SPECTRA_WEIGHTS_RESIDENT) {
-    if (b->md ? (!b->mb || !b->mb->processed) : !b->processed)
-      return fail(GPDLA_ERR_INVALID_ARGUMENT, "resident weights: the batch has not been processed");
-  }
+  if (want_mom && rq->weights_source == GPDLA_SPECTRA_WEIGHTS_RESIDENT && (rc = check_processed(b, "resident weights: "))) return rc;
   const int64_t nsel = rq->num_selected;
   HIP_TRY(hipSetDevice(c->device_id));
   hipStream_t st = c->stream;
@@ -120,52 +105,22 @@ int gpdla_batch_model_spectra(gpdla_context *c, gpdla_batch *b, const gpdla_mode
                 (long long)total, (long long)rq->capacity);
   if (nsel == 0) return GPDLA_OK;
 
-  std::vector<int64_t> abs_off, rows((size_t)nsel);
+  std::vector<int64_t> rows((size_t)nsel);
   std::vector<int32_t> status((size_t)nsel);
-  DeviceTemps tmp;
-  StreamDrain drain{st};  // drained before the temporaries and the host vectors above go
-  int64_t *d_sel = nullptr, *d_off = nullptr, *d_abs_off = nullptr;
-  double *d_abs_z = nullptr, *d_abs_n = nullptr;
-  auto put = [&](auto **dst, const auto *src, size_t count) -> int {
-    int r = tmp.alloc(dst, count);
-    if (r) return r;
-    if (count) HIP_TRY(hipMemcpyAsync(*dst, src, count * sizeof(**dst), hipMemcpyHostToDevice, st));
-    return GPDLA_OK;
-  };
-  if ((rc = put(&d_sel, sel.data(), (size_t)nsel))) return rc;
-  if ((rc = put(&d_off, off.data(), (size_t)nsel + 1))) return rc;
-  const bool have_abs = rq->absorber_offsets && rq->absorber_offsets[nsel] > rq->absorber_offsets[0];
-  if (have_abs) {
-    const int64_t a0 = rq->absorber_offsets[0], na = rq->absorber_offsets[nsel] - a0;
-    abs_off.resize((size_t)nsel + 1);
-    for (int64_t s = 0; s <= nsel; ++s) abs_off[(size_t)s] = rq->absorber_offsets[s] - a0;
-    if ((rc = put(&d_abs_off, abs_off.data(), (size_t)nsel + 1))) return rc;
-    if ((rc = put(&d_abs_z, rq->absorber_z + a0, (size_t)na))) return rc;
-    if ((rc = put(&d_abs_n, rq->absorber_nhi + a0, (size_t)na))) return rc;
-  }
+  AbsorberLists lists;
+  Staging sg(st);
+  int64_t *d_sel = nullptr, *d_off = nullptr;
+  if ((rc = sg.put(&d_sel, sel.data(), (size_t)nsel))) return rc;
+  if ((rc = sg.put(&d_off, off.data(), (size_t)nsel + 1))) return rc;
+  if ((rc = lists.upload(sg, nsel, rq->absorber_offsets, rq->absorber_z, rq->absorber_nhi))) return rc;
   const size_t tot = (size_t)total;
-  auto fetch = [&](double *host, const double *dev) -> int {
-    if (host && tot) HIP_TRY(hipMemcpyAsync(host, dev, tot * sizeof(double), hipMemcpyDeviceToHost, st));
-    return GPDLA_OK;
-  };
 
   // P1 (also the absorption the continuum conditions on)
   double *d_map = nullptr;
-  if (want_map || (want_cont && have_abs)) {
-    if ((rc = tmp.alloc(&d_map, tot))) return rc;
-    SpectraMapArgs ma;
-    ma.meta = b->d_meta;
-    ma.lam_pad = b->d_lam;
-    ma.sel = d_sel;
-    ma.abs_off = d_abs_off;
-    ma.abs_z = d_abs_z;
-    ma.abs_n = d_abs_n;
-    ma.out_off = d_off;
-    ma.num_lines = c->cfg.num_lines;
-    ma.out = d_map;
-    hipLaunchKernelGGL(k_spectra_map, dim3((unsigned)nsel), dim3(256), 0, st, ma);
-    HIP_TRY(hipGetLastError());
-    if (want_map && (rc = fetch(out->map_absorption, d_map))) return rc;
+  if (want_map || (want_cont && lists.have_abs)) {
+    if ((rc = sg.tmp.alloc(&d_map, tot))) return rc;
+    if ((rc = launch_spectra_map(c, b, nsel, d_sel, d_off, lists, d_map, st))) return rc;
+    if (want_map && (rc = sg.fetch(out->map_absorption, d_map, tot))) return rc;
   }
 
   // P2
@@ -176,19 +131,17 @@ int gpdla_batch_model_spectra(gpdla_context *c, gpdla_batch *b, const gpdla_mode
     int32_t *d_flag = nullptr;
     const double *table;
     if (rq->weights_source == GPDLA_SPECTRA_WEIGHTS_HOST) {
-      if ((rc = put(&d_table, rq->sample_log_likelihoods, (size_t)nsel * S))) return rc;
+      if ((rc = sg.put(&d_table, rq->sample_log_likelihoods, (size_t)nsel * S))) return rc;
       table = d_table;
       for (int64_t s = 0; s < nsel; ++s) rows[(size_t)s] = s * S;
-    } else if (b->md) {  // [nq][max_dlas][S]: model DLA(1) is row 0 of a quasar; the sub-DLA table is [nq][S]
-      table = rq->sub_dla ? b->mb->sll_lls : b->mb->sll_dla;
-      for (int64_t s = 0; s < nsel; ++s) rows[(size_t)s] = sel[(size_t)s] * (rq->sub_dla ? S : (int64_t)b->md * S);
     } else {
-      table = b->d_sample_ll;
-      for (int64_t s = 0; s < nsel; ++s) rows[(size_t)s] = sel[(size_t)s] * S;
+      const SampleTable t = resident_samples(b, rq->sub_dla != 0);
+      table = t.table;
+      for (int64_t s = 0; s < nsel; ++s) rows[(size_t)s] = sel[(size_t)s] * t.width;
     }
-    if ((rc = put(&d_rows, rows.data(), (size_t)nsel))) return rc;
-    if ((rc = tmp.alloc(&d_w, (size_t)nsel * S)) || (rc = tmp.alloc(&d_flag, (size_t)nsel)) ||
-        (rc = tmp.alloc(&d_mean, tot)) || (rc = tmp.alloc(&d_var, tot)))
+    if ((rc = sg.put(&d_rows, rows.data(), (size_t)nsel))) return rc;
+    if ((rc = sg.tmp.alloc(&d_w, (size_t)nsel * S)) || (rc = sg.tmp.alloc(&d_flag, (size_t)nsel)) ||
+        (rc = sg.tmp.alloc(&d_mean, tot)) || (rc = sg.tmp.alloc(&d_var, tot)))
       return rc;
     SpectraWeightsArgs wa;
     wa.table = table;
@@ -204,9 +157,9 @@ int gpdla_batch_model_spectra(gpdla_context *c, gpdla_batch *b, const gpdla_mode
     const size_t per_q = (size_t)chunks * 2 * (size_t)stride;
     const int64_t nsub = std::min<int64_t>(nsel, std::max<int64_t>(1, (int64_t)(kSpectraPartialBytes / (per_q * sizeof(double)))));
     if ((int64_t)nsub * chunks > 2147483647LL) return fail(GPDLA_ERR_UNSUPPORTED, "selection too large for one launch");
-    if ((rc = tmp.alloc(&d_part, (size_t)nsub * per_q))) return rc;
+    if ((rc = sg.tmp.alloc(&d_part, (size_t)nsub * per_q))) return rc;
     // (gpdla_context_set_timing: the moments kernels of this call are what gpdla_context_last_sweep_ms reports)
-    if (c->timing) HIP_TRY(hipEventRecord(c->ev0, st));
+    if ((rc = begin_timing(c, st))) return rc;
     for (int64_t s0 = 0; s0 < nsel; s0 += nsub) {
       const int64_t n = std::min(nsub, nsel - s0);
       SpectraMomentsArgs pa;
@@ -239,11 +192,8 @@ int gpdla_batch_model_spectra(gpdla_context *c, gpdla_batch *b, const gpdla_mode
       hipLaunchKernelGGL(k_spectra_combine, dim3((unsigned)n), dim3(256), 0, st, ca);
       HIP_TRY(hipGetLastError());
     }
-    if (c->timing) {
-      HIP_TRY(hipEventRecord(c->ev1, st));
-      c->have_timing = true;
-    }
-    if ((rc = fetch(out->mean_absorption, d_mean)) || (rc = fetch(out->var_absorption, d_var))) return rc;
+    if ((rc = end_timing(c, st))) return rc;
+    if ((rc = sg.fetch(out->mean_absorption, d_mean, tot)) || (rc = sg.fetch(out->var_absorption, d_var, tot))) return rc;
   }
 
   // P3
@@ -251,7 +201,7 @@ int gpdla_batch_model_spectra(gpdla_context *c, gpdla_batch *b, const gpdla_mode
   if (want_cont) {
     double *d_cont = nullptr, *d_flux = nullptr;
     int32_t *d_status = nullptr;
-    if ((rc = tmp.alloc(&d_cont, tot)) || (rc = tmp.alloc(&d_flux, tot)) || (rc = tmp.alloc(&d_status, (size_t)nsel))) return rc;
+    if ((rc = sg.tmp.alloc(&d_cont, tot)) || (rc = sg.tmp.alloc(&d_flux, tot)) || (rc = sg.tmp.alloc(&d_status, (size_t)nsel))) return rc;
     SpectraContinuumArgs ka;
     ka.meta = b->d_meta;
     ka.pix = b->d_pix;
@@ -260,7 +210,7 @@ int gpdla_batch_model_spectra(gpdla_context *c, gpdla_batch *b, const gpdla_mode
     ka.z_qsos = b->d_z;
     ka.sel = d_sel;
     ka.out_off = d_off;
-    ka.absorption = have_abs ? d_map : nullptr;
+    ka.absorption = lists.have_abs ? d_map : nullptr;
     ka.model = c->model;
     ka.lya_wavelength = c->cfg.lya_wavelength;
     ka.prev_tau_0 = c->cfg.prev_tau_0;
@@ -272,8 +222,9 @@ int gpdla_batch_model_spectra(gpdla_context *c, gpdla_batch *b, const gpdla_mode
     ka.status = d_status;
     hipLaunchKernelGGL(k_spectra_continuum, dim3((unsigned)nsel), dim3(256), 0, st, ka);
     HIP_TRY(hipGetLastError());
-    if ((rc = fetch(out->continuum, d_cont)) || (rc = fetch(out->model_flux, d_flux))) return rc;
-    HIP_TRY(hipMemcpyAsync(status.data(), d_status, (size_t)nsel * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if ((rc = sg.fetch(out->continuum, d_cont, tot)) || (rc = sg.fetch(out->model_flux, d_flux, tot)) ||
+        (rc = sg.fetch(status.data(), d_status, (size_t)nsel)))
+      return rc;
   }
   HIP_TRY(hipStreamSynchronize(st));
   if (out->status) std::memcpy(out->status, status.data(), (size_t)nsel * sizeof(int32_t));
@@ -281,25 +232,21 @@ int gpdla_batch_model_spectra(gpdla_context *c, gpdla_batch *b, const gpdla_mode
 } GPDLA_NO_THROW
 
 int gpdla_debug_profiles_ms(gpdla_context *c, gpdla_batch *b, double *ms_out) try {
-  if (!c || !b || b->ctx != c || !ms_out) return fail(GPDLA_ERR_INVALID_ARGUMENT, "null/mismatched argument");
+  int rc = check_batch_pair(c, b, ms_out != nullptr);
+  if (rc) return rc;
   if (!b->md) return fail(GPDLA_ERR_INVALID_ARGUMENT, "not a multi-DLA batch (upload it with log_priors_lls)");
   if (b->S != c->S || b->k != c->model.k || !c->d_lls_nhi)
     return fail(GPDLA_ERR_INVALID_ARGUMENT, "model/samples changed after the batch was uploaded, or no lls_nhi_samples");
   HIP_TRY(hipSetDevice(c->device_id));
   std::lock_guard<std::mutex> multi_lock(c->multi_mu);
   hipStream_t st = c->stream;
-  int rc = multi_alloc(b);
-  if (rc) return rc;
+  if ((rc = multi_alloc(b))) return rc;
   if ((rc = launch_prepare(c, b, true))) return rc;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  HIP_TRY(hipEventCreate(&e0));
-  if (hipEventCreate(&e1) != hipSuccess) {
-    (void)hipEventDestroy(e0);
-    return fail(GPDLA_ERR_HIP, "hipEventCreate failed");
-  }
-  hipError_t e = hipEventRecord(e0, st);
+  EventPair ev;
+  if ((rc = ev.create())) return rc;
+  HIP_TRY(hipEventRecord(ev.e0, st));
   const int64_t nq_sub = b->mb->prof_quasars;
-  for (int64_t q0 = 0; q0 < b->nq && e == hipSuccess; q0 += nq_sub) {
+  for (int64_t q0 = 0; q0 < b->nq; q0 += nq_sub) {
     ProfilesArgs pa;
     pa.meta = b->d_meta;
     pa.lam_pad = b->d_lam;
@@ -315,15 +262,12 @@ int gpdla_debug_profiles_ms(gpdla_context *c, gpdla_batch *b, double *ms_out) tr
     pa.prof = c->d_prof;
     const int64_t waves = (int64_t)pa.nq_sub * ((b->S + 63) / 64);
     hipLaunchKernelGGL(k_profiles, dim3((unsigned)((waves + kProfWaves - 1) / kProfWaves)), dim3(kProfWaves * 64), 0, st, pa);
-    e = hipGetLastError();
+    HIP_TRY(hipGetLastError());
   }
-  if (e == hipSuccess) e = hipEventRecord(e1, st);
-  if (e == hipSuccess) e = hipEventSynchronize(e1);
+  HIP_TRY(hipEventRecord(ev.e1, st));
+  HIP_TRY(hipEventSynchronize(ev.e1));
   float ms = -1.f;
-  if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  if (e != hipSuccess) return fail(GPDLA_ERR_HIP, "gpdla_debug_profiles_ms: %s", hipGetErrorString(e));
+  HIP_TRY(hipEventElapsedTime(&ms, ev.e0, ev.e1));
   *ms_out = (double)ms;
   return GPDLA_OK;
 } GPDLA_NO_THROW
@@ -343,36 +287,21 @@ int gpdla_model_mean(const gpdla_model *model, int64_t num_items, const double *
   if ((rc = select_device(device_id))) return rc;
   if ((rc = ensure_line_table(device_id))) return rc;
   const size_t G = (size_t)model->num_rest_pixels, n = (size_t)num_items;
-  std::vector<int64_t> off(n + 1, 0);
-  int64_t a0 = 0;
-  if (absorber_offsets) {
-    a0 = absorber_offsets[0];
-    for (size_t i = 0; i <= n; ++i) off[i] = absorber_offsets[i] - a0;
-  }
-  const size_t na = (size_t)off[n];
-  DeviceTemps tmp;
-  double *d_rest = nullptr, *d_mu = nullptr, *d_z = nullptr, *d_az = nullptr, *d_an = nullptr, *d_out = nullptr;
-  int64_t *d_off = nullptr;
-  if ((rc = tmp.alloc(&d_rest, G)) || (rc = tmp.alloc(&d_mu, G)) || (rc = tmp.alloc(&d_z, n)) || (rc = tmp.alloc(&d_az, na)) ||
-      (rc = tmp.alloc(&d_an, na)) || (rc = tmp.alloc(&d_out, n * G)) || (rc = tmp.alloc(&d_off, n + 1)))
+  AbsorberLists lists;
+  Staging sg(nullptr);  // the default stream, which the blocking copy of the result waits for
+  double *d_rest = nullptr, *d_mu = nullptr, *d_z = nullptr, *d_out = nullptr;
+  if ((rc = sg.put(&d_rest, model->rest_wavelengths, G)) || (rc = sg.put(&d_mu, model->mu, G)) || (rc = sg.put(&d_z, z_qsos, n)) ||
+      (rc = lists.upload(sg, num_items, absorber_offsets, absorber_z, absorber_nhi, true)) || (rc = sg.tmp.alloc(&d_out, n * G)))
     return rc;
-  HIP_TRY(hipMemcpy(d_rest, model->rest_wavelengths, G * sizeof(double), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_mu, model->mu, G * sizeof(double), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_z, z_qsos, n * sizeof(double), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_off, off.data(), (n + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
-  if (na) {
-    HIP_TRY(hipMemcpy(d_az, absorber_z + a0, na * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_an, absorber_nhi + a0, na * sizeof(double), hipMemcpyHostToDevice));
-  }
   SpectraModelMeanArgs ma;
   ma.rest = d_rest;
   ma.mu = d_mu;
   ma.G = (int32_t)G;
   ma.num_items = num_items;
   ma.z_qsos = d_z;
-  ma.abs_off = d_off;
-  ma.abs_z = d_az;
-  ma.abs_n = d_an;
+  ma.abs_off = lists.d_off;
+  ma.abs_z = lists.d_z;
+  ma.abs_n = lists.d_nhi;
   ma.num_voigt_lines = num_voigt_lines;
   ma.num_forest_lines = num_forest_lines;
   ma.suppressed = suppressed ? 1 : 0;

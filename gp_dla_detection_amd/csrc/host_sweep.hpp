@@ -233,17 +233,14 @@ int gpdla_batch_process(gpdla_context *c, gpdla_batch *b) try {
   sa.blocks_per_quasar = 0;  // set by launch_sweep_kernel
   // the timed region of gpdla_context_last_sweep_ms spans the sweeps of all groups (one group unless
   // the records exceed cfg.record_pool_bytes)
-  if (c->timing) HIP_TRY(hipEventRecord(c->ev0, st));
+  if ((rc = begin_timing(c, st))) return rc;
   for (const auto &g : b->groups) {
     if ((rc = launch_build_records(c, b, g.first, g.second, f32, cls))) return rc;
     sa.order = b->d_order + g.first;
     sa.nq = g.second - g.first;
     if ((rc = launch_sweep(c, b, cls, f32, sa))) return rc;
   }
-  if (c->timing) {
-    HIP_TRY(hipEventRecord(c->ev1, st));
-    c->have_timing = true;
-  }
+  if ((rc = end_timing(c, st))) return rc;
 
   EvidenceArgs ea;
   ea.meta = b->d_meta;

@@ -182,6 +182,7 @@ def test_mock_validate_needs_no_gpu(lib):
     assert lib.gpdla_mock_validate(None, 5) == -1
     many, keep = _request([0, 9], np.full(9, 2.5), np.full(9, 1e21))
     assert lib.gpdla_mock_validate(C.byref(many), 1) == -1 and b"at most 8" in lib.gpdla_last_error()
+    assert lib.gpdla_last_error() == b"9 absorbers for entry 0: at most 8"
     eight, keep = _request([0, 8], np.full(8, 2.5), np.full(8, 1e21))
     assert lib.gpdla_mock_validate(C.byref(eight), 1) == 0
     dec, keep = _request([0, 2, 1], [2.1, 2.2], [1e20, 1e21])

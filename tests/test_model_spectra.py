@@ -3,6 +3,7 @@ compare against is itself held to reference-produced numbers, the host helper th
 absorbers, request validation without a device, the file round trip, and the dense-versus-Woodbury
 agreement of the restatement's continuum that sets the GPU test's tolerance."""
 import ctypes as C
+import os
 
 import numpy as np
 import pytest
@@ -121,16 +122,21 @@ def test_invalid_requests_are_rejected_without_a_device(lib):
     z, n = np.full(9, 2.5), np.full(9, 1e20)
     bad, keep = _request(absorber_offsets=np.array([0, 9, 9], dtype=np.int64), absorber_z=z, absorber_nhi=n)
     assert f(C.byref(bad), 3, 10, 0) == _lib.ERR_INVALID_ARGUMENT and b"at most 8" in lib.gpdla_last_error()
+    assert lib.gpdla_last_error() == b"9 absorbers for entry 0: at most 8"
     eight, keep = _request(absorber_offsets=np.array([0, 8, 9], dtype=np.int64), absorber_z=z, absorber_nhi=n)
     assert f(C.byref(eight), 3, 10, 0) == 0
     bad, keep = _request(absorber_offsets=np.array([0, 3, 2], dtype=np.int64), absorber_z=z, absorber_nhi=n)
     assert f(C.byref(bad), 3, 10, 0) == -1 and b"non-decreasing" in lib.gpdla_last_error()
     bad, keep = _request(selection=np.array([0, 3], dtype=np.int64))
     assert f(C.byref(bad), 3, 10, 0) == -1 and b"selection[1] = 3" in lib.gpdla_last_error()
+    # (the two selection messages are worded in one place, csrc/host_consumers.hpp, for every entry that takes one)
+    assert lib.gpdla_last_error() == b"selection[1] = 3 outside the batch of 3 quasars"
     bad, keep = _request(selection=np.array([-1, 0], dtype=np.int64))
-    assert f(C.byref(bad), 3, 10, 0) == -1
+    assert f(C.byref(bad), 3, 10, 0) == -1 and lib.gpdla_last_error() == b"selection[0] = -1 outside the batch of 3 quasars"
     bad, _ = _request(nsel=4)                                   # no selection: the first num_selected quasars
-    assert f(C.byref(bad), 3, 10, 0) == -1
+    assert f(C.byref(bad), 3, 10, 0) == -1 and lib.gpdla_last_error() == b"num_selected = 4 outside [0, 3]"
+    bad, _ = _request(nsel=-1)
+    assert f(C.byref(bad), 3, 10, 0) == -1 and lib.gpdla_last_error() == b"num_selected = -1 outside [0, 3]"
     bad, _ = _request(products=_lib.SPECTRA_MOMENTS)            # no weights source
     assert f(C.byref(bad), 3, 10, 0) == -1 and b"weights source" in lib.gpdla_last_error()
     bad, _ = _request(products=_lib.SPECTRA_MOMENTS, weights_source=_lib.SPECTRA_WEIGHTS_HOST)
@@ -147,6 +153,14 @@ def test_invalid_requests_are_rejected_without_a_device(lib):
     out = _lib.ModelSpectra()
     assert lib.gpdla_batch_model_spectra(None, None, C.byref(ok), C.byref(out)) == -1
     assert lib.gpdla_batch_unmasked_counts(None, None, None) == -1
+
+
+def test_the_consumers_header_is_a_host_source():
+    """csrc/host_consumers.hpp is found by the rebuild check and the source-reading tests, between the sweeps
+    it builds on and the first entry that uses it."""
+    units = [os.path.basename(p) for p in _lib.host_sources()]
+    assert "host_consumers.hpp" in units
+    assert units.index("host_multi.hpp") < units.index("host_consumers.hpp") < units.index("host_spectra.hpp")
 
 
 def test_model_mean_validates_before_the_device(lib):
