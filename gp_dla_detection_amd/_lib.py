@@ -198,6 +198,11 @@ class RefinedResults(C.Structure):
                                    "MAP_log_nhis_refined", "MAP_inds_refined")] + [("status", _i32p)]
 
 
+class RefinedPosteriors(C.Structure):
+    """gpdla_refined_posteriors"""
+    _fields_ = [("model_posteriors_refined", _dp), ("p_no_dlas_refined", _dp), ("p_dlas_refined", _dp), ("refined", _i32p)]
+
+
 REFINE_MAX_LEVELS, REFINE_UNUSABLE, REFINE_NOT_REFINED = 4, 1, -1   # GPDLA_REFINE_*
 POSTERIOR_MAX_MODELS, POSTERIOR_MAX_PROBABILITIES, POSTERIOR_MAX_THRESHOLDS = 4, 8, 4   # GPDLA_POSTERIOR_MAX_*
 POSTERIOR_UNUSABLE, POSTERIOR_NAN_RANGE = 1, 2                                          # status bits
@@ -269,6 +274,10 @@ SYMBOLS = [
     ("gpdla_training_download", C.c_int, [C.c_void_p, _dp, _dp, _dp]),
     ("gpdla_stats_bin_posteriors", C.c_int, [C.c_int64, C.c_int64, _dp, C.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
                                              C.c_int, C.POINTER(BinRequest), C.POINTER(BinOutput), C.c_int]),
+    ("gpdla_stats_bin_posteriors_boxed", C.c_int, [C.c_int64, C.c_int64, _dp, C.c_int64, _dp, _dp, _dp, _dp, _dp,
+                                                   C.c_int, C.POINTER(BinRequest), C.POINTER(BinOutput), _dp, C.c_int]),
+    ("gpdla_debug_time_bin_kernels", None, [C.c_int]),
+    ("gpdla_debug_last_bin_ms", C.c_double, []),
     ("gpdla_stats_poisson_binomial_cf", C.c_int, [C.c_int64, _i64p, _dp, _dp, _dp, C.c_int]),
     ("gpdla_stats_sightline_snrs", C.c_int, [C.c_int64, _i64p, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int]),
     ("gpdla_stats_path_lengths", C.c_int, [C.c_int64, _dp, _dp, C.c_int, _dp, C.c_int, C.c_double, C.c_double, _dp,
@@ -305,6 +314,7 @@ SYMBOLS = [
     ("gpdla_batch_download_refined", C.c_int, [C.c_void_p, C.c_void_p, _i64p, C.c_int64, C.POINTER(RefinedResults)]),
     ("gpdla_batch_refined_summaries", C.c_int, [C.c_void_p, C.c_void_p, _i64p, C.c_int64, C.POINTER(SummaryRequest),
                                                 C.POINTER(ParameterSummaries)]),
+    ("gpdla_batch_refined_posteriors", C.c_int, [C.c_void_p, C.c_void_p, _i64p, C.c_int64, C.POINTER(RefinedPosteriors)]),
     ("gpdla_debug_last_refine_ms", C.c_double, []),
     ("gpdla_debug_near_poly", C.c_int, [C.c_int, C.c_double, _dp, _dp]),
     ("gpdla_debug_prepared_rows", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, _dp, C.c_int64, _i64p]),

@@ -456,11 +456,16 @@ class Batch:
         self._refined = (int(levels), int(self.ctx.refine_points[0].size))
         return self.download_refined(sel, None, with_samples) if download else None
 
-    def download_refined(self, selection=None, levels: int | None = None, with_samples: bool = True) -> dict:
+    def download_refined(self, selection=None, levels: int | None = None, with_samples=True, out: dict | None = None,
+                         at: int = 0) -> dict:
         """The resident results of the last :meth:`refine` for quasars of its selection
         (gpdla_batch_download_refined).  The arrays are sized by what that call was made with -- its levels
         and the point set of that time, which the batch remembers; ``levels``, if given, must agree.  The
-        library checks the sizes again and refuses a mismatch."""
+        library checks the sizes again and refuses a mismatch.  ``with_samples``: True (both sample tables),
+        False, or the names of the tables wanted -- a table not asked for is not copied off the device.
+        ``out`` / ``at``: write the rows into rows ``at .. at + n`` of arrays made by
+        :func:`refine.empty_results` (a pipeline's one set of output arrays) instead of allocating; keys
+        ``out`` does not hold are not downloaded."""
         from . import refine as _refine
         if self._refined is None:
             raise _lib.GpdlaError(_lib.ERR_INVALID_ARGUMENT, "the batch has not been refined")
@@ -468,14 +473,39 @@ class Batch:
         if levels is not None and int(levels) != last_levels:
             raise ValueError(f"levels = {levels}, but the batch was refined with {last_levels} levels")
         sel = self._selection(selection)
-        out = _refine.empty_results(sel.size, last_levels, num_points, with_samples)
+        fields = {name for name, _ in _lib.RefinedResults._fields_}
+        if out is None:
+            out, at = _refine.empty_results(sel.size, last_levels, num_points, with_samples), 0
+            views = out
+        else:
+            views = {name: a[at:at + sel.size] for name, a in out.items() if name in fields}
+            if views["boxes"].shape[1:] != (last_levels, 4) or any(
+                    views[k].shape[1] != num_points for k in _refine.TABLES if k in views):
+                raise ValueError("the output arrays were not made for this refine's levels and points")
         r = _lib.RefinedResults()
         r.levels, r.num_points = last_levels, num_points
-        for name in out:
-            setattr(r, name, out[name].ctypes.data_as(_i32p if name == "status" else _dp))
+        for name, view in views.items():
+            if name in fields:
+                assert view.flags.c_contiguous and view.shape[0] == sel.size
+                setattr(r, name, view.ctypes.data_as(_i32p if name == "status" else _dp))
         _lib.check(self.ctx.lib.gpdla_batch_download_refined(self.ctx._h, self._h, sel.ctypes.data_as(_i64p),
                                                              sel.size, C.byref(r)))
-        out["selection"] = sel
+        if views is out:
+            out["selection"] = sel
+        return out
+
+    def refined_posteriors(self, selection=None) -> dict:
+        """The model posteriors of the selected quasars with the refined evidence in the place of the first
+        pass's (gpdla_batch_refined_posteriors, after :meth:`refine`):
+        ``model_posteriors_refined`` [n, 2], ``p_no_dlas_refined``, ``p_dlas_refined`` and ``refined`` (1: from
+        the refined evidence; 0: the quasar was not refined or is unusable, and the three hold the first
+        pass's numbers)."""
+        from . import refine as _refine
+        sel = self._selection(selection)
+        out = _refine.empty_posteriors(sel.size)
+        r = _lib.RefinedPosteriors(*[out[name].ctypes.data_as(ct) for name, ct in _lib.RefinedPosteriors._fields_])
+        _lib.check(self.ctx.lib.gpdla_batch_refined_posteriors(self.ctx._h, self._h, sel.ctypes.data_as(_i64p),
+                                                               sel.size, C.byref(r)))
         return out
 
     # ---- parameter summaries (DESIGN.md 4.17) ----

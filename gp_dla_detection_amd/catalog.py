@@ -202,6 +202,51 @@ def generate_json_catalogue_with_intervals(results: dict, quasar_info: dict, sum
     return out
 
 
+def generate_json_catalogue_refined(results: dict, quasar_info: dict, refined: dict, summaries: dict | None = None,
+                                    outfile: str | None = None, occams_razor: float = 10000.0,
+                                    drop_nan: bool = True) -> list:
+    """The records of :func:`generate_json_catalogue` for a SINGLE-DLA run (``model_posteriors`` [nq, 2], the
+    MAP vectors of :meth:`api.Batch.download`) with the refine pass's numbers where there are any (DESIGN.md
+    4.19).  ``refined``: the dict of ``refine.refine_absorbers(posteriors=True)`` or ``io.load_refined_results``.
+    For a quasar of its ``selection`` with ``refined`` == 1, ``p_dla`` / ``p_no_dla`` / ``max_model_posterior``
+    come from ``model_posteriors_refined`` (Occam's razor applied to that pair as to every other) and the listed
+    absorber is (``MAP_z_dlas_refined``, ``MAP_log_nhis_refined``); every other quasar keeps its first-pass
+    record.  Each record carries a boolean ``refined``.  ``summaries``: the refined parameter summaries
+    (``refined["summaries"]``) -- the records of refined quasars then gain the fields of
+    :func:`generate_json_catalogue_with_intervals`.  Multi-DLA results are a ValueError."""
+    mp = np.array(results["model_posteriors"], dtype=np.float64)
+    if mp.ndim != 2 or mp.shape[1] != 2 or np.ndim(results["MAP_z_dlas"]) != 1:
+        raise ValueError("generate_json_catalogue_refined serves single-DLA results (model_posteriors [nq, 2]) only")
+    if "model_posteriors_refined" not in refined:
+        raise ValueError("the refined results hold no model_posteriors_refined (refine_absorbers(posteriors=True))")
+    nq = mp.shape[0]
+    sel = np.asarray(refined["selection"], dtype=np.int64).reshape(-1)
+    rows = np.flatnonzero(np.asarray(refined["refined"]).reshape(-1) == 1)
+    map_z, map_n = (np.array(results[k], dtype=np.float64) for k in ("MAP_z_dlas", "MAP_log_nhis"))
+    mp[sel[rows]] = np.asarray(refined["model_posteriors_refined"], dtype=np.float64)[rows]
+    map_z[sel[rows]] = np.asarray(refined["MAP_z_dlas_refined"], dtype=np.float64)[rows]
+    map_n[sel[rows]] = np.asarray(refined["MAP_log_nhis_refined"], dtype=np.float64)[rows]
+    view = dict(results, model_posteriors=mp, MAP_z_dlas=map_z.reshape(nq, 1, 1), MAP_log_nhis=map_n.reshape(nq, 1, 1))
+    if summaries is None:
+        out = generate_json_catalogue(view, quasar_info, None, False, occams_razor, drop_nan)
+    else:  # the rows of the refined quasars alone: an unrefined quasar has no refined interval
+        srow = np.asarray(summaries.get("selection", sel), dtype=np.int64).reshape(-1)
+        take = np.flatnonzero(np.isin(srow, sel[rows]))
+        sub = {k: (np.asarray(v)[take] if k not in ("probabilities", "thresholds") else v) for k, v in summaries.items()}
+        sub["selection"] = srow[take]
+        out = generate_json_catalogue_with_intervals(view, quasar_info, sub, None, False, occams_razor, drop_nan)
+    _, _, keep = loader_view(view, quasar_info, False, occams_razor, drop_nan)
+    is_refined = np.zeros(nq, dtype=bool)
+    is_refined[sel[rows]] = True
+    for spec, i in zip(out, keep):
+        spec["refined"] = bool(is_refined[i])
+    if outfile is not None:
+        import json
+        with open(outfile, "w") as f:
+            json.dump(out, f, indent=2)
+    return out
+
+
 def generate_sub_dla_catalogue(results: dict, quasar_info: dict, outfile: str | None = None,
                                sub_dla: bool = True, occams_razor: float = 10000.0,
                                drop_nan: bool = True) -> list:

@@ -13,12 +13,14 @@ Only DLA(1) enters: the reference's DLA(k >= 2) branch (:922-94
 for every sample, so it never passes ``p_thresh_sample``.
 
     python -m gp_dla_detection_amd.cddf PROCESSED SAMPLES [--snrs F] [--z-min 2 --z-max 4 ...] [--json OUT]
-                                        [--sample-errors R [--seed N]]
+                                        [--sample-errors R [--seed N]] [--refined FILE]
 
 ``--snrs`` takes the table ``python -m gp_dla_detection_amd.snrs`` writes.  ``--sample-errors`` adds the
 stratified bootstrap over sightlines (DLAStatistics.sample_errors): sample-variance
 percentiles of dN/dX, Omega_DLA and f(N_HI), the sightline draws and their sums on the GPU
-(k_path_lengths, k_bootstrap_sums).
+(k_path_lengths, k_bootstrap_sums).  ``--refined`` takes the file ``python -m gp_dla_detection_amd.refine ...
+--tables --posteriors`` writes: the quasars it refined enter with their refined P(DLA) and are binned from their
+own refined sample tables (k_bin_posteriors_boxed).
 """
 from __future__ import annotations
 
@@ -356,6 +358,18 @@ def bin_posteriors(sll, shift, p_dla, z_min, z_max, upper_z, offset_samples, log
     if off.size != S or lnhi.size != S:
         raise ValueError(f"{S} sample columns but {off.size} offsets and {lnhi.size} log N_HI samples")
     lib = _lib.load()
+    reqs, outs, keep, res = _bin_structs(requests, n)
+    rc = lib.gpdla_stats_bin_posteriors(n, S, sll.ctypes.data_as(_lib._dp), sll.strides[0] // 8,
+                                        *[_lib.ptr(a) for a in vec], _lib.ptr(off), _lib.ptr(lnhi),
+                                        len(requests), reqs, outs, int(device))
+    _check_kept(rc, res)
+    return res
+
+
+def _bin_structs(requests, n):
+    """The gpdla_bin_request / gpdla_bin_output arrays of a per-spectrum pass over ``n`` rows, the edge
+    arrays they point into, and the result dicts the outputs point into."""
+    from . import _lib
     reqs = (_lib.BinRequest * len(requests))()
     outs = (_lib.BinOutput * len(requests))()
     keep, res = [], []
@@ -373,16 +387,51 @@ def bin_posteriors(sll, shift, p_dla, z_min, z_max, upper_z, offset_samples, log
         outs[i] = _lib.BinOutput(_lib.ptr(o["pois"]), _lib.ptr(o["mean"]), _lib.ptr(o["var"]),
                                  o["count"].ctypes.data_as(_lib._i32p), o["kept_bin"].ctypes.data_as(_lib._i32p),
                                  _lib.ptr(o["kept_p"]))
-    rc = lib.gpdla_stats_bin_posteriors(n, S, sll.ctypes.data_as(_lib._dp), sll.strides[0] // 8,
-                                        *[_lib.ptr(a) for a in vec], _lib.ptr(off), _lib.ptr(lnhi),
-                                        len(requests), reqs, outs, int(device))
+    return reqs, outs, keep, res
+
+
+def _check_kept(rc, res):
+    from . import _lib
     if rc == _lib.ERR_UNSUPPORTED:  # the outputs are written; a count above the capacity names the spectrum
         for o in res:
             over = np.flatnonzero(o["count"] > KEPT_CAPACITY)
             if over.size:
                 raise KeptCapacityError(int(over[0]), int(o["count"][over[0]]))
     _lib.check(rc)
-    return res
+
+
+def bin_posteriors_boxed(lam, p_dla, boxes, upper_z, u, v, requests, device=0):
+    """k_bin_posteriors_boxed on one block of refined rows: ``lam`` [n, S'] the
+    ``sample_log_posteriors_refined`` of each row, ``boxes`` [n, 4] its (z_lo, z_hi, n_lo, n_hi) of the
+    last level, ``u`` / ``v`` the shared unit points.  The row's samples are z = z_lo + (z_hi - z_lo) u,
+    log N = n_lo + (n_hi - n_lo) v, p = exp(lam - shift) p_dla with shift = log Sum exp(lam) formed on the
+    GPU (NaN for a row without a finite entry).  Returns (what :func:`bin_posteriors` returns, shift [n])."""
+    from . import _lib
+    requests = list(requests)
+    check_requests(requests)
+    lam = np.asarray(lam, dtype=np.float64)
+    if lam.ndim != 2 or lam.shape[1] < 1 or lam.strides[1] != 8:
+        raise ValueError("refined sample log-posteriors must be [n, S'] with S' >= 1 and unit sample stride")
+    n, S = lam.shape
+    if lam.strides[0] < 8 * S:   # (reversed or overlapping rows: the library takes a forward stride of at least S')
+        lam = np.ascontiguousarray(lam)
+    vec = [np.ascontiguousarray(a, dtype=np.float64).reshape(-1) for a in (p_dla, upper_z)]
+    if any(a.size != n for a in vec):
+        raise ValueError("p_dla and upper_z need one entry per row")
+    boxes = np.ascontiguousarray(boxes, dtype=np.float64)
+    if boxes.shape != (n, 4):
+        raise ValueError(f"boxes must be [n, 4] = {(n, 4)}, got {boxes.shape}")
+    u = np.ascontiguousarray(u, dtype=np.float64).reshape(-1)
+    v = np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
+    if u.size != S or v.size != S:
+        raise ValueError(f"{S} sample columns but {u.size} u and {v.size} v")
+    reqs, outs, keep, res = _bin_structs(requests, n)
+    shift = np.full(n, np.nan)
+    rc = _lib.load().gpdla_stats_bin_posteriors_boxed(n, S, lam.ctypes.data_as(_lib._dp), lam.strides[0] // 8, _lib.ptr(vec[0]),
+                                                      _lib.ptr(boxes), _lib.ptr(vec[1]), _lib.ptr(u), _lib.ptr(v),
+                                                      len(requests), reqs, outs, _lib.ptr(shift), int(device))
+    _check_kept(rc, res)
+    return res, shift
 
 
 def poisson_binomial_cf(segments, device=0):
@@ -593,11 +642,19 @@ class DLAStatistics:
     ``results``: the dict process_qsos, process_qsos_multiple_dlas_meanflux or
     io.load_processed_qsos returns; ``samples``: the sample dict (offset_samples,
     log_nhi_samples); ``snrs``: one per searched quasar.  The sample table is read by the GPU pass
-    in blocks of ``block_size`` selected spectra; results do not depend on the block size."""
+    in blocks of ``block_size`` selected spectra; results do not depend on the block size.
+
+    ``refined`` (single-DLA runs): the dict of ``refine.refine_absorbers(with_samples=True,
+    posteriors=True)`` or of ``io.load_refined_results``.  The quasars of its ``selection`` with status 0 enter
+    with the refined P(DLA) (Occam's razor applied to the refined pair), also into the choice of the selected
+    spectra, and their partials come from their own refined tables (:func:`bin_posteriors_boxed`: S' points in
+    each quasar's last box, S' need not equal S); every other quasar goes through :func:`bin_posteriors` as
+    without ``refined``.  The sightline's own ``min_z_dlas`` / ``max_z_dlas`` stay the path-length limits and the
+    source of the proximity cut."""
 
     def __init__(self, results, samples, snrs, *, sub_dla, occams_razor=10000, snr_thresh=-2, lowzcut=False,
                  p_thresh_spec=5e-2, p_thresh_sample=1e-4, p_switch=0.25, proximity_zone=0.1, bins_per_z=6,
-                 block_size=2048, device=0):
+                 block_size=2048, device=0, refined=None):
         p_dla, lld = posterior_inputs(results["model_posteriors"], results["log_likelihoods_dla"],
                                       sub_dla=sub_dla, occams_razor=occams_razor)
         sll = np.asarray(results["sample_log_likelihoods_dla"])
@@ -606,13 +663,20 @@ class DLAStatistics:
                    np.asarray(results["max_z_dlas"], dtype=np.float64), samples, snrs, first.shape[1],
                    occams_razor=occams_razor, snr_thresh=snr_thresh, lowzcut=lowzcut, p_thresh_spec=p_thresh_spec,
                    p_thresh_sample=p_thresh_sample, p_switch=p_switch, proximity_zone=proximity_zone,
-                   bins_per_z=bins_per_z, block_size=block_size, device=device)
+                   bins_per_z=bins_per_z, block_size=block_size, device=device, refined=refined,
+                   single_dla=sll.ndim == 2 and not sub_dla)
         self._rows = lambda sel: first[sel]
 
     def _init(self, p_dla, lld, z_min, z_max, samples, snrs, num_samples, *, occams_razor, snr_thresh, lowzcut,
-              p_thresh_spec, p_thresh_sample, p_switch, proximity_zone, bins_per_z, block_size, device):
+              p_thresh_spec, p_thresh_sample, p_switch, proximity_zone, bins_per_z, block_size, device, refined=None,
+              single_dla=True):
         if block_size < 1:
             raise ValueError("block_size must be >= 1")
+        self._refined = None
+        if refined is not None:
+            if not single_dla:
+                raise ValueError("refined results belong to a single-DLA run (no multi-DLA tables, no sub_dla)")
+            p_dla = self._take_refined(refined, p_dla, occams_razor)
         self.occams_razor, self.snr_thresh, self.lowzcut = occams_razor, snr_thresh, lowzcut
         self.p_thresh_spec, self.p_thresh_sample, self.p_switch = p_thresh_spec, p_thresh_sample, p_switch
         self.proximity_zone, self.bins_per_z = proximity_zone, bins_per_z
@@ -629,12 +693,44 @@ class DLAStatistics:
         self._upper_z = z_max[sel] - proximity_zone                          # proximity() (:965-968)
         self._cache = {}
 
+    def _take_refined(self, refined, p_dla, occams_razor):
+        """Checks ``refined`` and keeps what the boxed pass reads: per refined quasar (status 0) its row of
+        the refined arrays.  Returns ``p_dla`` with the refined P(DLA) of those quasars."""
+        if isinstance(refined, str):
+            from . import io
+            refined = io.load_refined_results(refined)
+        need = ("selection", "status", "boxes", "sample_log_posteriors_refined", "refine_u", "refine_v")
+        if any(k not in refined for k in need):
+            raise ValueError("the refined results hold no sample table: " + ", ".join(k for k in need if k not in refined)
+                             + " missing (refine_absorbers(with_samples=True), or refine's --tables)")
+        if "model_posteriors_refined" not in refined:
+            raise ValueError("the refined results hold no model_posteriors_refined "
+                             "(refine_absorbers(posteriors=True), or refine's --posteriors)")
+        sel = np.asarray(refined["selection"], dtype=np.int64).reshape(-1)
+        lam = np.asarray(refined["sample_log_posteriors_refined"], dtype=np.float64)
+        u = np.asarray(refined["refine_u"], dtype=np.float64).reshape(-1)
+        v = np.asarray(refined["refine_v"], dtype=np.float64).reshape(-1)
+        boxes = np.asarray(refined["boxes"], dtype=np.float64)
+        if lam.ndim != 2 or lam.shape != (sel.size, u.size) or v.size != u.size or boxes.shape[::2] != (sel.size, 4):
+            raise ValueError("the refined tables do not fit their selection and unit points")
+        if sel.size and (sel.min() < 0 or sel.max() >= p_dla.size or np.unique(sel).size != sel.size):
+            raise ValueError("the refined selection must name quasars of the run, each once")
+        rows = np.flatnonzero(np.asarray(refined["status"]).reshape(-1) == 0)
+        mp = catalog.occams_model_posteriors(np.asarray(refined["model_posteriors_refined"], dtype=np.float64)[rows], occams_razor)
+        p_dla = np.array(p_dla, dtype=np.float64)
+        p_dla[sel[rows]] = mp[:, 1]
+        row_of = np.full(p_dla.size, -1, dtype=np.int64)
+        row_of[sel[rows]] = rows
+        self._refined = dict(row_of=row_of, lam=lam, boxes=boxes[:, -1, :], u=u, v=v)
+        return p_dla
+
     @classmethod
     def from_processed_file(cls, processed, samples_file, snrs, *, sub_dla, **kw):
         """The same statistics from a processed_qsos file, its sample table streamed in quasar
         blocks (hdf5.Dataset.read_slab).  Each read spans at most ``block_size`` quasars, so the host
         holds at most 2 x block_size rows of S samples: the block of selected rows being built and
-        one read.  ``samples_file`` / ``snrs``: a path or the arrays (dict / vector)."""
+        one read.  ``samples_file`` / ``snrs``: a path or the arrays (dict / vector).  ``refined``: the file
+        ``refine --tables --posteriors`` wrote, or the dict (see the class)."""
         from . import hdf5, io
         small = io.loadmat73(processed, ["model_posteriors", "log_likelihoods_dla", "min_z_dlas", "max_z_dlas"])
         mp = np.asarray(small["model_posteriors"], dtype=np.float64)
@@ -648,12 +744,14 @@ class DLAStatistics:
         f = hdf5.File(processed)
         ds = f["sample_log_likelihoods_dla"]                                  # HDF5: [S, nq] or [md, S, nq]
         S = ds.shape[-2]
+        refined = kw.pop("refined", None)
         opts = {k: kw.pop(k) for k in list(kw) if k not in ("block_size", "device")}
         self._init(p_dla, lld1, np.asarray(small["min_z_dlas"], dtype=np.float64).reshape(-1),
                    np.asarray(small["max_z_dlas"], dtype=np.float64).reshape(-1), samples, snrs, S,
                    **{**dict(occams_razor=10000, snr_thresh=-2, lowzcut=False, p_thresh_spec=5e-2,
                              p_thresh_sample=1e-4, p_switch=0.25, proximity_zone=0.1, bins_per_z=6), **opts,
-                      **dict(block_size=kw.get("block_size", 2048), device=kw.get("device", 0))})
+                      **dict(block_size=kw.get("block_size", 2048), device=kw.get("device", 0), refined=refined,
+                             single_dla=lld.ndim == 1 and not sub_dla)})
 
         span = self.block_size
 
@@ -690,20 +788,33 @@ class DLAStatistics:
         if todo:
             sel = self.selected
             parts = [[] for _ in todo]
-            for a in range(0, sel.size, self.block_size):
-                b = sel[a:a + self.block_size]
-                i = slice(a, a + b.size)
-                try:
-                    res = bin_posteriors(self._rows(b), self._shift[i], self.p_dla[b], self.z_min[b],
-                                         self.z_max[b], self._upper_z[i], self.offset_samples,
-                                         self.log_nhi_samples, todo, device=self.device)
-                except KeptCapacityError as e:
-                    raise KeptCapacityError(int(b[e.spectrum]), e.count, "quasar") from None
-                for k, r in enumerate(res):
-                    parts[k].append(r)
+            # the spectra with a refined table are binned from it, the others from the first pass's; both in
+            # blocks of block_size, and `at` remembers where each block's rows belong in quasar order
+            ref = self._refined
+            boxed = ref["row_of"][sel] >= 0 if ref is not None else np.zeros(sel.size, dtype=bool)
+            at = []
+            for group in (np.flatnonzero(~boxed), np.flatnonzero(boxed)):
+                for a in range(0, group.size, self.block_size):
+                    i = group[a:a + self.block_size]
+                    b = sel[i]
+                    try:
+                        if boxed[i[0]]:
+                            rows = ref["row_of"][b]
+                            res, _ = bin_posteriors_boxed(ref["lam"][rows], self.p_dla[b], ref["boxes"][rows], self._upper_z[i],
+                                                          ref["u"], ref["v"], todo, device=self.device)
+                        else:
+                            res = bin_posteriors(self._rows(b), self._shift[i], self.p_dla[b], self.z_min[b],
+                                                 self.z_max[b], self._upper_z[i], self.offset_samples,
+                                                 self.log_nhi_samples, todo, device=self.device)
+                    except KeptCapacityError as e:
+                        raise KeptCapacityError(int(b[e.spectrum]), e.count, "quasar") from None
+                    at.append(i)
+                    for k, part in enumerate(res):
+                        parts[k].append(part)
+            order = np.argsort(np.concatenate(at), kind="stable") if at else None   # the identity without `refined`
             for r, ps in zip(todo, parts):
                 nb = len(r.edges) - 1
-                self._cache[r] = {k: (np.concatenate([p[k] for p in ps]) if ps else
+                self._cache[r] = {k: (np.concatenate([p[k] for p in ps])[order] if ps else
                                       (np.zeros((0, nb)) if k in ("pois", "mean", "var") else
                                        np.zeros((0,) + ((KEPT_CAPACITY,) if k.startswith("kept") else ()))))
                                   for k in ("pois", "mean", "var", "count", "kept_bin", "kept_p")}
@@ -850,6 +961,8 @@ def main(argv=None):
     ap.add_argument("--sample-errors", type=int, metavar="R",
                     help="add bootstrap sample errors from R replicates (keys sample_errors_*)")
     ap.add_argument("--seed", type=int, default=None, help="seed of the bootstrap")
+    ap.add_argument("--refined", metavar="FILE",
+                    help="refined results with tables and posteriors (refine --tables --posteriors): single-DLA runs")
     a = ap.parse_args(argv)
     from . import io
     snrs = a.snrs
@@ -858,7 +971,8 @@ def main(argv=None):
         snrs = np.full(nq, np.inf)
     st = DLAStatistics.from_processed_file(a.processed, a.samples, snrs, sub_dla=a.sub_dla,
                                            occams_razor=a.occams_razor, snr_thresh=a.snr_thresh,
-                                           lowzcut=a.lowzcut, block_size=a.block_size, device=a.device)
+                                           lowzcut=a.lowzcut, block_size=a.block_size, device=a.device,
+                                           **({} if a.refined is None else dict(refined=a.refined)))
     try:
         out = {k: _jsonable(v) for k, v in st.statistics(a.z_min, a.z_max, a.lnhi_nbins).items()}
         if a.sample_errors is not None:

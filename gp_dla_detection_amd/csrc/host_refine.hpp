@@ -1,7 +1,8 @@
 // host_refine.hpp -- the refine pass of a processed single-DLA batch (the contract is in
 // include/gpdla.h): the argument checks, the refine points of a context, gpdla_batch_refine over
-// k_refine_boxes, the boxed sweeps and k_refine_finish (refine_kernels.hpp), the download of its results
-// and the summaries of the refined tables through k_parameter_summaries.
+// k_refine_boxes, the boxed sweeps and k_refine_finish (refine_kernels.hpp), the download of its results,
+// the summaries of the refined tables through k_parameter_summaries, and the model posteriors of the
+// refined evidence (k_refined_posteriors).
 #pragma once
 
 static_assert(GPDLA_REFINE_MAX_LEVELS == gpdla::kRefineMaxLevels, "gpdla.h and sweep_kernels.hpp disagree");
@@ -352,6 +353,45 @@ int gpdla_batch_refined_summaries(gpdla_context *c, gpdla_batch *b, const int64_
   }
   return run_parameter_summaries(nsel, Sr, rf->lam, row_start, nullptr, none, z_lo.data(), z_hi.data(), c->h_ru.data(),
                                  c->h_rv.data(), *request, *outputs, st, n_lo.data(), n_hi.data());
+} GPDLA_NO_THROW
+
+int gpdla_batch_refined_posteriors(gpdla_context *c, gpdla_batch *b, const int64_t *selection, int64_t num_selected,
+                                   gpdla_refined_posteriors *out) try {
+  int rc = check_refinable(c, b);
+  if (rc) return rc;
+  if (!out) return fail(GPDLA_ERR_INVALID_ARGUMENT, "null outputs");
+  if ((rc = check_selection(b->nq, selection, num_selected))) return rc;
+  RefineBuffers *rf = b->rf;
+  if (!rf || rf->levels < 1 || rf->nq != b->nq) return fail(GPDLA_ERR_INVALID_ARGUMENT, "the batch has not been refined");
+  const int64_t n = num_selected;
+  if (n == 0) return GPDLA_OK;
+  HIP_TRY(hipSetDevice(c->device_id));
+  std::vector<int64_t> sel((size_t)n);
+  for (int64_t s = 0; s < n; ++s) sel[(size_t)s] = selection ? selection[s] : s;
+  std::vector<double> post((size_t)n * 4);
+  Staging up(c->stream);  // (after the host buffers of its copies)
+  HIP_TRY(hipStreamWaitEvent(c->stream, b->ev_done, 0));
+  RefinedPosteriorArgs a{};
+  int64_t *d_sel;
+  if ((rc = up.put(&d_sel, sel.data(), (size_t)n)) || (rc = up.tmp.alloc(&a.post, (size_t)n * 4)) ||
+      (rc = up.tmp.alloc(&a.refined, (size_t)n)))
+    return rc;
+  a.n = n;
+  a.sel = d_sel;
+  a.summary = b->d_summary;
+  a.scal = rf->scal;
+  a.status = rf->status;
+  hipLaunchKernelGGL(k_refined_posteriors, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, a);
+  HIP_TRY(hipGetLastError());
+  if ((rc = up.fetch(post.data(), a.post, post.size())) || (rc = up.fetch(out->refined, a.refined, (size_t)n))) return rc;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (int64_t s = 0; s < n; ++s) {
+    const double *p = post.data() + 4 * s;
+    if (out->model_posteriors_refined) std::memcpy(out->model_posteriors_refined + 2 * s, p, 2 * sizeof(double));
+    if (out->p_no_dlas_refined) out->p_no_dlas_refined[s] = p[2];
+    if (out->p_dlas_refined) out->p_dlas_refined[s] = p[3];
+  }
+  return GPDLA_OK;
 } GPDLA_NO_THROW
 
 double gpdla_debug_last_refine_ms(void) { return t_refine_ms; }

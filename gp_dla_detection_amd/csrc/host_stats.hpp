@@ -7,6 +7,138 @@ static_assert(GPDLA_STATS_MAX_BINS == gpdla::kStatsMaxBins && GPDLA_STATS_MAX_RE
               "gpdla.h and stats_kernels.hpp disagree");
 static_assert(GPDLA_BOOTSTRAP_MAX_COLUMNS == gpdla::kBootMaxColumns, "gpdla.h and stats_kernels.hpp disagree");
 
+namespace {
+
+// Measuring aid (tools/bench_refined_stats.py): once gpdla_debug_time_bin_kernels(1) has been called on a thread,
+// its launches of k_bin_posteriors / k_bin_posteriors_boxed are bracketed by device events and
+// gpdla_debug_last_bin_ms returns the last duration.  Off by default: a call then launches as it always did.
+thread_local bool t_bin_timing = false;
+thread_local double t_bin_ms = -1.0;
+
+template <typename Args>
+int launch_bin_kernel(void (*kernel)(Args), int64_t n, const Args &a) {
+  EventPair ev;
+  if (t_bin_timing) {
+    int rc = ev.create();
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(ev.e0, 0));
+  }
+  hipLaunchKernelGGL(kernel, dim3((unsigned)n), dim3(256), 0, 0, a);
+  HIP_TRY(hipGetLastError());
+  if (t_bin_timing) {
+    HIP_TRY(hipEventRecord(ev.e1, 0));
+    HIP_TRY(hipEventSynchronize(ev.e1));
+    float ms = -1.f;
+    HIP_TRY(hipEventElapsedTime(&ms, ev.e0, ev.e1));
+    t_bin_ms = (double)ms;
+  }
+  return GPDLA_OK;
+}
+
+// The bin requests of a per-spectrum pass, checked and turned into the kernels' form: req[r] and the edges
+// table [R][kStatsMaxBins + 1].  need_outputs: the outputs each request writes must not be null.
+int stats_bin_requests(int num_requests, const gpdla_bin_request *requests, const gpdla_bin_output *outputs, bool need_outputs,
+                       gpdla::StatsRequest *req, std::vector<double> &edges) {
+  using namespace gpdla;
+  edges.assign((size_t)num_requests * (kStatsMaxBins + 1), 0.0);
+  for (int r = 0; r < num_requests; ++r) {
+    const gpdla_bin_request &q = requests[r];
+    const gpdla_bin_output &o = outputs[r];
+    if (q.num_bins < 1 || q.num_bins > kStatsMaxBins)
+      return fail(GPDLA_ERR_INVALID_ARGUMENT, "request %d: %d bins; a request takes 1 to %d", r, q.num_bins, kStatsMaxBins);
+    if (!q.edges) return fail(GPDLA_ERR_INVALID_ARGUMENT, "request %d: null edges", r);
+    if (q.quantity != 0 && q.quantity != 1) return fail(GPDLA_ERR_INVALID_ARGUMENT, "request %d: quantity must be 0 or 1", r);
+    for (int b = 0; b <= q.num_bins; ++b) {
+      if (!std::isfinite(q.edges[b]) || (b > 0 && !(q.edges[b] > q.edges[b - 1])))
+        return fail(GPDLA_ERR_INVALID_ARGUMENT, "request %d: edges must be finite and strictly increasing", r);
+      edges[(size_t)r * (kStatsMaxBins + 1) + b] = q.edges[b];
+    }
+    for (double v : {q.z_lo, q.z_hi, q.lnhi_lo, q.lnhi_hi, q.p_thresh_sample, q.p_switch})
+      if (std::isnan(v)) return fail(GPDLA_ERR_INVALID_ARGUMENT, "request %d: NaN window or threshold", r);
+    if (need_outputs && (q.histogram ? (!o.mean || !o.var) : (!o.pois || !o.kept_count || !o.kept_bin || !o.kept_p)))
+      return fail(GPDLA_ERR_INVALID_ARGUMENT, "request %d: null output", r);
+    req[r] = StatsRequest{q.quantity, q.num_bins, q.histogram != 0, q.moment != 0, q.lowzcut != 0,
+                          q.z_lo, q.z_hi, q.lnhi_lo, q.lnhi_hi, q.p_thresh_sample, q.p_switch};
+  }
+  return GPDLA_OK;
+}
+
+// The output tables of a per-spectrum pass on the device: sums = pois, mean, var ([R][n][kStatsMaxBins] each,
+// zeroed), the kept pairs and their counts.
+struct StatsBinTables {
+  double *sums, *kp;
+  int32_t *cnt, *kb;
+  int alloc(DeviceTemps &tmp, int64_t R, int64_t n) {
+    using namespace gpdla;
+    int rc;
+    if ((rc = tmp.alloc(&sums, (size_t)3 * R * n * kStatsMaxBins)) || (rc = tmp.alloc(&kp, (size_t)R * n * kStatsKept)) ||
+        (rc = tmp.alloc(&cnt, (size_t)R * n)) || (rc = tmp.alloc(&kb, (size_t)R * n * kStatsKept)))
+      return rc;
+    HIP_TRY(hipMemset(sums, 0, (size_t)3 * R * n * kStatsMaxBins * sizeof(double)));
+    return GPDLA_OK;
+  }
+  template <typename Args>
+  void bind(Args &a, int64_t R, int64_t n) const {
+    a.pois = sums;
+    a.mean = sums + R * n * gpdla::kStatsMaxBins;
+    a.var = sums + 2 * R * n * gpdla::kStatsMaxBins;
+    a.count = cnt;
+    a.kept_bin = kb;
+    a.kept_p = kp;
+  }
+  // into the caller's arrays; a row above the kept capacity makes the call GPDLA_ERR_UNSUPPORTED, outputs written
+  int unpack(int64_t R, int64_t n, const gpdla_bin_request *requests, gpdla_bin_output *outputs) const;
+};
+
+int StatsBinTables::unpack(int64_t R, int64_t n, const gpdla_bin_request *requests, gpdla_bin_output *outputs) const {
+  using namespace gpdla;
+  std::vector<double> hs((size_t)3 * R * n * kStatsMaxBins), hkp((size_t)R * n * kStatsKept);
+  std::vector<int32_t> hcnt((size_t)R * n), hkb((size_t)R * n * kStatsKept);
+  HIP_TRY(hipMemcpy(hs.data(), sums, hs.size() * sizeof(double), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(hkp.data(), kp, hkp.size() * sizeof(double), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(hcnt.data(), cnt, hcnt.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(hkb.data(), kb, hkb.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+  int64_t over = -1;
+  int over_r = 0;
+  for (int64_t r = 0; r < R; ++r) {
+    const gpdla_bin_output &o = outputs[r];
+    const int nb = requests[r].num_bins;
+    for (int64_t s = 0; s < n; ++s) {
+      const size_t base = ((size_t)r * n + s) * kStatsMaxBins;
+      for (int b = 0; b < nb; ++b) {
+        if (o.pois) o.pois[s * nb + b] = hs[base + b];
+        if (o.mean) o.mean[s * nb + b] = hs[(size_t)R * n * kStatsMaxBins + base + b];
+        if (o.var) o.var[s * nb + b] = hs[(size_t)2 * R * n * kStatsMaxBins + base + b];
+      }
+      const int c = requests[r].histogram ? 0 : hcnt[r * n + s];
+      if (c > kStatsKept && over < 0) {
+        over = s;
+        over_r = (int)r;
+      }
+      if (o.kept_count) o.kept_count[s] = c;
+      for (int i = 0; i < kStatsKept; ++i) {
+        const bool used = i < c;
+        if (o.kept_bin) o.kept_bin[s * kStatsKept + i] = used ? hkb[((size_t)r * n + s) * kStatsKept + i] : -1;
+        if (o.kept_p) o.kept_p[s * kStatsKept + i] = used ? hkp[((size_t)r * n + s) * kStatsKept + i] : 0.0;
+      }
+    }
+  }
+  if (over >= 0)
+    return fail(GPDLA_ERR_UNSUPPORTED, "spectrum %lld of the block keeps %d samples directly in request %d (capacity %d)",
+                (long long)over, hcnt[over_r * n + over], over_r, kStatsKept);
+  return GPDLA_OK;
+}
+
+// the rows of a host table [n][S] at stride row_stride as one packed block (`rows` holds it when a copy is needed)
+const double *stats_packed_rows(const double *src, int64_t n, int64_t S, int64_t row_stride, std::vector<double> &rows) {
+  if (row_stride == S) return src;
+  rows.resize((size_t)n * S);
+  for (int64_t s = 0; s < n; ++s) std::memcpy(rows.data() + s * S, src + s * row_stride, S * sizeof(double));
+  return rows.data();
+}
+
+}  // namespace
+
 extern "C" {
 
 int gpdla_stats_bin_posteriors(int64_t num_spectra, int64_t num_samples, const double *sample_log_likelihoods,
@@ -25,47 +157,22 @@ int gpdla_stats_bin_posteriors(int64_t num_spectra, int64_t num_samples, const d
     return fail(GPDLA_ERR_INVALID_ARGUMENT, "null per-spectrum input");
   if (num_spectra > 2147483647LL) return fail(GPDLA_ERR_UNSUPPORTED, "more than 2^31 - 1 spectra in one block");
   StatsBinArgs a{};
-  std::vector<double> edges((size_t)num_requests * (kStatsMaxBins + 1), 0.0);
-  for (int r = 0; r < num_requests; ++r) {
-    const gpdla_bin_request &q = requests[r];
-    const gpdla_bin_output &o = outputs[r];
-    if (q.num_bins < 1 || q.num_bins > kStatsMaxBins)
-      return fail(GPDLA_ERR_INVALID_ARGUMENT, "request %d: %d bins; a request takes 1 to %d", r, q.num_bins, kStatsMaxBins);
-    if (!q.edges) return fail(GPDLA_ERR_INVALID_ARGUMENT, "request %d: null edges", r);
-    if (q.quantity != 0 && q.quantity != 1) return fail(GPDLA_ERR_INVALID_ARGUMENT, "request %d: quantity must be 0 or 1", r);
-    for (int b = 0; b <= q.num_bins; ++b) {
-      if (!std::isfinite(q.edges[b]) || (b > 0 && !(q.edges[b] > q.edges[b - 1])))
-        return fail(GPDLA_ERR_INVALID_ARGUMENT, "request %d: edges must be finite and strictly increasing", r);
-      edges[(size_t)r * (kStatsMaxBins + 1) + b] = q.edges[b];
-    }
-    for (double v : {q.z_lo, q.z_hi, q.lnhi_lo, q.lnhi_hi, q.p_thresh_sample, q.p_switch})
-      if (std::isnan(v)) return fail(GPDLA_ERR_INVALID_ARGUMENT, "request %d: NaN window or threshold", r);
-    if (num_spectra > 0 && (q.histogram ? (!o.mean || !o.var) : (!o.pois || !o.kept_count || !o.kept_bin || !o.kept_p)))
-      return fail(GPDLA_ERR_INVALID_ARGUMENT, "request %d: null output", r);
-    a.req[r] = StatsRequest{q.quantity, q.num_bins, q.histogram != 0, q.moment != 0, q.lowzcut != 0,
-                            q.z_lo, q.z_hi, q.lnhi_lo, q.lnhi_hi, q.p_thresh_sample, q.p_switch};
-  }
-  if (num_spectra == 0) return GPDLA_OK;
-  int rc = select_device(device_id);
+  std::vector<double> edges;
+  int rc = stats_bin_requests(num_requests, requests, outputs, num_spectra > 0, a.req, edges);
   if (rc) return rc;
+  if (num_spectra == 0) return GPDLA_OK;
+  if ((rc = select_device(device_id))) return rc;
   const int64_t n = num_spectra, S = num_samples, R = num_requests;
   std::vector<double> w10(S);
   for (int64_t j = 0; j < S; ++j) w10[j] = std::pow(10.0, log_nhi_samples[j]);  // numpy's 10**lnhi: libm pow
   std::vector<double> rows;
-  const double *src = sample_log_likelihoods;
+  const double *src = stats_packed_rows(sample_log_likelihoods, n, S, row_stride, rows);  // the device copy is [n][S]
   const int64_t ld = S;
-  if (row_stride != S) {  // pack the rows: the device copy is [n][S]
-    rows.resize((size_t)n * S);
-    for (int64_t s = 0; s < n; ++s) std::memcpy(rows.data() + s * S, src + s * row_stride, S * sizeof(double));
-    src = rows.data();
-  }
   DeviceTemps tmp;
-  double *d_sll, *d_vec, *d_smp, *d_edges, *d_sums, *d_kp;
-  int32_t *d_cnt, *d_kb;
+  double *d_sll, *d_vec, *d_smp, *d_edges;
+  StatsBinTables tab;
   if ((rc = tmp.alloc(&d_sll, (size_t)n * S)) || (rc = tmp.alloc(&d_vec, (size_t)5 * n)) ||
-      (rc = tmp.alloc(&d_smp, (size_t)3 * S)) || (rc = tmp.alloc(&d_edges, edges.size())) ||
-      (rc = tmp.alloc(&d_sums, (size_t)3 * R * n * kStatsMaxBins)) || (rc = tmp.alloc(&d_kp, (size_t)R * n * kStatsKept)) ||
-      (rc = tmp.alloc(&d_cnt, (size_t)R * n)) || (rc = tmp.alloc(&d_kb, (size_t)R * n * kStatsKept)))
+      (rc = tmp.alloc(&d_smp, (size_t)3 * S)) || (rc = tmp.alloc(&d_edges, edges.size())) || (rc = tab.alloc(tmp, R, n)))
     return rc;
   HIP_TRY(hipMemcpy(d_sll, src, (size_t)n * S * sizeof(double), hipMemcpyHostToDevice));
   const double *vecs[5] = {shift, p_dla, z_min, z_max, upper_z};
@@ -74,7 +181,6 @@ int gpdla_stats_bin_posteriors(int64_t num_spectra, int64_t num_samples, const d
   HIP_TRY(hipMemcpy(d_smp + S, log_nhi_samples, S * sizeof(double), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(d_smp + 2 * S, w10.data(), S * sizeof(double), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(d_edges, edges.data(), edges.size() * sizeof(double), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemset(d_sums, 0, (size_t)3 * R * n * kStatsMaxBins * sizeof(double)));
   a.n = n;
   a.S = S;
   a.ld = ld;
@@ -89,50 +195,72 @@ int gpdla_stats_bin_posteriors(int64_t num_spectra, int64_t num_samples, const d
   a.w10 = d_smp + 2 * S;
   a.edges = d_edges;
   a.R = (int32_t)R;
-  a.pois = d_sums;
-  a.mean = d_sums + R * n * kStatsMaxBins;
-  a.var = d_sums + 2 * R * n * kStatsMaxBins;
-  a.count = d_cnt;
-  a.kept_bin = d_kb;
-  a.kept_p = d_kp;
-  hipLaunchKernelGGL(k_bin_posteriors, dim3((unsigned)n), dim3(256), 0, 0, a);
-  HIP_TRY(hipGetLastError());
-  std::vector<double> sums((size_t)3 * R * n * kStatsMaxBins), kp((size_t)R * n * kStatsKept);
-  std::vector<int32_t> cnt((size_t)R * n), kb((size_t)R * n * kStatsKept);
-  HIP_TRY(hipMemcpy(sums.data(), d_sums, sums.size() * sizeof(double), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(kp.data(), d_kp, kp.size() * sizeof(double), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(cnt.data(), d_cnt, cnt.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(kb.data(), d_kb, kb.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-  int64_t over = -1;
-  int over_r = 0;
-  for (int64_t r = 0; r < R; ++r) {
-    const gpdla_bin_output &o = outputs[r];
-    const int nb = requests[r].num_bins;
-    for (int64_t s = 0; s < n; ++s) {
-      const size_t base = ((size_t)r * n + s) * kStatsMaxBins;
-      for (int b = 0; b < nb; ++b) {
-        if (o.pois) o.pois[s * nb + b] = sums[base + b];
-        if (o.mean) o.mean[s * nb + b] = sums[(size_t)R * n * kStatsMaxBins + base + b];
-        if (o.var) o.var[s * nb + b] = sums[(size_t)2 * R * n * kStatsMaxBins + base + b];
-      }
-      const int c = requests[r].histogram ? 0 : cnt[r * n + s];
-      if (c > kStatsKept && over < 0) {
-        over = s;
-        over_r = (int)r;
-      }
-      if (o.kept_count) o.kept_count[s] = c;
-      for (int i = 0; i < kStatsKept; ++i) {
-        const bool used = i < c;
-        if (o.kept_bin) o.kept_bin[s * kStatsKept + i] = used ? kb[((size_t)r * n + s) * kStatsKept + i] : -1;
-        if (o.kept_p) o.kept_p[s * kStatsKept + i] = used ? kp[((size_t)r * n + s) * kStatsKept + i] : 0.0;
-      }
-    }
-  }
-  if (over >= 0)
-    return fail(GPDLA_ERR_UNSUPPORTED, "spectrum %lld of the block keeps %d samples directly in request %d (capacity %d)",
-                (long long)over, cnt[over_r * n + over], over_r, kStatsKept);
-  return GPDLA_OK;
+  tab.bind(a, R, n);
+  if ((rc = launch_bin_kernel(k_bin_posteriors, n, a))) return rc;
+  return tab.unpack(R, n, requests, outputs);
 } GPDLA_NO_THROW
+
+int gpdla_stats_bin_posteriors_boxed(int64_t num_rows, int64_t num_points, const double *sample_log_posteriors,
+                                     int64_t row_stride, const double *p_dla, const double *boxes, const double *upper_z,
+                                     const double *u, const double *v, int num_requests, const gpdla_bin_request *requests,
+                                     gpdla_bin_output *outputs, double *shift, int device_id) try {
+  using namespace gpdla;
+  if (num_rows < 0 || num_points < 1 || row_stride < num_points)
+    return fail(GPDLA_ERR_INVALID_ARGUMENT, "need num_rows >= 0, S' >= 1 and row_stride >= S'");
+  if (num_requests < 1 || num_requests > kStatsMaxRequests || !requests || !outputs)
+    return fail(GPDLA_ERR_INVALID_ARGUMENT, "%d bin requests; one pass takes 1 to %d", num_requests, kStatsMaxRequests);
+  if (!u || !v) return fail(GPDLA_ERR_INVALID_ARGUMENT, "null unit points");
+  if (num_rows > 0 && (!sample_log_posteriors || !p_dla || !boxes || !upper_z || !shift))
+    return fail(GPDLA_ERR_INVALID_ARGUMENT, "null per-row input or null shift");
+  if (num_rows > 2147483647LL) return fail(GPDLA_ERR_UNSUPPORTED, "more than 2^31 - 1 rows in one block");
+  for (int64_t j = 0; j < num_points; ++j) {
+    if (!(u[j] >= 0.0 && u[j] < 1.0)) return fail(GPDLA_ERR_INVALID_ARGUMENT, "u[%lld] = %g is not inside [0, 1)", (long long)j, u[j]);
+    if (!(v[j] >= 0.0 && v[j] < 1.0)) return fail(GPDLA_ERR_INVALID_ARGUMENT, "v[%lld] = %g is not inside [0, 1)", (long long)j, v[j]);
+  }
+  StatsBoxedArgs a{};
+  std::vector<double> edges;
+  int rc = stats_bin_requests(num_requests, requests, outputs, num_rows > 0, a.req, edges);
+  if (rc) return rc;
+  if (num_rows == 0) return GPDLA_OK;
+  if ((rc = select_device(device_id))) return rc;
+  const int64_t n = num_rows, S = num_points, R = num_requests;
+  std::vector<double> rows;
+  const double *src = stats_packed_rows(sample_log_posteriors, n, S, row_stride, rows);  // the device copy is [n][S]
+  DeviceTemps tmp;
+  double *d_lam, *d_vec, *d_box, *d_uv, *d_edges, *d_shift;
+  StatsBinTables tab;
+  if ((rc = tmp.alloc(&d_lam, (size_t)n * S)) || (rc = tmp.alloc(&d_vec, (size_t)2 * n)) || (rc = tmp.alloc(&d_box, (size_t)4 * n)) ||
+      (rc = tmp.alloc(&d_uv, (size_t)2 * S)) || (rc = tmp.alloc(&d_edges, edges.size())) || (rc = tmp.alloc(&d_shift, (size_t)n)) ||
+      (rc = tab.alloc(tmp, R, n)))
+    return rc;
+  HIP_TRY(hipMemcpy(d_lam, src, (size_t)n * S * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_vec, p_dla, n * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_vec + n, upper_z, n * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_box, boxes, 4 * n * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_uv, u, S * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_uv + S, v, S * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_edges, edges.data(), edges.size() * sizeof(double), hipMemcpyHostToDevice));
+  a.n = n;
+  a.S = S;
+  a.ld = S;
+  a.lam = d_lam;
+  a.p_dla = d_vec;
+  a.upper_z = d_vec + n;
+  a.boxes = d_box;
+  a.offsets = d_uv;
+  a.lnhi = d_uv + S;
+  a.edges = d_edges;
+  a.R = (int32_t)R;
+  a.shift = d_shift;
+  tab.bind(a, R, n);
+  if ((rc = launch_bin_kernel(k_bin_posteriors_boxed, n, a))) return rc;
+  HIP_TRY(hipMemcpy(shift, d_shift, n * sizeof(double), hipMemcpyDeviceToHost));
+  return tab.unpack(R, n, requests, outputs);
+} GPDLA_NO_THROW
+
+void gpdla_debug_time_bin_kernels(int on) { t_bin_timing = on != 0; }
+
+double gpdla_debug_last_bin_ms(void) { return t_bin_ms; }
 
 int gpdla_stats_poisson_binomial_cf(int64_t num_segments, const int64_t *offsets, const double *p,
                                     double *logsum, double *argsum, int device_id) try {

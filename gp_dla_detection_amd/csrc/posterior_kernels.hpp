@@ -64,25 +64,7 @@ struct PosteriorArgs {
 
 __device__ inline double post_log_n(bool mapped, double lo, double width, double v) { return mapped ? lo + width * v : v; }
 
-// Sum over the block, the same bits in every thread: butterfly inside each wave, then the four wave
-// totals as (w0 + w1) + (w2 + w3).
-__device__ inline double post_block_sum(double v, double *red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-__device__ inline double post_block_max(double v, double *red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
-}
+// (post_block_sum and post_block_max, the block reductions of every sum and maximum here, are in stats_kernels.hpp)
 
 // l_i of model m as the summaries see it: NaN when a slot of the model was never drawn for sample i
 // (stored index 0; an index above S is refused by the host and read here as "never drawn" too)

@@ -13,6 +13,10 @@
 //                     kernels with one prologue line changed (N = exp10(n_lo + (n_hi - n_lo) v)).
 //   k_refine_finish   one block per quasar: lambda_j = l'_j + log p_N(n'_j), its maximum, first argmax
 //                     and sum; at the last level the refined evidence and MAP.
+//   k_refined_posteriors   one thread per selected quasar: the model posteriors of the first pass's
+//                     log_posteriors_no_dla against the refined log_posteriors_dla, by the five operations of
+//                     k_evidence's tail; a quasar that was not refined, or is unusable,
+//                     gets the first pass's own four numbers.
 //
 // No atomics.  Minima and maxima are exact in any order; every sum runs in an order fixed by (S, thread
 // index) alone (a thread's samples in sample order into a CompSum, then post_block_sum).  Every output is
@@ -240,6 +244,41 @@ __global__ __launch_bounds__(256) void k_refine_finish(RefineFinishArgs a) {
     out[3] = n_lo + dn * a.v[arg];
     out[4] = (double)(arg + 1);
   }
+}
+
+struct RefinedPosteriorArgs {
+  int64_t n;                  // selected quasars
+  const int64_t *sel;         // [n] quasars of the batch
+  const double *summary;      // [nq][kSummaryCols] of the first pass
+  const double *scal;         // [nq][kRefineScalars]
+  const int32_t *status;      // [nq] refine status
+  double *post;               // [n][4]: model posteriors (no DLA, DLA), p_no_dla, p_dla
+  int32_t *refined;           // [n]
+};
+
+__global__ __launch_bounds__(256) void k_refined_posteriors(RefinedPosteriorArgs a) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.n) return;
+  const int64_t q = a.sel[i];
+  const double *sm = a.summary + q * kSummaryCols;
+  double *out = a.post + 4 * i;
+  if (a.status[q] != 0) {   // not refined or unusable: the first pass's columns, so that the table is complete
+    for (int c = 0; c < 4; ++c) out[c] = sm[8 + c];
+    a.refined[i] = 0;
+    return;
+  }
+  // k_evidence's tail (process_qsos.m:224-233) with the refined log posterior of the DLA model
+  const double lp_no = sm[6], lp_dla = a.scal[q * kRefineScalars + 1];
+  const double mxp = fmax(lp_no, lp_dla);
+  double p0 = exp(lp_no - mxp), p1 = exp(lp_dla - mxp);
+  const double tot = p0 + p1;
+  p0 /= tot;
+  p1 /= tot;
+  out[0] = p0;
+  out[1] = p1;
+  out[2] = p0;
+  out[3] = 1 - p0;
+  a.refined[i] = 1;
 }
 
 }  // namespace gpdla

@@ -7,6 +7,9 @@
 //                           Poisson sum of the small probabilities and the directly kept (bin, p)
 //                           pairs (strict rule, :994-1034), or the moment sums of np.histogram's
 //                           bins (:1101-1125)
+//   k_bin_posteriors_boxed  the same for the rows of a refine pass: the samples are unit points mapped
+//                           into each row's own box, and the row's normaliser is formed first, by all
+//                           four waves (stats_bin_body.hpp holds both kernels)
 //   k_poisson_binomial_cf   one thread per (segment, n): fsum_j log|1 + p_j (w^n - 1)| and
 //                           fsum_j arg(...), w = e^{-2 pi i/(N+1)} (:1293-1295, :1307-1317)
 //
@@ -40,6 +43,26 @@ struct CompSum {
   __device__ inline double value() const { return s + c; }
 };
 
+// Sum over the block, the same bits in every thread: butterfly inside each wave, then the four wave
+// totals as (w0 + w1) + (w2 + w3).
+__device__ inline double post_block_sum(double v, double *red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+__device__ inline double post_block_max(double v, double *red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+}
+
 struct StatsRequest {
   int32_t quantity;      // 0: z, 1: log10 N_HI
   int32_t nb;            // bins, 1 .. kStatsMaxBins
@@ -63,78 +86,38 @@ struct StatsBinArgs {
   double *kept_p;                         // [R][n][kStatsKept]
 };
 
-__global__ __launch_bounds__(256) void k_bin_posteriors(StatsBinArgs a) {
-  __shared__ double sp[kStatsTile], sz[kStatsTile], sl[kStatsTile], sw[kStatsTile];
-  const int64_t s = blockIdx.x;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const double shift = a.shift[s], pd = a.p_dla[s], zmin = a.z_min[s], dz = a.z_max[s] - a.z_min[s];
-  const double *row = a.sll + s * a.ld;
+// The rows of a refine pass: every row has its own box of the last level, the
+// samples are the shared unit points mapped into it, and the row's normaliser is formed by the kernel.
+// The field names the walk uses are StatsBinArgs' (offsets = u, lnhi = v).
+struct StatsBoxedArgs {
+  int64_t n, S, ld;                       // rows, refine points, row stride of lam (elements)
+  const double *lam;                      // [n][ld] lambda of the last level
+  const double *p_dla, *upper_z;          // [n]
+  const double *boxes;                    // [n][4] (z_lo, z_hi, n_lo, n_hi) of the last level
+  const double *offsets, *lnhi;           // [S] the unit points u and v
+  const double *edges;                    // [R][kStatsMaxBins + 1]
+  int32_t R;
+  StatsRequest req[kStatsMaxRequests];
+  double *shift;                          // [n] out: m + log Sum_j exp(lambda_j - m)
+  double *pois, *mean, *var;              // [R][n][kStatsMaxBins]
+  int32_t *count;                         // [R][n]
+  int32_t *kept_bin;                      // [R][n][kStatsKept]
+  double *kept_p;                         // [R][n][kStatsKept]
+};
 
-  const bool active = wave < a.R;
-  StatsRequest rq = a.req[active ? wave : 0];
-  const bool mine = active && lane < rq.nb;
-  const double e_lo = mine ? a.edges[wave * (kStatsMaxBins + 1) + lane] : 0.0;
-  const double e_hi = mine ? a.edges[wave * (kStatsMaxBins + 1) + lane + 1] : 0.0;
-  const bool last = lane == rq.nb - 1;
-  const double z_up = rq.lowzcut ? fmin(a.upper_z[s], rq.z_hi) : rq.z_hi;
-  CompSum acc0, acc1;        // strict: Poisson sum; histogram: w p and w^2 (1 - p) p
-  bool poison = false;       // histogram: a NaN weight at or below this bin (np.histogram's cumsum)
-  int kept = 0;              // wave-uniform
-
-  for (int64_t t0 = 0; t0 < a.S; t0 += kStatsTile) {
-    const int nt = (int)((a.S - t0 < kStatsTile) ? (a.S - t0) : kStatsTile);
-    __syncthreads();
-    for (int j = tid; j < nt; j += 256) {
-      const int64_t g = t0 + j;
-      sp[j] = exp(row[g] - shift) * pd;
-      sz[j] = zmin + dz * a.offsets[g];
-      sl[j] = a.lnhi[g];
-      sw[j] = a.w10[g];
-    }
-    __syncthreads();
-    if (!active) continue;
-    for (int j = 0; j < nt; ++j) {     // every lane reads the same sample: LDS broadcasts
-      const double p = sp[j], z = sz[j], l = sl[j];
-      const double q = rq.quantity ? l : z;
-      if (!rq.histogram) {
-        if (!(l > rq.lnhi_lo && l < rq.lnhi_hi && z < z_up && z > rq.z_lo && p > rq.p_thresh)) continue;
-        const bool inb = mine && q > e_lo && q < e_hi;
-        if (p < rq.p_switch) {
-          if (inb) acc0.add(p);
-        } else if (__ballot(inb)) {
-          if (inb && kept < kStatsKept) {
-            const int64_t o = ((int64_t)wave * a.n + s) * kStatsKept + kept;
-            a.kept_bin[o] = lane;
-            a.kept_p[o] = p;
-          }
-          ++kept;
-        }
-      } else {
-        if (!(l > rq.lnhi_lo && l < rq.lnhi_hi && z < rq.z_hi && z > rq.z_lo)) continue;
-        const double w = rq.moment ? sw[j] : 1.0;
-        const double wm = w * p, wv = w * w * (1 - p) * p;
-        const bool below = last ? q <= e_hi : q < e_hi;
-        if (mine && q >= e_lo && below) {
-          acc0.add(wm);
-          acc1.add(wv);
-        }
-        if (mine && below && wm != wm) poison = true;
-      }
-    }
-  }
-  if (!active) return;
-  const int64_t o = (int64_t)wave * a.n + s;
-  if (mine) {
-    const double nan = __builtin_nan("");
-    if (rq.histogram) {
-      a.mean[o * kStatsMaxBins + lane] = poison ? nan : acc0.value();
-      a.var[o * kStatsMaxBins + lane] = poison ? nan : acc1.value();
-    } else {
-      a.pois[o * kStatsMaxBins + lane] = acc0.value();
-    }
-  }
-  if (lane == 0) a.count[o] = kept;
-}
+// The kernel lives in stats_bin_body.hpp, a header WITHOUT an include guard that is included twice.
+#define GPDLA_STATS_BIN_KERNEL k_bin_posteriors
+#define GPDLA_STATS_BIN_ARGS StatsBinArgs
+#include "stats_bin_body.hpp"
+#undef GPDLA_STATS_BIN_KERNEL
+#undef GPDLA_STATS_BIN_ARGS
+#define GPDLA_STATS_BIN_KERNEL k_bin_posteriors_boxed
+#define GPDLA_STATS_BIN_ARGS StatsBoxedArgs
+#define GPDLA_STATS_BIN_BOXED
+#include "stats_bin_body.hpp"
+#undef GPDLA_STATS_BIN_BOXED
+#undef GPDLA_STATS_BIN_KERNEL
+#undef GPDLA_STATS_BIN_ARGS
 
 struct StatsCfArgs {
   const int64_t *seg_off;   // [nseg + 1] into p

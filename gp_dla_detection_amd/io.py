@@ -943,11 +943,17 @@ def load_parameter_summaries(path: str) -> dict:
 # refined absorber posteriors
 # ---------------------------------------------------------------------------------------------
 
+#: largest transposed piece of a refined sample table save_refined_results holds at a time
+REFINED_SLAB_BYTES = 64 << 20
+
+
 def save_refined_results(path: str, refined: dict, **run_metadata) -> None:
     """What :meth:`api.Batch.refine` / :func:`refine.refine_absorbers` return as a ``-v7.3`` file:
     ``quasar_ind`` (the selection, 1-based), the per-quasar scalars as columns, ``boxes`` [n x level x 4],
     ``status``, the two sample tables when present, and the refined parameter summaries (the dict under
-    ``summaries``) with a ``summary_`` prefix.  ``run_metadata``: scalars and strings, as given."""
+    ``summaries``) with a ``summary_`` prefix.  When present, too: the refined model posteriors (``refine.POSTERIORS``,
+    DESIGN.md 4.19) and the unit points ``refine_u`` / ``refine_v`` the tables were swept on.  ``run_metadata``:
+    scalars and strings, as given."""
     from . import refine as _refine
     n = np.asarray(refined["status"]).shape[0]
     w = _MatWriter(path)
@@ -960,8 +966,17 @@ def save_refined_results(path: str, refined: dict, **run_metadata) -> None:
         for k in _refine.SCALARS:
             w.put(k, np.asarray(refined[k], dtype=np.float64).reshape(-1, 1))
         for k in _refine.TABLES:
+            if k in refined:  # streamed in slabs of sample columns: no transposed copy of the table
+                a = np.asarray(refined[k], dtype=np.float64)
+                step = max(1, REFINED_SLAB_BYTES // max(8 * a.shape[0], 1))
+                if a.size:
+                    w.put_streamed(k, a.shape, np.float64, (a[:, j:j + step].T for j in range(0, a.shape[1], step)))
+                else:
+                    w.put(k, a)
+        for k in _refine.POSTERIORS + _refine.POINTS:
             if k in refined:
-                w.put(k, np.asarray(refined[k], dtype=np.float64))
+                a = np.asarray(refined[k], dtype=np.float64)
+                w.put(k, a if a.ndim == 2 else a.reshape(-1, 1))
         for k, v in (refined.get("summaries") or {}).items():
             if k != "selection":
                 w.put("summary_" + k, np.asarray(v, dtype=np.float64))
@@ -980,8 +995,10 @@ def load_refined_results(path: str) -> dict:
             out["selection"] = _vec(v).astype(np.int64) - 1
         elif k == "status":
             out[k] = _vec(v).astype(np.int32)
-        elif k in _refine.SCALARS:
+        elif k in _refine.SCALARS or k in _refine.POINTS or k in ("p_no_dlas_refined", "p_dlas_refined"):
             out[k] = _vec(v).astype(np.float64)
+        elif k == "refined":
+            out[k] = _vec(v).astype(np.int32)
         elif k.startswith("summary_"):
             k = k[len("summary_"):]
             summ[k] = _vec(v).astype(np.float64) if k in ("probabilities", "thresholds") else \

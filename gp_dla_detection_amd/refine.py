@@ -10,9 +10,15 @@ include/gpdla.h; nothing of this exists in the reference.
 
     python -m gp_dla_detection_amd.refine PRELOADED CATALOG LEARNED SAMPLES PROCESSED OUT
         [--p-thresh P] [--levels L] [--delta D] [--pad PAD] [--points N] [--prior LOG_NHIS] [--batch B]
+        [--posteriors] [--tables]
 
 selects the quasars of a processed single-DLA file by ``p_dlas >= P``, processes and refines them batch by
-batch (:func:`api.run_pipeline`) and writes OUT (:func:`io.save_refined_results`).
+batch (:func:`api.run_pipeline`) and writes OUT (:func:`io.save_refined_results`).  ``--posteriors`` adds the
+model posteriors recomputed from the refined evidence; ``--tables`` adds the last level's
+``sample_log_posteriors_refined`` of the selected quasars and the unit points ``refine_u`` / ``refine_v``, which
+``python -m gp_dla_detection_amd.cddf --refined OUT`` bins.  Only that table is downloaded, each batch into its
+rows of one array, and the file writer streams it: the host holds 8 S' bytes per selected quasar until the file
+is written, plus one transposed slab of at most 64 MiB while it is.
 """
 from __future__ import annotations
 
@@ -25,6 +31,8 @@ from . import _lib
 SCALARS = ("log_likelihoods_dla_refined", "log_posteriors_dla_refined", "MAP_z_dlas_refined", "MAP_log_nhis_refined",
            "MAP_inds_refined")
 TABLES = ("sample_log_likelihoods_refined", "sample_log_posteriors_refined")
+POSTERIORS = ("model_posteriors_refined", "p_no_dlas_refined", "p_dlas_refined", "refined")
+POINTS = ("refine_u", "refine_v")   # the unit points the tables were swept on, stored beside them
 DEFAULT_LEVELS, DEFAULT_DELTA, DEFAULT_PAD = 2, 12.5, 2.0
 
 
@@ -55,28 +63,47 @@ def validate(levels: int = DEFAULT_LEVELS, delta: float = DEFAULT_DELTA, pad: fl
     _lib.check(_lib.load().gpdla_refine_validate(C.byref(rq), ps, n, up, vp))
 
 
-def empty_results(n: int, levels: int, num_points: int, with_samples: bool = True) -> dict:
-    """Host arrays of gpdla_refined_results for ``n`` quasars."""
+def tables_of(with_samples) -> tuple:
+    """The sample tables ``with_samples`` asks for: all of TABLES (True), none (False), or the names given."""
+    if isinstance(with_samples, (bool, np.bool_)):
+        return TABLES if with_samples else ()
+    names = (with_samples,) if isinstance(with_samples, str) else tuple(with_samples)
+    if any(k not in TABLES for k in names):
+        raise ValueError(f"with_samples names {names}; the tables are {TABLES}")
+    return names
+
+
+def empty_results(n: int, levels: int, num_points: int, with_samples=True) -> dict:
+    """Host arrays of gpdla_refined_results for ``n`` quasars.  ``with_samples``: True (both tables), False, or
+    the names of the tables wanted."""
     out = {k: np.full(n, np.nan) for k in SCALARS}
     out["boxes"] = np.full((n, int(levels), 4), np.nan)
     out["status"] = np.full(n, _lib.REFINE_NOT_REFINED, dtype=np.int32)
-    if with_samples:
-        for k in TABLES:
-            out[k] = np.full((n, int(num_points)), np.nan)
+    for k in tables_of(with_samples):
+        out[k] = np.full((n, int(num_points)), np.nan)
     return out
+
+
+def empty_posteriors(n: int) -> dict:
+    """Host arrays of gpdla_refined_posteriors for ``n`` quasars."""
+    return {"model_posteriors_refined": np.full((n, 2), np.nan), "p_no_dlas_refined": np.full(n, np.nan),
+            "p_dlas_refined": np.full(n, np.nan), "refined": np.zeros(n, dtype=np.int32)}
 
 
 def refine_absorbers(model: dict, samples: dict, spectra, results: dict, p_dla_threshold: float = 0.9, levels: int = DEFAULT_LEVELS,
                      delta: float = DEFAULT_DELTA, pad: float = DEFAULT_PAD, prior=None, points=None, params=None,
-                     device: int = 0, max_quasars_per_batch: int = 1024, pipeline_slots: int = 3, with_samples: bool = False,
-                     summaries: bool = True, probabilities=None, thresholds=None) -> dict:
+                     device: int = 0, max_quasars_per_batch: int = 1024, pipeline_slots: int = 3, with_samples=False,
+                     summaries: bool = True, probabilities=None, thresholds=None, posteriors: bool = False) -> dict:
     """The host-arrays convenience: refine the quasars of ``spectra`` (a list of per-quasar dicts) whose
     ``results["p_dlas"]`` (of :func:`api.process_qsos` on the same list) reach ``p_dla_threshold``.  The
     selected quasars are processed again and refined batch by batch through :func:`api.run_pipeline`.
     ``points``: (u, v), default :func:`default_points` with as many points as there are DLA samples.
     Returns ``selection`` (indices into ``spectra``) and, per selected quasar, what :meth:`api.Batch.refine`
-    returns, plus (``summaries``) the refined parameter summaries under ``summaries``."""
-    from . import api, posteriors
+    returns, plus (``summaries``) the refined parameter summaries under ``summaries``, (``posteriors``) what
+    :meth:`api.Batch.refined_posteriors` returns and (``with_samples``: True, or the names of the tables wanted)
+    the unit points ``refine_u`` / ``refine_v``.  Every batch downloads into its rows of ONE set of output arrays:
+    the host holds 8 S' bytes per selected quasar and table asked for, and no second copy."""
+    from . import api, posteriors as _post
     from .parameters import Parameters
     spectra = list(spectra)
     with np.errstate(invalid="ignore"):
@@ -84,16 +111,22 @@ def refine_absorbers(model: dict, samples: dict, spectra, results: dict, p_dla_t
     validate(levels, delta, pad, prior, *(points if points is not None else (None, None)))
     lp_no = np.asarray(results["log_priors_no_dla"], dtype=np.float64)
     lp_dla = np.asarray(results["log_priors_dla"], dtype=np.float64)
-    p, t = posteriors.check_request(posteriors.DEFAULT_PROBABILITIES if probabilities is None else probabilities,
-                                    posteriors.DEFAULT_THRESHOLDS if thresholds is None else thresholds)
+    p, t = _post.check_request(_post.DEFAULT_PROBABILITIES if probabilities is None else probabilities,
+                               _post.DEFAULT_THRESHOLDS if thresholds is None else thresholds)
     blocks = api.batch_blocks(sel.size, max_quasars_per_batch)
     parts = [None] * len(blocks)
+    used_points = points
+    num_points = np.asarray(samples["offset_samples"]).size if points is None else np.asarray(points[0]).size
+    out = empty_results(sel.size, levels, num_points, with_samples)
+    if posteriors:
+        out.update(empty_posteriors(sel.size))
     if sel.size:
         ctx = api.Context(device, params or Parameters())
         try:
             ctx.set_model(model)
             ctx.set_samples(samples)
             ctx.set_refine_points(*(points if points is not None else (None, None)))
+            used_points = ctx.refine_points
 
             def inputs(i):
                 idx = sel[blocks[i][0]:blocks[i][1]]
@@ -104,19 +137,23 @@ def refine_absorbers(model: dict, samples: dict, spectra, results: dict, p_dla_t
                 batch.refine(None, levels, delta, pad, prior, download=False)
 
             def download(i, batch):
-                out = batch.download_refined(None, levels, with_samples)
+                batch.download_refined(None, levels, with_samples, out=out, at=blocks[i][0])
+                part = {}
                 if summaries:
-                    out["summaries"] = batch.parameter_summaries(refined=True, probabilities=p, thresholds=t)
-                parts[i] = out
+                    part["summaries"] = batch.parameter_summaries(refined=True, probabilities=p, thresholds=t)
+                if posteriors:
+                    for k, a in batch.refined_posteriors().items():
+                        out[k][blocks[i][0]:blocks[i][1]] = a
+                parts[i] = part
 
             api.run_pipeline(ctx, len(blocks), inputs, process, download, pipeline_slots)
         finally:
             ctx.close()
-    num_points = np.asarray(samples["offset_samples"]).size if points is None else np.asarray(points[0]).size
-    out = empty_results(0, levels, num_points, with_samples)
-    for k in out:
-        out[k] = np.concatenate([out[k]] + [part[k] for part in parts])
     out["selection"] = sel
+    if tables_of(with_samples):
+        if used_points is None:   # nothing was selected: the points a context would have made
+            used_points = default_points(num_points, device)
+        out["refine_u"], out["refine_v"] = (np.array(a, dtype=np.float64).reshape(-1) for a in used_points)
     if summaries and parts:
         out["summaries"] = {k: (np.concatenate([part["summaries"][k] for part in parts]) if k not in ("probabilities", "thresholds", "selection")
                                 else parts[0]["summaries"][k]) for k in parts[0]["summaries"]}
@@ -143,6 +180,9 @@ def main(argv=None):
     ap.add_argument("--prior", default=None, help="file of catalogue log10 N_HI values: fit the column density prior to them")
     ap.add_argument("--batch", type=int, default=1024)
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--posteriors", action="store_true", help="add the model posteriors recomputed from the refined evidence")
+    ap.add_argument("--tables", action="store_true",
+                    help="add sample_log_posteriors_refined of the selected quasars and the unit points (for cddf --refined)")
     args = ap.parse_args(argv)
     processed = io.load_processed_qsos(args.processed)
     if np.ndim(processed["log_priors_dla"]) != 1:
@@ -156,7 +196,8 @@ def main(argv=None):
     from .parameters import Parameters
     params = Parameters(num_lines=int(np.asarray(processed["num_lines"]).reshape(-1)[0])) if "num_lines" in processed else Parameters()
     out = refine_absorbers(model, smp, spectra, processed, args.p_thresh, args.levels, args.delta, args.pad, prior, points,
-                           params, args.device, args.batch, with_samples=False)
+                           params, args.device, args.batch, posteriors=args.posteriors,
+                           with_samples=("sample_log_posteriors_refined",) if args.tables else False)   # that table alone
     io.save_refined_results(args.out, out, p_thresh=np.float64(args.p_thresh), levels=np.float64(args.levels),
                             delta=np.float64(args.delta), pad=np.float64(args.pad))
     print(f"refined {out['selection'].size} of {len(spectra)} quasars -> {args.out}")

@@ -503,6 +503,34 @@ int gpdla_stats_bin_posteriors(int64_t num_spectra, int64_t num_samples, const d
 int gpdla_stats_poisson_binomial_cf(int64_t num_segments, const int64_t *offsets, const double *p, double *logsum,
                                     double *argsum, int device_id);
 
+/* gpdla_stats_bin_posteriors for the rows of a refine pass.  Additive: GPDLA_ABI_VERSION is
+ * unchanged.  Row s holds lambda_j, j < S' (sample_log_posteriors_refined, at sample_log_posteriors + s *
+ * row_stride); boxes[s] = (z_lo, z_hi, n_lo, n_hi) is the row's box of the last level; u, v are the shared
+ * unit points, each inside [0, 1).  Per row, each operation rounded on its own:
+ *   shift[s] = m + log(Sum_j exp(lambda_j - m)), m = the maximum of the row, NaN entries skipped by both; a
+ *              row without a finite entry, or with +inf, has shift NaN.  The sum is compensated and runs in an
+ *              order fixed by S' alone.
+ *   p_j = exp(lambda_j - shift[s]) * p_dla[s],  z_j = z_lo + (z_hi - z_lo) u_j,  lnhi_j = n_lo + (n_hi - n_lo)
+ *   v_j,  w_j = exp10(lnhi_j) (the N' the boxed sweep itself used, where gpdla_stats_bin_posteriors takes the
+ *   host's pow).
+ * The requests, every comparison, the kept-pair rule and its capacity, the NaN poisoning of histogram bins
+ * and the output layouts are gpdla_stats_bin_posteriors'.  A NaN shift makes every p of the row NaN, and the
+ * row is treated as that entry treats NaN p.  A zero-width box is legal.  No atomics: a row's outputs depend
+ * on that row only and are bit-identical from run to run and for any blocking of the rows.  The argument
+ * checks (null pointers, row_stride < S', edges, the number of requests, u or v outside [0, 1)) run before
+ * the device is touched and need no GPU. */
+int gpdla_stats_bin_posteriors_boxed(int64_t num_rows, int64_t num_points, const double *sample_log_posteriors,
+                                     int64_t row_stride, const double *p_dla, const double *boxes, const double *upper_z,
+                                     const double *u, const double *v, int num_requests,
+                                     const gpdla_bin_request *requests, gpdla_bin_output *outputs, double *shift,
+                                     int device_id);
+/* Measuring aids for tools/bench_refined_stats.py.  gpdla_debug_time_bin_kernels(1) makes the calling thread's
+ * later calls of the two entries above bracket their kernel launch with device events (0: off, the default --
+ * a call then launches as it always did); gpdla_debug_last_bin_ms returns the duration of the k_bin_posteriors
+ * or k_bin_posteriors_boxed launch of that thread's most recent timed call (-1 before the first). */
+void gpdla_debug_time_bin_kernels(int on);
+double gpdla_debug_last_bin_ms(void);
+
 /* ---------------------------------------------------------------------------------------------
  * Sightline S/N, path length per sightline and bin, stratified bootstrap.  Additive:
  * GPDLA_ABI_VERSION is unchanged.
@@ -926,6 +954,16 @@ double gpdla_debug_last_summaries_ms(void);
  * gpdla_batch_refined_summaries: gpdla_parameter_summaries (num_models = 1) of the resident lambda table
  * as weights over (z'_j, n'_j) of the last level: same definitions, outputs [n][1][1]...  Refused
  * (GPDLA_ERR_INVALID_ARGUMENT) once gpdla_context_set_refine_points has been called again after the refine.
+ * gpdla_batch_refined_posteriors: the model posteriors of the selected quasars with the
+ * refined evidence in the place of the first pass's.  For a quasar of refine status 0, with lp_no = the
+ * first pass's log_posteriors_no_dla and lp_dla = log_posteriors_dla_refined, the five operations of the
+ * first pass, each rounded on its own: mx = max(lp_no, lp_dla), p0 = exp(lp_no - mx), p1 = exp(lp_dla - mx),
+ * model_posteriors_refined = (p0, p1) / (p0 + p1), p_no_dlas_refined = the first of the two, p_dlas_refined =
+ * 1 - it, refined = 1.  Any other quasar (outside the refine's selection, or unusable) gets the first pass's
+ * model_posteriors, p_no_dlas and p_dlas and refined = 0, so the table is complete.  The kernel runs on the
+ * context's stream behind the refine; the call returns when the rows are in the caller's arrays.  Legal only
+ * after a gpdla_batch_refine of the same spectra (else GPDLA_ERR_INVALID_ARGUMENT, nothing written);
+ * selection as for gpdla_batch_download_refined; any output pointer may be NULL.
  * ------------------------------------------------------------------------------------------- */
 #define GPDLA_REFINE_MAX_LEVELS 4
 #define GPDLA_REFINE_UNUSABLE 1        /* status bit 1 */
@@ -955,6 +993,13 @@ int gpdla_batch_download_refined(gpdla_context *ctx, gpdla_batch *batch, const i
 int gpdla_batch_refined_summaries(gpdla_context *ctx, gpdla_batch *batch, const int64_t *selection,
                                   int64_t num_selected, const gpdla_summary_request *request,
                                   gpdla_parameter_summaries *outputs);
+typedef struct {
+  double *model_posteriors_refined;             /* [n][2] (no DLA, DLA) */
+  double *p_no_dlas_refined, *p_dlas_refined;   /* [n] */
+  int32_t *refined;                             /* [n] 1: from the refined evidence, 0: the first pass's */
+} gpdla_refined_posteriors;
+int gpdla_batch_refined_posteriors(gpdla_context *ctx, gpdla_batch *batch, const int64_t *selection,
+                                   int64_t num_selected, gpdla_refined_posteriors *out);
 /* Measuring aid for tools/bench_refine.py: device time of the calling thread's most recent gpdla_batch_refine
  * made with the context's timing on (all groups and levels; -1 before the first). */
 double gpdla_debug_last_refine_ms(void);
