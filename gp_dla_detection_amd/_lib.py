@@ -207,6 +207,7 @@ REFINE_MAX_LEVELS, REFINE_UNUSABLE, REFINE_NOT_REFINED = 4, 1, -1   # GPDLA_REFI
 POSTERIOR_MAX_MODELS, POSTERIOR_MAX_PROBABILITIES, POSTERIOR_MAX_THRESHOLDS = 4, 8, 4   # GPDLA_POSTERIOR_MAX_*
 POSTERIOR_UNUSABLE, POSTERIOR_NAN_RANGE = 1, 2                                          # status bits
 SPECTRA_MAX_ABSORBERS = 8                                   # GPDLA_SPECTRA_MAX_ABSORBERS
+MAX_FIXED_ABSORBERS = 8                                     # GPDLA_MAX_FIXED_ABSORBERS
 SPECTRA_MAP, SPECTRA_MOMENTS, SPECTRA_CONTINUUM = 1, 2, 4   # GPDLA_SPECTRA_* product bits
 SPECTRA_WEIGHTS_NONE, SPECTRA_WEIGHTS_RESIDENT, SPECTRA_WEIGHTS_HOST = 0, 1, 2
 
@@ -316,6 +317,10 @@ SYMBOLS = [
                                                 C.POINTER(ParameterSummaries)]),
     ("gpdla_batch_refined_posteriors", C.c_int, [C.c_void_p, C.c_void_p, _i64p, C.c_int64, C.POINTER(RefinedPosteriors)]),
     ("gpdla_debug_last_refine_ms", C.c_double, []),
+    ("gpdla_fixed_absorbers_validate", C.c_int, [C.c_int64, _i64p, _dp, _dp, C.c_double]),
+    ("gpdla_batch_set_fixed_absorbers", C.c_int, [C.c_void_p, C.c_void_p, _i64p, _dp, _dp, C.c_double, C.c_int32]),
+    ("gpdla_batch_clear_fixed_absorbers", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("gpdla_debug_conditioned_rows", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, _dp, _dp, C.c_int64, _i64p]),
     ("gpdla_debug_near_poly", C.c_int, [C.c_int, C.c_double, _dp, _dp]),
     ("gpdla_debug_prepared_rows", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, _dp, C.c_int64, _i64p]),
     ("gpdla_debug_philox4x32_10", None, [_u32p, _u32p, _u32p]),

@@ -360,6 +360,43 @@ class Batch:
                                                           rows.ctypes.data_as(_dp), cap, C.byref(n)))
         return rows[: n.value].copy()
 
+    # ---- fixed absorbers ----
+
+    def set_fixed_absorbers(self, absorbers, min_z_separation: float | None = None, meanflux_rows: bool | None = None):
+        """Condition this single-DLA batch on fixed absorbers (gpdla_batch_set_fixed_absorbers; the contract is in
+        include/gpdla.h): ``absorbers`` is the CSR triple ``(offsets [nq + 1], z_dlas, log_nhis)`` that
+        :func:`map_absorbers` returns, one list of at most 8 per quasar of the batch, or None to clear.  After it
+        :meth:`process` and :meth:`refine` evaluate ONE MORE absorber given the listed ones, and
+        ``log_likelihoods_no_dla`` is the likelihood of the listed ones alone.  ``min_z_separation``: default from
+        the context's parameters (a :class:`MultiParameters`' own, else the multi-DLA driver's 3000 km/s);
+        ``meanflux_rows``: the rows of the multi-DLA driver (default: whether the parameters are
+        :class:`MultiParameters`).  The batch is unprocessed afterwards; :meth:`reload` clears."""
+        lib, p = self.ctx.lib, self.ctx.params
+        if absorbers is None:
+            _lib.check(lib.gpdla_batch_clear_fixed_absorbers(self.ctx._h, self._h))
+        else:
+            off, z, ln = absorbers
+            off = np.ascontiguousarray(off, dtype=np.int64).reshape(-1)
+            if off.size != self.num_quasars + 1:
+                raise _lib.GpdlaError(-1, f"absorber offsets: {off.size} entries for {self.num_quasars} quasars")
+            z, ln = _f64(z)[0].reshape(-1), _f64(ln)[0].reshape(-1)
+            sep = getattr(p, "min_z_separation", MultiParameters().min_z_separation) if min_z_separation is None else min_z_separation
+            mf = isinstance(p, MultiParameters) if meanflux_rows is None else bool(meanflux_rows)
+            _lib.check(lib.gpdla_batch_set_fixed_absorbers(self.ctx._h, self._h, off.ctypes.data_as(_i64p), z.ctypes.data_as(_dp),
+                                                           ln.ctypes.data_as(_dp), float(sep), int(mf)))
+        self._refined = None
+
+    def debug_conditioned_rows(self, quasar: int = 0, meanflux_rows: bool = False):
+        """Test hook (gpdla_debug_conditioned_rows): ``(rows [n_u, 4], M [n_u, k])`` of one quasar on its
+        unmasked-range grid after the preparation kernel and, on a conditioned batch, the conditioning.
+        ``meanflux_rows`` chooses the preparation of an unconditioned batch; a conditioned one uses its own."""
+        cap = 8192
+        rows, M = np.empty((cap, 4)), np.empty((cap, self.ctx.k))
+        n = C.c_int64()
+        _lib.check(self.ctx.lib.gpdla_debug_conditioned_rows(self.ctx._h, self._h, int(bool(meanflux_rows)), int(quasar),
+                                                             rows.ctypes.data_as(_dp), M.ctypes.data_as(_dp), cap, C.byref(n)))
+        return rows[: n.value].copy(), M[: n.value].copy()
+
     # ---- model spectra (DESIGN.md 4.12) ----
 
     def unmasked_counts(self) -> np.ndarray:
@@ -969,6 +1006,14 @@ def refine_absorbers(model: dict, samples: dict, spectra, results: dict, p_dla_t
     ``p_dla_threshold``: :func:`refine.refine_absorbers`, which documents the keywords."""
     from . import refine
     return refine.refine_absorbers(model, samples, spectra, results, p_dla_threshold, **kw)
+
+
+def refine_multi_absorbers(model: dict, samples: dict, spectra, results_multi: dict, **kw) -> dict:
+    """Refine the reported absorbers of a multi-DLA run slot by slot, each conditioned on the others of its
+    quasar: :func:`conditional.refine_multi_absorbers`; :func:`conditional.refine_conditional`
+    documents the keywords."""
+    from . import conditional
+    return conditional.refine_multi_absorbers(model, samples, spectra, results_multi, **kw)
 
 
 # ----------------------------------------------------------------------------------------------

@@ -247,6 +247,48 @@ def generate_json_catalogue_refined(results: dict, quasar_info: dict, refined: d
     return out
 
 
+def generate_json_catalogue_conditional(results: dict, quasar_info: dict, conditional: dict, outfile: str | None = None,
+                                        sub_dla: bool = True, occams_razor: float = 10000.0, drop_nan: bool = True) -> list:
+    """:func:`generate_json_catalogue` of a multi-DLA run with the absorbers that :func:`conditional.refine_multi_absorbers`
+    refined slot by slot.  ``conditional``: its result (or ``io.load_conditional_results``), one row per
+    searched quasar.  An entry of ``dlas`` is matched to the slot whose STARTING value (``start_z_dlas``,
+    ``start_log_nhis``) equals it exactly -- the lists of :func:`api.map_absorbers` are the reported absorbers unless
+    Occam's razor moved the record to another model, whose absorbers were not refined.  Where that slot's ``status`` is
+    0, ``z_dla`` and ``log_nhi`` are replaced by the refined values and the entry gains ``z_dla_mean``, ``z_dla_std``,
+    ``log_nhi_mean``, ``log_nhi_std``, the quantiles as ``z_dla_q<p>`` / ``log_nhi_q<p>``, ``effective_samples`` and
+    ``log_bayes_factor`` (the conditional evidence of this absorber given the others of its list).  Every entry carries
+    a boolean ``refined``; an entry without a usable slot (a NaN slot, another model's absorber, status != 0) and every
+    other field of every record are as :func:`generate_json_catalogue` writes them."""
+    from .posteriors import quantile_key
+    out = generate_json_catalogue(results, quasar_info, None, sub_dla, occams_razor, drop_nan)
+    _, _, keep = loader_view(results, quasar_info, sub_dla, occams_razor, drop_nan)
+    c = {k: np.asarray(v) for k, v in conditional.items() if k != "history"}
+    nq = np.asarray(results["model_posteriors"]).shape[0]
+    if c["z_dlas"].shape[0] != nq:
+        raise ValueError(f"the conditional results hold {c['z_dlas'].shape[0]} quasars, the run {nq}")
+    probs = c["probabilities"].reshape(-1)
+    for spec, i in zip(out, keep):
+        for dla in spec["dlas"]:
+            hit = np.flatnonzero((c["start_z_dlas"][i] == dla["z_dla"]) & (c["start_log_nhis"][i] == dla["log_nhi"]))
+            s = int(hit[0]) if hit.size else -1
+            dla["refined"] = bool(s >= 0 and c["status"][i, s] == 0)
+            if not dla["refined"]:
+                continue
+            dla["z_dla"], dla["log_nhi"] = _py(c["z_dlas"][i, s]), _py(c["log_nhis"][i, s])
+            dla["z_dla_mean"], dla["z_dla_std"] = _py(c["mean_z"][i, s]), _py(c["std_z"][i, s])
+            dla["log_nhi_mean"], dla["log_nhi_std"] = _py(c["mean_log_nhi"][i, s]), _py(c["std_log_nhi"][i, s])
+            for q, p in enumerate(probs):
+                dla[quantile_key("z_dla", p)] = _py(c["quantiles_z"][i, s, q])
+                dla[quantile_key("log_nhi", p)] = _py(c["quantiles_log_nhi"][i, s, q])
+            dla["effective_samples"] = _py(c["effective_samples"][i, s])
+            dla["log_bayes_factor"] = _py(c["log_bayes_factor"][i, s])
+    if outfile is not None:
+        import json
+        with open(outfile, "w") as f:
+            json.dump(out, f, indent=2)
+    return out
+
+
 def generate_sub_dla_catalogue(results: dict, quasar_info: dict, outfile: str | None = None,
                                sub_dla: bool = True, occams_razor: float = 10000.0,
                                drop_nan: bool = True) -> list:

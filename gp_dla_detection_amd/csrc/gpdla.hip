@@ -38,6 +38,7 @@
 #include "preload_kernels.hpp"
 #include "posterior_kernels.hpp"
 #include "refine_kernels.hpp"
+#include "condition_kernels.hpp"
 #include "training_kernels.hpp"
 #include "training_mfma_kernels.hpp"
 
@@ -58,5 +59,6 @@ using namespace gpdla;
 #include "host_preload.hpp"
 #include "host_posterior.hpp"
 #include "host_refine.hpp"
+#include "host_condition.hpp"
 // libgpdla_legacy.so (-DGPDLA_WITH_LEGACY): the superseded kernels and their environment switches
 #include "host_legacy.hpp"

@@ -40,6 +40,15 @@ int check_unchanged(const gpdla_context *c, const gpdla_batch *b, bool model_too
   return GPDLA_OK;
 }
 
+// The entries that run k_prepare again (model spectra, mock draws and their hooks) would put unconditioned
+// rows where a conditioned batch's refine pass expects its own, and their products are not defined for a
+// batch whose results are about "one more absorber" (DESIGN.md 4.20): they refuse it.
+int check_unconditioned(const gpdla_batch *b, const char *what) {
+  if (b->fx && b->fx->on)
+    return fail(GPDLA_ERR_UNSUPPORTED, "%s: the batch is conditioned on fixed absorbers (gpdla_batch_clear_fixed_absorbers first)", what);
+  return GPDLA_OK;
+}
+
 // The resident sample log-likelihoods of a processed batch: quasar q's row (multi-DLA: its model
 // DLA(1) row, [nq][max_dlas][S]; the sub-DLA table is [nq][S]) starts at table + q * width.
 struct SampleTable {

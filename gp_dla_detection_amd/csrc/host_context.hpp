@@ -90,6 +90,24 @@ struct gpdla_batch {
   bool processed = false;  // single-DLA batch: gpdla_batch_process has run on the current spectra
   struct MultiBuffers *mb = nullptr;
   struct RefineBuffers *rf = nullptr;  // the refine pass's tables, allocated by the first gpdla_batch_refine
+  struct FixedAbsorbers *fx = nullptr;  // gpdla_batch_set_fixed_absorbers (host_condition.hpp); kept across reloads
+};
+
+// The fixed absorbers a single-DLA batch is conditioned on: CSR lists per quasar in HBM,
+// allocated by the first gpdla_batch_set_fixed_absorbers and grown only.  `on` is what makes the batch a
+// conditioned one; a reload or gpdla_batch_clear_fixed_absorbers turns it off and keeps the arrays.
+struct FixedAbsorbers {
+  bool on = false;
+  int32_t meanflux = 0;     // rows prepared as the multi-DLA driver prepares them
+  double sep = 0.0;         // min_z_separation of the call
+  int64_t *d_off = nullptr; // [nq + 1]
+  double *d_z = nullptr, *d_n = nullptr;  // redshifts, column densities
+  size_t cap_off = 0, cap_z = 0, cap_n = 0;
+  ~FixedAbsorbers() {
+    if (d_off) (void)hipFree(d_off);
+    if (d_z) (void)hipFree(d_z);
+    if (d_n) (void)hipFree(d_n);
+  }
 };
 
 // What gpdla_batch_refine keeps per batch (host_refine.hpp): tables indexed by the batch's quasar, kept
@@ -409,6 +427,7 @@ void gpdla_batch_destroy(gpdla_batch *b) {
   dev_free(b->d_records);
   delete b->mb;
   delete b->rf;
+  delete b->fx;
   delete b;
 }
 
@@ -494,6 +513,7 @@ int batch_fill(gpdla_context *c, gpdla_batch *b, const gpdla_spectra *sp, int md
   b->plan_budget = -1;  // the record plan is remade by the next process call
   b->processed = false;
   if (b->rf) b->rf->levels = 0;  // (the tables are kept; their contents belong to the previous spectra)
+  if (b->fx) b->fx->on = false;  // fixed absorbers belong to the previous spectra as well
   if (b->md != md) {  // (reload with a different kind of batch)
     delete b->mb;
     b->mb = nullptr;

@@ -32,7 +32,7 @@ int gpdla_mock_validate(const gpdla_mock_request *rq, int64_t num_quasars) try {
 
 int gpdla_batch_draw_mocks(gpdla_context *c, gpdla_batch *b, const gpdla_mock_request *rq, gpdla_mock_spectra *out) try {
   int rc = check_batch_pair(c, b, rq && out && out->grid_offsets);
-  if (rc || (rc = validate_mock(rq, b->nq)) || (rc = check_unchanged(c, b, true))) return rc;
+  if (rc || (rc = check_unconditioned(b, "mock draws")) || (rc = validate_mock(rq, b->nq)) || (rc = check_unchanged(c, b, true))) return rc;
   if (b->k > GPDLA_MAX_K) return fail(GPDLA_ERR_UNSUPPORTED, "k = %d above %d", b->k, GPDLA_MAX_K);
   if (out->flux && rq->capacity_stored < b->total_pix)
     return fail(GPDLA_ERR_INVALID_ARGUMENT, "the batch stores %lld pixels, capacity_stored is %lld", (long long)b->total_pix,

@@ -251,6 +251,9 @@ int gpdla_batch_refine(gpdla_context *c, gpdla_batch *b, const int64_t *selectio
       sa.nq = count;
       sa.box = rf->box + 4 * l;
       if ((rc = launch_boxed_sweep(c, b, cls, count, sa))) return rc;
+      if (is_conditioned(b) &&
+          (rc = launch_condition_mask(c, b, rf->rows + r0, count, rf->status, rf->box + 4 * l, c->d_ru, Sr, rf->ell)))
+        return rc;
       fa.rows = rf->rows + r0;
       fa.level = l;
       fa.last = l + 1 == L;

@@ -71,7 +71,7 @@ int gpdla_model_spectra_validate(const gpdla_model_spectra_request *rq, int64_t 
 
 int gpdla_batch_unmasked_counts(gpdla_context *c, gpdla_batch *b, int64_t *n_u) try {
   int rc = check_batch_pair(c, b, n_u != nullptr);
-  if (rc || (rc = check_unchanged(c, b, true))) return rc;
+  if (rc || (rc = check_unconditioned(b, "unmasked counts")) || (rc = check_unchanged(c, b, true))) return rc;
   HIP_TRY(hipSetDevice(c->device_id));
   std::vector<QuasarMeta> meta;
   if ((rc = spectra_prepare(c, b, b->md != 0, meta))) return rc;
@@ -82,7 +82,7 @@ int gpdla_batch_unmasked_counts(gpdla_context *c, gpdla_batch *b, int64_t *n_u) 
 int gpdla_batch_model_spectra(gpdla_context *c, gpdla_batch *b, const gpdla_model_spectra_request *rq,
                               gpdla_model_spectra *out) try {
   int rc = check_batch_pair(c, b, rq && out && out->offsets);
-  if (rc || (rc = validate_model_spectra(rq, b->nq, b->S, c->d_lls_nhi != nullptr)) || (rc = check_unchanged(c, b, true))) return rc;
+  if (rc || (rc = check_unconditioned(b, "model spectra")) || (rc = validate_model_spectra(rq, b->nq, b->S, c->d_lls_nhi != nullptr)) || (rc = check_unchanged(c, b, true))) return rc;
   const bool want_map = (rq->products & GPDLA_SPECTRA_MAP) && out->map_absorption;
   const bool want_mom = (rq->products & GPDLA_SPECTRA_MOMENTS) && (out->mean_absorption || out->var_absorption);
   const bool want_cont = (rq->products & GPDLA_SPECTRA_CONTINUUM) && (out->continuum || out->model_flux);

@@ -166,6 +166,16 @@ int legacy_sweep(gpdla_context *c, gpdla_batch *b, const SweepArgs &args);
 template <class Args>
 int legacy_sweep_multi(gpdla_context *c, gpdla_batch *b, const Args &args);
 
+// A batch conditioned on fixed absorbers (host_condition.hpp): k_condition_rows behind
+// k_prepare, and k_condition_mask on a swept table of S entries per quasar -- the first pass's (rows ==
+// nullptr: every quasar of the batch, z over its search range) or a boxed level's (the `count` quasars of
+// `rows`, z over box + q * kRefineBoxStride, the rows of refine status != 0 skipped).
+bool is_conditioned(const gpdla_batch *b) { return b->fx && b->fx->on; }
+int check_conditionable(const gpdla_context *c, const gpdla_batch *b);
+int launch_condition_rows(gpdla_context *c, gpdla_batch *b);
+int launch_condition_mask(gpdla_context *c, gpdla_batch *b, const int32_t *rows, int64_t count, const int32_t *status,
+                          const double *box, const double *su, int64_t S, double *table);
+
 // The sweep of one group of quasars (args.order, args.nq) over records of class `cls`; three
 // lines at compile time, any other count at run time.  fp64 sweeps slim records, the fp32 study
 // pre-expanded ones.  (The grids of all but k_sweep_split_slim cover the batch's quasars: the blocks
@@ -207,9 +217,11 @@ int gpdla_batch_process(gpdla_context *c, gpdla_batch *b) try {
   // study (contraction_precision == 1) sweeps pre-expanded ones (k_sweep<float, ...>)
   const bool f32 = c->cfg.contraction_precision == 1;
   const RecordClass cls = legacy_record_class(b->k, f32 ? kRecExpanded : b->k <= 20 ? kRecSlim20 : kRecSlim40);
-  int rc = plan_records(c, b, record_class_doubles(cls, b->ntiles, false), false);
-  if (rc) return rc;
-  if ((rc = launch_prepare(c, b, false))) return rc;
+  const bool conditioned = is_conditioned(b);
+  int rc = conditioned ? check_conditionable(c, b) : GPDLA_OK;  // (the configuration may have changed since the lists were set)
+  if (rc || (rc = plan_records(c, b, record_class_doubles(cls, b->ntiles, false), false))) return rc;
+  if ((rc = launch_prepare(c, b, conditioned && b->fx->meanflux))) return rc;
+  if (conditioned && (rc = launch_condition_rows(c, b))) return rc;
 
   // NaN pre-fill, as process_qsos.m:74-82 does for quasars that are skipped
   HIP_TRY(hipMemsetAsync(b->d_sample_ll, 0xFF, (size_t)b->nq * b->S * sizeof(double), st));
@@ -241,6 +253,7 @@ int gpdla_batch_process(gpdla_context *c, gpdla_batch *b) try {
     if ((rc = launch_sweep(c, b, cls, f32, sa))) return rc;
   }
   if ((rc = end_timing(c, st))) return rc;
+  if (conditioned && (rc = launch_condition_mask(c, b, nullptr, b->nq, nullptr, nullptr, c->d_offset, b->S, b->d_sample_ll))) return rc;
 
   EvidenceArgs ea;
   ea.meta = b->d_meta;
@@ -418,6 +431,7 @@ extern "C" int gpdla_debug_prepared_rows(gpdla_context *c, gpdla_batch *b, int m
   if (!c || !b || b->ctx != c || !rows_out || !num_rows_out)
     return fail(GPDLA_ERR_INVALID_ARGUMENT, "null/mismatched argument");
   if (quasar < 0 || quasar >= b->nq) return fail(GPDLA_ERR_INVALID_ARGUMENT, "quasar %lld outside the batch", (long long)quasar);
+  if (b->fx && b->fx->on) return fail(GPDLA_ERR_UNSUPPORTED, "prepared rows: the batch is conditioned on fixed absorbers (gpdla_debug_conditioned_rows)");
   HIP_TRY(hipSetDevice(c->device_id));
   int rc = plan_records(c, b, b->k <= 20 ? kSlimRec : record_doubles(b->ntiles, 0), true);
   if (rc) return rc;

@@ -1012,6 +1012,40 @@ def load_refined_results(path: str) -> dict:
 
 
 # ---------------------------------------------------------------------------------------------
+# absorbers refined slot by slot
+# ---------------------------------------------------------------------------------------------
+
+_CONDITIONAL_INT = {"status": np.int32, "discovered": np.int32, "num_absorbers": np.int64, "num_start": np.int64}
+
+
+def save_conditional_results(path: str, conditional: dict, **run_metadata) -> None:
+    """What :func:`conditional.refine_conditional` returns as a ``-v7.3`` file: every array under its own name
+    ([nq x slot ...]; the per-quasar counts and ``probabilities`` as columns), integers as doubles; the history of
+    the passes is not stored.  ``run_metadata``: scalars and strings, as given."""
+    w = _MatWriter(path)
+    try:
+        for k, v in run_metadata.items():
+            w.put(k, v)
+        for k, v in conditional.items():
+            if k == "history":
+                continue
+            a = np.asarray(v, dtype=np.float64)
+            w.put(k, a.reshape(-1, 1) if a.ndim == 1 else a)
+    finally:
+        w.close()
+
+
+def load_conditional_results(path: str) -> dict:
+    """The reader of :func:`save_conditional_results`: this package's shapes and integer types again."""
+    out = {}
+    for k, v in loadmat73(path).items():
+        if k in ("num_absorbers", "num_start", "probabilities"):
+            v = _vec(v)
+        out[k] = np.asarray(v).astype(_CONDITIONAL_INT[k]) if k in _CONDITIONAL_INT else v
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
 # chunk files of a sharded run (CDDF_analysis/sbatch_reunion.py:13-63)
 # ---------------------------------------------------------------------------------------------
 

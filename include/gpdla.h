@@ -1004,6 +1004,67 @@ int gpdla_batch_refined_posteriors(gpdla_context *ctx, gpdla_batch *batch, const
  * made with the context's timing on (all groups and levels; -1 before the first). */
 double gpdla_debug_last_refine_ms(void);
 
+/* ---------------------------------------------------------------------------------------------
+ * A batch conditioned on fixed absorbers.  Additive: GPDLA_ABI_VERSION is unchanged.
+ * Single-DLA batches (uploaded without log_priors_lls), fp64, k <= 40; anything else is
+ * GPDLA_ERR_UNSUPPORTED.  Nothing of this exists in the reference; the identity it rests on is the
+ * reference's own k-DLA likelihood (multi :342-351), which multiplies mu, M and omega by the product of all k
+ * profiles.  With k - 1 absorbers held fixed, their product A is a vector per quasar; on the rows mu A, M A,
+ * omega2 A^2 the single-DLA sweep is the k-DLA likelihood as a function of the remaining absorber alone.
+ *
+ * gpdla_fixed_absorbers_validate: the checks that gpdla_batch_set_fixed_absorbers makes of its lists, in
+ * this order; the first that fails is GPDLA_ERR_INVALID_ARGUMENT, its message names the field and the quasar,
+ * and nothing is written.  offsets [num_quasars + 1] into z_dlas / log_nhis (log10 N_HI), non-decreasing, at
+ * most GPDLA_MAX_FIXED_ABSORBERS per quasar; min_z_separation finite and >= 0; every z_dla and log_nhi finite;
+ * no two fixed absorbers of one quasar closer than min_z_separation (larger - smaller < min_z_separation).
+ * Needs no GPU.
+ *
+ * gpdla_batch_set_fixed_absorbers: copies the lists (N = pow(10, log_nhi), taken by the host) and makes the
+ * batch a conditioned one.  meanflux_rows = 1: the rows are prepared as the multi-DLA driver prepares them
+ * (Lyman-series noise scaling and mean-flux suppression by the context's num_forest_lines, prev_tau_0,
+ * prev_beta), so that the sweep is the multi-DLA model's likelihood; 0: the rows of process_qsos.m.
+ * gpdla_batch_clear_fixed_absorbers makes it an ordinary batch again.  Either marks the batch unprocessed and
+ * not refined; gpdla_batch_reload clears.
+ *
+ * gpdla_batch_process on a conditioned batch: k_prepare, then per quasar with at least one fixed absorber
+ * and status 0
+ *   A_u = the product, in list order, of the instrument-broadened Lyman-series profiles (the context's
+ *         num_lines) of its fixed absorbers on its unmasked-range grid: what gpdla_batch_model_spectra
+ *         returns as map_absorption for the same list, bit for bit,
+ *   mu_u <- mu_u A_u,  omega2_u <- omega2_u (A_u A_u),  M_uc <- M_uc A_u  (c < k), each rounded once;
+ * y and nu are not touched, a masked (neutral) row stays neutral.  Records and sweep as for any batch.  Then
+ * the separation rule of multi :386-392 for one free absorber among fixed ones: sample i, whose own
+ * z_i = min_z + (max_z - min_z) offset_samples[i], gets sample_log_likelihoods_dla = -inf where
+ * max(z_i, z_f) - min(z_i, z_f) < min_z_separation for any fixed z_f.  -inf, not the reference's NaN: zero
+ * likelihood inside the separation (the refine contract's "NaN contributes 0"), which keeps the mean over S
+ * of log_likelihoods_dla defined; the reference's nanmean would renormalise by the surviving samples instead.
+ * A quasar without fixed absorbers is not touched: its results equal an unconditioned batch's bit for bit.
+ *
+ * gpdla_batch_refine on a conditioned batch: as above; the records are rebuilt from the conditioned rows,
+ * and the same rule runs on l' of each level, z'_j = z_lo + (z_hi - z_lo) u_j, before lambda is formed.
+ *
+ * What the results mean: log_likelihoods_no_dla is the likelihood of the fixed absorbers alone; every other
+ * result (evidences, posteriors, MAPs, the refined tables, their summaries) is about ONE MORE absorber given
+ * them.  gpdla_batch_download, gpdla_batch_download_refined, gpdla_batch_refined_summaries,
+ * gpdla_batch_refined_posteriors and gpdla_batch_parameter_summaries serve such a batch as they are.  The
+ * entries that prepare the batch's rows again (gpdla_batch_model_spectra, gpdla_batch_unmasked_counts,
+ * gpdla_batch_draw_mocks, gpdla_debug_prepared_rows) refuse it with GPDLA_ERR_UNSUPPORTED.
+ *
+ * gpdla_debug_conditioned_rows (test hook): k_prepare and, on a conditioned batch, the conditioning alone;
+ * then the rows (y, mu, omega2, nu) [n][4] and, if M_out is not NULL, the M rows [n][k] of one quasar on its
+ * unmasked-range grid, n = min(n_u, capacity_rows).  meanflux_rows chooses the preparation of an
+ * UNconditioned batch; a conditioned one uses its own.
+ * ------------------------------------------------------------------------------------------- */
+#define GPDLA_MAX_FIXED_ABSORBERS 8
+int gpdla_fixed_absorbers_validate(int64_t num_quasars, const int64_t *offsets, const double *z_dlas,
+                                   const double *log_nhis, double min_z_separation);
+int gpdla_batch_set_fixed_absorbers(gpdla_context *ctx, gpdla_batch *batch, const int64_t *offsets,
+                                    const double *z_dlas, const double *log_nhis, double min_z_separation,
+                                    int32_t meanflux_rows);
+int gpdla_batch_clear_fixed_absorbers(gpdla_context *ctx, gpdla_batch *batch);
+int gpdla_debug_conditioned_rows(gpdla_context *ctx, gpdla_batch *batch, int32_t meanflux_rows, int64_t quasar,
+                                 double *rows_out, double *M_out, int64_t capacity_rows, int64_t *num_rows_out);
+
 #ifdef __cplusplus
 }
 #endif
