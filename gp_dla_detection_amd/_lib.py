@@ -141,6 +141,21 @@ class ModelSpectra(C.Structure):
                 ("continuum", _dp), ("model_flux", _dp), ("status", _i32p)]
 
 
+class ModelSpectraMultiRequest(C.Structure):
+    """gpdla_model_spectra_multi_request"""
+    _fields_ = [("num_selected", C.c_int64), ("selection", _i64p), ("max_dlas", C.c_int32), ("first_model", C.c_int32),
+                ("last_model", C.c_int32), ("tables_source", C.c_int32), ("sample_log_likelihoods_dla", _dp),
+                ("base_sample_inds", _u32p), ("sample_log_likelihoods_lls", _dp), ("model_weights", _dp),
+                ("meanflux", C.c_int32), ("products", C.c_int32), ("capacity", C.c_int64)]
+
+
+class ModelSpectraMulti(C.Structure):
+    """gpdla_model_spectra_multi"""
+    _fields_ = [("offsets", _i64p), ("mean_absorption_models", _dp), ("var_absorption_models", _dp),
+                ("mean_absorption_lls", _dp), ("var_absorption_lls", _dp), ("expected_absorption", _dp),
+                ("expected_var_absorption", _dp), ("status", _i32p), ("model_flags", _u32p)]
+
+
 class MockRequest(C.Structure):
     """gpdla_mock_request"""
     _fields_ = [("seed", C.c_uint64), ("absorber_offsets", _i64p), ("absorber_z", _dp), ("absorber_nhi", _dp),
@@ -210,6 +225,8 @@ SPECTRA_MAX_ABSORBERS = 8                                   # GPDLA_SPECTRA_MAX_
 MAX_FIXED_ABSORBERS = 8                                     # GPDLA_MAX_FIXED_ABSORBERS
 SPECTRA_MAP, SPECTRA_MOMENTS, SPECTRA_CONTINUUM = 1, 2, 4   # GPDLA_SPECTRA_* product bits
 SPECTRA_WEIGHTS_NONE, SPECTRA_WEIGHTS_RESIDENT, SPECTRA_WEIGHTS_HOST = 0, 1, 2
+SPECTRA_MULTI_MODELS, SPECTRA_MULTI_AVERAGE = 1, 2            # GPDLA_SPECTRA_MULTI_* product bits
+SPECTRA_AVERAGE_UNDEFINED, SPECTRA_MULTI_FLAG_LLS = 8, 0x40000000   # status bit; model_flags bit of the sub-DLA model
 
 
 def ptr(a):
@@ -289,6 +306,10 @@ SYMBOLS = [
     ("gpdla_batch_unmasked_counts", C.c_int, [C.c_void_p, C.c_void_p, _i64p]),
     ("gpdla_batch_model_spectra", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(ModelSpectraRequest),
                                             C.POINTER(ModelSpectra)]),
+    ("gpdla_model_spectra_multi_validate", C.c_int, [C.POINTER(ModelSpectraMultiRequest), C.c_int64, C.c_int64, C.c_int,
+                                                     C.c_int, C.c_int]),
+    ("gpdla_batch_model_spectra_multi", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(ModelSpectraMultiRequest),
+                                                  C.POINTER(ModelSpectraMulti)]),
     ("gpdla_debug_profiles_ms", C.c_int, [C.c_void_p, C.c_void_p, _dp]),
     ("gpdla_model_mean", C.c_int, [C.POINTER(Model), C.c_int64, _dp, _i64p, _dp, _dp, C.c_int, C.c_int, C.c_int,
                                    C.c_double, C.c_double, _dp, C.c_int]),

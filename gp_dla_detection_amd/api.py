@@ -281,6 +281,7 @@ class Batch:
     def _fill(self, spectra, log_priors_no_dla, log_priors_dla, log_priors_lls):
         ctx = self.ctx
         self._refined = None
+        self._multi_processed = False   # process_multi() has run on the current spectra
         csr = spectra if isinstance(spectra, dict) else spectra_to_csr(spectra)
         self.num_quasars = csr["z_qsos"].size
         self.num_pixels = int(csr["offsets"][-1] - csr["offsets"][0])
@@ -463,6 +464,95 @@ class Batch:
                 out[name] = np.empty(total)
                 setattr(ms, name, out[name].ctypes.data_as(_dp))
         _lib.check(lib.gpdla_batch_model_spectra(self.ctx._h, self._h, C.byref(rq), C.byref(ms)))
+        return out
+
+    def model_spectra_multi(self, selection=None, tables="resident", model_weights=None, models=None,
+                            products=("models", "average"), meanflux: bool | None = None, sub_dla: bool = True) -> dict:
+        """The per-pixel absorption of a multi-DLA run averaged over the samples of every model and over
+        the models (gpdla_batch_model_spectra_multi; the definitions are in include/gpdla.h), on the grid
+        and in the layout of :meth:`model_spectra`.
+
+        ``tables``: ``"resident"`` -- the batch's own tables after :meth:`process_multi` -- or a dict with
+        ``sample_log_likelihoods_dla [nsel, max_dlas, S]``, ``base_sample_inds [nsel, max_dlas-1, S]``
+        (1-based, 0 = never drawn) and ``sample_log_likelihoods_lls [nsel, S]`` of the SELECTED quasars (a
+        processed file needs no second sweep); ``max_dlas`` is then the tables', and the batch may be any.
+        ``model_weights``: ``[nsel, 2 + max_dlas]`` as (null, sub-DLA, DLA(1..max_dlas)), or None: the
+        resident ``model_posteriors`` (resident tables only).  A NaN row (the reference's early exit) gives
+        NaN averages; :func:`renormalised_model_posteriors` makes weights that include such quasars.
+        ``models``: ``(first, last)`` or one model number (default: all).  ``products``: ``"models"``
+        (``mean_absorption_models`` / ``var_absorption_models [max_dlas, total]``, NaN outside ``models``, and,
+        ``sub_dla``, ``mean_absorption_lls`` / ``var_absorption_lls``) and ``"average"``
+        (``expected_absorption``, ``expected_var_absorption``).
+        Returns those with ``offsets [nsel + 1]``, ``status [nsel]`` and ``model_flags [nsel]`` (bit n-1: model
+        DLA(n) has no weight; bit 30: the sub-DLA model)."""
+        lib = self.ctx.lib
+        sel = self._selection(selection)
+        nsel, S = sel.size, self.num_samples
+        rq = _lib.ModelSpectraMultiRequest()
+        rq.num_selected = nsel
+        rq.selection = sel.ctypes.data_as(_i64p)
+        keep = [sel]
+        if isinstance(tables, str):
+            if tables != "resident":
+                raise ValueError("tables: 'resident' or a dict of host tables")
+            rq.tables_source, md = _lib.SPECTRA_WEIGHTS_RESIDENT, self.max_dlas
+        else:
+            rq.tables_source = _lib.SPECTRA_WEIGHTS_HOST
+            dla = np.ascontiguousarray(tables["sample_log_likelihoods_dla"], dtype=np.float64)
+            if dla.ndim != 3 or dla.shape[0] != nsel or dla.shape[2] != S:
+                raise _lib.GpdlaError(-1, f"sample_log_likelihoods_dla must be [nsel, max_dlas, S] = ({nsel}, max_dlas, {S}), got {dla.shape}")
+            md = dla.shape[1]
+            keep.append(dla)
+            rq.sample_log_likelihoods_dla = dla.ctypes.data_as(_dp)
+            if tables.get("sample_log_likelihoods_lls") is not None:
+                lls = np.ascontiguousarray(tables["sample_log_likelihoods_lls"], dtype=np.float64)
+                if lls.shape != (nsel, S):
+                    raise _lib.GpdlaError(-1, f"sample_log_likelihoods_lls must be [nsel, S] = {(nsel, S)}, got {lls.shape}")
+                keep.append(lls)
+                rq.sample_log_likelihoods_lls = lls.ctypes.data_as(_dp)
+            if tables.get("base_sample_inds") is not None:
+                base = np.ascontiguousarray(tables["base_sample_inds"], dtype=np.uint32)
+                if base.shape != (nsel, md - 1, S):
+                    raise _lib.GpdlaError(-1, f"base_sample_inds must be [nsel, max_dlas-1, S] = {(nsel, md - 1, S)}, got {base.shape}")
+                keep.append(base)
+                rq.base_sample_inds = base.ctypes.data_as(C.POINTER(C.c_uint32))
+        rq.max_dlas = md
+        first, last = (1, md) if models is None else ((int(models), int(models)) if np.isscalar(models) else
+                                                      (int(models[0]), int(models[-1])))
+        rq.first_model, rq.last_model = first, last
+        if model_weights is not None:
+            w = np.ascontiguousarray(model_weights, dtype=np.float64)
+            if w.shape != (nsel, 2 + md):
+                raise _lib.GpdlaError(-1, f"model_weights must be [nsel, 2 + max_dlas] = {(nsel, 2 + md)}, got {w.shape}")
+            keep.append(w)
+            rq.model_weights = w.ctypes.data_as(_dp)
+        bits = {"models": _lib.SPECTRA_MULTI_MODELS, "average": _lib.SPECTRA_MULTI_AVERAGE}
+        products = set(products)
+        rq.products = int(sum(bits[p] for p in products))
+        rq.meanflux = int(bool(self.max_dlas) if meanflux is None else bool(meanflux))
+        # refused requests never reach the device
+        _lib.check(lib.gpdla_model_spectra_multi_validate(C.byref(rq), self.num_quasars, S, int(self.ctx.has_lls_samples),
+                                                          self.max_dlas, int(self._multi_processed)))
+        total = int(self.unmasked_counts()[sel].sum())
+        rq.capacity = total
+        out = {"offsets": np.zeros(nsel + 1, dtype=np.int64), "status": np.zeros(nsel, dtype=np.int32),
+               "model_flags": np.zeros(nsel, dtype=np.uint32)}
+        ms = _lib.ModelSpectraMulti()
+        ms.offsets = out["offsets"].ctypes.data_as(_i64p)
+        ms.status = out["status"].ctypes.data_as(_i32p)
+        ms.model_flags = out["model_flags"].ctypes.data_as(C.POINTER(C.c_uint32))
+        shapes = {}
+        if "models" in products:
+            shapes.update(mean_absorption_models=(md, total), var_absorption_models=(md, total))
+            if sub_dla:
+                shapes.update(mean_absorption_lls=(total,), var_absorption_lls=(total,))
+        if "average" in products:
+            shapes.update(expected_absorption=(total,), expected_var_absorption=(total,))
+        for name, shape in shapes.items():
+            out[name] = np.empty(shape)
+            setattr(ms, name, out[name].ctypes.data_as(_dp))
+        _lib.check(lib.gpdla_batch_model_spectra_multi(self.ctx._h, self._h, C.byref(rq), C.byref(ms)))
+        del keep
         return out
 
     # ---- refined posteriors (DESIGN.md 4.18) ----
@@ -667,6 +757,7 @@ class Batch:
                 raise _lib.GpdlaError(-1, f"base_sample_inds must be [nq, max_dlas-1, S], got {base.shape}")
             base_ptr = base.ctypes.data_as(C.POINTER(C.c_uint32))
         _lib.check(self.ctx.lib.gpdla_batch_process_multi(self.ctx._h, self._h, base_ptr))
+        self._multi_processed = True
 
     @staticmethod
     def empty_results_multi(nq: int, md: int, S: int, with_samples: bool = True) -> dict:
@@ -1106,6 +1197,29 @@ def process_qsos_multiple_dlas_meanflux(model: dict, samples: dict, spectra, log
 # ----------------------------------------------------------------------------------------------
 
 MODEL_SPECTRA_ARRAYS = ("map_absorption", "mean_absorption", "var_absorption", "continuum", "model_flux")
+#: what ``multi_models`` adds: flat per-pixel arrays, and per-model planes [max_dlas, total]
+MODEL_SPECTRA_MULTI_ARRAYS = ("mean_absorption_lls", "var_absorption_lls", "expected_absorption", "expected_var_absorption")
+MODEL_SPECTRA_MULTI_PLANES = ("mean_absorption_models", "var_absorption_models")
+
+
+def renormalised_model_posteriors(results: dict) -> np.ndarray:
+    """Model weights ``[nq, 2 + max_dlas]`` as (null, sub-DLA, DLA(1..max_dlas)) from the LOG posteriors of a
+    multi-DLA run: a softmax over the finite ``log_posteriors_no_dla``, ``log_posteriors_lls`` and
+    ``log_posteriors_dla`` of each quasar, a NaN (or -inf) model getting probability 0.  The reference's early
+    exit (multi :460-464) leaves the models it did not reach NaN, and with them the whole ``model_posteriors``
+    row (:482-495); this is the row renormalised over the models that were evaluated, for a caller of
+    :meth:`Batch.model_spectra_multi` who wants those quasars in the average.  A quasar without any finite
+    log posterior keeps a NaN row."""
+    null = np.asarray(results["log_posteriors_no_dla"], dtype=np.float64).reshape(-1, 1)
+    lp = np.concatenate([null, np.asarray(results["log_posteriors_lls"], dtype=np.float64).reshape(-1, 1),
+                         np.asarray(results["log_posteriors_dla"], dtype=np.float64).reshape(null.shape[0], -1)], axis=1)
+    finite = np.isfinite(lp)
+    mx = np.where(finite, lp, -np.inf).max(axis=1, keepdims=True)
+    with np.errstate(invalid="ignore"):
+        e = np.where(finite, np.exp(np.where(finite, lp, 0.0) - np.where(np.isfinite(mx), mx, 0.0)), 0.0)
+        out = e / e.sum(axis=1, keepdims=True)
+    out[~finite.any(axis=1)] = np.nan
+    return out
 
 
 def split_cells(flat, offsets) -> list:
@@ -1161,7 +1275,8 @@ def _take_absorbers(absorbers, idx):
 def model_spectra(model: dict, samples: dict, spectra, results: dict | None = None,
                   params: Parameters | None = None, selection=None, absorbers="map", sub_dla: bool | None = None,
                   moments_sub_dla: bool = False, products=("map", "moments", "continuum"), sample_rows=None,
-                  device: int = 0, max_quasars_per_batch: int | None = None) -> dict:
+                  device: int = 0, max_quasars_per_batch: int | None = None, multi_models: bool = False,
+                  model_weights=None, multi_rows=None) -> dict:
     """Model spectra of the selected quasars of a processed run, batched like :func:`process_qsos`:
     the selected spectra are uploaded block by block and nothing is swept again -- the posterior
     weights come from the saved sample log-likelihoods.
@@ -1174,6 +1289,12 @@ def model_spectra(model: dict, samples: dict, spectra, results: dict | None = No
     for multi-DLA results).  Moments weight the DLA(1) table ``sample_log_likelihoods_dla`` (``[nq, S]``,
     or ``[nq, max_dlas, S]``), or ``sample_log_likelihoods_lls`` with ``moments_sub_dla``;
     ``sample_rows(idx) -> [len(idx), S]`` supplies the rows instead (a file streamed block by block).
+    ``multi_models``: also what :meth:`Batch.model_spectra_multi` returns for a multi-DLA run (the moments of
+    every model DLA(1 .. max_dlas) and of the sub-DLA model, and their average over the models): ``results``
+    must then carry ``base_sample_inds``, the 3-D ``sample_log_likelihoods_dla`` and ``sample_log_likelihoods_lls``
+    -- or ``multi_rows(idx)`` returns the dict of those three for quasars ``idx`` -- and ``model_weights``
+    ``[nq, 2 + max_dlas]`` over ALL quasars weighs the models (default: ``results["model_posteriors"]``;
+    :func:`renormalised_model_posteriors` includes the quasars of the reference's early exit).
     Returns ``selection``, ``offsets``, ``status`` and the flat per-pixel arrays of
     :meth:`Batch.model_spectra`, in selection order; results do not depend on the batching."""
     p = params or Parameters()
@@ -1192,6 +1313,17 @@ def model_spectra(model: dict, samples: dict, spectra, results: dict | None = No
             raise ValueError("moments need results or sample_rows")
         table = np.asarray(results["sample_log_likelihoods_lls" if moments_sub_dla else "sample_log_likelihoods_dla"])
         sample_rows = (lambda idx: table[idx]) if table.ndim == 2 else (lambda idx: table[idx, 0, :])
+    if multi_models:
+        if multi_rows is None:
+            if results is None or "base_sample_inds" not in results or np.asarray(results["sample_log_likelihoods_dla"]).ndim != 3:
+                raise ValueError("multi_models needs results with base_sample_inds and sample_log_likelihoods_dla [nq, max_dlas, S]")
+            multi_rows = lambda idx: {name: np.asarray(results[name])[idx] for name in  # noqa: E731
+                                      ("sample_log_likelihoods_dla", "base_sample_inds", "sample_log_likelihoods_lls")}
+        if model_weights is None:
+            if results is None:
+                raise ValueError("multi_models needs model_weights or results")
+            model_weights = results["model_posteriors"]
+        model_weights = np.asarray(model_weights, dtype=np.float64)
     S = np.asarray(samples["offset_samples"]).size
     longest = max([np.asarray(spectra[i]["wavelengths"]).size for i in sel], default=1)
     per = int(max_quasars_per_batch or default_batch_size(sel.size, longest, np.asarray(model["M"]).shape[1], S, 1))
@@ -1221,12 +1353,18 @@ def model_spectra(model: dict, samples: dict, spectra, results: dict | None = No
                 for name in MODEL_SPECTRA_ARRAYS:
                     if name in res:
                         parts.setdefault(name, []).append(res[name])
+                if multi_models:
+                    more = batch.model_spectra_multi(tables=multi_rows(idx), model_weights=model_weights[idx])
+                    out.setdefault("model_flags", np.zeros(sel.size, dtype=np.uint32))[lo:hi] = more["model_flags"]
+                    out["status"][lo:hi] |= more["status"]
+                    for name in MODEL_SPECTRA_MULTI_ARRAYS + MODEL_SPECTRA_MULTI_PLANES:
+                        parts.setdefault(name, []).append(more[name])
         finally:
             if batch is not None:
                 batch.close()
             ctx.close()
     for name, ps in parts.items():
-        out[name] = np.concatenate(ps)
+        out[name] = np.concatenate(ps, axis=-1)   # (the per-model planes are [max_dlas, pixels])
     return out
 
 

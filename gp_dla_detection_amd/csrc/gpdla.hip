@@ -33,6 +33,7 @@
 #include "learn_kernels.hpp"
 #include "stats_kernels.hpp"
 #include "spectra_kernels.hpp"
+#include "spectra_multi_kernels.hpp"
 #include "mock_kernels.hpp"
 #include "sample_kernels.hpp"
 #include "preload_kernels.hpp"
@@ -54,6 +55,7 @@ using namespace gpdla;
 #include "host_learn.hpp"
 #include "host_stats.hpp"
 #include "host_spectra.hpp"
+#include "host_spectra_multi.hpp"
 #include "host_mock.hpp"
 #include "host_samples.hpp"
 #include "host_preload.hpp"

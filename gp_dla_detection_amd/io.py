@@ -842,6 +842,9 @@ def load_processed_qsos(path: str) -> dict:
 # ---------------------------------------------------------------------------------------------
 
 MODEL_SPECTRA_CELLS = ("map_absorption", "mean_absorption", "var_absorption", "continuum", "model_flux")
+#: the products of a multi-DLA run's models: per-pixel cells, and cells of [pixels x max_dlas]
+MODEL_SPECTRA_MULTI_CELLS = ("mean_absorption_lls", "var_absorption_lls", "expected_absorption", "expected_var_absorption")
+MODEL_SPECTRA_MULTI_PLANE_CELLS = ("mean_absorption_models", "var_absorption_models")
 
 
 def save_model_spectra(path: str, spectra: dict, **run_metadata) -> None:
@@ -850,7 +853,10 @@ def save_model_spectra(path: str, spectra: dict, **run_metadata) -> None:
     cells ``map_z_dlas`` / ``map_log_nhis`` (when ``absorber_offsets``, ``absorber_z_dlas`` and
     ``absorber_log_nhis`` are present), and each per-pixel product as a ragged N x 1 cell array with
     one column vector per selected quasar (a quasar with no pixel in the modelled range holds an empty
-    one; an empty selection gives empty cells).  ``run_metadata``: scalars and strings, as given."""
+    one; an empty selection gives empty cells).  The products of ``multi_models`` are written beside them
+    when present: the sub-DLA and expected rows as such cells, ``mean_absorption_models`` /
+    ``var_absorption_models`` as cells of [pixels x max_dlas] matrices, ``model_flags`` as a column.
+    ``run_metadata``: scalars and strings, as given."""
     off = np.asarray(spectra["offsets"], dtype=np.int64)
     nsel = off.size - 1
     w = _MatWriter(path)
@@ -865,10 +871,16 @@ def save_model_spectra(path: str, spectra: dict, **run_metadata) -> None:
             for name, key in (("map_z_dlas", "absorber_z_dlas"), ("map_log_nhis", "absorber_log_nhis")):
                 v = np.asarray(spectra[key], dtype=np.float64)
                 w.put(name, [v[a[i]:a[i + 1]].reshape(-1, 1) for i in range(nsel)])
-        for name in MODEL_SPECTRA_CELLS:
+        for name in MODEL_SPECTRA_CELLS + MODEL_SPECTRA_MULTI_CELLS:
             if name in spectra:
                 v = np.asarray(spectra[name], dtype=np.float64)
                 w.put(name, [v[off[i]:off[i + 1]].reshape(-1, 1) for i in range(nsel)])
+        for name in MODEL_SPECTRA_MULTI_PLANE_CELLS:   # [max_dlas, total]: one [pixels x max_dlas] matrix per quasar
+            if name in spectra:
+                v = np.asarray(spectra[name], dtype=np.float64)
+                w.put(name, [np.ascontiguousarray(v[:, off[i]:off[i + 1]].T) for i in range(nsel)])
+        if "model_flags" in spectra:
+            w.put("model_flags", np.asarray(spectra["model_flags"], dtype=np.float64))
     finally:
         w.close()
 
@@ -885,6 +897,8 @@ def load_model_spectra(path: str) -> dict:
             out["offsets"] = np.concatenate([[0], np.cumsum(_vec(v).astype(np.int64))])
         elif k == "status":
             out["status"] = _vec(v).astype(np.int32)
+        elif isinstance(v, list) and k in MODEL_SPECTRA_MULTI_PLANE_CELLS:   # [pixels, max_dlas] per quasar
+            out[k] = [np.asarray(c, dtype=np.float64) for c in v]
         elif isinstance(v, list):
             out[k] = [_vec(c) for c in v]
         else:

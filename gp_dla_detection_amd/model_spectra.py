@@ -52,6 +52,39 @@ def sample_row_reader(processed: str, sub_dla: bool = False, span: int = 2048):
     return rows, f.close
 
 
+def multi_row_reader(processed: str, span: int = 2048):
+    """``rows(idx) -> dict`` of ``sample_log_likelihoods_dla [len(idx), max_dlas, S]``, ``base_sample_inds
+    [len(idx), max_dlas-1, S]`` and ``sample_log_likelihoods_lls [len(idx), S]`` over the tables of a multi-DLA
+    processed file (stored ``[max_dlas, S, nq]``, ``[max_dlas-1, S, nq]`` and ``[S, nq]``), read like
+    :func:`sample_row_reader` reads one row: what ``api.model_spectra(multi_models=True)`` streams.  ``idx``
+    ascending.  Returns ``(rows, close)``."""
+    f = hdf5.File(processed)
+    dla, lls = f["sample_log_likelihoods_dla"], f["sample_log_likelihoods_lls"]
+    if len(dla.shape) != 3:
+        f.close()
+        raise ValueError(f"{processed}: not a multi-DLA processed file (sample_log_likelihoods_dla is {len(dla.shape)}-D)")
+    md, S = dla.shape[0], dla.shape[1]
+    base = f["base_sample_inds"] if md > 1 else None
+
+    def rows(idx):
+        idx = np.asarray(idx, dtype=np.int64)
+        out = {"sample_log_likelihoods_dla": np.empty((idx.size, md, S)), "sample_log_likelihoods_lls": np.empty((idx.size, S)),
+               "base_sample_inds": np.zeros((idx.size, md - 1, S), dtype=np.uint32)}
+        i = 0
+        while i < idx.size:
+            lo = int(idx[i])
+            j = int(np.searchsorted(idx, lo + span))
+            hi = int(idx[j - 1]) + 1
+            take = idx[i:j] - lo
+            out["sample_log_likelihoods_dla"][i:j] = dla.read_slab(0, md, axis1=(0, S), axis2=(lo, hi))[:, :, take].transpose(2, 0, 1)
+            out["sample_log_likelihoods_lls"][i:j] = lls.read_slab(0, S, axis1=(lo, hi))[:, take].T
+            if base is not None:
+                out["base_sample_inds"][i:j] = base.read_slab(0, md - 1, axis1=(0, S), axis2=(lo, hi))[:, :, take].transpose(2, 0, 1)
+            i = j
+        return out
+    return rows, f.close
+
+
 def select(results: dict, p_dla: float | None, indices) -> np.ndarray:
     """Positions within the run: an explicit (sorted, unique) list, or ``p_dlas >= p_dla``."""
     if indices is not None:
@@ -62,7 +95,8 @@ def select(results: dict, p_dla: float | None, indices) -> np.ndarray:
 
 def run(preloaded: str, catalog: str, model_file: str, samples_file: str, processed: str, out: str,
         p_dla: float | None = None, indices=None, products=("map", "moments", "continuum"), multi: bool | None = None,
-        moments_sub_dla: bool = False, device: int = 0, max_quasars_per_batch: int | None = None) -> dict:
+        moments_sub_dla: bool = False, device: int = 0, max_quasars_per_batch: int | None = None,
+        multi_models: bool = False) -> dict:
     small = [k for k in ("model_posteriors", "p_dlas", "MAP_z_dlas", "MAP_log_nhis", "single_MAP_z_dlas",
                          "single_MAP_log_nhis", "test_ind")]
     results = io.loadmat73(processed, small)
@@ -81,14 +115,20 @@ def run(preloaded: str, catalog: str, model_file: str, samples_file: str, proces
     absorbers = api.map_absorbers(results, sub_dla=is_multi)
     absorbers_sel = api._take_absorbers(absorbers, sel)
     model, samples = io.load_learned_model(model_file), io.load_dla_samples(samples_file)
+    if multi_models and not is_multi:
+        raise ValueError("--multi-models needs a multi-DLA processed file")
     rows, close = sample_row_reader(processed, sub_dla=moments_sub_dla)
+    multi_rows, close_multi = multi_row_reader(processed) if multi_models else (None, lambda: None)
     try:  # the loaded list holds the selected quasars only: positions 0 .. len(sel) - 1 map to sel
         res = api.model_spectra(model, samples, spectra_sel, None, params=MultiParameters() if is_multi else Parameters(),
                                 absorbers=absorbers_sel, moments_sub_dla=moments_sub_dla, products=products,
                                 sample_rows=lambda idx: rows(sel[idx]), device=device,
-                                max_quasars_per_batch=max_quasars_per_batch)
+                                max_quasars_per_batch=max_quasars_per_batch, multi_models=multi_models,
+                                model_weights=mp[sel] if multi_models else None,
+                                multi_rows=(lambda idx: multi_rows(sel[idx])) if multi_models else None)
     finally:
         close()
+        close_multi()
     res["selection"] = sel
     res["absorber_offsets"], res["absorber_z_dlas"], res["absorber_log_nhis"] = absorbers_sel
     io.save_model_spectra(out, res, processed_file=str(processed), multi_dla=np.float64(is_multi))
@@ -103,13 +143,16 @@ def main(argv=None) -> int:
     ap.add_argument("--indices", type=str, default=None, help="comma-separated positions within the run (0-based)")
     ap.add_argument("--products", type=str, default="map,moments,continuum")
     ap.add_argument("--moments-sub-dla", action="store_true", help="weight the sub-DLA sample table")
+    ap.add_argument("--multi-models", action="store_true",
+                    help="a multi-DLA processed file: also the moments of every model DLA(1..max_dlas) and of the "
+                         "sub-DLA model, and the absorption averaged over the models by model_posteriors")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--max-quasars-per-batch", type=int, default=None)
     a = ap.parse_args(argv)
     idx = None if a.indices is None else [int(x) for x in a.indices.split(",") if x]
     res = run(a.preloaded, a.catalog, a.model, a.samples, a.processed, a.out, p_dla=a.p_dla, indices=idx,
               products=tuple(a.products.split(",")), moments_sub_dla=a.moments_sub_dla, device=a.device,
-              max_quasars_per_batch=a.max_quasars_per_batch)
+              max_quasars_per_batch=a.max_quasars_per_batch, multi_models=a.multi_models)
     print(f"wrote {a.out}: {res['selection'].size} quasars, {int(res['offsets'][-1])} grid pixels")
     return 0
 

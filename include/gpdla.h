@@ -592,7 +592,8 @@ int gpdla_stats_bootstrap_sums(int64_t num_rows, int num_columns, const double *
  *                   the batch's resident table after gpdla_batch_process / gpdla_batch_process_multi
  *                   (multi-DLA batch: model DLA(1), or the sub-DLA table with sub_dla), or row s of
  *                   the caller's host table sample_log_likelihoods[num_selected][S] -- a processed file
- *                   needs no second sweep.  Models with two or more absorbers are not averaged.
+ *                   needs no second sweep.  Models with two or more absorbers:
+ *                   gpdla_batch_model_spectra_multi.
  *  continuum, model_flux
  *                   with a = map_absorption (ones for an empty list) and the prepared rows y, mu, M,
  *                   omega2, nu of the kept pixels (meanflux != 0: with the Lyman-series suppression of
@@ -668,6 +669,89 @@ int gpdla_model_mean(const gpdla_model *model, int64_t num_items, const double *
                      const int64_t *absorber_offsets, const double *absorber_z, const double *absorber_nhi,
                      int num_voigt_lines, int num_forest_lines, int suppressed, double prev_tau_0,
                      double prev_beta, double *out, int device_id);
+
+/* ---------------------------------------------------------------------------------------------
+ * Model spectra of a multi-DLA run: the per-pixel absorption averaged over the samples of
+ * every model and over the models.  Additive: GPDLA_ABI_VERSION is unchanged.  Everything lives on the
+ * quasar's unmasked-range grid of gpdla_batch_model_spectra, in the same CSR layout; the padded
+ * wavelengths, z_i = min_z_dla + (max_z_dla - min_z_dla) offset_i, nhi_samples, the context's num_lines and
+ * the seven taps are those of mean_absorption there.
+ *
+ * Per entry s of the selection (quasar q), model n = 1 .. max_dlas, sample i = 0 .. S-1:
+ *  slots    s_1(i) = i;  s_j(i) = base_sample_inds[q][j-2][i] - 1 for j = 2 .. n  (1-based uint32,
+ *           [nq][max_dlas-1][S]: the rule of gpdla_stats_parameter_summaries)
+ *  profile  A_{n,i}(p) = Prod_{j=1..n} c_{s_j(i)}(p), c_s the instrument-BROADENED profile of sample s
+ *           (multi :342-351: a product of convolved profiles, not the convolution of a product),
+ *           multiplied in slot order
+ *  weights  w_i = exp(l_i - max l) / Sum from row sample_log_likelihoods_dla[q][n-1][.]: a NaN l_i weighs
+ *           0; a sample one of whose slots j >= 2 has base index 0 ("never drawn") is read as a NaN l_i
+ *           whatever its log-likelihood says; a row with nothing above -inf, or with a +inf entry, is
+ *           FLAGGED: NaN rows for that model, bit (n-1) of model_flags[s]
+ *  moments  mean_n(p) = Sum_i w_i A_{n,i}(p), var_n(p) = Sum_i w_i (A_{n,i}(p) - mean_n(p))^2, accumulated
+ *           as mb = Sum w b and m2 = Sum w b^2 of the absorbed fraction b = 1 - A: mean = 1 - mb, var =
+ *           max(m2 - mb^2, 0).  Model DLA(1) is mean_absorption / var_absorption of
+ *           gpdla_batch_model_spectra for the same row, bit for bit; the sub-DLA model is its sub_dla form
+ *           (lls_nhi_samples, the sub-DLA table; flagged: GPDLA_SPECTRA_MULTI_FLAG_LLS of model_flags[s])
+ *  average  with model weights P = (P_null, P_lls, P_1 .. P_md) (row s of model_weights, or the batch's
+ *           resident model_posteriors of quasar q):
+ *             Eb(p) = P_lls mb_lls(p) + Sum_n P_n mb_n(p),  Eb2(p) = P_lls m2_lls(p) + Sum_n P_n m2_n(p)
+ *           added in the order sub-DLA, DLA(1), .., DLA(md) (the null model absorbs nothing):
+ *             expected_absorption = 1 - Eb,  expected_var_absorption = max(Eb2 - Eb^2, 0)
+ *           A model with P_m == 0 is skipped even if it is flagged.  A NaN entry of P, or P_m != 0 on a
+ *           flagged model, makes the entry's two rows NaN and sets GPDLA_SPECTRA_AVERAGE_UNDEFINED in
+ *           status[s] -- the early exit of the reference leaves a whole model_posteriors row NaN, and
+ *           nothing here papers over it.
+ * A quasar without a usable sweep (status 1 or 3) has NaN rows everywhere.
+ *
+ * Sums run in a fixed order without atomics: outputs are bit-identical from run to run, for any
+ * selection order and grouping, and for the resident and the host form of the same tables.
+ * ------------------------------------------------------------------------------------------- */
+#define GPDLA_SPECTRA_MULTI_MODELS 1   /* products bit: the per-model rows and the sub-DLA rows */
+#define GPDLA_SPECTRA_MULTI_AVERAGE 2  /* expected_absorption and expected_var_absorption */
+#define GPDLA_SPECTRA_AVERAGE_UNDEFINED 8        /* status bit */
+#define GPDLA_SPECTRA_MULTI_FLAG_LLS 0x40000000u /* model_flags bit of the sub-DLA model */
+typedef struct {
+  int64_t num_selected;
+  const int64_t *selection;          /* [num_selected] quasars of the batch; NULL = 0 .. num_selected-1 */
+  int32_t max_dlas;                  /* models of the tables: 1 .. GPDLA_POSTERIOR_MAX_MODELS */
+  int32_t first_model, last_model;   /* the models whose rows are returned, 1 <= first <= last <= max_dlas */
+  int32_t tables_source;             /* GPDLA_SPECTRA_WEIGHTS_RESIDENT (after gpdla_batch_process_multi) or _HOST */
+  const double *sample_log_likelihoods_dla;  /* host: [num_selected][max_dlas][S] */
+  const uint32_t *base_sample_inds;          /* host: [num_selected][max_dlas-1][S], 1-based, 0 = never drawn;
+                                                may be NULL when max_dlas == 1 */
+  const double *sample_log_likelihoods_lls;  /* host: [num_selected][S] */
+  const double *model_weights;       /* host [num_selected][2 + max_dlas], or NULL: the resident model_posteriors */
+  int32_t meanflux;                  /* != 0: prepared rows of the mean-flux model */
+  int32_t products;                  /* GPDLA_SPECTRA_MULTI_MODELS | _AVERAGE */
+  int64_t capacity;                  /* entries of each per-pixel output plane */
+} gpdla_model_spectra_multi_request;
+typedef struct {
+  int64_t *offsets;                  /* [num_selected + 1]; required */
+  double *mean_absorption_models, *var_absorption_models; /* [max_dlas][capacity]: plane n-1 is model DLA(n); NaN
+                                                             outside first_model .. last_model; either may be NULL */
+  double *mean_absorption_lls, *var_absorption_lls;       /* [capacity] or NULL */
+  double *expected_absorption, *expected_var_absorption;  /* [capacity] or NULL */
+  int32_t *status;                   /* [num_selected] or NULL: the quasar's sweep status (0, 1, 3), with
+                                        GPDLA_SPECTRA_AVERAGE_UNDEFINED where the average is */
+  uint32_t *model_flags;             /* [num_selected] or NULL: bit n-1 = model DLA(n) has no weight */
+} gpdla_model_spectra_multi;
+
+/* The checks gpdla_batch_model_spectra_multi makes before its first device call, for a batch of num_quasars
+ * quasars uploaded for batch_max_dlas models (0: a single-DLA batch) that has (batch_processed != 0) or has
+ * not run gpdla_batch_process_multi: models outside 1 .. max_dlas, a resident source on a single-DLA batch,
+ * on a batch of another max_dlas or on one that has not been processed, host tables with a missing pointer,
+ * a host base index above num_samples, the average of host tables without model_weights, no product or an
+ * unknown one, a selection index outside the batch, no lls_nhi_samples.  Returns GPDLA_OK or
+ * GPDLA_ERR_INVALID_ARGUMENT.  Needs no GPU. */
+int gpdla_model_spectra_multi_validate(const gpdla_model_spectra_multi_request *request, int64_t num_quasars,
+                                       int64_t num_samples, int has_lls_nhi_samples, int batch_max_dlas,
+                                       int batch_processed);
+/* The selected quasars are taken in groups whose partial sums (every model's) fit 256 MiB; results do not
+ * depend on the grouping.  With gpdla_context_set_timing enabled, gpdla_context_last_sweep_ms reports the
+ * weights, moments, combine and average launches of the most recent call.  A batch conditioned on fixed
+ * absorbers is refused with GPDLA_ERR_UNSUPPORTED. */
+int gpdla_batch_model_spectra_multi(gpdla_context *ctx, gpdla_batch *batch,
+                                    const gpdla_model_spectra_multi_request *request, gpdla_model_spectra_multi *out);
 
 /* ---------------------------------------------------------------------------------------------
  * Mock spectra: one draw per quasar of a resident batch from the distribution

@@ -16,6 +16,16 @@ posteriors supplied as a host table (no sweep is run).  Reports, from device eve
 tenth quasar of the run selected, ``python -m gp_dla_detection_amd.model_spectra``'s ``run`` from the
 -v7.3 inputs and the processed file's streamed sample rows to the -v7.3 output.
 
+``--multi-models`` times the moments of the models of two or more absorbers instead:
+``--distinct`` quasars (default 16) are swept once by ``process_multi`` at ``--max-dlas`` (default 4) -- with the
+driver's own resampled base indices, or uniform random ones (``--multi-base random``: the gathered redshifts of a
+wave are then no neighbours at all) -- and a selection of ``--quasars`` entries repeating them is reduced from
+the resident tables.  Reports the per-entry time of models 2 .. max_dlas (k_spectra_weights_multi,
+k_spectra_moments_multi and their combines: gpdla_context_last_sweep_ms after Batch.model_spectra_multi), the
+per-entry time of k_spectra_moments (+ combine) for the DLA(1) rows of the SAME selection in the same process,
+their ratio, the profiles evaluated per sample (n (n + 1) / 2 - 1 summed over the models: 9 for max_dlas = 4)
+and the (entry, model) rows the kernel skipped because they carry no weight.
+
 Prints one JSON line.  Kernel times: run under rocprofv3 --kernel-trace --stats."""
 import argparse
 import ctypes as C
@@ -75,8 +85,58 @@ def files_run(nq, S):
                           finite_mean_rows=int(sum(np.isfinite(c).all() for c in gp.split_cells(out["mean_absorption"], out["offsets"]))))))
 
 
+def multi_models_run(a):
+    nq, n, S, md = a.quasars, a.pixels, a.samples, a.max_dlas
+    model = synthetic.make_model(20)
+    samples = synthetic.make_samples(S)
+    nd = min(nq, a.distinct)
+    spectra = [synthetic.make_spectrum(9000 + i, n, model, mask_fraction=0.03) for i in range(nd)]
+    sel = (np.arange(nq) % nd).astype(np.int64)
+    out = dict(mode="multi_models", entries=nq, distinct_quasars=nd, pixels=n, samples=S, max_dlas=md, base=a.multi_base,
+               libgpdla_sha256=hashlib.sha256(open(_lib.lib_path(), "rb").read()).hexdigest()[:16])
+    p = MultiParameters(max_dlas=md)
+    ctx = gp.Context(0, p)
+    try:
+        ctx.set_model(model)
+        ctx.set_samples(samples)
+        ctx.set_timing(True)
+        lp_dla = np.log(np.full((nd, md), 0.1) ** np.arange(1, md + 1))
+        batch = ctx.upload(spectra, np.full(nd, np.log(0.85)), lp_dla, np.full(nd, np.log(0.05)))
+        base = None
+        if a.multi_base == "random":
+            base = np.random.default_rng(5).integers(1, S + 1, (nd, md - 1, S)).astype(np.uint32)
+        batch.process_multi(base)
+        ctx.synchronize()
+        kw = dict(models=(2, md), products=("models",), sub_dla=False)
+        batch.model_spectra_multi(selection=sel[:8], **kw)                                              # warm-up
+        batch.model_spectra(selection=sel[:8], weights="resident", products=("moments",))
+        multi_ms, one_ms, wall_s = [], [], []
+        for _ in range(a.repeats):
+            t0 = time.perf_counter()
+            res = batch.model_spectra_multi(selection=sel, **kw)
+            wall_s.append(time.perf_counter() - t0)
+            multi_ms.append(ctx.last_sweep_ms())
+            batch.model_spectra(selection=sel, weights="resident", products=("moments",))
+            one_ms.append(ctx.last_sweep_ms())
+        batch.close()
+    finally:
+        ctx.close()
+    flagged = int(sum(bin(int(f) >> 1 & ((1 << (md - 1)) - 1)).count("1") for f in res["model_flags"]))
+    profiles = sum(range(2, md + 1))
+    m, o = float(np.median(multi_ms)), float(np.median(one_ms))
+    out.update(multi_ms=multi_ms, single_profile_ms=one_ms, multi_ms_per_entry=m / nq, single_profile_ms_per_entry=o / nq,
+               multi_over_single_profile=m / o, profiles_per_sample=profiles, ratio_per_profile=m / o / profiles,
+               flagged_rows_skipped=flagged, rows=nq * (md - 1), model_spectra_multi_call_s=float(np.median(wall_s)),
+               finite_rows=int(np.isfinite(res["mean_absorption_models"][1:]).all(axis=1).sum()))
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--multi-models", action="store_true", help="time the models of two or more absorbers (DESIGN.md 4.21)")
+    ap.add_argument("--max-dlas", type=int, default=4)
+    ap.add_argument("--distinct", type=int, default=16, help="--multi-models: quasars swept; the entries repeat them")
+    ap.add_argument("--multi-base", choices=("resampled", "random"), default="resampled")
     ap.add_argument("--files", type=int, default=0, help="time the file-to-file command on a shard of this many quasars")
     ap.add_argument("--quasars", type=int, default=1000)
     ap.add_argument("--pixels", type=int, default=1500)
@@ -87,6 +147,8 @@ def main():
     a = ap.parse_args()
     if a.files:
         return files_run(a.files, a.samples)
+    if a.multi_models:
+        return multi_models_run(a)
     nq, n, S = a.quasars, a.pixels, a.samples
     model = synthetic.make_model(20)
     samples = synthetic.make_samples(S)
