@@ -218,6 +218,20 @@ class RefinedPosteriors(C.Structure):
     _fields_ = [("model_posteriors_refined", _dp), ("p_no_dlas_refined", _dp), ("p_dlas_refined", _dp), ("refined", _i32p)]
 
 
+class PosteriorMapsRequest(C.Structure):
+    """gpdla_posterior_maps_request"""
+    _fields_ = [("num_models", C.c_int32), ("nz", C.c_int32), ("nn", C.c_int32), ("num_levels", C.c_int32),
+                ("levels", C.c_double * 8), ("mix", C.c_int32)]
+
+
+class PosteriorMaps(C.Structure):
+    """gpdla_posterior_maps"""
+    _fields_ = [("mass", _dp), ("hpd_level", _dp), ("outside", _dp), ("mode", _i32p), ("hpd_cells", _i32p),
+                ("hpd_threshold", _dp), ("intensity", _dp), ("expected_absorbers", _dp), ("status", _i32p)]
+
+
+MAPS_MAX_SIDE, MAPS_MAX_LEVELS = 64, 8                                                  # GPDLA_MAPS_MAX_*
+MAPS_UNUSABLE, MAPS_BAD_GRID, MAPS_SHORT, MAPS_BAD_WEIGHTS = 1, 4, 8, 16                # status bits
 REFINE_MAX_LEVELS, REFINE_UNUSABLE, REFINE_NOT_REFINED = 4, 1, -1   # GPDLA_REFINE_*
 POSTERIOR_MAX_MODELS, POSTERIOR_MAX_PROBABILITIES, POSTERIOR_MAX_THRESHOLDS = 4, 8, 4   # GPDLA_POSTERIOR_MAX_*
 POSTERIOR_UNUSABLE, POSTERIOR_NAN_RANGE = 1, 2                                          # status bits
@@ -342,6 +356,15 @@ SYMBOLS = [
     ("gpdla_batch_set_fixed_absorbers", C.c_int, [C.c_void_p, C.c_void_p, _i64p, _dp, _dp, C.c_double, C.c_int32]),
     ("gpdla_batch_clear_fixed_absorbers", C.c_int, [C.c_void_p, C.c_void_p]),
     ("gpdla_debug_conditioned_rows", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, _dp, _dp, C.c_int64, _i64p]),
+    ("gpdla_stats_posterior_maps", C.c_int, [C.c_int64, C.c_int64, _dp, C.c_int64, _u32p, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
+                                             _dp, C.POINTER(PosteriorMapsRequest), C.POINTER(PosteriorMaps), C.c_int]),
+    ("gpdla_batch_posterior_maps", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _i64p, C.c_int64, _dp, _dp, _dp, _dp,
+                                             _dp, C.POINTER(PosteriorMapsRequest), C.POINTER(PosteriorMaps)]),
+    ("gpdla_batch_refined_posterior_maps", C.c_int, [C.c_void_p, C.c_void_p, _i64p, C.c_int64, _dp, _dp, _dp, _dp, _dp,
+                                                     C.POINTER(PosteriorMapsRequest), C.POINTER(PosteriorMaps)]),
+    ("gpdla_posterior_maps_rows_per_launch", C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    ("gpdla_debug_last_maps_ms", C.c_double, [C.c_int]),
+    ("gpdla_debug_last_maps_launches", C.c_int64, []),
     ("gpdla_debug_near_poly", C.c_int, [C.c_int, C.c_double, _dp, _dp]),
     ("gpdla_debug_prepared_rows", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, _dp, C.c_int64, _i64p]),
     ("gpdla_debug_philox4x32_10", None, [_u32p, _u32p, _u32p]),

@@ -210,6 +210,12 @@ class Context:
         self._log_nhi_scale = [float(np.max(np.abs(samples["log_nhi_samples"]))) if samples.get("log_nhi_samples") is not None else np.nan,
                                float(np.max(np.abs(np.log10(samples["lls_nhi_samples"])))) if self.has_lls_samples else np.nan]
 
+        # ranges of log N: the default log N axis of Batch.posterior_maps (DLA table, sub-DLA table)
+        ln = samples.get("log_nhi_samples")
+        ln = np.asarray(ln, dtype=np.float64) if ln is not None else np.log10(np.asarray(samples["nhi_samples"], dtype=np.float64))
+        lls = np.log10(np.asarray(samples["lls_nhi_samples"], dtype=np.float64)) if self.has_lls_samples else np.array([np.nan])
+        self._log_nhi_range = [(float(ln.min()), float(ln.max())), (float(lls.min()), float(lls.max()))]
+
     def set_refine_points(self, u=None, v=None, num: int | None = None):
         """The unit-square point set of :meth:`Batch.refine` (gpdla_context_set_refine_points): ``u`` and
         ``v`` in [0, 1), any number of them.  Without arguments: ``num`` (default: the number of DLA samples)
@@ -671,6 +677,57 @@ class Batch:
         res = self.download_multi(with_samples=False) if self.max_dlas else self.download(with_samples=False)
         z_min, z_max = res["min_z_dlas"][sel], res["max_z_dlas"][sel]
         out = posteriors.finish(out, z_min, z_max, self.ctx._log_nhi_scale[int(bool(sub_dla))], p, t)
+        out["selection"] = sel
+        return out
+
+    # ---- posterior maps ----
+
+    def posterior_maps(self, selection=None, multi: bool = False, sub_dla: bool = False, refined: bool = False, grid=None,
+                       shape=(32, 32), levels=None, mix: bool = True, with_maps: bool = True, num_models: int | None = None,
+                       model_weights=None) -> dict:
+        """Posterior maps of (z_DLA, log N_HI) of the selected quasars from the batch's RESIDENT tables
+        (gpdla_batch_posterior_maps; ``multi`` / ``sub_dla`` as :meth:`parameter_summaries` takes them), or,
+        ``refined``, from the last level of :meth:`refine` (gpdla_batch_refined_posterior_maps).  ``grid``:
+        (gz_lo, gz_hi, gn_lo, gn_hi) for all quasars or [n, 4]; None: the search range and the log N range of
+        the table in use (``refined``: the quasar's last box).  ``mix``: the absorber intensity, weighted by
+        ``model_weights`` [n, models] or, None, by the resident model posteriors of DLA(1 ..) (p_lls for the
+        sub-DLA table, p_dla for a single-DLA batch, refined or not).  ``with_maps`` False: no per-cell
+        array of a slot leaves the device.  Returns what :func:`posteriors.posterior_maps` returns, plus
+        ``selection``."""
+        from . import posteriors
+        shape, lv = posteriors.check_maps_request(shape, posteriors.DEFAULT_LEVELS if levels is None else levels)
+        sel = self._selection(selection)
+        n = sel.size
+        if refined and (multi or sub_dla or num_models not in (None, 1)):
+            raise ValueError("refined=True: the refined table holds one single-DLA model (no multi, sub_dla or num_models)")
+        md = 1 if refined else (int(num_models) if num_models is not None else (self.max_dlas if (multi and not sub_dla) else 1))
+        # The default grid is made here and handed over, so that the grid returned is the grid used: the search
+        # range as the downloads report it (NaN for a quasar that was not processed: a bad grid).
+        if n and (sel.min() < 0 or sel.max() >= self.num_quasars):
+            raise ValueError(f"selection outside the batch of {self.num_quasars} quasars")
+        if grid is not None:
+            g = posteriors._grid_rows(grid, n)
+        elif refined:
+            g = np.ascontiguousarray(self.download_refined(sel, None, with_samples=False)["boxes"][:, -1]) if n else np.zeros((0, 4))
+        else:
+            res = self.download_multi(with_samples=False) if self.max_dlas else self.download(with_samples=False)
+            lo, hi = self.ctx._log_nhi_range[int(bool(sub_dla))]
+            g = np.ascontiguousarray(np.stack([res["min_z_dlas"][sel], res["max_z_dlas"][sel], np.full(n, lo), np.full(n, hi)], axis=1))
+        keep = posteriors._grid_columns(g)                          # (alive until the call returns)
+        cols = [_lib.ptr(c) for c in keep]
+        w = None if model_weights is None else posteriors._weights_rows(model_weights, n, md)
+        use_mix = bool(mix) or w is not None
+        out, pm = posteriors.maps_outputs(n, md, shape, len(lv), use_mix, with_maps)
+        rq = posteriors.maps_request(md, shape, lv, mix=use_mix)
+        wp = _lib.ptr(w) if w is not None else None
+        if refined:
+            _lib.check(self.ctx.lib.gpdla_batch_refined_posterior_maps(
+                self.ctx._h, self._h, sel.ctypes.data_as(_i64p), n, *cols, wp, C.byref(rq), C.byref(pm)))
+        else:
+            _lib.check(self.ctx.lib.gpdla_batch_posterior_maps(
+                self.ctx._h, self._h, int(bool(multi)), int(bool(sub_dla)), sel.ctypes.data_as(_i64p), n, *cols, wp,
+                C.byref(rq), C.byref(pm)))
+        out = posteriors.finish_maps(out, g, shape, lv)
         out["selection"] = sel
         return out
 

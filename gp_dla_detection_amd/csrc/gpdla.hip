@@ -38,6 +38,7 @@
 #include "sample_kernels.hpp"
 #include "preload_kernels.hpp"
 #include "posterior_kernels.hpp"
+#include "posterior_maps_kernels.hpp"
 #include "refine_kernels.hpp"
 #include "condition_kernels.hpp"
 #include "training_kernels.hpp"
@@ -62,5 +63,6 @@ using namespace gpdla;
 #include "host_posterior.hpp"
 #include "host_refine.hpp"
 #include "host_condition.hpp"
+#include "host_posterior_maps.hpp"
 // libgpdla_legacy.so (-DGPDLA_WITH_LEGACY): the superseded kernels and their environment switches
 #include "host_legacy.hpp"

@@ -954,6 +954,62 @@ def load_parameter_summaries(path: str) -> dict:
 
 
 # ---------------------------------------------------------------------------------------------
+# posterior maps
+# ---------------------------------------------------------------------------------------------
+
+POSTERIOR_MAPS_FIELDS = ("mass", "hpd_level", "outside", "hpd_threshold", "intensity", "expected_absorbers", "grid",
+                         "edges_z", "edges_log_nhi", "marginal_z", "marginal_log_nhi")
+POSTERIOR_MAPS_INT_FIELDS = ("mode", "hpd_cells", "status")
+
+
+def save_posterior_maps(path: str, maps: dict, **run_metadata) -> None:
+    """What :func:`posteriors.posterior_maps` / ``maps_from_processed_file`` / :meth:`api.Batch.posterior_maps`
+    return as a ``-v7.3`` file: ``quasar_ind`` (the selection, 1-based), ``levels`` and ``map_shape`` as
+    columns, every array present as MATLAB sees this package's array ([n x model x slot x nz x nn] ...);
+    ``mode`` stays the 0-based flat index cz * nn + cn (-1: none).  ``run_metadata``: scalars and strings."""
+    n = np.asarray(maps["status"]).shape[0]
+    w = _MatWriter(path)
+    try:
+        for k, v in run_metadata.items():
+            w.put(k, v)
+        w.put("quasar_ind", np.asarray(maps.get("selection", np.arange(n)), dtype=np.float64).reshape(-1, 1) + 1)
+        w.put("levels", np.asarray(maps["levels"], dtype=np.float64).reshape(-1, 1))
+        w.put("map_shape", np.asarray(maps["shape"], dtype=np.float64).reshape(-1, 1))
+        for k in POSTERIOR_MAPS_INT_FIELDS + POSTERIOR_MAPS_FIELDS:
+            if k in maps:
+                w.put(k, np.asarray(maps[k], dtype=np.float64))
+    finally:
+        w.close()
+
+
+def load_posterior_maps(path: str) -> dict:
+    """The reader of :func:`save_posterior_maps`: this package's shapes and integer types again."""
+    m = loadmat73(path)
+    nz, nn = (int(x) for x in _vec(m["map_shape"]))
+    L = _vec(m["levels"]).size
+    n = _vec(m["quasar_ind"]).size
+    md = 1 if n == 0 else int(np.asarray(m["status"]).size // n)
+    shapes = {"mass": (n, md, md, nz, nn), "hpd_level": (n, md, md, nz, nn), "outside": (n, md, md), "mode": (n, md, md),
+              "hpd_cells": (n, md, md, L), "hpd_threshold": (n, md, md, L), "intensity": (n, nz, nn),
+              "expected_absorbers": (n,), "status": (n, md), "grid": (n, 4), "edges_z": (n, nz + 1),
+              "edges_log_nhi": (n, nn + 1), "marginal_z": (n, md, md, nz), "marginal_log_nhi": (n, md, md, nn)}
+    out = {}
+    for k, v in m.items():
+        if k == "quasar_ind":
+            out["selection"] = _vec(v).astype(np.int64) - 1
+        elif k == "levels":
+            out[k] = _vec(v).astype(np.float64)
+        elif k == "map_shape":
+            out["shape"] = _vec(v).astype(np.int64)
+        elif k in shapes:   # (MATLAB drops trailing singleton axes)
+            a = np.asarray(v).reshape(shapes[k])
+            out[k] = a.astype(np.int32) if k in POSTERIOR_MAPS_INT_FIELDS else a.astype(np.float64)
+        else:
+            out[k] = v
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
 # refined absorber posteriors (DESIGN.md 4.18)
 # ---------------------------------------------------------------------------------------------
 

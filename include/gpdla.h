@@ -1149,6 +1149,112 @@ int gpdla_batch_clear_fixed_absorbers(gpdla_context *ctx, gpdla_batch *batch);
 int gpdla_debug_conditioned_rows(gpdla_context *ctx, gpdla_batch *batch, int32_t meanflux_rows, int64_t quasar,
                                  double *rows_out, double *M_out, int64_t capacity_rows, int64_t *num_rows_out);
 
+/* ---------------------------------------------------------------------------------------------
+ * Posterior maps of (z_DLA, log10 N_HI): highest posterior density (HPD) regions per (row, model, slot),
+ * and the absorber intensity averaged over the models.  Additive: GPDLA_ABI_VERSION is
+ * unchanged.  Nothing of this exists in the reference; tests/posterior_maps_restatement.py states the same
+ * in NumPy.  Every operation is rounded on its own.
+ *
+ * Per row r, model m (1 .. num_models <= GPDLA_POSTERIOR_MAX_MODELS) and slot j <= m:
+ *  - weights: exactly those of the parameter summaries above: the base-index-0 and above-S rule, w_i =
+ *    exp(l_i - max l), NaN and -inf weighing 0, T = Sum w_i summed as there.  No finite entry, or a maximum
+ *    of +inf: every output of the (row, model) is NaN (-1 for the integer outputs) and status bit 1
+ *    (GPDLA_MAPS_UNUSABLE) is set.  A sample of weight 0 does not exist for anything below.
+ *  - slot values: exactly those of the parameter summaries: z = min_z + (max_z - min_z) offset_samples[b],
+ *    log N = log_nhi_samples[b], or n_lo + (n_hi - n_lo) v[b] for the refined tables.  (A NaN min_z or max_z
+ *    makes every z NaN: all of the row's mass is outside.)
+ *  - grid: the row's (gz_lo, gz_hi, gn_lo, gn_hi) and the request's counts nz, nn, each 1 ..
+ *    GPDLA_MAPS_MAX_SIDE.  Per axis (lo, hi, n): edge e_c = lo + (hi - lo) * (c / n) for c < n, c / n a double
+ *    division, and e_n = hi itself.  The cell of v is the largest c with e_c <= v for lo <= v < hi; v == hi
+ *    is in cell n - 1; v outside [lo, hi], or NaN, is "outside".  Cells are lower-closed, the last closed.
+ *    A non-finite grid entry, hi <= lo on either axis, or a width hi - lo that overflows: every map output
+ *    of the row is NaN (-1), the row's intensity and expected_absorbers included, and status bit 4
+ *    (GPDLA_MAPS_BAD_GRID) is set.
+ *  - mass[r][m][j][cz][cn] = (Sum over the cell's samples of w_i, added in sample order) / T;
+ *    outside[r][m][j] = the same over the samples with either coordinate outside.
+ *  - ranking: the cells of positive mass by mass descending, ties by flat index cz * nn + cn ascending;
+ *    C_k = C_(k-1) + mass_(k), accumulated one after the other in rank order, C_0 = 0.
+ *  - hpd_level[cell] = C at the cell's rank, NaN for a cell of mass 0: the smallest credible mass whose
+ *    region holds the cell.  mode = the flat index of rank 1 (-1 when no cell has mass).  Per requested
+ *    credible mass p (0 .. GPDLA_MAPS_MAX_LEVELS of them, each in (0, 1), strictly increasing): hpd_cells[p]
+ *    = the smallest k with C_k >= p, hpd_threshold[p] = mass_(k): the region is {cell : mass >= threshold},
+ *    cut by index among equal masses.  If no k reaches p (too much mass outside), k is the number of
+ *    positive cells (threshold NaN when there is none) and status bit 8 (GPDLA_MAPS_SHORT) is set.
+ *  - intensity, when model weights are given: a model of weight exactly 0 is skipped, unusable or not;
+ *    s_m = mass[r][m][1][cell] + ... + mass[r][m][m][cell] in slot order from 0; intensity[r][cz][cn] = the
+ *    sum of model_weights[r][m] * s_m over the remaining models in model order from 0;
+ *    expected_absorbers[r] = the sum of the row's intensity in flat-index order from 0.  A NaN or negative
+ *    weight, or a positive weight on an unusable model, makes both NaN and sets status bit 16
+ *    (GPDLA_MAPS_BAD_WEIGHTS) in every model's status of the row (a bad grid shows as bit 4 alone).
+ * Every sum runs in the stated order without atomics of any kind: an output depends on its own row only and
+ * is bit-identical from run to run, for any selection, order and launch grouping, and for the host and the
+ * resident form of the same table.
+ *
+ * Outputs are [n][num_models][num_models] in (model, slot) order per field, NaN / -1 where slot > model:
+ * mass and hpd_level with a trailing [nz][nn], hpd_cells and hpd_threshold with a trailing [num_levels];
+ * intensity is [n][nz][nn], expected_absorbers [n], status [n][num_models] (the OR over the model's slots).
+ * Any output pointer may be NULL; with mass and hpd_level NULL no per-cell array of a slot leaves the
+ * device.  intensity / expected_absorbers without weights are GPDLA_ERR_INVALID_ARGUMENT.
+ *
+ * Every entry checks its request (counts, credible masses, the sample tables' size and finiteness, the
+ * base index range) before the device is touched and names the offending field.
+ * gpdla_stats_posterior_maps: host tables, the arguments of gpdla_stats_parameter_summaries, the four grid
+ * arrays [num_rows] and model_weights [num_rows][num_models] or NULL.
+ * gpdla_batch_posterior_maps: the resident tables as gpdla_batch_parameter_summaries reads them (multi,
+ * sub_dla, selection).  The four grid arrays [num_selected] come together or are all NULL: then z is the
+ * quasar's search range and log N the range of the sample table in use.  model_weights NULL and
+ * request->mix != 0: the resident model posteriors of DLA(1 .. num_models) (p_lls for the sub-DLA table,
+ * p_dla for a single-DLA batch).
+ * gpdla_batch_refined_posterior_maps: the last refine level, as gpdla_batch_refined_summaries reads it
+ * (num_models = 1); the default grid is the quasar's last box, the default weight the first pass's p_dla.
+ * It serves a conditioned batch as it is.
+ * gpdla_posterior_maps_rows_per_launch: the rows one launch group takes: the group's maps
+ * ([rows][num_models][num_models][nz][nn] doubles) stay within 256 MiB of device memory; 0 for counts out
+ * of range.  gpdla_debug_last_maps_ms (kernel 0: k_posterior_maps, 1: k_posterior_maps_mix, -1 where it
+ * did not run) and gpdla_debug_last_maps_launches: device time summed over the groups, and the number of
+ * groups, of the calling thread's most recent successful call (tools/bench_posterior_maps.py).
+ * ------------------------------------------------------------------------------------------- */
+#define GPDLA_MAPS_MAX_SIDE 64
+#define GPDLA_MAPS_MAX_LEVELS 8
+#define GPDLA_MAPS_UNUSABLE 1      /* status bit 1 */
+#define GPDLA_MAPS_BAD_GRID 4      /* status bit 4 */
+#define GPDLA_MAPS_SHORT 8         /* status bit 8 */
+#define GPDLA_MAPS_BAD_WEIGHTS 16  /* status bit 16 */
+typedef struct {
+  int32_t num_models;                /* 1 .. GPDLA_POSTERIOR_MAX_MODELS */
+  int32_t nz, nn;                    /* cells per axis, 1 .. GPDLA_MAPS_MAX_SIDE each */
+  int32_t num_levels;
+  double levels[GPDLA_MAPS_MAX_LEVELS];
+  int32_t mix;                       /* batch entries: with NULL model_weights, mix by the resident posteriors */
+} gpdla_posterior_maps_request;
+typedef struct {
+  double *mass, *hpd_level;          /* [n][md][md][nz][nn] */
+  double *outside;                   /* [n][md][md] */
+  int32_t *mode;                     /* [n][md][md] */
+  int32_t *hpd_cells;                /* [n][md][md][num_levels] */
+  double *hpd_threshold;             /* [n][md][md][num_levels] */
+  double *intensity;                 /* [n][nz][nn] */
+  double *expected_absorbers;        /* [n] */
+  int32_t *status;                   /* [n][md] */
+} gpdla_posterior_maps;
+int gpdla_stats_posterior_maps(int64_t num_rows, int64_t num_samples, const double *sample_log_likelihoods,
+                               int64_t row_stride, const uint32_t *base_sample_inds, const double *min_z_dlas,
+                               const double *max_z_dlas, const double *offset_samples, const double *log_nhi_samples,
+                               const double *grid_z_lo, const double *grid_z_hi, const double *grid_n_lo,
+                               const double *grid_n_hi, const double *model_weights,
+                               const gpdla_posterior_maps_request *request, gpdla_posterior_maps *outputs, int device_id);
+int gpdla_batch_posterior_maps(gpdla_context *ctx, gpdla_batch *batch, int multi, int sub_dla, const int64_t *selection,
+                               int64_t num_selected, const double *grid_z_lo, const double *grid_z_hi,
+                               const double *grid_n_lo, const double *grid_n_hi, const double *model_weights,
+                               const gpdla_posterior_maps_request *request, gpdla_posterior_maps *outputs);
+int gpdla_batch_refined_posterior_maps(gpdla_context *ctx, gpdla_batch *batch, const int64_t *selection,
+                                       int64_t num_selected, const double *grid_z_lo, const double *grid_z_hi,
+                                       const double *grid_n_lo, const double *grid_n_hi, const double *model_weights,
+                                       const gpdla_posterior_maps_request *request, gpdla_posterior_maps *outputs);
+int64_t gpdla_posterior_maps_rows_per_launch(int num_models, int nz, int nn);
+double gpdla_debug_last_maps_ms(int kernel);
+int64_t gpdla_debug_last_maps_launches(void);
+
 #ifdef __cplusplus
 }
 #endif
