@@ -369,6 +369,7 @@ SYMBOLS = [
     ("gpdla_debug_prepared_rows", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, _dp, C.c_int64, _i64p]),
     ("gpdla_debug_philox4x32_10", None, [_u32p, _u32p, _u32p]),
     ("gpdla_debug_throw", C.c_int, [C.c_int]),
+    ("gpdla_debug_slim_sweep_blocks_per_cu", C.c_int, [C.c_int, C.POINTER(C.c_int)]),
 ]
 
 _lib = None

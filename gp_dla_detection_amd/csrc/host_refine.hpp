@@ -76,8 +76,8 @@ int refine_reserve(gpdla_batch *b, int64_t Sr) {
 int launch_boxed_sweep(gpdla_context *c, gpdla_batch *b, RecordClass cls, int64_t count, const BoxedSweepArgs &args) {
   const bool three = args.num_lines == 3;
   if (cls == kRecSlim20)
-    return launch_sweep_kernel(c, three ? &k_sweep_slim_boxed<3> : &k_sweep_slim_boxed<0>, kSweepWaves * 64,
-                               (size_t)kSlimLdsDoubles * sizeof(double), kSweepWaves * kSamplesPerWave, count, args);
+    return launch_sweep_kernel(c, three ? &k_sweep_slim_boxed<3> : &k_sweep_slim_boxed<0>, kSlimWaves * 64,
+                               (size_t)kSlimLdsDoubles * sizeof(double), kSlimWaves * kSamplesPerWave, count, args);
   const size_t lds = std::max(sweep_split_slim_lds_doubles(false), kExpTab + kSplitEpilogueDoubles) * sizeof(double);
   if (lds > 160 * 1024) return fail(GPDLA_ERR_UNSUPPORTED, "split sweep needs %zu B of LDS", lds);
   return launch_sweep_kernel(c, three ? &k_sweep_split_slim<3, 0, BoxedSweepArgs> : &k_sweep_split_slim<0, 0, BoxedSweepArgs>, 512, lds,
@@ -398,5 +398,17 @@ int gpdla_batch_refined_posteriors(gpdla_context *c, gpdla_batch *b, const int64
 } GPDLA_NO_THROW
 
 double gpdla_debug_last_refine_ms(void) { return t_refine_ms; }
+
+int gpdla_debug_slim_sweep_blocks_per_cu(int kernel, int *blocks_out) try {
+  if (!blocks_out || kernel < 0 || kernel > 3)
+    return fail(GPDLA_ERR_INVALID_ARGUMENT, "gpdla_debug_slim_sweep_blocks_per_cu: kernel %d", kernel);
+  const void *const f[4] = {reinterpret_cast<const void *>(&k_sweep_slim<3>), reinterpret_cast<const void *>(&k_sweep_slim<0>),
+                            reinterpret_cast<const void *>(&k_sweep_slim_boxed<3>),
+                            reinterpret_cast<const void *>(&k_sweep_slim_boxed<0>)};
+  const size_t lds = (size_t)kSlimLdsDoubles * sizeof(double);
+  HIP_TRY(hipFuncSetAttribute(f[kernel], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_out, f[kernel], kSlimWaves * 64, lds));
+  return GPDLA_OK;
+} GPDLA_NO_THROW
 
 }  // extern "C"

@@ -184,8 +184,8 @@ int launch_sweep(gpdla_context *c, gpdla_batch *b, RecordClass cls, bool f32, co
   const bool three = args.num_lines == 3;
   if (b->k <= 20) {
     if (cls == kRecSlim20)  // vech(m m') formed inside the sweep
-      return launch_sweep_kernel(c, three ? &k_sweep_slim<3> : &k_sweep_slim<0>, kSweepWaves * 64,
-                                 (size_t)kSlimLdsDoubles * sizeof(double), kSweepWaves * kSamplesPerWave, b->nq, args);
+      return launch_sweep_kernel(c, three ? &k_sweep_slim<3> : &k_sweep_slim<0>, kSlimWaves * 64,
+                                 (size_t)kSlimLdsDoubles * sizeof(double), kSlimWaves * kSamplesPerWave, b->nq, args);
     if (!f32) return legacy_sweep<20>(c, b, args);
     // compact class: 13 w-tiles + 1 u-tile on the matrix cores, 2 + 4 columns on the VALU
     return three ? launch_sweep_expanded<float, 8, 14, 1, 8, 13, 3>(c, b, args) : launch_sweep_expanded<float, 8, 14, 1, 4, 13, 0>(c, b, args);

@@ -7,15 +7,15 @@
 // than one with a flag: k_sweep_slim<3> keeps its name, its arguments and its code.
 //
 // LINES: 3 (set_parameters.m:63, the production value: the three-line wing tier wing_sum3), or 0: the
-// line count is a.num_lines, read at run time (voigt.c:16, 266 default to all 31).  The 160 KiB of LDS
-// are spoken for, so the run-time form keeps no per-sample table of line multipliers: the wing tier
+// line count is a.num_lines, read at run time (voigt.c:16, 266 default to all 31).  The block's 80 KiB of
+// LDS are spoken for, so the run-time form keeps no per-sample table of line multipliers: the wing tier
 // takes x_j = (lambda / (1 + z_DLA)) kms_j - c / (sqrt2 sigma) with kms_j from constant memory (scalar
 // loads; wing_sum_runtime), and the rare near tier forms the reference's own multiplier (voigt.c:278-279) on the spot.
 template <int LINES>
-__global__ __launch_bounds__(512) void GPDLA_SWEEP_SLIM_KERNEL(GPDLA_SWEEP_SLIM_ARGS a) {
+__global__ __launch_bounds__(kSlimWaves * 64, 2) void GPDLA_SWEEP_SLIM_KERNEL(GPDLA_SWEEP_SLIM_ARGS a) {
   static_assert(LINES == 3 || LINES == 0, "three lines at compile time, or a run-time count");
   extern __shared__ double smem[];
-  constexpr int WAVES = kSweepWaves, CH = kSlimCH;
+  constexpr int WAVES = kSlimWaves, CH = kSlimSweepCH;
   const int64_t xj = blockIdx.x >> 3;
   const int64_t pos = 8 * (xj / a.blocks_per_quasar) + (blockIdx.x & 7);
   const int bq = (int)(xj % a.blocks_per_quasar);
@@ -26,9 +26,9 @@ __global__ __launch_bounds__(512) void GPDLA_SWEEP_SLIM_KERNEL(GPDLA_SWEEP_SLIM_
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int s = lane & 15, jj = lane >> 4;
 
-  double *ring = smem;                                   // [8][16][33]; pad slot 32 of row j: 2^(j/64)
-  double *blocks = ring + kSlimRingD;                    // [2 parities]{[8 steps][13 tiles][64], [8 steps][112]}
-  double *land = blocks + 2 * kSlimBlock + wave * kSlimLand;  // this wave's landing zone: [4][32] rows twice, [4][4] m16..19
+  double *ring = smem;                                   // [4][16][33]; pad slot 32 of row j: 2^(j/64)
+  double *blocks = ring + kSlimSweepRingD;               // [2 parities]{[4 steps][13 tiles][64], [4 steps][112]}
+  double *land = blocks + 2 * kSlimSweepBlock + wave * kSlimLand;  // this wave's landing zone: [4][32] rows twice, [4][4] m16..19
   const double *exp_pad = ring + 32;
 
   const int64_t slot0 = (int64_t)bq * (WAVES * kSamplesPerWave) + wave * kSamplesPerWave;
@@ -62,10 +62,13 @@ __global__ __launch_bounds__(512) void GPDLA_SWEEP_SLIM_KERNEL(GPDLA_SWEEP_SLIM_
   const int nchunks = (m.steps + CH - 1) / CH;
 
   const int wave_s = __builtin_amdgcn_readfirstlane(wave);
-  const uint32_t raw_lds = __builtin_amdgcn_readfirstlane(lds_address(blocks + kSlimTileBuf));
-  auto issue_chunk = [&](int c) {  // the block's copy of chunk c's raw records (7 KiB)
-    glds_chunk<CH * kSlimRec / 128, WAVES>(rec_base + (size_t)c * CH * kSlimRec,
-                                           raw_lds + (uint32_t)(c & 1) * (uint32_t)(kSlimBlock * 8), wave_s, lane);
+  // The block's copy of chunk c's raw records (3584 B): wave w brings record w, 896 B, with its lanes 0..55 -- one
+  // copy instruction per wave and chunk, and nothing lands behind the parity's raw buffer (the other parity's tiles
+  // or the landing zones follow it at once)
+  double *const raw_mine = blocks + kSlimSweepTileBuf + wave_s * kSlimRec;
+  const double *const raw_src = rec_base + (size_t)wave_s * kSlimRec + 2 * lane;
+  auto issue_chunk = [&](int c) {
+    if (lane < kSlimRec / 2) glds16(raw_src + (size_t)c * CH * kSlimRec, raw_mine + (c & 1) * kSlimSweepBlock);
   };
   // This wave's private copy of K-step `wave` of chunk c: its 4 M rows, each laid down twice
   // (lane 16 jj + p fetches doubles 2 (p & 7), 2 (p & 7) + 1 of pixel jj's row), and m[16..19] of
@@ -87,7 +90,7 @@ __global__ __launch_bounds__(512) void GPDLA_SWEEP_SLIM_KERNEL(GPDLA_SWEEP_SLIM_
   const double *a8 = s < 8 ? row : bc + (slim_pair_i(8, s) - 16);
   const double *b8 = s < 8 ? row + 8 : bc + (slim_pair_j(8, s) - 16);
   struct Operands {
-    double mc, o[2], p8;
+    double mc, o[5], p8;
   };
   auto expand_load = [&](int t0, int t1, Operands &x) {
     x.mc = row[0];
@@ -109,8 +112,8 @@ __global__ __launch_bounds__(512) void GPDLA_SWEEP_SLIM_KERNEL(GPDLA_SWEEP_SLIM_
   // pixel block of a raw record, the u tile of a raw record
   double *const xd0 = blocks + (size_t)wave_s * kSlimStepTiles + lane;
   const double *const tb0 = blocks + lane;
-  const double *const mb0 = blocks + kSlimTileBuf + kSlimExtras * jj;
-  const double *const ub0 = blocks + kSlimTileBuf + 4 * kSlimExtras + lane;
+  const double *const mb0 = blocks + kSlimSweepTileBuf + kSlimExtras * jj;
+  const double *const ub0 = blocks + kSlimSweepTileBuf + 4 * kSlimExtras + lane;
   // an address the compiler must keep in a register instead of re-deriving it in every K-step
   auto pinned = [](const double *p) {
     uint32_t v = lds_address(p);
@@ -173,44 +176,48 @@ __global__ __launch_bounds__(512) void GPDLA_SWEEP_SLIM_KERNEL(GPDLA_SWEEP_SLIM_
   glds_wait();
   __syncthreads();
 
-  // One chunk of 8 K-steps per iteration, from parity c & 1.  While it runs, this wave expands its
-  // K-step of chunk c + 1 into the other parity: two tiles in each of K-steps 0..5, one in K-step 6
-  // (operands requested before the MFMA burst, multiplied and stored behind it; unconditionally:
-  // after the last chunk the products of stale rows land in a buffer nobody reads), and in K-step
-  // 7 refills its landing zone for chunk c + 2 -- every read of it has been consumed by a multiply
-  // by then, and the 1-KiB copy lands during that K-step's burst, before the chunk's closing
-  // barrier.  Measured against the alternatives on one box (tools/ab.sh, ms per launch): this
-  // 149.6; three tiles per K-step over five K-steps 150.1; products stored before the burst 152.0;
-  // without the explicit lgkmcnt(0) at the top of a K-step 153.1; pre-expanded records (k_sweep) 149.5.
+  // One chunk of 4 K-steps per iteration, from parity c & 1.  While it runs, this wave expands its
+  // K-step of chunk c + 1 into the other parity: five tiles in K-step 0, four in each of K-steps 1
+  // and 2 (operands requested before the MFMA burst, multiplied and stored behind its 11th MFMA;
+  // unconditionally: after the last chunk the products of stale rows land in a buffer nobody reads),
+  // and in K-step 3 refills its landing zone for chunk c + 2 -- every read of it has been consumed
+  // by a multiply by then, and the 1-KiB copy lands during that K-step's burst, before the chunk's
+  // closing barrier.  Measured on the 8-wave block with 8-step chunks this kernel had before, on one
+  // box (tools/ab.sh, ms per launch): two tiles per K-step over seven K-steps 149.6; three over five
+  // 150.1; products stored before the burst 152.0; without the explicit lgkmcnt(0) at the top of a
+  // K-step 153.1; pre-expanded records (k_sweep) 149.5.
   //
   // LDS latency.  Inside a chunk the ring taps and the pixel row of K-step tt + 1 are requested in K-step tt's MFMA
   // burst, after its 11th MFMA (most B fragments are dead by then and three MFMAs, >= 190 cycles, still cover the
   // round trip), carried in n0..n6 / n01, n23 as lam_next is, and consumed behind the lgkmcnt(0) at the top of the
   // next K-step.  The reads stand behind this step's ring write: lanes jj = 2, 3 of step tt + 1 read what step tt
-  // writes.  A read for a step that does not exist (rn + 1 == m.steps) fetches valid LDS and is dropped.  K-step 0
+  // writes.  A read for a step that does not exist (rn + 1 == m.steps) fetches valid LDS and is dropped.  The taps
+  // are requested across the chunk edge in the same way (the ring is wave-private; chunk 0's behind the priming),
+  // which a chunk of 4 steps pays for: 142.3 against 143.1 ms per launch (profiles/ab_half_blocks.txt).  K-step 0
   // of a chunk has its row in the other parity's raw buffer, complete only behind the chunk barrier: it requests
-  // wavelength, taps and row itself and runs the part of the wing tier that needs the wavelength alone in front of
+  // wavelength and row itself and runs the part of the wing tier that needs the wavelength alone in front of
   // their first use.  The exp table entry is covered by the series and the weights.  Measurements and the variants
   // that lost: LABBOOK, "Taps and row under the MFMA burst".
+  // taps of the next K-step, carried across the chunk barrier too (the ring is this wave's own)
+  double n0 = my_ring[0], n1 = my_ring[1], n2 = my_ring[2], n3 = my_ring[3], n4 = my_ring[4], n5 = my_ring[5], n6 = my_ring[6];
   for (int c = 0; c < nchunks; ++c) {
     // vmcnt(0): nothing of ours is in flight (see k_sweep).  lgkmcnt(0): no LDS request is open behind the chunk
     // barrier either, but the compiler cannot know that no scalar load of the prologue is (they return out of order),
     // and would make K-step 0's first use of LDS data wait for ALL of that step's requests
     __builtin_amdgcn_s_waitcnt(0x0070);
     if (c + 1 < nchunks) issue_chunk(c + 1);
-    const int par = (c & 1) * kSlimBlock;
+    const int par = (c & 1) * kSlimSweepBlock;
     const double *tbuf = pinned(tb0 + par);
     const double *mine0 = pinned(mb0 + par);
     const double *ubuf = pinned(ub0 + par);
-    double *xdst = pinned(xd0 + (kSlimBlock - par));
+    double *xdst = pinned(xd0 + (kSlimSweepBlock - par));
     double lam_next = 0.0;
-    double n0 = 0.0, n1 = 0.0, n2 = 0.0, n3 = 0.0, n4 = 0.0, n5 = 0.0, n6 = 0.0;  // taps of the next K-step
     double2 n01 = {0.0, 0.0}, n23 = {0.0, 0.0};                                    // its pixel row
 #pragma unroll
     for (int tt = 0; tt < CH; ++tt) {
       const int rn = c * CH + tt;
-      constexpr int kXS = 7;  // K-steps that carry expansion work
-      constexpr int kT0[7] = {0, 2, 4, 6, 8, 10, 12}, kT1[7] = {2, 4, 6, 8, 10, 12, 13};
+      constexpr int kXS = 3;  // K-steps that carry expansion work
+      constexpr int kT0[3] = {0, 5, 9}, kT1[3] = {5, 9, 13};
       if (tt == kXS && c + 2 < nchunks) issue_private(c + 2);
       if (rn < m.steps) {
         const double *tl = tbuf + (size_t)tt * kSlimStepTiles;
@@ -222,8 +229,6 @@ __global__ __launch_bounds__(512) void GPDLA_SWEEP_SLIM_KERNEL(GPDLA_SWEEP_SLIM_
         double g0 = n0, g1 = n1, g2 = n2, g3 = n3, g4 = n4, g5 = n5, g6 = n6;
         double2 p01 = n01, p23 = n23;
         if (tt == 0) {
-          const double *g = my_ring + slot_p;
-          g0 = g[0], g1 = g[1], g2 = g[2], g3 = g[3], g4 = g[4], g5 = g[5], g6 = g[6];
           p01 = *reinterpret_cast<const double2 *>(mine);
           p23 = *reinterpret_cast<const double2 *>(mine + 2);
         }
@@ -308,6 +313,11 @@ __global__ __launch_bounds__(512) void GPDLA_SWEEP_SLIM_KERNEL(GPDLA_SWEEP_SLIM_
           n0 = g[0], n1 = g[1], n2 = g[2], n3 = g[3], n4 = g[4], n5 = g[5], n6 = g[6];
           n01 = *reinterpret_cast<const double2 *>(mine + kSlimRec);
           n23 = *reinterpret_cast<const double2 *>(mine + kSlimRec + 2);
+          __builtin_amdgcn_sched_barrier(0);
+        } else {  // K-step 0 of the next chunk finds its taps in registers (ring slots 0..9: 4 CH is a multiple of 16)
+          __builtin_amdgcn_sched_barrier(0);
+          const double *g = my_ring;
+          n0 = g[0], n1 = g[1], n2 = g[2], n3 = g[3], n4 = g[4], n5 = g[5], n6 = g[6];
           __builtin_amdgcn_sched_barrier(0);
         }
 #pragma unroll

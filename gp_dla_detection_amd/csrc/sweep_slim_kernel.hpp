@@ -16,9 +16,9 @@
 //        tile 9 + r    :  m[c] * m[16 + r]               r = 0..3
 //     and the last two pairs, (19, 18) and (19, 19), stay on the VALU as in k_sweep (vech columns
 //     208, 209).  Per tile: one ds_read_b64 (immediate offset 8 n), one v_mul_f64, one ds_write_b64.
-//   * Who does it.  Wave w of the block expands K-step w of the NEXT chunk (8 steps per chunk, 8
+//   * Who does it.  Wave w of the block expands K-step w of the NEXT chunk (4 steps per chunk, 4
 //     waves) into the tile buffer the block will read after the next barrier, spread over K-steps
-//     0..6 of the current chunk: 13 multiplies per wave and chunk, 1.6 per K-step, against 93 VALU
+//     0..2 of the current chunk: 13 multiplies per wave and chunk, 3.3 per K-step, against 93 VALU
 //     instructions a K-step already has.  Its 4 M rows arrive by a private 1-KiB LDS-DMA whose
 //     per-lane source addresses lay each 16-double row down twice (that is what makes (c + n) mod 16
 //     an immediate offset); nobody else reads that landing zone, so it needs no barrier.
@@ -26,10 +26,23 @@
 //     columns 0..15 in lane order, which IS the u tile) is copied whole by the block's chunk DMA,
 //     double-buffered as before.  One barrier per chunk, as before.
 //
-// LDS (exactly the CU's 160 KiB): ring 33 792 | two parities of [8 x 13 tiles of 512 B | 8 raw records
-// = 7 KiB] | 8 landing zones of 1152 B.  The 64-entry exp table lives in the ring's 128 pad slots.
-// Every per-parity address is (per-lane constant) + parity x 60 416 B: four adds per chunk, none per
-// K-step.
+// Block shape.  k_sweep_slim and k_sweep_slim_boxed run 4 waves (64 sample slots) on 4-step chunks in
+// exactly HALF of a CU's LDS, so that two blocks share a CU: the two waves of a SIMD then belong to
+// different blocks, meet no common barrier and do not enter prologue and epilogue together (the
+// fp64 MFMA and the VALU do not overlap within a SIMD; what one wave leaves idle only an independent
+// wave can fill).  __launch_bounds__(256, 2) keeps a wave at 256 registers for that.  The multi-DLA
+// kernel (sweep_multi_slim_kernel.hpp) keeps the 8-wave block and 8-step chunks of kSlimCH below.
+//
+// LDS of a block (80 KiB):
+//        0  ring: 4 waves x 16 samples x 33 doubles                                       16 896 B
+//           (the 64-entry exp table lives in the pad slot, 32, of its 64 rows)
+//   16 896  parity 0: 4 K-steps x 13 tiles of 512 B (26 624 B) | 4 raw records (3584 B)    30 208 B
+//   47 104  parity 1: the same                                                            30 208 B
+//   77 312  4 landing zones of 1152 B                                                      4 608 B
+//   81 920
+// Every per-parity address is (per-lane constant) + parity x 30 208 B: four adds per chunk, none per
+// K-step.  The raw chunk is copied record by record, wave w record w with 56 lanes: 3584 B is no
+// whole number of KiB and nothing may land behind a parity's raw buffer.
 // Results are bit-identical to k_sweep's: the same products, the same MFMA sequence per column.
 #pragma once
 #include <type_traits>
@@ -40,18 +53,30 @@ namespace gpdla {
 
 constexpr int kSlimExtras = 12;                      // doubles per pixel: y mu omega2 nu | m16..19 | p208 p209 | lam | pad
 constexpr int kSlimRec = 4 * kSlimExtras + 64;       // 112 doubles = 896 B per K-step: extras, then m[0..15] of 4 pixels
-constexpr int kSlimCH = 8;                           // K-steps per chunk = waves per block
+constexpr int kSlimCH = 8;                           // K-steps per chunk = waves per block (k_sweep_multi_slim)
 constexpr int kSlimTilesW = 13;
 constexpr int kSlimStepTiles = kSlimTilesW * 64;     // doubles of expanded tiles per K-step
-constexpr int kSlimRingD = kSweepWaves * kSamplesPerWave * kRing2;   // 4224
 constexpr int kSlimTileBuf = kSlimCH * kSlimStepTiles;               // 6656
 constexpr int kSlimRawBuf = kSlimCH * kSlimRec;                      // 896
 constexpr int kSlimLand = 4 * 32 + 4 * 4;                            // per wave: 4 doubled rows + 4 x m16..19
 constexpr int kSlimBlock = kSlimTileBuf + kSlimRawBuf;               // one parity: tiles, then raw records (7552 doubles)
-constexpr int kSlimLdsDoubles = kSlimRingD + 2 * kSlimBlock + kSweepWaves * kSlimLand;
 static_assert((kSlimBlock * 8) % 512 == 0, "both parities reachable with ds_read2st64 offsets");
-static_assert(kSlimLdsDoubles * 8 == 160 * 1024, "the slim sweep uses the whole LDS of a CU");
 static_assert((kSlimCH * kSlimRec) % 128 == 0, "a raw chunk is a whole number of KiB");
+// k_sweep_slim / k_sweep_slim_boxed: 4 waves, 4-step chunks, half a CU's LDS (see "Block shape" above)
+constexpr int kSlimWaves = 4;
+constexpr int kSlimSweepCH = 4;                                                  // K-steps per chunk = waves per block
+constexpr int kSlimSweepRingD = kSlimWaves * kSamplesPerWave * kRing2;           // 2112
+constexpr int kSlimSweepTileBuf = kSlimSweepCH * kSlimStepTiles;                 // 3328
+constexpr int kSlimSweepBlock = kSlimSweepTileBuf + kSlimSweepCH * kSlimRec;     // one parity: 3776 doubles
+constexpr int kSlimLdsDoubles = kSlimSweepRingD + 2 * kSlimSweepBlock + kSlimWaves * kSlimLand;
+static_assert(kSlimSweepCH == kSlimWaves, "wave w expands, and copies, K-step w of the next chunk");
+static_assert((kSlimSweepBlock * 8) % 512 == 0, "both parities reachable with ds_read2st64 offsets");
+static_assert(kSlimLdsDoubles * 8 == 80 * 1024, "two blocks of the slim sweep fill the LDS of a CU exactly");
+static_assert(kSlimWaves * kSamplesPerWave == kExpTab, "the exp table has one ring row's pad slot per entry");
+static_assert((kSlimSweepCH * 4) % 16 == 0, "the ring slots of a K-step depend on its place in the chunk alone");
+static_assert(kSlimRec % 2 == 0 && kSlimRec / 2 <= 64, "one wave copies one record, 16 bytes per lane");
+static_assert(kSlimWaves * EpilogueShape<13, 1>::SPP * EpilogueShape<13, 1>::stride(16) <= kSlimLdsDoubles,
+              "the epilogue's rows fit the block's LDS");
 
 // (i, j), i >= j, of column `col` of tile `tile` (see the column map above)
 __host__ __device__ constexpr int slim_pair_i(int tile, int col) {

@@ -452,6 +452,12 @@ void gpdla_debug_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uin
  * never a C++ exception (which would end MATLAB / Python).  Needs no GPU. */
 int gpdla_debug_throw(int kind);
 
+/* Test hook: what hipOccupancyMaxActiveBlocksPerMultiprocessor answers for a k <= 20 single-DLA sweep kernel
+ * at its own launch shape (256 threads, 80 KiB of dynamic LDS).  kernel: 0 = k_sweep_slim<3>, 1 =
+ * k_sweep_slim<0>, 2 = k_sweep_slim_boxed<3>, 3 = k_sweep_slim_boxed<0>.  The kernels are built for TWO blocks
+ * per compute unit: the two waves of a SIMD belong to different blocks.  Needs a GPU. */
+int gpdla_debug_slim_sweep_blocks_per_cu(int kernel, int *blocks_out);
+
 /* ---------------------------------------------------------------------------------------------
  * CDDF statistics (CDDF_analysis/calc_cddf.py, class DLACatalogue).
  *
