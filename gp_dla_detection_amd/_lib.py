@@ -156,6 +156,20 @@ class ModelSpectraMulti(C.Structure):
                 ("expected_var_absorption", _dp), ("status", _i32p), ("model_flags", _u32p)]
 
 
+class MarginalContinuumRequest(C.Structure):
+    """gpdla_marginal_continuum_request"""
+    _fields_ = [("num_selected", C.c_int64), ("selection", _i64p), ("weights_source", C.c_int32),
+                ("sample_log_likelihoods_dla", _dp), ("sample_log_likelihoods_lls", _dp), ("model_weights", _dp),
+                ("meanflux", C.c_int32), ("sample_coefficients", C.c_int32), ("capacity", C.c_int64)]
+
+
+class MarginalContinuum(C.Structure):
+    """gpdla_marginal_continuum"""
+    _fields_ = [("offsets", _i64p), ("continuum_mean", _dp), ("continuum_var", _dp), ("continuum_var_between", _dp),
+                ("coef_mean", _dp), ("coef_cov_within", _dp), ("coef_cov_between", _dp), ("sample_coefficients", _dp),
+                ("status", _i32p)]
+
+
 class MockRequest(C.Structure):
     """gpdla_mock_request"""
     _fields_ = [("seed", C.c_uint64), ("absorber_offsets", _i64p), ("absorber_z", _dp), ("absorber_nhi", _dp),
@@ -324,6 +338,9 @@ SYMBOLS = [
                                                      C.c_int, C.c_int]),
     ("gpdla_batch_model_spectra_multi", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(ModelSpectraMultiRequest),
                                                   C.POINTER(ModelSpectraMulti)]),
+    ("gpdla_marginal_continuum_validate", C.c_int, [C.POINTER(MarginalContinuumRequest), C.c_int64, C.c_int64, C.c_int]),
+    ("gpdla_batch_marginal_continuum", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(MarginalContinuumRequest),
+                                                 C.POINTER(MarginalContinuum)]),
     ("gpdla_debug_profiles_ms", C.c_int, [C.c_void_p, C.c_void_p, _dp]),
     ("gpdla_model_mean", C.c_int, [C.POINTER(Model), C.c_int64, _dp, _i64p, _dp, _dp, C.c_int, C.c_int, C.c_int,
                                    C.c_double, C.c_double, _dp, C.c_int]),

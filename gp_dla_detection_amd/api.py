@@ -561,6 +561,93 @@ class Batch:
         del keep
         return out
 
+    # ---- marginal continuum ----
+
+    def marginal_continuum(self, selection=None, weights="resident", components=("dla",), model_weights=None,
+                           meanflux: bool | None = None, sample_coefficients: bool = False) -> dict:
+        """The GP continuum of the selected quasars averaged over the absorber posterior instead of
+        conditioned on one absorber list (gpdla_batch_marginal_continuum; the definitions are in
+        include/gpdla.h): its posterior mean and variance per pixel of each quasar's unmasked-range grid,
+        in the CSR layout of :meth:`model_spectra`.
+
+        ``components``: which of ``"null"`` (no absorber), ``"sub_dla"`` (the sub-DLA sample table) and
+        ``"dla"`` (the DLA sample table; a multi-DLA batch: model DLA(1)) are mixed.
+        ``model_weights``: ``[nsel, 3]`` in the order (null, sub-DLA, DLA) -- columns of components that are
+        not listed are ignored -- or None: equal weights over the listed components.  Rows are non-negative,
+        finite and of positive sum; each is normalised by its sum.  A component of weight exactly 0 is not
+        evaluated.
+        ``weights``: ``"resident"`` (the batch's tables after :meth:`process` / :meth:`process_multi`), a host
+        array ``[nsel, S]`` of sample log-likelihoods when one sampled component is listed, or a dict
+        ``{"dla": ..., "sub_dla": ...}`` of them.
+        ``meanflux``: prepared rows of the mean-flux model (default: on for a multi-DLA batch).
+        ``sample_coefficients``: also ``sample_coefficients [nsel, S, k]``, the coefficient mean of every
+        sample of the ONE sampled component, NaN rows for samples of weight 0.
+        Returns ``offsets``, ``status``, the flat per-pixel ``continuum_mean``, ``continuum_var`` (within +
+        between) and ``continuum_var_between``, ``coef_mean [nsel, k]``, ``coef_cov_within`` and
+        ``coef_cov_between`` ``[nsel, k (k + 1) / 2]`` (packed lower triangles, row by row).  The variance is
+        that of the low-rank part of the GP: the pixel-diagonal omega term predicts nothing at an
+        unmeasured pixel and is left out, as in ``continuum`` of :meth:`model_spectra`."""
+        lib = self.ctx.lib
+        sel = self._selection(selection)
+        nsel, S, k = sel.size, self.num_samples, self.ctx.k
+        names = ("null", "sub_dla", "dla")
+        components = tuple(components)
+        if not components or any(c not in names for c in components):
+            raise ValueError(f"components: a non-empty subset of {names}")
+        listed = np.array([c in components for c in names])
+        if model_weights is None:
+            pw = np.tile(listed.astype(np.float64), (nsel, 1))
+        else:
+            pw = np.array(model_weights, dtype=np.float64)
+            if pw.shape != (nsel, 3):
+                raise _lib.GpdlaError(-1, f"model_weights must be [nsel, 3] = {(nsel, 3)}, got {pw.shape}")
+            pw[:, ~listed] = 0.0
+        pw = np.ascontiguousarray(pw)
+        rq = _lib.MarginalContinuumRequest()
+        rq.num_selected = nsel
+        rq.selection = sel.ctypes.data_as(_i64p)
+        rq.model_weights = pw.ctypes.data_as(_dp)
+        keep = [sel, pw]
+        if isinstance(weights, str):
+            if weights != "resident":
+                raise ValueError("weights: 'resident', an array [nsel, S], a dict of them or None")
+            rq.weights_source = _lib.SPECTRA_WEIGHTS_RESIDENT
+        elif weights is not None:
+            if not isinstance(weights, dict):
+                sampled = [c for c in components if c != "null"]
+                if len(sampled) != 1:
+                    raise ValueError("weights: one array serves one sampled component; pass {'dla': ..., 'sub_dla': ...}")
+                weights = {sampled[0]: weights}
+            rq.weights_source = _lib.SPECTRA_WEIGHTS_HOST
+            for name, field in (("dla", "sample_log_likelihoods_dla"), ("sub_dla", "sample_log_likelihoods_lls")):
+                if weights.get(name) is not None:
+                    w = np.ascontiguousarray(weights[name], dtype=np.float64)
+                    if w.shape != (nsel, S):
+                        raise _lib.GpdlaError(-1, f"weights[{name!r}] must be [nsel, S] = {(nsel, S)}, got {w.shape}")
+                    keep.append(w)
+                    setattr(rq, field, w.ctypes.data_as(_dp))
+        rq.meanflux = int(bool(self.max_dlas) if meanflux is None else bool(meanflux))
+        rq.sample_coefficients = int(bool(sample_coefficients))
+        # refused requests never reach the device
+        _lib.check(lib.gpdla_marginal_continuum_validate(C.byref(rq), self.num_quasars, S, int(self.ctx.has_lls_samples)))
+        total = int(self.unmasked_counts()[sel].sum())
+        rq.capacity = total
+        nb = k * (k + 1) // 2
+        out = {"offsets": np.zeros(nsel + 1, dtype=np.int64), "status": np.zeros(nsel, dtype=np.int32),
+               "continuum_mean": np.empty(total), "continuum_var": np.empty(total), "continuum_var_between": np.empty(total),
+               "coef_mean": np.empty((nsel, k)), "coef_cov_within": np.empty((nsel, nb)), "coef_cov_between": np.empty((nsel, nb))}
+        if sample_coefficients:
+            out["sample_coefficients"] = np.empty((nsel, S, k))
+        mc = _lib.MarginalContinuum()
+        mc.offsets = out["offsets"].ctypes.data_as(_i64p)
+        mc.status = out["status"].ctypes.data_as(_i32p)
+        for name in out:
+            if name not in ("offsets", "status"):
+                setattr(mc, name, out[name].ctypes.data_as(_dp))
+        _lib.check(lib.gpdla_batch_marginal_continuum(self.ctx._h, self._h, C.byref(rq), C.byref(mc)))
+        del keep
+        return out
+
     # ---- refined posteriors (DESIGN.md 4.18) ----
 
     def _selection(self, selection):
@@ -1422,6 +1509,110 @@ def model_spectra(model: dict, samples: dict, spectra, results: dict | None = No
             ctx.close()
     for name, ps in parts.items():
         out[name] = np.concatenate(ps, axis=-1)   # (the per-model planes are [max_dlas, pixels])
+    return out
+
+
+MARGINAL_CONTINUUM_ARRAYS = ("continuum_mean", "continuum_var", "continuum_var_between")
+MARGINAL_CONTINUUM_ROWS = ("coef_mean", "coef_cov_within", "coef_cov_between", "sample_coefficients")
+
+
+def posterior_model_weights(results: dict) -> np.ndarray:
+    """``[nq, 3]`` as (p_no_dlas, p_lls or 0, p_dlas) from a results dict or processed file: the model weights
+    :func:`marginal_continuum` mixes by with ``model_weights="posteriors"``.  A NaN probability weighs 0, and so does
+    a negative one (p_dlas is a difference of probabilities and can round to -1e-166)."""
+    p_no = np.asarray(results["p_no_dlas"], dtype=np.float64).reshape(-1)
+    p_lls = np.asarray(results["p_lls"], dtype=np.float64).reshape(-1) if "p_lls" in results else np.zeros(p_no.size)
+    p_dla = np.asarray(results["p_dlas"], dtype=np.float64).reshape(-1)
+    return np.maximum(np.nan_to_num(np.stack([p_no, p_lls, p_dla], axis=1), nan=0.0), 0.0)
+
+
+def marginal_continuum(model: dict, samples: dict, spectra, results: dict | None = None,
+                       params: Parameters | None = None, selection=None, components=("dla",), model_weights=None,
+                       sample_coefficients: bool = False, sample_rows=None, device: int = 0,
+                       max_quasars_per_batch: int | None = None) -> dict:
+    """The marginal continuum (:meth:`Batch.marginal_continuum`) of the selected quasars of a processed run,
+    batched like :func:`model_spectra`: nothing is swept again, the posterior weights come from the saved
+    sample log-likelihoods.
+
+    ``spectra``, ``results``, ``params``, ``selection``: as :func:`model_spectra`.  ``components``: which of
+    ``"null"``, ``"sub_dla"`` and ``"dla"`` are mixed.  ``model_weights``: ``[nq, 3]`` over ALL quasars of
+    ``spectra`` in the order (null, sub-DLA, DLA), None (equal weights over the listed components) or
+    ``"posteriors"``: (p_no_dlas, p_lls or 0, p_dlas) of ``results``, a quasar whose listed posteriors are all
+    0 or NaN falling back to equal weights.  The tables are ``sample_log_likelihoods_dla`` (``[nq, S]``, or
+    model DLA(1) of ``[nq, max_dlas, S]``) and ``sample_log_likelihoods_lls`` of ``results``;
+    ``sample_rows(idx, name) -> [len(idx), S]`` (``name`` ``"dla"`` or ``"sub_dla"``) supplies the rows
+    instead (a file streamed block by block).  Returns ``selection``, ``offsets``, ``status`` and the arrays of
+    :meth:`Batch.marginal_continuum` in selection order; results do not depend on the batching."""
+    p = params or Parameters()
+    multi = isinstance(p, MultiParameters)
+    spectra = list(spectra)
+    sel = np.arange(len(spectra), dtype=np.int64) if selection is None else np.asarray(selection, dtype=np.int64).reshape(-1)
+    components = tuple(components)
+    sampled = [c for c in components if c != "null"]
+    if isinstance(model_weights, str):
+        if model_weights != "posteriors":
+            raise ValueError("model_weights: 'posteriors', an array [nq, 3] or None")
+        if results is None:
+            raise ValueError("model_weights='posteriors' needs results")
+        model_weights = posterior_model_weights(results)
+        listed = np.array([c in components for c in ("null", "sub_dla", "dla")])
+        empty = ~(model_weights[:, listed].sum(axis=1) > 0)
+        model_weights[np.ix_(empty, listed)] = 1.0
+    elif model_weights is not None:
+        model_weights = np.asarray(model_weights, dtype=np.float64)
+    if sampled and sample_rows is None:
+        if results is None:
+            raise ValueError("a sampled component needs results or sample_rows")
+        tables = {}
+        for name, key in (("dla", "sample_log_likelihoods_dla"), ("sub_dla", "sample_log_likelihoods_lls")):
+            if name in sampled:
+                t = np.asarray(results[key])
+                tables[name] = t if t.ndim == 2 else t[:, 0, :]
+        sample_rows = lambda idx, name: tables[name][idx]  # noqa: E731
+    S = np.asarray(samples["offset_samples"]).size
+    k = np.asarray(model["M"]).shape[1]
+    longest = max([np.asarray(spectra[i]["wavelengths"]).size for i in sel], default=1)
+    per = int(max_quasars_per_batch or default_batch_size(sel.size, longest, k, S, 1))
+    out = {"selection": sel, "offsets": np.zeros(sel.size + 1, dtype=np.int64), "status": np.zeros(sel.size, dtype=np.int32)}
+    parts = {}
+    if sel.size:
+        ctx = Context(device, p)
+        batch = None
+        try:
+            ctx.set_model(model)
+            ctx.set_samples(samples)
+            md = p.max_dlas if multi else 0
+            for lo, hi in batch_blocks(sel.size, per):
+                idx = sel[lo:hi]
+                n = idx.size
+                args = ([spectra[i] for i in idx], np.zeros(n), np.zeros((n, md)) if multi else np.zeros(n),
+                        np.zeros(n) if multi else None)
+                if batch is None:
+                    batch = ctx.upload(*args)
+                else:
+                    batch.reload(*args)
+                res = batch.marginal_continuum(weights={c: np.asarray(sample_rows(idx, c), dtype=np.float64) for c in sampled} or None,
+                                               components=components,
+                                               model_weights=None if model_weights is None else model_weights[idx],
+                                               sample_coefficients=sample_coefficients)
+                out["offsets"][lo + 1:hi + 1] = out["offsets"][lo] + res["offsets"][1:]
+                out["status"][lo:hi] = res["status"]
+                for name in MARGINAL_CONTINUUM_ARRAYS + MARGINAL_CONTINUUM_ROWS:
+                    if name in res:
+                        parts.setdefault(name, []).append(res[name])
+        finally:
+            if batch is not None:
+                batch.close()
+            ctx.close()
+    nb = k * (k + 1) // 2
+    shapes = {"coef_mean": (0, k), "coef_cov_within": (0, nb), "coef_cov_between": (0, nb), "sample_coefficients": (0, S, k)}
+    for name in MARGINAL_CONTINUUM_ARRAYS:
+        out[name] = np.concatenate(parts[name]) if name in parts else np.zeros(0)
+    for name in MARGINAL_CONTINUUM_ROWS:
+        if name in parts:
+            out[name] = np.concatenate(parts[name], axis=0)
+        elif name != "sample_coefficients" or sample_coefficients:
+            out[name] = np.zeros(shapes[name])
     return out
 
 

@@ -1,0 +1,684 @@
+// marginal_continuum_kernels.hpp -- device side of the "marginal continuum" subsystem:
+// the GP posterior mean and variance of the low-rank continuum, averaged over the sample table(s) and
+// over the models instead of conditioned on one absorber list (k_spectra_continuum).
+//
+//   k_mc_contract   per (selected quasar, chunk of samples in z_DLA order): the Voigt stage of
+//                   k_spectra_moments fused with the contraction of the two per-sample weight vectors
+//                   a^2/d and a (y - a mu)/d onto [vech(m_p m_p') | m_p] on v_mfma_f64_16x16x4_f64;
+//                   writes [vech(M' diag(a^2/d) M) | M'(a r/d)] per sample to a scratch table
+//   k_mc_solve      per (selected quasar, 64 samples): B_i = I + ..., packed Cholesky, L^-1, c_i, Sigma_i =
+//                   L^-T L^-1 of every sample of weight > 0, one sample per wave; the block's weighted
+//                   partial sums of c_i, Sigma_i and c_i c_i', a not-positive-definite flag, the optional c_i row
+//   k_mc_finish     per selected quasar: the chunk partials in chunk order, the null component (a = 1: the
+//                   accumulation and solve of k_spectra_continuum, restated here so that kernel stays as it
+//                   is), the mixture over (null, sub-DLA table, DLA table), the coefficient outputs and the
+//                   three per-pixel arrays on the unmasked-range grid
+//
+// Every sum runs in a fixed order and nothing is accumulated with atomics: within a wave the samples in
+// index order, the four waves in wave order, the chunks in chunk order, the components in the order
+// (null, sub-DLA, DLA).  A block depends on its own (quasar, chunk) only, so outputs are bit-identical
+// for any selection order, any launch grouping and either source of the weights.
+#pragma once
+#include "spectra_kernels.hpp"
+
+namespace gpdla {
+
+constexpr int kMcNb = GPDLA_MAX_K * (GPDLA_MAX_K + 1) / 2;
+constexpr int kMcSolveChunk = 64;  // samples (z_DLA positions) per block of k_mc_solve
+constexpr int kMcComponents = 3;   // null, sub-DLA table, DLA table
+
+typedef double mc_d4 __attribute__((ext_vector_type(4)));
+
+// (i, j), i >= j, of entry e of a packed lower triangle stored row by row (s_B of k_spectra_continuum)
+__device__ __forceinline__ void mc_unpack(int e, int *pi, int *pj) {
+  int i = (int)((sqrt(8.0 * e + 1.0) - 1.0) * 0.5);
+  while ((i + 1) * (i + 2) / 2 <= e) ++i;
+  while (i * (i + 1) / 2 > e) --i;
+  *pi = i;
+  *pj = e - i * (i + 1) / 2;
+}
+
+// ------------------------------------------------------------------------------------------
+// k_mc_contract<RT, CPW, PT>: 256 threads, NS = 16 RT samples of one quasar (consecutive in the
+// context's z_DLA order), PT pixels a tile.
+//   Voigt stage (the arithmetic of k_spectra_moments): thread t takes sample t % NS and the sub-run
+//   of PT / (256 / NS) pixels t / NS of the tile; seven raw values in registers, the accurate tier by
+//   whole waves under __any(near).  RT = 4: a lane is a sample and a wave is a quarter of the tile.
+//   The two weights of (sample, pixel) go to LDS as the A operands, [pixel][sample].
+//   Contraction: D[sample][column] += Sum_p A[sample][p] F[p][column].  The columns are nbt = ceil(nb / 16)
+//   tiles of vech(m_p m_p') (weight a^2/d) followed by ceil(k / 16) tiles of m_p (weight a r/d); wave w owns
+//   column tiles w, w + 4, ... (CPW of them at most) for all RT row tiles.  The B operand is formed in
+//   registers from the tile's Mi rows in LDS, F = M[p][i] M[p][j]; the rows carry a 1 in column k (the
+//   m_p tiles: j = k) and a 0 in column k + 1 (padding columns).  Pixels past n_u weigh 0; a masked
+//   pixel's Mi row is 0 (k_prepare).
+// scratch[((sl * S + pos) * (nb + k)) + column], pos = the sample's position in z_DLA order.
+// A block whose samples all weigh exactly 0 (or lie past S) returns at once: k_mc_solve never reads
+// their rows.
+// ------------------------------------------------------------------------------------------
+struct McContractArgs {
+  const QuasarMeta *meta;
+  const PixelRow *pix;
+  const double *Mi;
+  const double *lam_pad;
+  const double *offset_samples, *nhi;  // nhi: nhi_samples, or lls_nhi_samples for the sub-DLA table
+  const int32_t *perm;
+  const int64_t *sel;   // [nsel]; this launch takes sel[s0 .. s0 + nsub)
+  const double *w;      // [nsel][S] of this component
+  const double *pm;     // [nsel] model weight of this component: 0 = not evaluated
+  int64_t S;
+  int32_t num_lines, k;
+  int64_t s0;
+  int32_t chunks;       // ceil(S / NS): blocks per quasar
+  double *scratch;
+};
+
+template <int RT, int CPW, int PT>
+__global__ __launch_bounds__(256) void k_mc_contract(McContractArgs a) {
+  constexpr int NS = 16 * RT, NSUB = 256 / NS, PPS = PT / NSUB, KS = GPDLA_MAX_K + 2;
+  static_assert(PPS >= 1 && PPS * NSUB == PT && PT % 4 == 0, "tile shape");
+  __shared__ double s_exp[kExpTab];
+  __shared__ double s_wt[PT * NS], s_ut[PT * NS];
+  __shared__ double s_M[PT * KS];
+  __shared__ int s_any;
+
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int64_t sl = blockIdx.x / a.chunks;
+  const int chunk = blockIdx.x - sl * a.chunks;
+  const int64_t s = a.s0 + sl;
+  const QuasarMeta m = a.meta[a.sel[s]];
+  if (m.status != 0 || a.pm[s] == 0.0) return;  // (the whole block)
+  const int smp = tid % NS, sub = tid / NS;
+  const int64_t pos = (int64_t)chunk * NS + smp;
+  const bool live = pos < a.S;
+  const int64_t i = a.perm[pos < a.S ? pos : a.S - 1];
+  const double wgt = live ? a.w[s * a.S + i] : 0.0;
+  if (tid == 0) s_any = 0;
+  for (int e = tid; e < kExpTab; e += 256) s_exp[e] = exp2((double)e * (1.0 / kExpTab));
+  __syncthreads();
+  if (wgt > 0.0) s_any = 1;
+  __syncthreads();
+  if (!s_any) return;
+
+  const int k = a.k, nb = k * (k + 1) / 2, ncol = nb + k;
+  const int nbt = (nb + 15) / 16, nct = nbt + (k + 15) / 16;
+  const int L = a.num_lines;
+  const double z_dla = m.min_z_dla + (m.max_z_dla - m.min_z_dla) * a.offset_samples[i];
+  const double c_light = g_lines.c, inv_s = g_lines.inv_sqrt2_sigma;
+  double mult[3], ms[3];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    mult[j] = g_lines.c / (g_lines.wavelength_cm[j] * (1 + z_dla)) / 1e8;  // voigt.c:278-279
+    ms[j] = mult[j] * inv_s;
+  }
+  const double cs = c_light * inv_s;
+  const double inv_opz = 1.0 / (1 + z_dla);
+  const double nscale = -a.nhi[i] * g_lines.inv_sqrt2pi_sigma * kInvSqrtPi * kExpScale;
+  const double *lam = a.lam_pad + m.lam_off;
+  const int n_pad = m.n_u + 6;
+  const double t0 = g_lines.taps[0], t1 = g_lines.taps[1], t2 = g_lines.taps[2], t3 = g_lines.taps[3],
+               t4 = g_lines.taps[4], t5 = g_lines.taps[5], t6 = g_lines.taps[6];
+
+  auto raw = [&](int P) -> double {  // voigt.c:282-291 for this thread's sample at padded pixel P (as k_spectra_moments)
+    const double lamP = lam[min(P, n_pad - 1)];
+    double total;
+    bool near = false;
+    if (L == 3) total = wing_sum3(lamP, ms[0], ms[1], ms[2], cs, &near);
+    else total = wing_sum_runtime(lamP * inv_opz, cs, L, &near);
+    if (__any(near)) {  // accurate tier, wave-uniformly
+      if (L == 3) {
+        total = 0.0;
+        for (int j = 0; j < 3; ++j) {
+          const double ax = fabs((lamP * mult[j] - c_light) * inv_s);
+          total += ax < 30.0 ? 1.7724538509055159 * g_lines.leading[j] *
+                                   near_poly(g_lines.near_poly + j * kNearLineDoubles, ax)
+                             : g_lines.cwing[j] * wing_core(ax * ax, g_lines.y2[j]);
+        }
+      } else {
+        total = total_near_at(lamP, 1 + z_dla, L);
+      }
+    }
+    return exp_table_scaled(nscale * total, s_exp);
+  };
+
+  // this lane's B-operand columns: (fi, fj) index the LDS copy of an Mi row, F = row[fi] * row[fj]
+  const int r = lane >> 4, c = lane & 15;
+  int fi[CPW], fj[CPW], ocol[CPW];
+  bool isv[CPW], valid[CPW];
+  mc_d4 acc[CPW][RT];
+#pragma unroll
+  for (int cc = 0; cc < CPW; ++cc) {
+    const int ct = wave + 4 * cc;
+    fi[cc] = fj[cc] = k + 1;
+    ocol[cc] = -1;
+    valid[cc] = ct < nct;
+    isv[cc] = ct >= nbt;
+    if (ct < nbt) {
+      const int e = ct * 16 + c;
+      if (e < nb) {
+        mc_unpack(e, &fi[cc], &fj[cc]);
+        ocol[cc] = e;
+      }
+    } else if (ct < nct) {
+      const int iv = (ct - nbt) * 16 + c;
+      if (iv < k) {
+        fi[cc] = iv;
+        fj[cc] = k;
+        ocol[cc] = nb + iv;
+      }
+    }
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) acc[cc][rt] = mc_d4{0.0, 0.0, 0.0, 0.0};
+  }
+
+  const PixelRow *pix = a.pix + m.pix_off;
+  const double *Mi = a.Mi + m.pix_off * k;
+  for (int p0 = 0; p0 < m.n_u; p0 += PT) {
+    // the Mi rows of the tile, with the 1 and the 0
+    for (int e = tid; e < PT * (k + 2); e += 256) {
+      const int pl = e / (k + 2), cm = e - pl * (k + 2);
+      const int p = p0 + pl;
+      double val = cm == k ? 1.0 : 0.0;
+      if (cm < k && p < m.n_u) val = Mi[(int64_t)p * k + cm];
+      s_M[pl * KS + cm] = val;
+    }
+    // Voigt stage and the two weights
+    const int pp = p0 + sub * PPS;
+    double a0 = raw(pp), a1 = raw(pp + 1), a2 = raw(pp + 2), a3 = raw(pp + 3), a4 = raw(pp + 4), a5 = raw(pp + 5), a6;
+#pragma unroll
+    for (int u = 0; u < PPS; ++u) {
+      a6 = raw(pp + u + 6);
+      double ab = a0 * t0;  // voigt.c:297-299, taps in ascending order
+      ab = fma(a1, t1, ab);
+      ab = fma(a2, t2, ab);
+      ab = fma(a3, t3, ab);
+      ab = fma(a4, t4, ab);
+      ab = fma(a5, t5, ab);
+      ab = fma(a6, t6, ab);
+      a0 = a1; a1 = a2; a2 = a3; a3 = a4; a4 = a5; a5 = a6;
+      const int p = pp + u;
+      double wt = 0.0, ut = 0.0;
+      if (p < m.n_u) {
+        const PixelRow row = pix[p];
+        const double d = ab * ab * row.omega2 + row.nu;
+        const double rr = row.y - ab * row.mu;
+        wt = ab * ab / d;
+        ut = ab * rr / d;
+      }
+      s_wt[(sub * PPS + u) * NS + smp] = wt;
+      s_ut[(sub * PPS + u) * NS + smp] = ut;
+    }
+    __syncthreads();
+    // contraction: PT / 4 K-steps of 4 pixels
+    for (int st = 0; st < PT / 4; ++st) {
+      const int pl = 4 * st + r;
+      double aw[RT], au[RT];
+#pragma unroll
+      for (int rt = 0; rt < RT; ++rt) {
+        aw[rt] = s_wt[pl * NS + rt * 16 + c];
+        au[rt] = s_ut[pl * NS + rt * 16 + c];
+      }
+      const double *Mrow = s_M + pl * KS;
+#pragma unroll
+      for (int cc = 0; cc < CPW; ++cc) {
+        if (!valid[cc]) continue;  // (wave-uniform)
+        const double f = Mrow[fi[cc]] * Mrow[fj[cc]];
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt)
+          acc[cc][rt] = __builtin_amdgcn_mfma_f64_16x16x4f64(isv[cc] ? au[rt] : aw[rt], f, acc[cc][rt], 0, 0, 0);
+      }
+    }
+    __syncthreads();
+  }
+  // result register rr of row tile rt: sample rt * 16 + (lane >> 4) + 4 rr, column tile's column lane & 15
+  double *out = a.scratch + (sl * a.S) * (int64_t)ncol;
+#pragma unroll
+  for (int cc = 0; cc < CPW; ++cc) {
+    if (!valid[cc] || ocol[cc] < 0) continue;
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) {
+        const int64_t po = (int64_t)chunk * NS + rt * 16 + r + 4 * rr;
+        if (po < a.S) out[po * ncol + ocol[cc]] = acc[cc][rt][rr];
+      }
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// k_mc_solve: 256 threads, the 64 consecutive z_DLA positions `chunk` of one selected quasar.  Wave 0 lists
+// the positions of weight > 0 in index order; the four waves take them round robin, a sample per
+// wave: L L' = B_i = I + scratch row (column by column, as k_spectra_continuum), X = L^-1 (lane c solves
+// column c), z = X v, c_i = X' z, Sigma_i = X' X.  A sample of weight exactly 0 is never factorised.
+// part[(sl * chunks + chunk) * (k + 2 nb)]: Sum w c_i [k] | Sum w Sigma_i [nb] | Sum w c_i c_i' [nb];
+// notpd[sl * chunks + chunk] != 0: a pivot of a sample of weight > 0 was not positive.
+// ------------------------------------------------------------------------------------------
+struct McSolveArgs {
+  const QuasarMeta *meta;
+  const int32_t *perm;
+  const int64_t *sel;
+  const double *w;      // [nsel][S]
+  const double *pm;     // [nsel]
+  int64_t S;
+  int32_t k;
+  int64_t s0;
+  int32_t chunks;       // ceil(S / kMcSolveChunk)
+  const double *scratch;
+  double *part;
+  int32_t *notpd;
+  double *sample_coef;  // [nsel][S][k] in sample order, or nullptr
+};
+
+__global__ __launch_bounds__(256) void k_mc_solve(McSolveArgs a) {
+  constexpr int kMine = (kMcNb + 63) / 64;
+  __shared__ double s_L[4][kMcNb + GPDLA_MAX_K];  // packed L, then v (then c_i)
+  __shared__ double s_X[4][kMcNb + GPDLA_MAX_K];  // packed L^-1, then z
+  __shared__ int s_live[kMcSolveChunk];
+  __shared__ int s_nlive, s_bad;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int64_t sl = blockIdx.x / a.chunks;
+  const int chunk = blockIdx.x - sl * a.chunks;
+  const int64_t s = a.s0 + sl;
+  const QuasarMeta m = a.meta[a.sel[s]];
+  const int k = a.k, nb = k * (k + 1) / 2, ncol = nb + k, plen = k + 2 * nb;
+  double *part = a.part + (sl * a.chunks + chunk) * (int64_t)plen;
+  const bool off = m.status != 0 || a.pm[s] == 0.0;
+  if (wave == 0) {
+    const int64_t pos = (int64_t)chunk * kMcSolveChunk + lane;
+    const int64_t i = a.perm[pos < a.S ? pos : a.S - 1];
+    const bool live = !off && pos < a.S && a.w[s * a.S + i] > 0.0;
+    const unsigned long long mask = __ballot(live);
+    if (live) s_live[__popcll(mask & ((1ull << lane) - 1ull))] = (int)(pos - (int64_t)chunk * kMcSolveChunk);
+    if (lane == 0) {
+      s_nlive = __popcll(mask);
+      s_bad = 0;
+    }
+    if (a.sample_coef && pos < a.S && !live)
+      for (int cidx = 0; cidx < k; ++cidx) a.sample_coef[(s * a.S + i) * k + cidx] = NAN;
+  }
+  __syncthreads();
+  const int nl = s_nlive;
+  if (nl == 0) {
+    for (int e = tid; e < plen; e += 256) part[e] = 0.0;
+    if (tid == 0) a.notpd[sl * a.chunks + chunk] = 0;
+    return;
+  }
+  // the packed entries this lane adds up: e = lane + 64 t as (ea, eb), ea >= eb
+  int ea[kMine], eb[kMine];
+  double accW[kMine], accV[kMine], accC = 0.0;
+#pragma unroll
+  for (int t = 0; t < kMine; ++t) {
+    const int e = lane + 64 * t;
+    ea[t] = eb[t] = -1;
+    accW[t] = accV[t] = 0.0;
+    if (e < nb) mc_unpack(e, &ea[t], &eb[t]);
+  }
+  double *Lw = s_L[wave], *Xw = s_X[wave];
+  double *v = Lw + nb, *z = Xw + nb;
+  bool bad = false;
+  for (int it = 0; it * 4 < nl; ++it) {
+    const int idx = it * 4 + wave;
+    const bool has = idx < nl;
+    const int64_t pos = (int64_t)chunk * kMcSolveChunk + (has ? s_live[idx] : s_live[0]);
+    const int64_t i = a.perm[pos];
+    const double wi = a.w[s * a.S + i];
+    const double *row = a.scratch + (sl * a.S + pos) * (int64_t)ncol;
+    if (has) {
+#pragma unroll
+      for (int t = 0; t < kMine; ++t)
+        if (ea[t] >= 0) Lw[lane + 64 * t] = row[lane + 64 * t] + (ea[t] == eb[t] ? 1.0 : 0.0);
+      if (lane < k) v[lane] = row[nb + lane];
+    }
+    for (int j = 0; j < k; ++j) {  // Cholesky of the packed lower triangle, column by column
+      __syncthreads();
+      if (has) {
+        const int rj = j * (j + 1) / 2;
+        double sum = Lw[rj + j];
+        for (int mm = 0; mm < j; ++mm) sum = fma(-Lw[rj + mm], Lw[rj + mm], sum);
+        if (!(sum > 0.0)) bad = true;
+        const double ljj = sqrt(sum);
+        for (int ii = j + 1 + lane; ii < k; ii += 64) {
+          const int ri = ii * (ii + 1) / 2;
+          double t = Lw[ri + j];
+          for (int mm = 0; mm < j; ++mm) t = fma(-Lw[ri + mm], Lw[rj + mm], t);
+          Lw[ri + j] = t / ljj;
+        }
+        __builtin_amdgcn_wave_barrier();
+        if (lane == 0) Lw[rj + j] = ljj;
+      }
+    }
+    __syncthreads();
+    if (has && lane < k) {  // column `lane` of X = L^-1
+      const int cx = lane;
+      Xw[cx * (cx + 1) / 2 + cx] = 1.0 / Lw[cx * (cx + 1) / 2 + cx];
+      for (int ii = cx + 1; ii < k; ++ii) {
+        const int ri = ii * (ii + 1) / 2;
+        double sum = 0.0;
+        for (int mm = cx; mm < ii; ++mm) sum = fma(Lw[ri + mm], Xw[mm * (mm + 1) / 2 + cx], sum);
+        Xw[ri + cx] = -sum / Lw[ri + ii];
+      }
+    }
+    __syncthreads();
+    if (has && lane < k) {  // z = X v
+      const int ri = lane * (lane + 1) / 2;
+      double sum = 0.0;
+      for (int mm = 0; mm <= lane; ++mm) sum = fma(Xw[ri + mm], v[mm], sum);
+      z[lane] = sum;
+    }
+    __syncthreads();
+    if (has && lane < k) {  // c_i = X' z, over v
+      double sum = 0.0;
+      for (int ii = lane; ii < k; ++ii) sum = fma(Xw[ii * (ii + 1) / 2 + lane], z[ii], sum);
+      v[lane] = sum;
+      accC += wi * sum;
+      if (a.sample_coef) a.sample_coef[(s * a.S + i) * k + lane] = sum;
+    }
+    __syncthreads();
+    if (has) {
+#pragma unroll
+      for (int t = 0; t < kMine; ++t) {
+        if (ea[t] < 0) continue;
+        double sig = 0.0;  // Sigma_i[ea][eb] = Sum_{m >= ea} X[m][ea] X[m][eb]
+        for (int mm = ea[t]; mm < k; ++mm) {
+          const int rm = mm * (mm + 1) / 2;
+          sig = fma(Xw[rm + ea[t]], Xw[rm + eb[t]], sig);
+        }
+        accW[t] += wi * sig;
+        accV[t] += wi * (v[ea[t]] * v[eb[t]]);
+      }
+    }
+    __syncthreads();
+  }
+  if (bad) s_bad = 1;
+  // the four waves in wave order
+#pragma unroll
+  for (int t = 0; t < kMine; ++t)
+    if (ea[t] >= 0) {
+      Lw[lane + 64 * t] = accW[t];
+      Xw[lane + 64 * t] = accV[t];
+    }
+  if (lane < k) v[lane] = accC;
+  __syncthreads();
+  for (int e = tid; e < plen; e += 256) {
+    double sum;
+    if (e < k) {
+      sum = s_L[0][nb + e];
+      for (int wv = 1; wv < 4; ++wv) sum += s_L[wv][nb + e];
+    } else if (e < k + nb) {
+      sum = s_L[0][e - k];
+      for (int wv = 1; wv < 4; ++wv) sum += s_L[wv][e - k];
+    } else {
+      sum = s_X[0][e - k - nb];
+      for (int wv = 1; wv < 4; ++wv) sum += s_X[wv][e - k - nb];
+    }
+    part[e] = sum;
+  }
+  if (tid == 0) a.notpd[sl * a.chunks + chunk] = s_bad;
+}
+
+// ------------------------------------------------------------------------------------------
+// k_mc_finish: one block per selected quasar of a launch group.
+//   sampled component m (sub-DLA table, DLA table) of weight p_m > 0: cbar_m, W_m, S_m = Sum w c c' from
+//   the chunk partials in chunk order; the null component of weight p_0 > 0: B_0, v_0 accumulated, factorised
+//   and solved as k_spectra_continuum does with a = 1, Sigma_0 = B_0^-1 through L^-1, S_0 = c_0 c_0';
+//   c = Sum p_m cbar_m, W = Sum p_m W_m, V = Sum p_m S_m - c c' in component order.
+//   continuum_mean = mu + m_p' c, continuum_var = m_p' (W + V) m_p, continuum_var_between = m_p' V m_p at all n_u
+//   pixels, m_p interpolated (and suppressed) as k_spectra_continuum does.  The pixel-diagonal omega term
+//   is left out as there.
+// status: the quasar's prepare status (1, 3: NaN rows); 4 = some B not positive definite (NaN rows);
+// a component of weight > 0 whose weight row has no weights: NaN rows, status 0.
+// ------------------------------------------------------------------------------------------
+struct McFinishArgs {
+  const QuasarMeta *meta;
+  const PixelRow *pix;
+  const double *Mi;
+  const double *lam_pad;
+  const double *z_qsos;
+  const int64_t *sel;
+  const int64_t *out_off;
+  ModelDev model;
+  double lya_wavelength, prev_tau_0, prev_beta;
+  int32_t meanflux, num_forest_lines;
+  const double *pw;            // [nsel][3] normalised model weights (null, sub-DLA, DLA)
+  const int32_t *flag[2];      // [nsel] of the sub-DLA and the DLA weight rows, or nullptr
+  const double *part[2];       // [nsub][chunks][k + 2 nb], or nullptr
+  const int32_t *notpd[2];     // [nsub][chunks]
+  int64_t s0;
+  int32_t chunks;
+  double *mean, *var, *var_between;           // flat, out_off
+  double *coef_mean, *cov_within, *cov_between;  // [nsel][k], [nsel][nb], [nsel][nb]
+  int32_t *status;                            // [nsel]
+};
+
+constexpr int kMcPixTile = 64;
+
+__global__ __launch_bounds__(256) void k_mc_finish(McFinishArgs a) {
+  __shared__ double s_B[kMcNb + GPDLA_MAX_K];  // null component: packed B / L, then v (then c_0)
+  __shared__ double s_X[kMcNb];                // null component: L^-1
+  __shared__ double s_c[GPDLA_MAX_K], s_W[kMcNb], s_V[kMcNb];
+  __shared__ double s_wt[kContTile], s_ut[kContTile];
+  __shared__ double s_m[kMcPixTile][GPDLA_MAX_K + 1], s_mu[kMcPixTile];
+  __shared__ double s_piv;
+  __shared__ int s_pd, s_none;
+  const int tid = threadIdx.x;
+  const int64_t sl = blockIdx.x, s = a.s0 + sl;
+  const int64_t q = a.sel[s];
+  const QuasarMeta m = a.meta[q];
+  const int k = a.model.k, G = a.model.G, nb = k * (k + 1) / 2, plen = k + 2 * nb;
+  double *o_mean = a.mean + a.out_off[s], *o_var = a.var + a.out_off[s], *o_btw = a.var_between + a.out_off[s];
+  double *o_c = a.coef_mean + s * k, *o_W = a.cov_within + s * nb, *o_V = a.cov_between + s * nb;
+  if (m.status != 0) {
+    for (int p = tid; p < m.n_u; p += 256) o_mean[p] = o_var[p] = o_btw[p] = NAN;
+    for (int e = tid; e < nb; e += 256) o_W[e] = o_V[e] = NAN;
+    for (int e = tid; e < k; e += 256) o_c[e] = NAN;
+    if (tid == 0) a.status[s] = m.status;
+    return;
+  }
+  const double p0 = a.pw[s * 3];
+  for (int e = tid; e < nb; e += 256) s_W[e] = s_V[e] = 0.0;
+  for (int e = tid; e < k; e += 256) s_c[e] = 0.0;
+  if (tid == 0) {
+    s_pd = 1;
+    s_none = 0;
+  }
+  __syncthreads();
+
+  if (p0 > 0.0) {  // the null component: k_spectra_continuum with a = 1
+    const PixelRow *pix = a.pix + m.pix_off;
+    const double *Mi = a.Mi + m.pix_off * k;
+    constexpr int kMine = (kMcNb + GPDLA_MAX_K + 255) / 256;
+    int ei[kMine], ej[kMine];
+    double acc[kMine];
+#pragma unroll
+    for (int t = 0; t < kMine; ++t) {
+      const int e = tid + 256 * t;
+      acc[t] = 0.0;
+      ei[t] = ej[t] = -1;
+      if (e < nb) mc_unpack(e, &ei[t], &ej[t]);
+      else if (e < nb + k) ei[t] = e - nb;
+    }
+    for (int pt0 = 0; pt0 < m.n_u; pt0 += kContTile) {
+      if (tid < kContTile) {
+        const int p = pt0 + tid;
+        double wt = 0.0, ut = 0.0;
+        if (p < m.n_u) {
+          const PixelRow row = pix[p];
+          const double ab = 1.0;
+          const double d = ab * ab * row.omega2 + row.nu;
+          const double r = row.y - ab * row.mu;
+          wt = ab * ab / d;
+          ut = ab * r / d;
+        }
+        s_wt[tid] = wt;
+        s_ut[tid] = ut;
+      }
+      __syncthreads();
+      const int np = min(kContTile, m.n_u - pt0);
+#pragma unroll
+      for (int t = 0; t < kMine; ++t) {
+        if (ei[t] < 0) continue;
+        const double *Mp = Mi + (int64_t)pt0 * k;
+        double sum = acc[t];
+        if (ej[t] >= 0)
+          for (int p = 0; p < np; ++p) sum = fma(Mp[p * k + ei[t]] * s_wt[p], Mp[p * k + ej[t]], sum);
+        else
+          for (int p = 0; p < np; ++p) sum = fma(Mp[p * k + ei[t]], s_ut[p], sum);
+        acc[t] = sum;
+      }
+      __syncthreads();
+    }
+#pragma unroll
+    for (int t = 0; t < kMine; ++t)
+      if (ei[t] >= 0) s_B[tid + 256 * t] = acc[t] + ((ej[t] == ei[t]) ? 1.0 : 0.0);
+    __syncthreads();
+    double *v = s_B + nb;
+    for (int j = 0; j < k; ++j) {
+      const int rj = j * (j + 1) / 2;
+      __syncthreads();
+      if (tid == 0) {
+        double sum = s_B[rj + j];
+        for (int mm = 0; mm < j; ++mm) sum = fma(-s_B[rj + mm], s_B[rj + mm], sum);
+        if (!(sum > 0.0)) s_pd = 0;
+        const double ljj = sqrt(sum);
+        s_B[rj + j] = ljj;
+        s_piv = ljj;
+      }
+      __syncthreads();
+      const double ljj = s_piv;
+      for (int i = j + 1 + tid; i < k; i += 256) {
+        const int ri = i * (i + 1) / 2;
+        double sum = s_B[ri + j];
+        for (int mm = 0; mm < j; ++mm) sum = fma(-s_B[ri + mm], s_B[rj + mm], sum);
+        s_B[ri + j] = sum / ljj;
+      }
+    }
+    __syncthreads();
+    if (tid == 0) {  // c_0 = L'^-1 L^-1 v
+      for (int i = 0; i < k; ++i) {
+        const int ri = i * (i + 1) / 2;
+        double zi = v[i];
+        for (int mm = 0; mm < i; ++mm) zi = fma(-s_B[ri + mm], v[mm], zi);
+        v[i] = zi / s_B[ri + i];
+      }
+      for (int i = k - 1; i >= 0; --i) {
+        double ci = v[i];
+        for (int mm = i + 1; mm < k; ++mm) ci = fma(-s_B[mm * (mm + 1) / 2 + i], v[mm], ci);
+        v[i] = ci / s_B[i * (i + 1) / 2 + i];
+      }
+    }
+    if (tid >= 64 && tid < 64 + k) {  // column cx of X = L^-1 (another wave than the substitution's)
+      const int cx = tid - 64;
+      s_X[cx * (cx + 1) / 2 + cx] = 1.0 / s_B[cx * (cx + 1) / 2 + cx];
+      for (int ii = cx + 1; ii < k; ++ii) {
+        const int ri = ii * (ii + 1) / 2;
+        double sum = 0.0;
+        for (int mm = cx; mm < ii; ++mm) sum = fma(s_B[ri + mm], s_X[mm * (mm + 1) / 2 + cx], sum);
+        s_X[ri + cx] = -sum / s_B[ri + ii];
+      }
+    }
+    __syncthreads();
+    for (int e = tid; e < nb; e += 256) {
+      int ia, ib;
+      mc_unpack(e, &ia, &ib);
+      double sig = 0.0;
+      for (int mm = ia; mm < k; ++mm) {
+        const int rm = mm * (mm + 1) / 2;
+        sig = fma(s_X[rm + ia], s_X[rm + ib], sig);
+      }
+      s_W[e] += p0 * sig;
+      s_V[e] += p0 * (v[ia] * v[ib]);
+    }
+    for (int e = tid; e < k; e += 256) s_c[e] += p0 * v[e];
+    __syncthreads();
+  }
+
+  for (int comp = 0; comp < 2; ++comp) {  // the sub-DLA table, then the DLA table
+    const double pm = a.pw[s * 3 + 1 + comp];
+    if (!(pm > 0.0)) continue;
+    if (a.flag[comp][s] != 0) {
+      if (tid == 0) s_none = 1;
+      continue;
+    }
+    const int64_t first = sl * a.chunks;
+    const int nch = a.chunks;
+    for (int e = tid; e < plen; e += 256) {
+      double sum = 0.0;
+      for (int ch = 0; ch < nch; ++ch) sum += a.part[comp][(first + ch) * plen + e];
+      if (e < k) s_c[e] += pm * sum;
+      else if (e < k + nb) s_W[e - k] += pm * sum;
+      else s_V[e - k - nb] += pm * sum;
+    }
+    for (int ch = tid; ch < a.chunks; ch += 256)
+      if (a.notpd[comp][first + ch] != 0) s_pd = 0;
+  }
+  __syncthreads();
+  for (int e = tid; e < nb; e += 256) {
+    int ia, ib;
+    mc_unpack(e, &ia, &ib);
+    s_V[e] = s_V[e] - s_c[ia] * s_c[ib];
+  }
+  __syncthreads();
+  const bool ok = s_pd != 0 && s_none == 0;
+  for (int e = tid; e < nb; e += 256) {
+    o_W[e] = ok ? s_W[e] : NAN;
+    o_V[e] = ok ? s_V[e] : NAN;
+  }
+  for (int e = tid; e < k; e += 256) o_c[e] = ok ? s_c[e] : NAN;
+  if (tid == 0) a.status[s] = s_pd ? 0 : 4;
+
+  // the three per-pixel arrays: the interpolation of k_prepare (process_qsos.m:138-139, multi :287-288)
+  const double *lam = a.lam_pad + m.lam_off + 3;
+  const double z_qso = a.z_qsos[q];
+  for (int pt0 = 0; pt0 < m.n_u; pt0 += kMcPixTile) {
+    __syncthreads();
+    for (int e = tid; e < kMcPixTile * (k + 1); e += 256) {
+      const int pl = e / (k + 1), cm = e - pl * (k + 1);
+      const int p = min(pt0 + pl, m.n_u - 1);
+      const double wl = lam[p];
+      const double rest = wl / (1 + z_qso);
+      int lo = 0, hi = G - 1;
+      if (rest >= a.model.rest[G - 1]) lo = G - 2;
+      else if (rest > a.model.rest[0]) {
+        while (hi - lo > 1) {
+          const int mid = (lo + hi) >> 1;
+          if (a.model.rest[mid] <= rest) lo = mid; else hi = mid;
+        }
+      }
+      const double t = (rest - a.model.rest[lo]) / (a.model.rest[lo + 1] - a.model.rest[lo]);
+      if (cm == k) {
+        s_mu[pl] = a.model.mu[lo] + (a.model.mu[lo + 1] - a.model.mu[lo]) * t;
+      } else {
+        const double m0 = a.model.M[lo + (int64_t)cm * G], m1 = a.model.M[lo + 1 + (int64_t)cm * G];
+        s_m[pl][cm] = m0 + (m1 - m0) * t;
+      }
+    }
+    __syncthreads();
+    if (tid < kMcPixTile && pt0 + tid < m.n_u) {
+      const int p = pt0 + tid;
+      const double mf = a.meanflux ? spectra_mean_flux(lam[p], z_qso, a.lya_wavelength, a.prev_tau_0, a.prev_beta, a.num_forest_lines)
+                                   : 1.0;
+      double *mp = s_m[tid];
+      for (int cm = 0; cm < k; ++cm) mp[cm] = mp[cm] * mf;
+      double val = s_mu[tid];
+      if (a.meanflux) val = val * mf;
+      for (int cm = 0; cm < k; ++cm) val = fma(mp[cm], s_c[cm], val);
+      double qt = 0.0, qb = 0.0;  // m' (W + V) m and m' V m over the packed triangles, row by row
+      for (int ia = 0; ia < k; ++ia) {
+        const int ra = ia * (ia + 1) / 2;
+        double rt = 0.0, rb = 0.0;
+        for (int ib = 0; ib < ia; ++ib) {
+          rt = fma(s_W[ra + ib] + s_V[ra + ib], mp[ib], rt);
+          rb = fma(s_V[ra + ib], mp[ib], rb);
+        }
+        rt = 2.0 * rt + (s_W[ra + ia] + s_V[ra + ia]) * mp[ia];
+        rb = 2.0 * rb + s_V[ra + ia] * mp[ia];
+        qt = fma(rt, mp[ia], qt);
+        qb = fma(rb, mp[ia], qb);
+      }
+      o_mean[p] = ok ? val : NAN;
+      o_var[p] = ok ? fmax(qt, 0.0) : NAN;
+      o_btw[p] = ok ? fmax(qb, 0.0) : NAN;
+    }
+  }
+}
+
+}  // namespace gpdla

@@ -885,6 +885,41 @@ def save_model_spectra(path: str, spectra: dict, **run_metadata) -> None:
         w.close()
 
 
+#: the marginal continuum: per-pixel cells, and [n x columns] matrices
+MARGINAL_CONTINUUM_CELLS = ("continuum_mean", "continuum_var", "continuum_var_between")
+MARGINAL_CONTINUUM_MATRICES = ("coef_mean", "coef_cov_within", "coef_cov_between", "model_weights")
+
+
+def save_marginal_continuum(path: str, mc: dict, **run_metadata) -> None:
+    """What :func:`api.marginal_continuum` returns as a ``-v7.3`` file, in the layout of
+    :func:`save_model_spectra`: ``quasar_ind`` (1-based), ``num_pixels`` and ``status`` as columns, the three
+    per-pixel arrays as ragged N x 1 cell arrays, ``coef_mean`` [N x k], ``coef_cov_within`` and
+    ``coef_cov_between`` [N x k (k + 1) / 2] (packed lower triangles, row by row) and, when present,
+    ``model_weights`` [N x 3] as matrices and ``sample_coefficients`` as a cell of [S x k] matrices.
+    :func:`load_model_spectra` reads it."""
+    off = np.asarray(mc["offsets"], dtype=np.int64)
+    nsel = off.size - 1
+    w = _MatWriter(path)
+    try:
+        for k, v in run_metadata.items():
+            w.put(k, v)
+        w.put("quasar_ind", np.asarray(mc.get("selection", np.arange(nsel)), dtype=np.float64) + 1)
+        w.put("num_pixels", np.diff(off).astype(np.float64))
+        w.put("status", np.asarray(mc.get("status", np.zeros(nsel)), dtype=np.float64))
+        for name in MARGINAL_CONTINUUM_CELLS:
+            if name in mc:
+                v = np.asarray(mc[name], dtype=np.float64)
+                w.put(name, [v[off[i]:off[i + 1]].reshape(-1, 1) for i in range(nsel)])
+        for name in MARGINAL_CONTINUUM_MATRICES:
+            if name in mc:
+                w.put(name, np.ascontiguousarray(mc[name], dtype=np.float64))
+        if "sample_coefficients" in mc:
+            v = np.asarray(mc["sample_coefficients"], dtype=np.float64)
+            w.put("sample_coefficients", [np.ascontiguousarray(v[i]) for i in range(nsel)])
+    finally:
+        w.close()
+
+
 def load_model_spectra(path: str) -> dict:
     """The reader of :func:`save_model_spectra`: ``selection`` (0-based), ``offsets``, ``status``, every
     stored product as a LIST of per-quasar vectors, the absorbers as lists, the metadata as stored."""
@@ -897,7 +932,7 @@ def load_model_spectra(path: str) -> dict:
             out["offsets"] = np.concatenate([[0], np.cumsum(_vec(v).astype(np.int64))])
         elif k == "status":
             out["status"] = _vec(v).astype(np.int32)
-        elif isinstance(v, list) and k in MODEL_SPECTRA_MULTI_PLANE_CELLS:   # [pixels, max_dlas] per quasar
+        elif isinstance(v, list) and k in MODEL_SPECTRA_MULTI_PLANE_CELLS + ("sample_coefficients",):   # matrices per quasar
             out[k] = [np.asarray(c, dtype=np.float64) for c in v]
         elif isinstance(v, list):
             out[k] = [_vec(c) for c in v]

@@ -135,6 +135,39 @@ def run(preloaded: str, catalog: str, model_file: str, samples_file: str, proces
     return res
 
 
+def run_marginal_continuum(preloaded: str, catalog: str, model_file: str, samples_file: str, processed: str, out: str,
+                           p_dla: float | None = None, indices=None, components=("dla",), model_weights="posteriors",
+                           multi: bool | None = None, device: int = 0, max_quasars_per_batch: int | None = None) -> dict:
+    """``--marginal-continuum``: :func:`api.marginal_continuum` of the selected quasars of a processed file, its
+    sample tables streamed like the moments' rows, written by :func:`io.save_marginal_continuum`.
+    ``model_weights``: ``"posteriors"`` (p_no_dlas, p_lls or 0, p_dlas of the file) or ``"equal"``."""
+    small = ["model_posteriors", "p_dlas", "p_no_dlas", "p_lls", "test_ind"]
+    results = {k: np.asarray(v, dtype=np.float64).reshape(-1) if k.startswith("p_") else v
+               for k, v in io.loadmat73(processed, small).items()}
+    is_multi = np.asarray(results["model_posteriors"]).shape[1] > 2 if multi is None else bool(multi)
+    sel = select(results, p_dla, indices)
+    z_qsos = np.asarray(io.load_catalog(catalog, ("z_qsos",))["z_qsos"], dtype=np.float64)
+    test_ind = np.asarray(results["test_ind"]).reshape(-1).astype(bool) if "test_ind" in results else None
+    run_pos = np.flatnonzero(test_ind) if test_ind is not None else np.arange(z_qsos.size)
+    spectra_sel = io.load_preloaded_qsos(preloaded, z_qsos, run_pos[sel])
+    model, samples = io.load_learned_model(model_file), io.load_dla_samples(samples_file)
+    components = tuple(components)
+    readers = {name: sample_row_reader(processed, sub_dla=name == "sub_dla") for name in components if name != "null"}
+    res_sel = {k: v[sel] for k, v in results.items() if k.startswith("p_")}
+    try:  # the loaded list holds the selected quasars only: positions 0 .. len(sel) - 1 map to sel
+        res = api.marginal_continuum(model, samples, spectra_sel, res_sel, params=MultiParameters() if is_multi else Parameters(),
+                                     components=components, model_weights="posteriors" if model_weights == "posteriors" else None,
+                                     sample_rows=lambda idx, name: readers[name][0](sel[idx]), device=device,
+                                     max_quasars_per_batch=max_quasars_per_batch)
+    finally:
+        for _, close in readers.values():
+            close()
+    res["selection"] = sel
+    io.save_marginal_continuum(out, res, processed_file=str(processed), multi_dla=np.float64(is_multi),
+                               components=",".join(components))
+    return res
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     for name in ("preloaded", "catalog", "model", "samples", "processed", "out"):
@@ -146,10 +179,22 @@ def main(argv=None) -> int:
     ap.add_argument("--multi-models", action="store_true",
                     help="a multi-DLA processed file: also the moments of every model DLA(1..max_dlas) and of the "
                          "sub-DLA model, and the absorption averaged over the models by model_posteriors")
+    ap.add_argument("--marginal-continuum", action="store_true",
+                    help="write the marginal continuum instead (DESIGN.md 4.23): its posterior mean and variance over "
+                         "the sample tables and the models")
+    ap.add_argument("--components", type=str, default="dla", help="--marginal-continuum: any of null,sub_dla,dla")
+    ap.add_argument("--model-weights", choices=("posteriors", "equal"), default="posteriors",
+                    help="--marginal-continuum: mix the components by the file's posteriors, or equally")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--max-quasars-per-batch", type=int, default=None)
     a = ap.parse_args(argv)
     idx = None if a.indices is None else [int(x) for x in a.indices.split(",") if x]
+    if a.marginal_continuum:
+        res = run_marginal_continuum(a.preloaded, a.catalog, a.model, a.samples, a.processed, a.out, p_dla=a.p_dla, indices=idx,
+                                     components=tuple(x for x in a.components.split(",") if x), model_weights=a.model_weights,
+                                     device=a.device, max_quasars_per_batch=a.max_quasars_per_batch)
+        print(f"wrote {a.out}: {res['selection'].size} quasars, {int(res['offsets'][-1])} grid pixels")
+        return 0
     res = run(a.preloaded, a.catalog, a.model, a.samples, a.processed, a.out, p_dla=a.p_dla, indices=idx,
               products=tuple(a.products.split(",")), moments_sub_dla=a.moments_sub_dla, device=a.device,
               max_quasars_per_batch=a.max_quasars_per_batch, multi_models=a.multi_models)

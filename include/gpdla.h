@@ -1261,6 +1261,67 @@ int64_t gpdla_posterior_maps_rows_per_launch(int num_models, int nz, int nn);
 double gpdla_debug_last_maps_ms(int kernel);
 int64_t gpdla_debug_last_maps_launches(void);
 
+/* ---------------------------------------------------------------------------------------------
+ * Marginal continuum: the GP posterior mean and variance of the low-rank continuum over the sample tables
+ * and over the models.  Additive: GPDLA_ABI_VERSION is unchanged.  fp64 throughout;
+ * tests/marginal_continuum_restatement.py states the same in NumPy.
+ *
+ * Quasar q has the prepared rows (y, mu, M, omega2, nu) of the preparation kernel (meanflux != 0: the
+ * suppressed rows).  Sample i has the broadened profile a_i on the quasar's grid, exactly the profile of
+ * mean_absorption above (z_i, N_i from nhi_samples, or lls_nhi_samples for the sub-DLA table).  Per sample
+ *   d_i = a_i^2 omega2 + nu,  B_i = I + M' diag(a_i^2 / d_i) M,  v_i = M' (a_i (y - a_i mu) / d_i),
+ *   c_i = B_i^-1 v_i,  Sigma_i = B_i^-1:
+ * the posterior mean and covariance of the coefficients c ~ N(0, I) given sample i.  The weights w_i are
+ * those of mean_absorption (exp(l_i - max l) / Sum, NaN -> 0).  One sampled component:
+ *   cbar = Sum w_i c_i,  W = Sum w_i Sigma_i (within),  V = Sum w_i c_i c_i' - cbar cbar' (between).
+ * The null component is a = 1: c_0, Sigma_0, no spread.  The mixture runs over (null, sub-DLA table, DLA
+ * table) with the per-quasar model_weights p, each row non-negative, finite, of positive sum and normalised
+ * by its sum (NULL: (0, 0, 1) for every quasar):
+ *   c = Sum p_m cbar_m,  W = Sum p_m W_m,  V = Sum p_m (V_m + cbar_m cbar_m') - c c'.
+ * A component of weight exactly 0 is not evaluated; a sample of weight exactly 0 is skipped (its B_i is never
+ * factorised).  Per pixel p of the unmasked-range grid, m_p interpolated (and suppressed) as for continuum:
+ *   continuum_mean = mu_p + m_p' c,  continuum_var = m_p' (W + V) m_p,  continuum_var_between = m_p' V m_p.
+ * The pixel-diagonal omega term predicts nothing at a pixel that was not measured and is left out, as for
+ * continuum: continuum_var is the variance of the LOW-RANK part of the GP.
+ * coef_mean [num_selected][k] = c; coef_cov_within, coef_cov_between [num_selected][k (k + 1) / 2] = W, V as
+ * packed lower triangles stored row by row.  sample_coefficients [num_selected][S][k] (request flag; the
+ * model weights must reach exactly one table): c_i per sample, in sample order, NaN rows for samples of weight 0.
+ * status: the quasar's sweep status (1, 3: NaN rows); 4 = a B_i of positive weight, or B_0, is not positive
+ * definite (NaN rows).  A table of positive model weight whose row has no weights (all NaN, all -inf, a +inf)
+ * gives NaN rows and status 0.  For a multi-DLA batch the resident tables are model DLA(1) and the sub-DLA
+ * table.  A conditioned batch is refused.  Sums run in a fixed order without atomics: outputs are bit-identical
+ * for any selection order and launch grouping and for the resident and the host form of a table.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct {
+  int64_t num_selected;
+  const int64_t *selection;          /* [num_selected] quasars of the batch; NULL = 0 .. num_selected-1 */
+  int32_t weights_source;            /* GPDLA_SPECTRA_WEIGHTS_RESIDENT or _HOST (_NONE: null component only) */
+  const double *sample_log_likelihoods_dla; /* [num_selected][S], _HOST, where a row weighs the DLA table */
+  const double *sample_log_likelihoods_lls; /* [num_selected][S], _HOST, where a row weighs the sub-DLA table */
+  const double *model_weights;       /* [num_selected][3] (null, sub-DLA, DLA), or NULL = (0, 0, 1) */
+  int32_t meanflux;                  /* != 0: prepared rows of the mean-flux model (multi :245-293) */
+  int32_t sample_coefficients;       /* != 0: fill sample_coefficients */
+  int64_t capacity;                  /* entries of each per-pixel output array */
+} gpdla_marginal_continuum_request;
+typedef struct {
+  int64_t *offsets;                  /* [num_selected + 1]; required */
+  double *continuum_mean, *continuum_var, *continuum_var_between; /* per pixel; any may be NULL */
+  double *coef_mean;                 /* [num_selected][k] or NULL */
+  double *coef_cov_within, *coef_cov_between; /* [num_selected][k (k + 1) / 2] or NULL */
+  double *sample_coefficients;       /* [num_selected][S][k] or NULL */
+  int32_t *status;                   /* [num_selected] or NULL */
+} gpdla_marginal_continuum;
+/* The checks gpdla_batch_marginal_continuum makes before its first device call: a selection index outside the
+ * batch, a negative, NaN or infinite model weight or a row without a positive sum, a sampled component
+ * without a weights source (or a host source without that table), the sub-DLA table without lls_nhi_samples,
+ * sample_coefficients with both tables or none.  Returns GPDLA_OK or GPDLA_ERR_INVALID_ARGUMENT.  Needs no GPU. */
+int gpdla_marginal_continuum_validate(const gpdla_marginal_continuum_request *request, int64_t num_quasars,
+                                      int64_t num_samples, int has_lls_nhi_samples);
+/* With gpdla_context_set_timing enabled, gpdla_context_last_sweep_ms reports the k_mc_contract, k_mc_solve and
+ * k_mc_finish launches of the call. */
+int gpdla_batch_marginal_continuum(gpdla_context *ctx, gpdla_batch *batch, const gpdla_marginal_continuum_request *request,
+                                   gpdla_marginal_continuum *out);
+
 #ifdef __cplusplus
 }
 #endif
