@@ -591,16 +591,29 @@ __device__ __forceinline__ double exp_nonpos(double x) {
 
 // Re w(x+iy) sqrt(pi)/y for |x| >= 30 given x2 = x^2 (see faddeeva.hpp rew_wing), with the fast
 // reciprocal.  Returns the value with the y/sqrt(pi) factor left out.
-// The wing series T(rho) = Sum_{m<=6} (2m+1)!!/2^m rho^m economised to degree 5 on the interval the
-// wing tier uses, 0 <= rho <= 1/900 (|x| >= 30): rho^6 replaced by its shifted-Chebyshev remainder,
-// max change 1.9e-18 (derivation: 50-digit mpmath).  One FMA per line and K-step less.
-constexpr double kE1 = 0x1.8000000000236p+0, kE2 = 0x1.dffffffd2a557p+1, kE3 = 0x1.a4000aa13fb7fp+3,
-                 kE4 = 0x1.d86dfb645a1cbp+5, kE5 = 0x1.4be1ccccccccdp+8;
+// The wing series T(rho) = Sum_{m<=6} (2m+1)!!/2^m rho^m as 1 + rho (kE1 + kE2 rho + kE3 rho^2 + kE4 rho^3) on the
+// interval the wing tier uses, 0 <= rho <= 1/900 (|x| >= 30): the degree-4 minimax polynomial with the constant
+// term pinned at 1.0 (an inline constant).  Derivation, in 50-digit mpmath: Remez exchange on the error
+// 1 + rho q(rho) - T(rho), q cubic, five alternation points in (0, 1/900] (the error vanishes at 0 by construction),
+// its extrema located on a 4001-point grid, iterated until the points stop moving; the coefficients then rounded to
+// fp64.  Maximum relative error 1.25e-15 (the degree-5 economisation this replaces: 1.9e-18), below the 2.2e-15 of
+// fast_rcp that every rho carries anyway.  Two FMAs per line and evaluation less than the plain series;
+// tests/test_wing_exp_series.py reads these constants.
+constexpr double kE1 = 0x1.7fffffffd940ep+0, kE2 = 0x1.e0000294b4cbcp+1, kE3 = 0x1.a3f92a26b3728p+3,
+                 kE4 = 0x1.df9f0e43cd754p+5;
+// The leading Horner step kE4 rho + kE3 of the K-step's three lines as ONE three-address v_fma_f64 each (kE4 a scalar
+// operand, kE3 in a vector register the lines share).  Spelled `rho * kE4 + kE3` it is a multiply and an add under
+// the build's -ffp-contract=off, and as fma() the compiler picks v_fmac_f64 and copies the constant in front of
+// each: 139.59 against 140.38 ms per launch for the multiply and add (profiles/ab_fp64_ops.txt, session 4).
+__device__ __forceinline__ double wing_lead(double rho, double e3v) {
+  double t;
+  asm("v_fma_f64 %0, %1, %2, %3" : "=v"(t) : "v"(rho), "s"(kE4), "v"(e3v));
+  return t;
+}
 
 __device__ __forceinline__ double wing_core(double x2, double y2) {
   const double rho = fast_rcp(x2 + y2);
-  double t = fma(kE5, rho, kE4);
-  t = fma(t, rho, kE3);
+  double t = fma(kE4, rho, kE3);
   t = fma(t, rho, kE2);
   t = fma(t, rho, kE1);
   t = fma(t, rho, 1.0);
@@ -1222,7 +1235,7 @@ __device__ __forceinline__ double near_poly(const double *line_tab, double ax) {
 __device__ __forceinline__ uint32_t hi_word(double v) { return (uint32_t)__double2hiint(v); }
 
 // Wing-tier optical-depth sum for the three-line case (Ly-alpha, beta, gamma): FMA-form
-// velocities, ONE reciprocal for the three lines (1/(sa sb sc), then peeled), 6-term series.
+// velocities, ONE reciprocal for the three lines (1/(sa sb sc), then peeled), degree-4 series.
 // Returns Sum_j lead_j y_j [Re w_j sqrt(pi)/y_j]; *near: some line within 30 Doppler widths.
 __device__ __forceinline__ double wing_sum3(double lamP, double msa, double msb, double msc, double cs,
                                             bool *near) {
@@ -1239,10 +1252,9 @@ __device__ __forceinline__ double wing_sum3(double lamP, double msa, double msb,
   const double rinv = fast_rcp(pab * sc);
   const double ra = rinv * pbc, rb = rinv * pac, rc = rinv * pab;
   // T(rho) - 2 y^2 rho^2 by Horner; the -2 y_j^2 correction rides in the rho^2 coefficient (t2[j]).
-  // The leading step as a three-address v_fma_f64 with kE4 in a vector register (the compiler
-  // would pick v_fmac_f64 and copy the constant in front of each: two extra moves per line).
-  double ta = ra * kE5 + kE4, tb = rb * kE5 + kE4, tc = rc * kE5 + kE4;
-  ta = fma(ta, ra, kE3); tb = fma(tb, rb, kE3); tc = fma(tc, rc, kE3);
+  // The leading step as a multiply and an add (-ffp-contract=off): this form serves the primings and the kernels
+  // off the headline; the K-step's own spelling, wing_sum3_rcp4, has it as one v_fma_f64 (wing_lead).
+  double ta = ra * kE4 + kE3, tb = rb * kE4 + kE3, tc = rc * kE4 + kE3;
   ta = fma(ta, ra, g_lines.t2[0]); tb = fma(tb, rb, g_lines.t2[1]); tc = fma(tc, rc, g_lines.t2[2]);
   ta = fma(ta, ra, kE1); tb = fma(tb, rb, kE1); tc = fma(tc, rc, kE1);
   ta = fma(ta, ra, 1.0); tb = fma(tb, rb, 1.0); tc = fma(tc, rc, 1.0);
@@ -1269,8 +1281,8 @@ __device__ __forceinline__ double wing_sum3_rcp4(double lamP, double msa, double
   const double r3 = rinv * d;            // 1 / (sa sb sc)
   const double rc = r3 * pab, r2 = r3 * sc;  // 1 / sc, 1 / (sa sb)
   const double ra = r2 * sb, rb = r2 * sa;
-  double ta = ra * kE5 + kE4, tb = rb * kE5 + kE4, tc = rc * kE5 + kE4;
-  ta = fma(ta, ra, kE3); tb = fma(tb, rb, kE3); tc = fma(tc, rc, kE3);
+  const double e3v = kE3;
+  double ta = wing_lead(ra, e3v), tb = wing_lead(rb, e3v), tc = wing_lead(rc, e3v);
   ta = fma(ta, ra, g_lines.t2[0]); tb = fma(tb, rb, g_lines.t2[1]); tc = fma(tc, rc, g_lines.t2[2]);
   ta = fma(ta, ra, kE1); tb = fma(tb, rb, kE1); tc = fma(tc, rc, kE1);
   ta = fma(ta, ra, 1.0); tb = fma(tb, rb, 1.0); tc = fma(tc, rc, 1.0);
@@ -1380,7 +1392,7 @@ __device__ __forceinline__ double total_near(double lamP, double m0, double m1, 
 
 // Wing tier for a line count known at run time only: sqrt(pi) Sum_{j<L} lead_j Re w_j by the wing
 // formula, from rho = lambda / (1 + z_DLA), kLineUnroll lines at a time -- their scalar loads are
-// issued together and their dependent chains (reciprocal, Newton step, degree-5 Horner) interleave;
+// issued together and their dependent chains (reciprocal, Newton step, degree-4 Horner) interleave;
 // line by line, a wave waited for three scalar loads and one ~20-deep chain per line (measured at 31
 // lines on 200 x 1500 pixels x 10^4 samples: 115 ms one at a time).  *near: some line j < L is
 // within 30 Doppler widths of this lane's pixel (the caller then takes total_near_at).
@@ -1627,14 +1639,12 @@ __global__ __launch_bounds__(WAVES * 64) void k_sweep(SweepArgs a) {
         const double py = p01.x, pmu = p01.y, pom = p23.x, pnu = p23.y;
         __builtin_amdgcn_sched_barrier(0);  // keep the reads up here (the scheduler sinks them)
         // (2) instrument broadening for pixel 4 rn + jj: voigt.c:297-299 (symmetric taps) -- in front of
-        // (1) since round 5: the three-line wing tier takes d along (wing_sum3_rcp4)
-        double absorb = fma(g6, tap0, g0 * tap0);
-        {
-          double ab2 = fma(g5, tap1, g1 * tap1);
-          absorb = fma(g2, tap2, absorb);
-          ab2 = fma(g4, tap2, ab2);
-          absorb = fma(g3, tap3, absorb) + ab2;
-        }
+        // (1) since round 5: the three-line wing tier takes d along (wing_sum3_rcp4).  On the symmetric pairs:
+        // three adds, one multiply and three FMAs (k_sweep_slim spells the same operations: change them together).
+        double absorb = g3 * tap3;
+        absorb = fma(g0 + g6, tap0, absorb);
+        absorb = fma(g1 + g5, tap1, absorb);
+        absorb = fma(g2 + g4, tap2, absorb);
         if (is_null) absorb = 1.0;
         const double a2 = absorb * absorb;
         const double d = fma(pom, a2, pnu);

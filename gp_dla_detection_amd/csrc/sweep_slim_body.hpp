@@ -245,14 +245,12 @@ __global__ __launch_bounds__(kSlimWaves * 64, 2) void GPDLA_SWEEP_SLIM_KERNEL(GP
         // (2) instrument broadening for pixel 4 rn + jj: voigt.c:297-299 (symmetric taps).  In front of (1)
         // since round 5: the three-line wing tier takes this pixel's d along and returns 1/d from the same
         // v_rcp_f64 as its own three quotients (wing_sum3_rcp4): 151.06 -> 150.21 ms on one box
-        // (profiles/r05_ab_rcp4.txt), and the two spilled registers are gone.
-        double absorb = fma(g6, tap0, g0 * tap0);
-        {
-          double ab2 = fma(g5, tap1, g1 * tap1);
-          absorb = fma(g2, tap2, absorb);
-          ab2 = fma(g4, tap2, ab2);
-          absorb = fma(g3, tap3, absorb) + ab2;
-        }
+        // (profiles/r05_ab_rcp4.txt), and the two spilled registers are gone.  On the symmetric pairs: three adds,
+        // one multiply and three FMAs instead of eight operations (as k_sweep: change them together).
+        double absorb = g3 * tap3;
+        absorb = fma(g0 + g6, tap0, absorb);
+        absorb = fma(g1 + g5, tap1, absorb);
+        absorb = fma(g2 + g4, tap2, absorb);
         if (is_null) absorb = 1.0;
         const double a2 = absorb * absorb;
         const double d = fma(pom, a2, pnu);

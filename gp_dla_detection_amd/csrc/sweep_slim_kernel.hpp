@@ -191,8 +191,8 @@ __device__ __forceinline__ double wing3_back_rcp4(const WingFront &f, double d, 
   const double r3 = rinv * d;
   const double rc = r3 * f.pab, r2 = r3 * f.sc;
   const double ra = r2 * f.sb, rb = r2 * f.sa;
-  double ta = ra * kE5 + kE4, tb = rb * kE5 + kE4, tc = rc * kE5 + kE4;
-  ta = fma(ta, ra, kE3); tb = fma(tb, rb, kE3); tc = fma(tc, rc, kE3);
+  const double e3v = kE3;
+  double ta = wing_lead(ra, e3v), tb = wing_lead(rb, e3v), tc = wing_lead(rc, e3v);
   ta = fma(ta, ra, g_lines.t2[0]); tb = fma(tb, rb, g_lines.t2[1]); tc = fma(tc, rc, g_lines.t2[2]);
   ta = fma(ta, ra, kE1); tb = fma(tb, rb, kE1); tc = fma(tc, rc, kE1);
   ta = fma(ta, ra, 1.0); tb = fma(tb, rb, 1.0); tc = fma(tc, rc, 1.0);
