@@ -521,7 +521,7 @@ int gpdla_oracle_process_spectrum_multi(
     const uint8_t *pixel_mask, double z_qso, int num_threads, double *min_z_dla,
     double *max_z_dla, double *log_likelihood_no_dla, double *sample_ll /* [S x max_dlas] */,
     double *log_likelihoods_dla, double *sample_ll_lls, double *log_likelihood_lls,
-    double *MAP_z_dlas, double *MAP_log_nhis, double *MAP_inds) {
+    double *MAP_z_dlas, double *MAP_log_nhis, double *MAP_inds, gpdla_oracle_dump *dump) {
   selection s;
   const int k = mdl->k, G = mdl->num_rest, max_dlas = mul->max_dlas, L = mul->num_forest_lines;
   const double lya_f = oscillator_strengths[0]; /* lya_oscillator_strength, set_parameters_multi.m */
@@ -577,6 +577,15 @@ int gpdla_oracle_process_spectrum_multi(
   double *sample_z = (double *)malloc(sizeof(double) * (size_t)S);
   for (int64_t i = 0; i < S; i++)
     sample_z[i] = *min_z_dla + (*max_z_dla - *min_z_dla) * offset_samples[i]; /* multi :309-311 */
+  if (dump) { /* the rows and grids the sweep below consumes (mean-flux suppression applied) */
+    if (dump->n_kept) *dump->n_kept = n;
+    if (dump->n_unmasked) *dump->n_unmasked = s.n_u;
+    if (dump->this_mu) memcpy(dump->this_mu, this_mu, sizeof(double) * (size_t)n);
+    if (dump->this_M) memcpy(dump->this_M, this_M, sizeof(double) * (size_t)n * k);
+    if (dump->this_omega2) memcpy(dump->this_omega2, this_omega2, sizeof(double) * (size_t)n);
+    if (dump->padded_wavelengths) memcpy(dump->padded_wavelengths, padded, sizeof(double) * (size_t)n_pad);
+    if (dump->sample_z_dlas) memcpy(dump->sample_z_dlas, sample_z, sizeof(double) * (size_t)S);
+  }
   const double log_S = log((double)S);
 #ifdef _OPENMP
   if (num_threads > 0) omp_set_num_threads(num_threads);

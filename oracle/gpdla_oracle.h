@@ -129,8 +129,9 @@ double gpdla_oracle_mean_flux_suppression(double wavelength, double z_qso, doubl
  * sample_log_likelihoods_dla is [S x max_dlas] column-major (this_sample_log_likelihoods_dla, :146),
  * log_likelihoods_dla [max_dlas], sample_log_likelihoods_lls [S], MAP_* [max_dlas x max_dlas]
  * column-major (model index first) with NaN for unused slots, MAP_inds 1-based as doubles (:131).
- * Models after an early NaN exit (:460-464) stay NaN.  Returns 0, or -1 for an empty spectrum
- * (all_exceptions, :230-234). */
+ * Models after an early NaN exit (:460-464) stay NaN.  dump (may be NULL): the intermediates of
+ * :228-330 under the names of the single-DLA driver's, this_mu / this_M / this_omega2 with the mean-flux
+ * suppression of :267-293 applied.  Returns 0, or -1 for an empty spectrum (all_exceptions, :230-234). */
 int gpdla_oracle_process_spectrum_multi(
     const gpdla_oracle_params *prm, const gpdla_oracle_model *mdl, const gpdla_oracle_multi *mul,
     int64_t num_samples, const double *offset_samples, const double *nhi_samples,
@@ -139,7 +140,7 @@ int gpdla_oracle_process_spectrum_multi(
     double *min_z_dla, double *max_z_dla, double *log_likelihood_no_dla,
     double *sample_log_likelihoods_dla, double *log_likelihoods_dla,
     double *sample_log_likelihoods_lls, double *log_likelihood_lls, double *MAP_z_dlas,
-    double *MAP_log_nhis, double *MAP_inds);
+    double *MAP_log_nhis, double *MAP_inds, gpdla_oracle_dump *dump);
 
 /* spectrum_loss.m:14-76 (row N3 of SURVEY.md section 8f).  M, dM: n x k column-major. */
 int gpdla_oracle_spectrum_loss(const double *y, const double *lya_1pz, const double *noise_variance,

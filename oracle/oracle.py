@@ -79,7 +79,8 @@ def _bind(lib):
     lib.gpdla_oracle_process_spectrum_multi.restype = C.c_int
     lib.gpdla_oracle_process_spectrum_multi.argtypes = [
         C.POINTER(_Params), C.POINTER(_Model), C.POINTER(_Multi), C.c_int64, _dp, _dp, C.c_int64,
-        _dp, _dp, _dp, _u8p, C.c_double, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]
+        _dp, _dp, _dp, _u8p, C.c_double, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
+        C.POINTER(_Dump)]
     lib.gpdla_oracle_mean_flux_suppression.restype = C.c_double
     lib.gpdla_oracle_mean_flux_suppression.argtypes = [C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                                                        C.c_int]
@@ -250,10 +251,12 @@ def process_spectrum_multi(model, offset_samples, nhi_samples, log_nhi_samples, 
                            base_sample_inds, wavelengths, flux, noise_variance, pixel_mask, z_qso,
                            params: OracleParams | None = None, max_dlas=4, num_forest_lines=31,
                            min_z_separation=3000 * 1000 / 299792458, prev_tau_0=0.0023,
-                           prev_beta=3.65, num_threads=0):
+                           prev_beta=3.65, num_threads=0, dump=False):
     """multi_dlas/process_qsos_multiple_dlas_meanflux.m:141-477 for one quasar.
 
-    base_sample_inds: (max_dlas-1, S) uint32, 1-based (MATLAB this_base_sample_inds, :313)."""
+    base_sample_inds: (max_dlas-1, S) uint32, 1-based (MATLAB this_base_sample_inds, :313).
+    ``dump``: also return the rows the sweep consumed, under the names of :func:`process_spectrum`'s
+    dump (``this_mu``, ``this_M`` and ``this_omega2`` carry the mean-flux suppression of :267-293)."""
     lib = load()
     params = params or OracleParams()
     prm = params.c()
@@ -278,17 +281,31 @@ def process_spectrum_multi(model, offset_samples, nhi_samples, log_nhi_samples, 
     mapn = np.full((max_dlas, max_dlas), np.nan, order="F")
     mapi = np.full((max_dlas, max_dlas), np.nan, order="F")
     zmin, zmax, ll0, ll_lls = C.c_double(), C.c_double(), C.c_double(), C.c_double()
+    dptr = None
+    if dump:
+        npx, k = wl.size, mdl.k
+        nk, nu = C.c_int64(), C.c_int64()
+        tmu, tM, tom, pad, sz = np.zeros(npx), np.zeros(npx * k), np.zeros(npx), np.zeros(npx + 6), np.zeros(S)
+        dd = _Dump(C.pointer(nk), C.pointer(nu), tmu.ctypes.data_as(_dp), tM.ctypes.data_as(_dp),
+                   tom.ctypes.data_as(_dp), pad.ctypes.data_as(_dp), sz.ctypes.data_as(_dp))
+        dptr = C.byref(dd)
     rc = lib.gpdla_oracle_process_spectrum_multi(
         C.byref(prm), C.byref(mdl), C.byref(mul), S, offp, nhip, wl.size, wlp, flp, nvp,
         mk.ctypes.data_as(_u8p), float(z_qso), int(num_threads), C.byref(zmin), C.byref(zmax),
         C.byref(ll0), sll.ctypes.data_as(_dp), ll_dla.ctypes.data_as(_dp),
         sll_lls.ctypes.data_as(_dp), C.byref(ll_lls), mapz.ctypes.data_as(_dp),
-        mapn.ctypes.data_as(_dp), mapi.ctypes.data_as(_dp))
-    return dict(rc=rc, min_z_dla=zmin.value, max_z_dla=zmax.value,
-                log_likelihood_no_dla=ll0.value, sample_log_likelihoods_dla=np.array(sll),
-                log_likelihoods_dla=ll_dla, sample_log_likelihoods_lls=sll_lls,
-                log_likelihood_lls=ll_lls.value, MAP_z_dlas=np.array(mapz),
-                MAP_log_nhis=np.array(mapn), MAP_inds=np.array(mapi))
+        mapn.ctypes.data_as(_dp), mapi.ctypes.data_as(_dp), dptr)
+    out = dict(rc=rc, min_z_dla=zmin.value, max_z_dla=zmax.value,
+               log_likelihood_no_dla=ll0.value, sample_log_likelihoods_dla=np.array(sll),
+               log_likelihoods_dla=ll_dla, sample_log_likelihoods_lls=sll_lls,
+               log_likelihood_lls=ll_lls.value, MAP_z_dlas=np.array(mapz),
+               MAP_log_nhis=np.array(mapn), MAP_inds=np.array(mapi))
+    if dump and rc == 0:
+        n, n_u = nk.value, nu.value
+        out.update(n_kept=n, n_unmasked=n_u, this_mu=tmu[:n].copy(),
+                   this_M=tM[:n * k].reshape(k, n).T.copy(), this_omega2=tom[:n].copy(),
+                   padded_wavelengths=pad[:n_u + 6].copy(), sample_z_dlas=sz)
+    return out
 
 
 def objective_lyseries(x, centered_rest_fluxes, lya_1pzs, rest_noise_variances, num_forest_lines,
