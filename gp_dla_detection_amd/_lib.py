@@ -170,6 +170,19 @@ class MarginalContinuum(C.Structure):
                 ("status", _i32p)]
 
 
+class PredictiveFluxRequest(C.Structure):
+    """gpdla_predictive_flux_request"""
+    _fields_ = [("num_selected", C.c_int64), ("selection", _i64p), ("weights_source", C.c_int32),
+                ("sample_log_likelihoods_dla", _dp), ("sample_log_likelihoods_lls", _dp), ("model_weights", _dp),
+                ("meanflux", C.c_int32), ("capacity", C.c_int64)]
+
+
+class PredictiveFlux(C.Structure):
+    """gpdla_predictive_flux"""
+    _fields_ = [("offsets", _i64p), ("flux_mean", _dp), ("flux_var", _dp), ("flux_var_within", _dp),
+                ("flux_var_between", _dp), ("noise_var", _dp), ("status", _i32p)]
+
+
 class MockRequest(C.Structure):
     """gpdla_mock_request"""
     _fields_ = [("seed", C.c_uint64), ("absorber_offsets", _i64p), ("absorber_z", _dp), ("absorber_nhi", _dp),
@@ -341,6 +354,9 @@ SYMBOLS = [
     ("gpdla_marginal_continuum_validate", C.c_int, [C.POINTER(MarginalContinuumRequest), C.c_int64, C.c_int64, C.c_int]),
     ("gpdla_batch_marginal_continuum", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(MarginalContinuumRequest),
                                                  C.POINTER(MarginalContinuum)]),
+    ("gpdla_predictive_flux_validate", C.c_int, [C.POINTER(PredictiveFluxRequest), C.c_int64, C.c_int64, C.c_int]),
+    ("gpdla_batch_predictive_flux", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(PredictiveFluxRequest),
+                                              C.POINTER(PredictiveFlux)]),
     ("gpdla_debug_profiles_ms", C.c_int, [C.c_void_p, C.c_void_p, _dp]),
     ("gpdla_model_mean", C.c_int, [C.POINTER(Model), C.c_int64, _dp, _i64p, _dp, _dp, C.c_int, C.c_int, C.c_int,
                                    C.c_double, C.c_double, _dp, C.c_int]),

@@ -289,6 +289,7 @@ class Batch:
         self._refined = None
         self._multi_processed = False   # process_multi() has run on the current spectra
         csr = spectra if isinstance(spectra, dict) else spectra_to_csr(spectra)
+        self._csr = csr                 # (references: predictive_flux(residuals=True) reads the flux and the mask)
         self.num_quasars = csr["z_qsos"].size
         self.num_pixels = int(csr["offsets"][-1] - csr["offsets"][0])
         self.num_samples = ctx.num_samples
@@ -563,6 +564,49 @@ class Batch:
 
     # ---- marginal continuum ----
 
+    def _mixture_request(self, rq, selection, weights, components, model_weights, meanflux):
+        """Fill the fields the marginal-continuum and the predictive-flux requests share; returns (selection,
+        the arrays the request points into)."""
+        sel = self._selection(selection)
+        nsel, S = sel.size, self.num_samples
+        names = ("null", "sub_dla", "dla")
+        components = tuple(components)
+        if not components or any(c not in names for c in components):
+            raise ValueError(f"components: a non-empty subset of {names}")
+        listed = np.array([c in components for c in names])
+        if model_weights is None:
+            pw = np.tile(listed.astype(np.float64), (nsel, 1))
+        else:
+            pw = np.array(model_weights, dtype=np.float64)
+            if pw.shape != (nsel, 3):
+                raise _lib.GpdlaError(-1, f"model_weights must be [nsel, 3] = {(nsel, 3)}, got {pw.shape}")
+            pw[:, ~listed] = 0.0
+        pw = np.ascontiguousarray(pw)
+        rq.num_selected = nsel
+        rq.selection = sel.ctypes.data_as(_i64p)
+        rq.model_weights = pw.ctypes.data_as(_dp)
+        keep = [sel, pw]
+        if isinstance(weights, str):
+            if weights != "resident":
+                raise ValueError("weights: 'resident', an array [nsel, S], a dict of them or None")
+            rq.weights_source = _lib.SPECTRA_WEIGHTS_RESIDENT
+        elif weights is not None:
+            if not isinstance(weights, dict):
+                sampled = [c for c in components if c != "null"]
+                if len(sampled) != 1:
+                    raise ValueError("weights: one array serves one sampled component; pass {'dla': ..., 'sub_dla': ...}")
+                weights = {sampled[0]: weights}
+            rq.weights_source = _lib.SPECTRA_WEIGHTS_HOST
+            for name, field in (("dla", "sample_log_likelihoods_dla"), ("sub_dla", "sample_log_likelihoods_lls")):
+                if weights.get(name) is not None:
+                    w = np.ascontiguousarray(weights[name], dtype=np.float64)
+                    if w.shape != (nsel, S):
+                        raise _lib.GpdlaError(-1, f"weights[{name!r}] must be [nsel, S] = {(nsel, S)}, got {w.shape}")
+                    keep.append(w)
+                    setattr(rq, field, w.ctypes.data_as(_dp))
+        rq.meanflux = int(bool(self.max_dlas) if meanflux is None else bool(meanflux))
+        return sel, keep
+
     def marginal_continuum(self, selection=None, weights="resident", components=("dla",), model_weights=None,
                            meanflux: bool | None = None, sample_coefficients: bool = False) -> dict:
         """The GP continuum of the selected quasars averaged over the absorber posterior instead of
@@ -588,45 +632,9 @@ class Batch:
         that of the low-rank part of the GP: the pixel-diagonal omega term predicts nothing at an
         unmeasured pixel and is left out, as in ``continuum`` of :meth:`model_spectra`."""
         lib = self.ctx.lib
-        sel = self._selection(selection)
-        nsel, S, k = sel.size, self.num_samples, self.ctx.k
-        names = ("null", "sub_dla", "dla")
-        components = tuple(components)
-        if not components or any(c not in names for c in components):
-            raise ValueError(f"components: a non-empty subset of {names}")
-        listed = np.array([c in components for c in names])
-        if model_weights is None:
-            pw = np.tile(listed.astype(np.float64), (nsel, 1))
-        else:
-            pw = np.array(model_weights, dtype=np.float64)
-            if pw.shape != (nsel, 3):
-                raise _lib.GpdlaError(-1, f"model_weights must be [nsel, 3] = {(nsel, 3)}, got {pw.shape}")
-            pw[:, ~listed] = 0.0
-        pw = np.ascontiguousarray(pw)
         rq = _lib.MarginalContinuumRequest()
-        rq.num_selected = nsel
-        rq.selection = sel.ctypes.data_as(_i64p)
-        rq.model_weights = pw.ctypes.data_as(_dp)
-        keep = [sel, pw]
-        if isinstance(weights, str):
-            if weights != "resident":
-                raise ValueError("weights: 'resident', an array [nsel, S], a dict of them or None")
-            rq.weights_source = _lib.SPECTRA_WEIGHTS_RESIDENT
-        elif weights is not None:
-            if not isinstance(weights, dict):
-                sampled = [c for c in components if c != "null"]
-                if len(sampled) != 1:
-                    raise ValueError("weights: one array serves one sampled component; pass {'dla': ..., 'sub_dla': ...}")
-                weights = {sampled[0]: weights}
-            rq.weights_source = _lib.SPECTRA_WEIGHTS_HOST
-            for name, field in (("dla", "sample_log_likelihoods_dla"), ("sub_dla", "sample_log_likelihoods_lls")):
-                if weights.get(name) is not None:
-                    w = np.ascontiguousarray(weights[name], dtype=np.float64)
-                    if w.shape != (nsel, S):
-                        raise _lib.GpdlaError(-1, f"weights[{name!r}] must be [nsel, S] = {(nsel, S)}, got {w.shape}")
-                    keep.append(w)
-                    setattr(rq, field, w.ctypes.data_as(_dp))
-        rq.meanflux = int(bool(self.max_dlas) if meanflux is None else bool(meanflux))
+        sel, keep = self._mixture_request(rq, selection, weights, components, model_weights, meanflux)
+        nsel, S, k = sel.size, self.num_samples, self.ctx.k
         rq.sample_coefficients = int(bool(sample_coefficients))
         # refused requests never reach the device
         _lib.check(lib.gpdla_marginal_continuum_validate(C.byref(rq), self.num_quasars, S, int(self.ctx.has_lls_samples)))
@@ -646,6 +654,66 @@ class Batch:
                 setattr(mc, name, out[name].ctypes.data_as(_dp))
         _lib.check(lib.gpdla_batch_marginal_continuum(self.ctx._h, self._h, C.byref(rq), C.byref(mc)))
         del keep
+        return out
+
+    # ---- posterior predictive flux ----
+
+    def grid_flux(self, selection=None):
+        """``(flux, kept)`` of the selected quasars on their unmasked-range grids, flat in the CSR layout of
+        :meth:`model_spectra`, from the host copy of the uploaded spectra: the observed flux and whether the
+        pixel is not masked."""
+        sel = self._selection(selection)
+        csr, p = self._csr, self.ctx.params
+        off = np.asarray(csr["offsets"], dtype=np.int64)
+        ys, ks = [], []
+        for q in sel:
+            sl = slice(off[q], off[q + 1])
+            rest = np.asarray(csr["wavelengths"][sl], dtype=np.float64) / (1 + float(csr["z_qsos"][q]))
+            inside = (rest >= p.min_lambda) & (rest <= p.max_lambda)
+            ys.append(np.asarray(csr["flux"][sl], dtype=np.float64)[inside])
+            ks.append(np.asarray(csr["pixel_mask"][sl])[inside] == 0)
+        return (np.concatenate(ys) if ys else np.zeros(0)), (np.concatenate(ks) if ks else np.zeros(0, dtype=bool))
+
+    def predictive_flux(self, selection=None, weights="resident", components=("dla",), model_weights=None,
+                        meanflux: bool | None = None, residuals: bool = False) -> dict:
+        """The posterior predictive flux of the selected quasars (gpdla_batch_predictive_flux; the definitions
+        are in include/gpdla.h): per pixel of each quasar's unmasked-range grid, the mean and variance of the model
+        flux -- absorption times GP continuum -- averaged over the absorber posterior and the models.  It is the
+        curve to lay over the observed spectrum, with its error band; it is NOT the product of ``mean_absorption``
+        and ``continuum_mean``, because the continuum coefficients move with the absorber.
+
+        ``selection``, ``weights``, ``components``, ``model_weights``, ``meanflux``: as :meth:`marginal_continuum`.
+        Returns ``offsets``, ``status`` and the flat per-pixel ``flux_mean``, ``flux_var`` (within + between),
+        ``flux_var_within`` (the GP's spread given the absorber), ``flux_var_between`` (the spread over absorbers
+        and models) and ``noise_var`` (NaN on masked pixels).  ``flux_var`` is the variance of the low-rank,
+        noise-free model flux, as ``continuum_var`` is; ``flux_var + noise_var`` is the variance of a replicate
+        observation of the pixel (a new pixel-diagonal term and new noise under the same posterior).
+
+        ``residuals``: also ``residual`` = (y - flux_mean) / sqrt(flux_var + noise_var) per pixel, NaN on masked
+        pixels, and per quasar ``chi2`` (the sum of its squares over the kept pixels) and ``num_kept``.  This is the
+        IN-SAMPLE replicate residual: the pixel's own flux is among the data the posterior was formed from, so
+        it is conservative (residuals come out smaller than leave-one-out ones would); it is not a leave-one-out
+        residual."""
+        lib = self.ctx.lib
+        rq = _lib.PredictiveFluxRequest()
+        sel, keep = self._mixture_request(rq, selection, weights, components, model_weights, meanflux)
+        nsel, S = sel.size, self.num_samples
+        # refused requests never reach the device
+        _lib.check(lib.gpdla_predictive_flux_validate(C.byref(rq), self.num_quasars, S, int(self.ctx.has_lls_samples)))
+        total = int(self.unmasked_counts()[sel].sum())
+        rq.capacity = total
+        out = {"offsets": np.zeros(nsel + 1, dtype=np.int64), "status": np.zeros(nsel, dtype=np.int32)}
+        out.update({name: np.empty(total) for name in PREDICTIVE_FLUX_ARRAYS})
+        pf = _lib.PredictiveFlux()
+        pf.offsets = out["offsets"].ctypes.data_as(_i64p)
+        pf.status = out["status"].ctypes.data_as(_i32p)
+        for name in PREDICTIVE_FLUX_ARRAYS:
+            setattr(pf, name, out[name].ctypes.data_as(_dp))
+        _lib.check(lib.gpdla_batch_predictive_flux(self.ctx._h, self._h, C.byref(rq), C.byref(pf)))
+        del keep
+        if residuals:
+            y, kept = self.grid_flux(sel)
+            out.update(predictive_residuals(out, y, kept))
         return out
 
     # ---- refined posteriors (DESIGN.md 4.18) ----
@@ -1526,27 +1594,10 @@ def posterior_model_weights(results: dict) -> np.ndarray:
     return np.maximum(np.nan_to_num(np.stack([p_no, p_lls, p_dla], axis=1), nan=0.0), 0.0)
 
 
-def marginal_continuum(model: dict, samples: dict, spectra, results: dict | None = None,
-                       params: Parameters | None = None, selection=None, components=("dla",), model_weights=None,
-                       sample_coefficients: bool = False, sample_rows=None, device: int = 0,
-                       max_quasars_per_batch: int | None = None) -> dict:
-    """The marginal continuum (:meth:`Batch.marginal_continuum`) of the selected quasars of a processed run,
-    batched like :func:`model_spectra`: nothing is swept again, the posterior weights come from the saved
-    sample log-likelihoods.
-
-    ``spectra``, ``results``, ``params``, ``selection``: as :func:`model_spectra`.  ``components``: which of
-    ``"null"``, ``"sub_dla"`` and ``"dla"`` are mixed.  ``model_weights``: ``[nq, 3]`` over ALL quasars of
-    ``spectra`` in the order (null, sub-DLA, DLA), None (equal weights over the listed components) or
-    ``"posteriors"``: (p_no_dlas, p_lls or 0, p_dlas) of ``results``, a quasar whose listed posteriors are all
-    0 or NaN falling back to equal weights.  The tables are ``sample_log_likelihoods_dla`` (``[nq, S]``, or
-    model DLA(1) of ``[nq, max_dlas, S]``) and ``sample_log_likelihoods_lls`` of ``results``;
-    ``sample_rows(idx, name) -> [len(idx), S]`` (``name`` ``"dla"`` or ``"sub_dla"``) supplies the rows
-    instead (a file streamed block by block).  Returns ``selection``, ``offsets``, ``status`` and the arrays of
-    :meth:`Batch.marginal_continuum` in selection order; results do not depend on the batching."""
-    p = params or Parameters()
-    multi = isinstance(p, MultiParameters)
-    spectra = list(spectra)
-    sel = np.arange(len(spectra), dtype=np.int64) if selection is None else np.asarray(selection, dtype=np.int64).reshape(-1)
+def _mixture_inputs(results, components, model_weights, sample_rows):
+    """``(components, sampled, model_weights, sample_rows)`` as :func:`marginal_continuum` and
+    :func:`predictive_flux` take them: ``"posteriors"`` resolved against ``results``, the tables of ``results``
+    behind ``sample_rows`` when none is given."""
     components = tuple(components)
     sampled = [c for c in components if c != "null"]
     if isinstance(model_weights, str):
@@ -1569,6 +1620,31 @@ def marginal_continuum(model: dict, samples: dict, spectra, results: dict | None
                 t = np.asarray(results[key])
                 tables[name] = t if t.ndim == 2 else t[:, 0, :]
         sample_rows = lambda idx, name: tables[name][idx]  # noqa: E731
+    return components, sampled, model_weights, sample_rows
+
+
+def marginal_continuum(model: dict, samples: dict, spectra, results: dict | None = None,
+                       params: Parameters | None = None, selection=None, components=("dla",), model_weights=None,
+                       sample_coefficients: bool = False, sample_rows=None, device: int = 0,
+                       max_quasars_per_batch: int | None = None) -> dict:
+    """The marginal continuum (:meth:`Batch.marginal_continuum`) of the selected quasars of a processed run,
+    batched like :func:`model_spectra`: nothing is swept again, the posterior weights come from the saved
+    sample log-likelihoods.
+
+    ``spectra``, ``results``, ``params``, ``selection``: as :func:`model_spectra`.  ``components``: which of
+    ``"null"``, ``"sub_dla"`` and ``"dla"`` are mixed.  ``model_weights``: ``[nq, 3]`` over ALL quasars of
+    ``spectra`` in the order (null, sub-DLA, DLA), None (equal weights over the listed components) or
+    ``"posteriors"``: (p_no_dlas, p_lls or 0, p_dlas) of ``results``, a quasar whose listed posteriors are all
+    0 or NaN falling back to equal weights.  The tables are ``sample_log_likelihoods_dla`` (``[nq, S]``, or
+    model DLA(1) of ``[nq, max_dlas, S]``) and ``sample_log_likelihoods_lls`` of ``results``;
+    ``sample_rows(idx, name) -> [len(idx), S]`` (``name`` ``"dla"`` or ``"sub_dla"``) supplies the rows
+    instead (a file streamed block by block).  Returns ``selection``, ``offsets``, ``status`` and the arrays of
+    :meth:`Batch.marginal_continuum` in selection order; results do not depend on the batching."""
+    p = params or Parameters()
+    multi = isinstance(p, MultiParameters)
+    spectra = list(spectra)
+    sel = np.arange(len(spectra), dtype=np.int64) if selection is None else np.asarray(selection, dtype=np.int64).reshape(-1)
+    components, sampled, model_weights, sample_rows = _mixture_inputs(results, components, model_weights, sample_rows)
     S = np.asarray(samples["offset_samples"]).size
     k = np.asarray(model["M"]).shape[1]
     longest = max([np.asarray(spectra[i]["wavelengths"]).size for i in sel], default=1)
@@ -1613,6 +1689,84 @@ def marginal_continuum(model: dict, samples: dict, spectra, results: dict | None
             out[name] = np.concatenate(parts[name], axis=0)
         elif name != "sample_coefficients" or sample_coefficients:
             out[name] = np.zeros(shapes[name])
+    return out
+
+
+PREDICTIVE_FLUX_ARRAYS = ("flux_mean", "flux_var", "flux_var_within", "flux_var_between", "noise_var")
+PREDICTIVE_FLUX_RESIDUALS = ("residual",)
+PREDICTIVE_FLUX_ROWS = ("chi2", "num_kept")
+
+
+def predictive_residuals(pf: dict, flux, kept) -> dict:
+    """``residual`` = (y - flux_mean) / sqrt(flux_var + noise_var) per pixel (NaN on masked pixels), and per
+    quasar ``chi2`` and ``num_kept``, from what :meth:`Batch.predictive_flux` returns and the observed flux and
+    kept flags on the same grid.  The in-sample replicate residual (conservative), not a leave-one-out one."""
+    flux, kept = np.asarray(flux, dtype=np.float64), np.asarray(kept, dtype=bool)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        res = np.where(kept, (flux - pf["flux_mean"]) / np.sqrt(pf["flux_var"] + pf["noise_var"]), np.nan)
+    off = np.asarray(pf["offsets"])
+    n = off.size - 1
+    chi2, num = np.full(n, np.nan), np.zeros(n, dtype=np.int64)
+    for s in range(n):
+        r, kp = res[off[s]:off[s + 1]], kept[off[s]:off[s + 1]]
+        num[s] = int(kp.sum())
+        chi2[s] = float(np.sum(r[kp] ** 2)) if kp.any() else np.nan
+    return {"residual": res, "chi2": chi2, "num_kept": num}
+
+
+def predictive_flux(model: dict, samples: dict, spectra, results: dict | None = None,
+                    params: Parameters | None = None, selection=None, components=("dla",), model_weights=None,
+                    residuals: bool = False, sample_rows=None, device: int = 0,
+                    max_quasars_per_batch: int | None = None) -> dict:
+    """The posterior predictive flux (:meth:`Batch.predictive_flux`) of the selected quasars of a processed run,
+    batched like :func:`marginal_continuum`, whose arguments these are: nothing is swept again, the posterior weights
+    come from the saved sample log-likelihoods; ``model_weights="posteriors"`` mixes by
+    :func:`posterior_model_weights`.  ``residuals``: also the in-sample replicate ``residual`` per pixel and
+    ``chi2``, ``num_kept`` per quasar (conservative; not leave-one-out).  Returns ``selection``, ``offsets``,
+    ``status`` and the arrays of :meth:`Batch.predictive_flux` in selection order; results do not depend on the
+    batching."""
+    p = params or Parameters()
+    multi = isinstance(p, MultiParameters)
+    spectra = list(spectra)
+    sel = np.arange(len(spectra), dtype=np.int64) if selection is None else np.asarray(selection, dtype=np.int64).reshape(-1)
+    components, sampled, model_weights, sample_rows = _mixture_inputs(results, components, model_weights, sample_rows)
+    S = np.asarray(samples["offset_samples"]).size
+    k = np.asarray(model["M"]).shape[1]
+    longest = max([np.asarray(spectra[i]["wavelengths"]).size for i in sel], default=1)
+    per = int(max_quasars_per_batch or default_batch_size(sel.size, longest, k, S, 1))
+    out = {"selection": sel, "offsets": np.zeros(sel.size + 1, dtype=np.int64), "status": np.zeros(sel.size, dtype=np.int32)}
+    names = PREDICTIVE_FLUX_ARRAYS + ((PREDICTIVE_FLUX_RESIDUALS + PREDICTIVE_FLUX_ROWS) if residuals else ())
+    parts = {name: [] for name in names}
+    if sel.size:
+        ctx = Context(device, p)
+        batch = None
+        try:
+            ctx.set_model(model)
+            ctx.set_samples(samples)
+            md = p.max_dlas if multi else 0
+            for lo, hi in batch_blocks(sel.size, per):
+                idx = sel[lo:hi]
+                n = idx.size
+                args = ([spectra[i] for i in idx], np.zeros(n), np.zeros((n, md)) if multi else np.zeros(n),
+                        np.zeros(n) if multi else None)
+                if batch is None:
+                    batch = ctx.upload(*args)
+                else:
+                    batch.reload(*args)
+                res = batch.predictive_flux(weights={c: np.asarray(sample_rows(idx, c), dtype=np.float64) for c in sampled} or None,
+                                            components=components,
+                                            model_weights=None if model_weights is None else model_weights[idx],
+                                            residuals=residuals)
+                out["offsets"][lo + 1:hi + 1] = out["offsets"][lo] + res["offsets"][1:]
+                out["status"][lo:hi] = res["status"]
+                for name in names:
+                    parts[name].append(res[name])
+        finally:
+            if batch is not None:
+                batch.close()
+            ctx.close()
+    for name in names:
+        out[name] = np.concatenate(parts[name]) if parts[name] else np.zeros(0, dtype=np.int64 if name == "num_kept" else np.float64)
     return out
 
 

@@ -35,6 +35,7 @@
 #include "spectra_kernels.hpp"
 #include "spectra_multi_kernels.hpp"
 #include "marginal_continuum_kernels.hpp"
+#include "predictive_flux_kernels.hpp"
 #include "mock_kernels.hpp"
 #include "sample_kernels.hpp"
 #include "preload_kernels.hpp"
@@ -59,6 +60,7 @@ using namespace gpdla;
 #include "host_spectra.hpp"
 #include "host_spectra_multi.hpp"
 #include "host_marginal_continuum.hpp"
+#include "host_predictive_flux.hpp"
 #include "host_mock.hpp"
 #include "host_samples.hpp"
 #include "host_preload.hpp"

@@ -268,7 +268,10 @@ struct McSolveArgs {
   double *sample_coef;  // [nsel][S][k] in sample order, or nullptr
 };
 
-__global__ __launch_bounds__(256) void k_mc_solve(McSolveArgs a) {
+// KEEP (the predictive flux): the sample's scratch row, consumed by then, is overwritten in place
+// with [vech(Sigma_i) | c_i], and no partial sums are written (a.part is not read).
+template <bool KEEP>
+__device__ __forceinline__ void mc_solve_body(const McSolveArgs &a, double *keep) {
   constexpr int kMine = (kMcNb + 63) / 64;
   __shared__ double s_L[4][kMcNb + GPDLA_MAX_K];  // packed L, then v (then c_i)
   __shared__ double s_X[4][kMcNb + GPDLA_MAX_K];  // packed L^-1, then z
@@ -280,7 +283,7 @@ __global__ __launch_bounds__(256) void k_mc_solve(McSolveArgs a) {
   const int64_t s = a.s0 + sl;
   const QuasarMeta m = a.meta[a.sel[s]];
   const int k = a.k, nb = k * (k + 1) / 2, ncol = nb + k, plen = k + 2 * nb;
-  double *part = a.part + (sl * a.chunks + chunk) * (int64_t)plen;
+  double *part = KEEP ? nullptr : a.part + (sl * a.chunks + chunk) * (int64_t)plen;
   const bool off = m.status != 0 || a.pm[s] == 0.0;
   if (wave == 0) {
     const int64_t pos = (int64_t)chunk * kMcSolveChunk + lane;
@@ -298,7 +301,8 @@ __global__ __launch_bounds__(256) void k_mc_solve(McSolveArgs a) {
   __syncthreads();
   const int nl = s_nlive;
   if (nl == 0) {
-    for (int e = tid; e < plen; e += 256) part[e] = 0.0;
+    if constexpr (!KEEP)
+      for (int e = tid; e < plen; e += 256) part[e] = 0.0;
     if (tid == 0) a.notpd[sl * a.chunks + chunk] = 0;
     return;
   }
@@ -322,6 +326,7 @@ __global__ __launch_bounds__(256) void k_mc_solve(McSolveArgs a) {
     const int64_t i = a.perm[pos];
     const double wi = a.w[s * a.S + i];
     const double *row = a.scratch + (sl * a.S + pos) * (int64_t)ncol;
+    double *krow = KEEP ? keep + (sl * a.S + pos) * (int64_t)ncol : nullptr;
     if (has) {
 #pragma unroll
       for (int t = 0; t < kMine; ++t)
@@ -371,6 +376,7 @@ __global__ __launch_bounds__(256) void k_mc_solve(McSolveArgs a) {
       v[lane] = sum;
       accC += wi * sum;
       if (a.sample_coef) a.sample_coef[(s * a.S + i) * k + lane] = sum;
+      if constexpr (KEEP) krow[nb + lane] = sum;
     }
     __syncthreads();
     if (has) {
@@ -384,11 +390,17 @@ __global__ __launch_bounds__(256) void k_mc_solve(McSolveArgs a) {
         }
         accW[t] += wi * sig;
         accV[t] += wi * (v[ea[t]] * v[eb[t]]);
+        if constexpr (KEEP) krow[lane + 64 * t] = sig;
       }
     }
     __syncthreads();
   }
   if (bad) s_bad = 1;
+  if constexpr (KEEP) {
+    __syncthreads();
+    if (tid == 0) a.notpd[sl * a.chunks + chunk] = s_bad;
+    return;
+  }
   // the four waves in wave order
 #pragma unroll
   for (int t = 0; t < kMine; ++t)
@@ -414,6 +426,8 @@ __global__ __launch_bounds__(256) void k_mc_solve(McSolveArgs a) {
   }
   if (tid == 0) a.notpd[sl * a.chunks + chunk] = s_bad;
 }
+
+__global__ __launch_bounds__(256) void k_mc_solve(McSolveArgs a) { mc_solve_body<false>(a, nullptr); }
 
 // ------------------------------------------------------------------------------------------
 // k_mc_finish: one block per selected quasar of a launch group.

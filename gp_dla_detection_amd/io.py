@@ -920,6 +920,50 @@ def save_marginal_continuum(path: str, mc: dict, **run_metadata) -> None:
         w.close()
 
 
+#: the posterior predictive flux: per-pixel cells, and columns / matrices
+PREDICTIVE_FLUX_CELLS = ("flux_mean", "flux_var", "flux_var_within", "flux_var_between", "noise_var", "residual")
+PREDICTIVE_FLUX_COLUMNS = ("chi2", "num_kept")
+
+
+def save_predictive_flux(path: str, pf: dict, **run_metadata) -> None:
+    """What :func:`api.predictive_flux` returns as a ``-v7.3`` file, in the layout of :func:`save_marginal_continuum`:
+    ``quasar_ind`` (1-based), ``num_pixels`` and ``status`` as columns, the five per-pixel arrays (and ``residual``
+    when present) as ragged N x 1 cell arrays, ``chi2`` and ``num_kept`` as columns and ``model_weights`` [N x 3] as a
+    matrix when present.  :func:`load_predictive_flux` reads it."""
+    off = np.asarray(pf["offsets"], dtype=np.int64)
+    nsel = off.size - 1
+    w = _MatWriter(path)
+    try:
+        for k, v in run_metadata.items():
+            w.put(k, v)
+        w.put("quasar_ind", np.asarray(pf.get("selection", np.arange(nsel)), dtype=np.float64) + 1)
+        w.put("num_pixels", np.diff(off).astype(np.float64))
+        w.put("status", np.asarray(pf.get("status", np.zeros(nsel)), dtype=np.float64))
+        for name in PREDICTIVE_FLUX_CELLS:
+            if name in pf:
+                v = np.asarray(pf[name], dtype=np.float64)
+                w.put(name, [v[off[i]:off[i + 1]].reshape(-1, 1) for i in range(nsel)])
+        for name in PREDICTIVE_FLUX_COLUMNS:
+            if name in pf:
+                w.put(name, np.asarray(pf[name], dtype=np.float64))
+        if "model_weights" in pf:
+            w.put("model_weights", np.ascontiguousarray(pf["model_weights"], dtype=np.float64))
+    finally:
+        w.close()
+
+
+def load_predictive_flux(path: str) -> dict:
+    """The reader of :func:`save_predictive_flux`: :func:`load_model_spectra`'s layout (``selection`` 0-based,
+    ``offsets``, ``status``, the per-pixel products as LISTS of per-quasar vectors), ``chi2`` flat and ``num_kept`` as
+    integers."""
+    out = load_model_spectra(path)
+    if "chi2" in out:
+        out["chi2"] = _vec(out["chi2"])
+    if "num_kept" in out:
+        out["num_kept"] = _vec(out["num_kept"]).astype(np.int64)
+    return out
+
+
 def load_model_spectra(path: str) -> dict:
     """The reader of :func:`save_model_spectra`: ``selection`` (0-based), ``offsets``, ``status``, every
     stored product as a LIST of per-quasar vectors, the absorbers as lists, the metadata as stored."""

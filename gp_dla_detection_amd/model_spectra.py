@@ -135,12 +135,11 @@ def run(preloaded: str, catalog: str, model_file: str, samples_file: str, proces
     return res
 
 
-def run_marginal_continuum(preloaded: str, catalog: str, model_file: str, samples_file: str, processed: str, out: str,
-                           p_dla: float | None = None, indices=None, components=("dla",), model_weights="posteriors",
-                           multi: bool | None = None, device: int = 0, max_quasars_per_batch: int | None = None) -> dict:
-    """``--marginal-continuum``: :func:`api.marginal_continuum` of the selected quasars of a processed file, its
-    sample tables streamed like the moments' rows, written by :func:`io.save_marginal_continuum`.
-    ``model_weights``: ``"posteriors"`` (p_no_dlas, p_lls or 0, p_dlas of the file) or ``"equal"``."""
+def _run_mixture(call, preloaded, catalog, model_file, samples_file, processed, p_dla, indices, components, model_weights,
+                 multi, device, max_quasars_per_batch, **more):
+    """What ``--marginal-continuum`` and ``--predictive-flux`` share: the selection of a processed file, its spectra,
+    its sample tables streamed like the moments' rows, and ``call`` (:func:`api.marginal_continuum` or
+    :func:`api.predictive_flux`) on them.  Returns ``(result with its selection, is_multi, components)``."""
     small = ["model_posteriors", "p_dlas", "p_no_dlas", "p_lls", "test_ind"]
     results = {k: np.asarray(v, dtype=np.float64).reshape(-1) if k.startswith("p_") else v
                for k, v in io.loadmat73(processed, small).items()}
@@ -155,16 +154,42 @@ def run_marginal_continuum(preloaded: str, catalog: str, model_file: str, sample
     readers = {name: sample_row_reader(processed, sub_dla=name == "sub_dla") for name in components if name != "null"}
     res_sel = {k: v[sel] for k, v in results.items() if k.startswith("p_")}
     try:  # the loaded list holds the selected quasars only: positions 0 .. len(sel) - 1 map to sel
-        res = api.marginal_continuum(model, samples, spectra_sel, res_sel, params=MultiParameters() if is_multi else Parameters(),
-                                     components=components, model_weights="posteriors" if model_weights == "posteriors" else None,
-                                     sample_rows=lambda idx, name: readers[name][0](sel[idx]), device=device,
-                                     max_quasars_per_batch=max_quasars_per_batch)
+        res = call(model, samples, spectra_sel, res_sel, params=MultiParameters() if is_multi else Parameters(),
+                   components=components, model_weights="posteriors" if model_weights == "posteriors" else None,
+                   sample_rows=lambda idx, name: readers[name][0](sel[idx]), device=device,
+                   max_quasars_per_batch=max_quasars_per_batch, **more)
     finally:
         for _, close in readers.values():
             close()
     res["selection"] = sel
+    return res, is_multi, components
+
+
+def run_marginal_continuum(preloaded: str, catalog: str, model_file: str, samples_file: str, processed: str, out: str,
+                           p_dla: float | None = None, indices=None, components=("dla",), model_weights="posteriors",
+                           multi: bool | None = None, device: int = 0, max_quasars_per_batch: int | None = None) -> dict:
+    """``--marginal-continuum``: :func:`api.marginal_continuum` of the selected quasars of a processed file, its
+    sample tables streamed like the moments' rows, written by :func:`io.save_marginal_continuum`.
+    ``model_weights``: ``"posteriors"`` (p_no_dlas, p_lls or 0, p_dlas of the file) or ``"equal"``."""
+    res, is_multi, components = _run_mixture(api.marginal_continuum, preloaded, catalog, model_file, samples_file, processed,
+                                             p_dla, indices, components, model_weights, multi, device, max_quasars_per_batch)
     io.save_marginal_continuum(out, res, processed_file=str(processed), multi_dla=np.float64(is_multi),
                                components=",".join(components))
+    return res
+
+
+def run_predictive_flux(preloaded: str, catalog: str, model_file: str, samples_file: str, processed: str, out: str,
+                        p_dla: float | None = None, indices=None, components=("dla",), model_weights="posteriors",
+                        residuals: bool = False, multi: bool | None = None, device: int = 0,
+                        max_quasars_per_batch: int | None = None) -> dict:
+    """``--predictive-flux``: :func:`api.predictive_flux` of the selected quasars of a processed file, its sample
+    tables streamed like the moments' rows, written by :func:`io.save_predictive_flux`.  The arguments are those of
+    :func:`run_marginal_continuum`; ``residuals``: also the in-sample replicate residuals (``--residuals``)."""
+    res, is_multi, components = _run_mixture(api.predictive_flux, preloaded, catalog, model_file, samples_file, processed,
+                                             p_dla, indices, components, model_weights, multi, device, max_quasars_per_batch,
+                                             residuals=residuals)
+    io.save_predictive_flux(out, res, processed_file=str(processed), multi_dla=np.float64(is_multi),
+                            components=",".join(components))
     return res
 
 
@@ -182,13 +207,25 @@ def main(argv=None) -> int:
     ap.add_argument("--marginal-continuum", action="store_true",
                     help="write the marginal continuum instead (DESIGN.md 4.23): its posterior mean and variance over "
                          "the sample tables and the models")
-    ap.add_argument("--components", type=str, default="dla", help="--marginal-continuum: any of null,sub_dla,dla")
+    ap.add_argument("--predictive-flux", action="store_true",
+                    help="write the posterior predictive flux instead (DESIGN.md 4.24): per-pixel mean and variance of "
+                         "absorption times continuum over the sample tables and the models")
+    ap.add_argument("--residuals", action="store_true",
+                    help="--predictive-flux: also the in-sample replicate residuals, chi2 and num_kept")
+    ap.add_argument("--components", type=str, default="dla",
+                    help="--marginal-continuum, --predictive-flux: any of null,sub_dla,dla")
     ap.add_argument("--model-weights", choices=("posteriors", "equal"), default="posteriors",
-                    help="--marginal-continuum: mix the components by the file's posteriors, or equally")
+                    help="--marginal-continuum, --predictive-flux: mix the components by the file's posteriors, or equally")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--max-quasars-per-batch", type=int, default=None)
     a = ap.parse_args(argv)
     idx = None if a.indices is None else [int(x) for x in a.indices.split(",") if x]
+    if a.predictive_flux:
+        res = run_predictive_flux(a.preloaded, a.catalog, a.model, a.samples, a.processed, a.out, p_dla=a.p_dla, indices=idx,
+                                  components=tuple(x for x in a.components.split(",") if x), model_weights=a.model_weights,
+                                  residuals=a.residuals, device=a.device, max_quasars_per_batch=a.max_quasars_per_batch)
+        print(f"wrote {a.out}: {res['selection'].size} quasars, {int(res['offsets'][-1])} grid pixels")
+        return 0
     if a.marginal_continuum:
         res = run_marginal_continuum(a.preloaded, a.catalog, a.model, a.samples, a.processed, a.out, p_dla=a.p_dla, indices=idx,
                                      components=tuple(x for x in a.components.split(",") if x), model_weights=a.model_weights,

@@ -1322,6 +1322,74 @@ int gpdla_marginal_continuum_validate(const gpdla_marginal_continuum_request *re
 int gpdla_batch_marginal_continuum(gpdla_context *ctx, gpdla_batch *batch, const gpdla_marginal_continuum_request *request,
                                    gpdla_marginal_continuum *out);
 
+/* ---------------------------------------------------------------------------------------------
+ * Posterior predictive flux: per pixel, the mean and variance of the model flux -- absorption times continuum --
+ * over the sample tables and over the models.  Additive: GPDLA_ABI_VERSION is unchanged.  fp64
+ * throughout; tests/predictive_flux_restatement.py states the same in NumPy.
+ *
+ * Quasar q, component m of (null, sub-DLA table, DLA table) and sample i of weight w_i > 0 are exactly those of
+ * gpdla_batch_marginal_continuum above: the same prepared rows (y, mu, M, omega2, nu; meanflux != 0: the
+ * suppressed rows), the same broadened profile a_i on the quasar's grid (z_i, N_i from nhi_samples, or
+ * lls_nhi_samples for the sub-DLA table), the same weights w_i (exp(l_i - max l) / Sum, NaN -> 0), and per sample
+ *   d_i = a_i^2 omega2 + nu,  B_i = I + M' diag(a_i^2 / d_i) M,  v_i = M' (a_i (y - a_i mu) / d_i),
+ *   c_i = B_i^-1 v_i,  Sigma_i = B_i^-1,
+ * the posterior mean and covariance of the coefficients c ~ N(0, I) given sample i.  The model weights p_m are
+ * per quasar, each row non-negative, finite, of positive sum and normalised by its sum (NULL: (0, 0, 1)).
+ * For EVERY pixel p of the unmasked-range grid, mu_p and m_p are interpolated (and suppressed under meanflux)
+ * as for continuum_mean; a masked pixel is treated like a kept one.  Per sample
+ *   t_ip = mu_p + m_p' c_i  (the continuum given sample i),  s_ip = m_p' Sigma_i m_p  (its variance),
+ *   f_ip = a_ip t_ip        (the model flux given sample i).
+ * The null component has a = 1, c_0, Sigma_0 and one "sample" of weight 1.  Per component
+ *   F1 = Sum w_i f_ip,  F2 = Sum w_i f_ip^2,  FW = Sum w_i a_ip^2 s_ip,  FD = Sum w_i (a_ip^2 omega2_p + nu_p),
+ * and the mixture over the models, in the order (null, sub-DLA, DLA):
+ *   flux_mean        = Sum p_m F1_m
+ *   flux_var_within  = Sum p_m FW_m                             (the GP's own spread, given the absorber)
+ *   flux_var_between = max(Sum p_m F2_m - flux_mean^2, 0)       (the spread over absorbers and models)
+ *   flux_var         = flux_var_within + flux_var_between
+ *   noise_var        = Sum p_m FD_m on kept pixels, NaN on masked ones (they have no omega2 and nu).
+ * E[a t] is not E[a] E[t]: c_i moves with the absorber, which is why this is not a product of mean_absorption
+ * and continuum_mean.  Sum w f^2 - (Sum w f)^2 is evaluated unfused, so a one-hot weight row gives a
+ * flux_var_between of exactly 0.
+ * As for continuum and continuum_var, flux_var is the variance of the LOW-RANK, NOISE-FREE model flux: the
+ * pixel-diagonal omega term and the measurement noise are left out of it.  flux_var + noise_var is the variance
+ * of a REPLICATE observation of the pixel: a new draw of the pixel-diagonal term and of the noise under the same
+ * posterior.  These are in-sample moments (the pixel's own flux is in the data the posterior was formed from),
+ * not leave-one-out ones.
+ * A component of weight exactly 0 is not evaluated; a sample of weight exactly 0 is never touched (its B_i is
+ * never factorised, its column density may be NaN).  status: the quasar's sweep status (1, 3: NaN rows); 4 = a
+ * B_i of positive weight, or B_0, is not positive definite (NaN rows).  A table of positive model weight whose
+ * row has no weights (all NaN, all -inf, a +inf) gives NaN rows and status 0.  For a multi-DLA batch the
+ * resident tables are model DLA(1) and the sub-DLA table.  A conditioned batch is refused.  Sums run in a fixed
+ * order without atomics: outputs are bit-identical for any selection order and launch grouping and for the
+ * resident and the host form of a table.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct {
+  int64_t num_selected;
+  const int64_t *selection;          /* [num_selected] quasars of the batch; NULL = 0 .. num_selected-1 */
+  int32_t weights_source;            /* GPDLA_SPECTRA_WEIGHTS_RESIDENT or _HOST (_NONE: null component only) */
+  const double *sample_log_likelihoods_dla; /* [num_selected][S], _HOST, where a row weighs the DLA table */
+  const double *sample_log_likelihoods_lls; /* [num_selected][S], _HOST, where a row weighs the sub-DLA table */
+  const double *model_weights;       /* [num_selected][3] (null, sub-DLA, DLA), or NULL = (0, 0, 1) */
+  int32_t meanflux;                  /* != 0: prepared rows of the mean-flux model (multi :245-293) */
+  int64_t capacity;                  /* entries of each per-pixel output array */
+} gpdla_predictive_flux_request;
+typedef struct {
+  int64_t *offsets;                  /* [num_selected + 1]; required */
+  double *flux_mean, *flux_var, *flux_var_within, *flux_var_between, *noise_var; /* per pixel; any may be NULL */
+  int32_t *status;                   /* [num_selected] or NULL */
+} gpdla_predictive_flux;
+/* The checks gpdla_batch_predictive_flux makes before its first device call, which are those of
+ * gpdla_marginal_continuum_validate: a selection index outside the batch, a negative, NaN or infinite model
+ * weight or a row without a positive sum, a sampled component without a weights source (or a host source
+ * without that table), the sub-DLA table without lls_nhi_samples.  Returns GPDLA_OK or
+ * GPDLA_ERR_INVALID_ARGUMENT.  Needs no GPU. */
+int gpdla_predictive_flux_validate(const gpdla_predictive_flux_request *request, int64_t num_quasars,
+                                   int64_t num_samples, int has_lls_nhi_samples);
+/* With gpdla_context_set_timing enabled, gpdla_context_last_sweep_ms reports the k_mc_contract, k_pf_solve,
+ * k_pf_live, k_pf_pixels and k_pf_finish launches of the call. */
+int gpdla_batch_predictive_flux(gpdla_context *ctx, gpdla_batch *batch, const gpdla_predictive_flux_request *request,
+                                gpdla_predictive_flux *out);
+
 #ifdef __cplusplus
 }
 #endif
