@@ -20,6 +20,7 @@ PyTorch-ROCm tensors are staging only; all arithmetic happens in the HIP kernels
 from __future__ import annotations
 
 import ctypes as C
+from contextlib import closing
 from types import SimpleNamespace
 
 import numpy as np
@@ -414,6 +415,25 @@ class Batch:
         _lib.check(self.ctx.lib.gpdla_batch_unmasked_counts(self.ctx._h, self._h, n.ctypes.data_as(_i64p)))
         return n
 
+    def _grid_product(self, name: str, rq, sel, st, shapes, *validate_args) -> dict:
+        """Run the grid product ``name`` (gpdla_<name>_validate, then gpdla_batch_<name>) for request ``rq`` over the
+        selection ``sel`` into the output struct ``st``: ``offsets`` and ``status`` plus one float64 array per entry
+        of ``shapes(total)`` (field name -> shape; ``total`` = the grid pixels of the selection, the capacity)."""
+        lib = self.ctx.lib
+        # refused requests never reach the device
+        _lib.check(getattr(lib, f"gpdla_{name}_validate")(C.byref(rq), self.num_quasars, self.num_samples,
+                                                          int(self.ctx.has_lls_samples), *validate_args))
+        total = int(self.unmasked_counts()[sel].sum())
+        rq.capacity = total
+        out = {"offsets": np.zeros(sel.size + 1, dtype=np.int64), "status": np.zeros(sel.size, dtype=np.int32)}
+        st.offsets = out["offsets"].ctypes.data_as(_i64p)
+        st.status = out["status"].ctypes.data_as(_i32p)
+        for field, shape in shapes(total).items():
+            out[field] = np.empty(shape)
+            setattr(st, field, out[field].ctypes.data_as(_dp))
+        _lib.check(getattr(lib, f"gpdla_batch_{name}")(self.ctx._h, self._h, C.byref(rq), C.byref(st)))
+        return out
+
     def model_spectra(self, selection=None, absorbers=None, weights=None, sub_dla: bool = False,
                       meanflux: bool | None = None, products=("map", "moments", "continuum")) -> dict:
         """What the fitted model looks like on the selected quasars (gpdla_batch_model_spectra), per
@@ -432,7 +452,6 @@ class Batch:
         nothing at an unmeasured pixel and is left out).
         Returns ``offsets [nsel + 1]``, ``status [nsel]`` and the flat per-pixel arrays; quasar s of the
         selection owns ``[offsets[s], offsets[s + 1])`` (:func:`split_cells` cuts them up)."""
-        lib = self.ctx.lib
         sel = self._selection(selection)
         nsel = sel.size
         rq = _lib.ModelSpectraRequest()
@@ -455,23 +474,10 @@ class Batch:
             rq.weights_source, rq.sample_log_likelihoods = _lib.SPECTRA_WEIGHTS_HOST, w.ctypes.data_as(_dp)
         rq.sub_dla = int(bool(sub_dla))
         rq.meanflux = int(bool(self.max_dlas) if meanflux is None else bool(meanflux))
-        # refused requests never reach the device
-        _lib.check(lib.gpdla_model_spectra_validate(C.byref(rq), self.num_quasars, self.num_samples,
-                                                    int(self.ctx.has_lls_samples)))
-        total = int(self.unmasked_counts()[sel].sum())
-        rq.capacity = total
-        out = {"offsets": np.zeros(nsel + 1, dtype=np.int64), "status": np.zeros(nsel, dtype=np.int32)}
-        ms = _lib.ModelSpectra()
-        ms.offsets = out["offsets"].ctypes.data_as(_i64p)
-        ms.status = out["status"].ctypes.data_as(_i32p)
         names = {"map": ("map_absorption",), "moments": ("mean_absorption", "var_absorption"),
                  "continuum": ("continuum", "model_flux")}
-        for p in set(products):
-            for name in names[p]:
-                out[name] = np.empty(total)
-                setattr(ms, name, out[name].ctypes.data_as(_dp))
-        _lib.check(lib.gpdla_batch_model_spectra(self.ctx._h, self._h, C.byref(rq), C.byref(ms)))
-        return out
+        return self._grid_product("model_spectra", rq, sel, _lib.ModelSpectra(),
+                                  lambda total: {name: total for p in set(products) for name in names[p]})
 
     def model_spectra_multi(self, selection=None, tables="resident", model_weights=None, models=None,
                             products=("models", "average"), meanflux: bool | None = None, sub_dla: bool = True) -> dict:
@@ -492,7 +498,6 @@ class Batch:
         (``expected_absorption``, ``expected_var_absorption``).
         Returns those with ``offsets [nsel + 1]``, ``status [nsel]`` and ``model_flags [nsel]`` (bit n-1: model
         DLA(n) has no weight; bit 30: the sub-DLA model)."""
-        lib = self.ctx.lib
         sel = self._selection(selection)
         nsel, S = sel.size, self.num_samples
         rq = _lib.ModelSpectraMultiRequest()
@@ -537,28 +542,21 @@ class Batch:
         products = set(products)
         rq.products = int(sum(bits[p] for p in products))
         rq.meanflux = int(bool(self.max_dlas) if meanflux is None else bool(meanflux))
-        # refused requests never reach the device
-        _lib.check(lib.gpdla_model_spectra_multi_validate(C.byref(rq), self.num_quasars, S, int(self.ctx.has_lls_samples),
-                                                          self.max_dlas, int(self._multi_processed)))
-        total = int(self.unmasked_counts()[sel].sum())
-        rq.capacity = total
-        out = {"offsets": np.zeros(nsel + 1, dtype=np.int64), "status": np.zeros(nsel, dtype=np.int32),
-               "model_flags": np.zeros(nsel, dtype=np.uint32)}
+        flags = np.zeros(nsel, dtype=np.uint32)
         ms = _lib.ModelSpectraMulti()
-        ms.offsets = out["offsets"].ctypes.data_as(_i64p)
-        ms.status = out["status"].ctypes.data_as(_i32p)
-        ms.model_flags = out["model_flags"].ctypes.data_as(C.POINTER(C.c_uint32))
-        shapes = {}
-        if "models" in products:
-            shapes.update(mean_absorption_models=(md, total), var_absorption_models=(md, total))
-            if sub_dla:
-                shapes.update(mean_absorption_lls=(total,), var_absorption_lls=(total,))
-        if "average" in products:
-            shapes.update(expected_absorption=(total,), expected_var_absorption=(total,))
-        for name, shape in shapes.items():
-            out[name] = np.empty(shape)
-            setattr(ms, name, out[name].ctypes.data_as(_dp))
-        _lib.check(lib.gpdla_batch_model_spectra_multi(self.ctx._h, self._h, C.byref(rq), C.byref(ms)))
+        ms.model_flags = flags.ctypes.data_as(C.POINTER(C.c_uint32))
+
+        def shapes(total):
+            shapes = {}
+            if "models" in products:
+                shapes.update(mean_absorption_models=(md, total), var_absorption_models=(md, total))
+                if sub_dla:
+                    shapes.update(mean_absorption_lls=(total,), var_absorption_lls=(total,))
+            if "average" in products:
+                shapes.update(expected_absorption=(total,), expected_var_absorption=(total,))
+            return shapes
+        out = self._grid_product("model_spectra_multi", rq, sel, ms, shapes, self.max_dlas, int(self._multi_processed))
+        out["model_flags"] = flags
         del keep
         return out
 
@@ -631,28 +629,16 @@ class Batch:
         ``coef_cov_between`` ``[nsel, k (k + 1) / 2]`` (packed lower triangles, row by row).  The variance is
         that of the low-rank part of the GP: the pixel-diagonal omega term predicts nothing at an
         unmeasured pixel and is left out, as in ``continuum`` of :meth:`model_spectra`."""
-        lib = self.ctx.lib
         rq = _lib.MarginalContinuumRequest()
         sel, keep = self._mixture_request(rq, selection, weights, components, model_weights, meanflux)
         nsel, S, k = sel.size, self.num_samples, self.ctx.k
         rq.sample_coefficients = int(bool(sample_coefficients))
-        # refused requests never reach the device
-        _lib.check(lib.gpdla_marginal_continuum_validate(C.byref(rq), self.num_quasars, S, int(self.ctx.has_lls_samples)))
-        total = int(self.unmasked_counts()[sel].sum())
-        rq.capacity = total
         nb = k * (k + 1) // 2
-        out = {"offsets": np.zeros(nsel + 1, dtype=np.int64), "status": np.zeros(nsel, dtype=np.int32),
-               "continuum_mean": np.empty(total), "continuum_var": np.empty(total), "continuum_var_between": np.empty(total),
-               "coef_mean": np.empty((nsel, k)), "coef_cov_within": np.empty((nsel, nb)), "coef_cov_between": np.empty((nsel, nb))}
+        rows = {"coef_mean": (nsel, k), "coef_cov_within": (nsel, nb), "coef_cov_between": (nsel, nb)}
         if sample_coefficients:
-            out["sample_coefficients"] = np.empty((nsel, S, k))
-        mc = _lib.MarginalContinuum()
-        mc.offsets = out["offsets"].ctypes.data_as(_i64p)
-        mc.status = out["status"].ctypes.data_as(_i32p)
-        for name in out:
-            if name not in ("offsets", "status"):
-                setattr(mc, name, out[name].ctypes.data_as(_dp))
-        _lib.check(lib.gpdla_batch_marginal_continuum(self.ctx._h, self._h, C.byref(rq), C.byref(mc)))
+            rows["sample_coefficients"] = (nsel, S, k)
+        out = self._grid_product("marginal_continuum", rq, sel, _lib.MarginalContinuum(),
+                                 lambda total: {**{name: total for name in MARGINAL_CONTINUUM_ARRAYS}, **rows})
         del keep
         return out
 
@@ -694,22 +680,10 @@ class Batch:
         IN-SAMPLE replicate residual: the pixel's own flux is among the data the posterior was formed from, so
         it is conservative (residuals come out smaller than leave-one-out ones would); it is not a leave-one-out
         residual."""
-        lib = self.ctx.lib
         rq = _lib.PredictiveFluxRequest()
         sel, keep = self._mixture_request(rq, selection, weights, components, model_weights, meanflux)
-        nsel, S = sel.size, self.num_samples
-        # refused requests never reach the device
-        _lib.check(lib.gpdla_predictive_flux_validate(C.byref(rq), self.num_quasars, S, int(self.ctx.has_lls_samples)))
-        total = int(self.unmasked_counts()[sel].sum())
-        rq.capacity = total
-        out = {"offsets": np.zeros(nsel + 1, dtype=np.int64), "status": np.zeros(nsel, dtype=np.int32)}
-        out.update({name: np.empty(total) for name in PREDICTIVE_FLUX_ARRAYS})
-        pf = _lib.PredictiveFlux()
-        pf.offsets = out["offsets"].ctypes.data_as(_i64p)
-        pf.status = out["status"].ctypes.data_as(_i32p)
-        for name in PREDICTIVE_FLUX_ARRAYS:
-            setattr(pf, name, out[name].ctypes.data_as(_dp))
-        _lib.check(lib.gpdla_batch_predictive_flux(self.ctx._h, self._h, C.byref(rq), C.byref(pf)))
+        out = self._grid_product("predictive_flux", rq, sel, _lib.PredictiveFlux(),
+                                 lambda total: {name: total for name in PREDICTIVE_FLUX_ARRAYS})
         del keep
         if residuals:
             y, kept = self.grid_flux(sel)
@@ -1484,6 +1458,49 @@ def _take_absorbers(absorbers, idx):
     return new, np.asarray(z, dtype=np.float64)[take], np.asarray(n, dtype=np.float64)[take]
 
 
+def _block_size(max_quasars_per_batch, spectra, idx, model: dict, samples: dict) -> int:
+    """Quasars a block of the drivers below: what the caller asked for, or :func:`default_batch_size`."""
+    longest = max([np.asarray(spectra[i]["wavelengths"]).size for i in idx], default=1)
+    return int(max_quasars_per_batch or default_batch_size(len(idx), longest, np.asarray(model["M"]).shape[1],
+                                                           np.asarray(samples["offset_samples"]).size, 1))
+
+
+def _resident_blocks(model: dict, samples: dict, spectra, idx, params: Parameters, device: int, per: int):
+    """Generator over the quasars ``idx`` of ``spectra`` in blocks of ``per``, each resident in turn in ONE batch of a
+    context of its own (uploaded, then reloaded; placeholder priors, since nothing is swept): yields
+    ``(lo, hi, idx[lo:hi], batch)``.  Batch and context are closed when the generator is (``contextlib.closing``
+    around the loop makes that every exit path)."""
+    if not len(idx):
+        return
+    multi = isinstance(params, MultiParameters)
+    md = params.max_dlas if multi else 0
+    ctx = Context(device, params)
+    batch = None
+    try:
+        ctx.set_model(model)
+        ctx.set_samples(samples)
+        for lo, hi in batch_blocks(len(idx), per):
+            block = idx[lo:hi]
+            n = hi - lo
+            args = ([spectra[i] for i in block], np.zeros(n), np.zeros((n, md)) if multi else np.zeros(n),
+                    np.zeros(n) if multi else None)
+            if batch is None:
+                batch = ctx.upload(*args)
+            else:
+                batch.reload(*args)
+            yield lo, hi, block, batch
+    finally:
+        if batch is not None:
+            batch.close()
+        ctx.close()
+
+
+def _stitch(out: dict, lo: int, hi: int, res: dict):
+    """Offsets and status of block ``[lo, hi)`` into those of the whole selection."""
+    out["offsets"][lo + 1:hi + 1] = out["offsets"][lo] + res["offsets"][1:]
+    out["status"][lo:hi] = res["status"]
+
+
 def model_spectra(model: dict, samples: dict, spectra, results: dict | None = None,
                   params: Parameters | None = None, selection=None, absorbers="map", sub_dla: bool | None = None,
                   moments_sub_dla: bool = False, products=("map", "moments", "continuum"), sample_rows=None,
@@ -1536,45 +1553,24 @@ def model_spectra(model: dict, samples: dict, spectra, results: dict | None = No
                 raise ValueError("multi_models needs model_weights or results")
             model_weights = results["model_posteriors"]
         model_weights = np.asarray(model_weights, dtype=np.float64)
-    S = np.asarray(samples["offset_samples"]).size
-    longest = max([np.asarray(spectra[i]["wavelengths"]).size for i in sel], default=1)
-    per = int(max_quasars_per_batch or default_batch_size(sel.size, longest, np.asarray(model["M"]).shape[1], S, 1))
+    per = _block_size(max_quasars_per_batch, spectra, sel, model, samples)
     out = {"selection": sel, "offsets": np.zeros(sel.size + 1, dtype=np.int64), "status": np.zeros(sel.size, dtype=np.int32)}
     parts = {}
-    if sel.size:
-        ctx = Context(device, p)
-        batch = None
-        try:
-            ctx.set_model(model)
-            ctx.set_samples(samples)
-            md = p.max_dlas if multi else 0
-            for lo, hi in batch_blocks(sel.size, per):
-                idx = sel[lo:hi]
-                n = idx.size
-                args = ([spectra[i] for i in idx], np.zeros(n), np.zeros((n, md)) if multi else np.zeros(n),
-                        np.zeros(n) if multi else None)
-                if batch is None:
-                    batch = ctx.upload(*args)
-                else:
-                    batch.reload(*args)
-                res = batch.model_spectra(absorbers=None if absorbers is None else _take_absorbers(absorbers, idx),
-                                          weights=np.asarray(sample_rows(idx), dtype=np.float64) if "moments" in products else None,
-                                          sub_dla=moments_sub_dla, products=products)
-                out["offsets"][lo + 1:hi + 1] = out["offsets"][lo] + res["offsets"][1:]
-                out["status"][lo:hi] = res["status"]
-                for name in MODEL_SPECTRA_ARRAYS:
-                    if name in res:
-                        parts.setdefault(name, []).append(res[name])
-                if multi_models:
-                    more = batch.model_spectra_multi(tables=multi_rows(idx), model_weights=model_weights[idx])
-                    out.setdefault("model_flags", np.zeros(sel.size, dtype=np.uint32))[lo:hi] = more["model_flags"]
-                    out["status"][lo:hi] |= more["status"]
-                    for name in MODEL_SPECTRA_MULTI_ARRAYS + MODEL_SPECTRA_MULTI_PLANES:
-                        parts.setdefault(name, []).append(more[name])
-        finally:
-            if batch is not None:
-                batch.close()
-            ctx.close()
+    with closing(_resident_blocks(model, samples, spectra, sel, p, device, per)) as blocks:
+        for lo, hi, idx, batch in blocks:
+            res = batch.model_spectra(absorbers=None if absorbers is None else _take_absorbers(absorbers, idx),
+                                      weights=np.asarray(sample_rows(idx), dtype=np.float64) if "moments" in products else None,
+                                      sub_dla=moments_sub_dla, products=products)
+            _stitch(out, lo, hi, res)
+            for name in MODEL_SPECTRA_ARRAYS:
+                if name in res:
+                    parts.setdefault(name, []).append(res[name])
+            if multi_models:
+                more = batch.model_spectra_multi(tables=multi_rows(idx), model_weights=model_weights[idx])
+                out.setdefault("model_flags", np.zeros(sel.size, dtype=np.uint32))[lo:hi] = more["model_flags"]
+                out["status"][lo:hi] |= more["status"]
+                for name in MODEL_SPECTRA_MULTI_ARRAYS + MODEL_SPECTRA_MULTI_PLANES:
+                    parts.setdefault(name, []).append(more[name])
     for name, ps in parts.items():
         out[name] = np.concatenate(ps, axis=-1)   # (the per-model planes are [max_dlas, pixels])
     return out
@@ -1641,45 +1637,24 @@ def marginal_continuum(model: dict, samples: dict, spectra, results: dict | None
     instead (a file streamed block by block).  Returns ``selection``, ``offsets``, ``status`` and the arrays of
     :meth:`Batch.marginal_continuum` in selection order; results do not depend on the batching."""
     p = params or Parameters()
-    multi = isinstance(p, MultiParameters)
     spectra = list(spectra)
     sel = np.arange(len(spectra), dtype=np.int64) if selection is None else np.asarray(selection, dtype=np.int64).reshape(-1)
     components, sampled, model_weights, sample_rows = _mixture_inputs(results, components, model_weights, sample_rows)
     S = np.asarray(samples["offset_samples"]).size
     k = np.asarray(model["M"]).shape[1]
-    longest = max([np.asarray(spectra[i]["wavelengths"]).size for i in sel], default=1)
-    per = int(max_quasars_per_batch or default_batch_size(sel.size, longest, k, S, 1))
+    per = _block_size(max_quasars_per_batch, spectra, sel, model, samples)
     out = {"selection": sel, "offsets": np.zeros(sel.size + 1, dtype=np.int64), "status": np.zeros(sel.size, dtype=np.int32)}
     parts = {}
-    if sel.size:
-        ctx = Context(device, p)
-        batch = None
-        try:
-            ctx.set_model(model)
-            ctx.set_samples(samples)
-            md = p.max_dlas if multi else 0
-            for lo, hi in batch_blocks(sel.size, per):
-                idx = sel[lo:hi]
-                n = idx.size
-                args = ([spectra[i] for i in idx], np.zeros(n), np.zeros((n, md)) if multi else np.zeros(n),
-                        np.zeros(n) if multi else None)
-                if batch is None:
-                    batch = ctx.upload(*args)
-                else:
-                    batch.reload(*args)
-                res = batch.marginal_continuum(weights={c: np.asarray(sample_rows(idx, c), dtype=np.float64) for c in sampled} or None,
-                                               components=components,
-                                               model_weights=None if model_weights is None else model_weights[idx],
-                                               sample_coefficients=sample_coefficients)
-                out["offsets"][lo + 1:hi + 1] = out["offsets"][lo] + res["offsets"][1:]
-                out["status"][lo:hi] = res["status"]
-                for name in MARGINAL_CONTINUUM_ARRAYS + MARGINAL_CONTINUUM_ROWS:
-                    if name in res:
-                        parts.setdefault(name, []).append(res[name])
-        finally:
-            if batch is not None:
-                batch.close()
-            ctx.close()
+    with closing(_resident_blocks(model, samples, spectra, sel, p, device, per)) as blocks:
+        for lo, hi, idx, batch in blocks:
+            res = batch.marginal_continuum(weights={c: np.asarray(sample_rows(idx, c), dtype=np.float64) for c in sampled} or None,
+                                           components=components,
+                                           model_weights=None if model_weights is None else model_weights[idx],
+                                           sample_coefficients=sample_coefficients)
+            _stitch(out, lo, hi, res)
+            for name in MARGINAL_CONTINUUM_ARRAYS + MARGINAL_CONTINUUM_ROWS:
+                if name in res:
+                    parts.setdefault(name, []).append(res[name])
     nb = k * (k + 1) // 2
     shapes = {"coef_mean": (0, k), "coef_cov_within": (0, nb), "coef_cov_between": (0, nb), "sample_coefficients": (0, S, k)}
     for name in MARGINAL_CONTINUUM_ARRAYS:
@@ -1726,45 +1701,22 @@ def predictive_flux(model: dict, samples: dict, spectra, results: dict | None = 
     ``status`` and the arrays of :meth:`Batch.predictive_flux` in selection order; results do not depend on the
     batching."""
     p = params or Parameters()
-    multi = isinstance(p, MultiParameters)
     spectra = list(spectra)
     sel = np.arange(len(spectra), dtype=np.int64) if selection is None else np.asarray(selection, dtype=np.int64).reshape(-1)
     components, sampled, model_weights, sample_rows = _mixture_inputs(results, components, model_weights, sample_rows)
-    S = np.asarray(samples["offset_samples"]).size
-    k = np.asarray(model["M"]).shape[1]
-    longest = max([np.asarray(spectra[i]["wavelengths"]).size for i in sel], default=1)
-    per = int(max_quasars_per_batch or default_batch_size(sel.size, longest, k, S, 1))
+    per = _block_size(max_quasars_per_batch, spectra, sel, model, samples)
     out = {"selection": sel, "offsets": np.zeros(sel.size + 1, dtype=np.int64), "status": np.zeros(sel.size, dtype=np.int32)}
     names = PREDICTIVE_FLUX_ARRAYS + ((PREDICTIVE_FLUX_RESIDUALS + PREDICTIVE_FLUX_ROWS) if residuals else ())
     parts = {name: [] for name in names}
-    if sel.size:
-        ctx = Context(device, p)
-        batch = None
-        try:
-            ctx.set_model(model)
-            ctx.set_samples(samples)
-            md = p.max_dlas if multi else 0
-            for lo, hi in batch_blocks(sel.size, per):
-                idx = sel[lo:hi]
-                n = idx.size
-                args = ([spectra[i] for i in idx], np.zeros(n), np.zeros((n, md)) if multi else np.zeros(n),
-                        np.zeros(n) if multi else None)
-                if batch is None:
-                    batch = ctx.upload(*args)
-                else:
-                    batch.reload(*args)
-                res = batch.predictive_flux(weights={c: np.asarray(sample_rows(idx, c), dtype=np.float64) for c in sampled} or None,
-                                            components=components,
-                                            model_weights=None if model_weights is None else model_weights[idx],
-                                            residuals=residuals)
-                out["offsets"][lo + 1:hi + 1] = out["offsets"][lo] + res["offsets"][1:]
-                out["status"][lo:hi] = res["status"]
-                for name in names:
-                    parts[name].append(res[name])
-        finally:
-            if batch is not None:
-                batch.close()
-            ctx.close()
+    with closing(_resident_blocks(model, samples, spectra, sel, p, device, per)) as blocks:
+        for lo, hi, idx, batch in blocks:
+            res = batch.predictive_flux(weights={c: np.asarray(sample_rows(idx, c), dtype=np.float64) for c in sampled} or None,
+                                        components=components,
+                                        model_weights=None if model_weights is None else model_weights[idx],
+                                        residuals=residuals)
+            _stitch(out, lo, hi, res)
+            for name in names:
+                parts[name].append(res[name])
     for name in names:
         out[name] = np.concatenate(parts[name]) if parts[name] else np.zeros(0, dtype=np.int64 if name == "num_kept" else np.float64)
     return out
@@ -1790,46 +1742,26 @@ def draw_mock_spectra(model: dict, samples: dict, templates, truth=None, params:
     Returns ``flux`` (list of per-quasar arrays), ``status``, and per requested component a list of
     per-quasar arrays (``latents``: ``[nq, k]``)."""
     p = params or Parameters()
-    multi = isinstance(p, MultiParameters)
     templates = list(templates)
     nq = len(templates)
-    S = np.asarray(samples["offset_samples"]).size
     k = np.asarray(model["M"]).shape[1]
-    longest = max([np.asarray(t["wavelengths"]).size for t in templates], default=1)
-    per = int(max_quasars_per_batch or default_batch_size(nq, longest, k, S, 1))
+    per = _block_size(max_quasars_per_batch, templates, range(nq), model, samples)
     out = {"flux": [], "status": np.zeros(nq, dtype=np.int32)}
     for name in components:
         out[name] = np.empty((nq, k)) if name == "latents" else []
-    if nq:
-        ctx = Context(device, p)
-        batch = None
-        try:
-            ctx.set_model(model)
-            ctx.set_samples(samples)
-            md = p.max_dlas if multi else 0
-            for lo, hi in batch_blocks(nq, per):
-                n = hi - lo
-                args = (templates[lo:hi], np.zeros(n), np.zeros((n, md)) if multi else np.zeros(n),
-                        np.zeros(n) if multi else None)
-                if batch is None:
-                    batch = ctx.upload(*args)
+    with closing(_resident_blocks(model, samples, templates, range(nq), p, device, per)) as blocks:
+        for lo, hi, idx, batch in blocks:
+            batch.ctx.set_first_quasar_index(first_quasar_index + lo)
+            res = batch.draw_mocks(absorbers=None if truth is None else _take_absorbers(truth, idx),
+                                   seed=seed, write_resident=False, components=components)
+            sizes = np.array([np.asarray(t["wavelengths"]).size for t in templates[lo:hi]], dtype=np.int64)
+            out["flux"] += split_cells(res["flux"], np.concatenate([[0], np.cumsum(sizes)]))
+            out["status"][lo:hi] = res["status"]
+            for name in components:
+                if name == "latents":
+                    out[name][lo:hi] = res[name]
                 else:
-                    batch.reload(*args)
-                ctx.set_first_quasar_index(first_quasar_index + lo)
-                res = batch.draw_mocks(absorbers=None if truth is None else _take_absorbers(truth, range(lo, hi)),
-                                       seed=seed, write_resident=False, components=components)
-                sizes = np.array([np.asarray(t["wavelengths"]).size for t in templates[lo:hi]], dtype=np.int64)
-                out["flux"] += split_cells(res["flux"], np.concatenate([[0], np.cumsum(sizes)]))
-                out["status"][lo:hi] = res["status"]
-                for name in components:
-                    if name == "latents":
-                        out[name][lo:hi] = res[name]
-                    else:
-                        out[name] += split_cells(res[name], res["grid_offsets"])
-        finally:
-            if batch is not None:
-                batch.close()
-            ctx.close()
+                    out[name] += split_cells(res[name], res["grid_offsets"])
     return out
 
 

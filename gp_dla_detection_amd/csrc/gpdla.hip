@@ -53,6 +53,7 @@ using namespace gpdla;
 #include "host_sweep.hpp"
 #include "host_multi.hpp"
 #include "host_consumers.hpp"
+#include "host_grid.hpp"
 #include "host_pipeline.hpp"
 #include "host_training.hpp"
 #include "host_learn.hpp"

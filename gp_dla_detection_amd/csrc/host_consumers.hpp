@@ -2,7 +2,8 @@
 // mock draws, parameter summaries, the refine pass, its download and its summaries): the refusals
 // every one of them tests, the resident sample table, the absorber lists and the k_spectra_map launch.
 // (Staging and EventPair are in host_common.hpp, begin_timing / end_timing beside gpdla_context in
-// host_context.hpp: the sweeps use them too.)
+// host_context.hpp: the sweeps use them too.  What only the per-pixel grid products share -- the selection
+// and its offsets, the sample weights, the mixtures' plan -- follows in host_grid.hpp.)
 #pragma once
 
 namespace {

@@ -44,22 +44,6 @@ int validate_model_spectra(const gpdla_model_spectra_request *rq, int64_t nq, in
   return GPDLA_OK;
 }
 
-// k_prepare for the batch (its metadata and rows are a pure function of the spectra, the model and
-// the configuration: running it again changes nothing a later process call relies on), then the
-// metadata on the host
-int spectra_prepare(gpdla_context *c, gpdla_batch *b, bool meanflux, std::vector<QuasarMeta> &meta) {
-  hipStream_t st = c->stream;
-  HIP_TRY(hipStreamWaitEvent(st, b->ev_done, 0));
-  // (no record plan is needed: k_prepare copies the planned record offsets into the metadata, and
-  // the next process call plans and prepares again before it reads them)
-  int rc = launch_prepare(c, b, meanflux);
-  if (rc) return rc;
-  meta.resize((size_t)b->nq);
-  HIP_TRY(hipMemcpyAsync(meta.data(), b->d_meta, (size_t)b->nq * sizeof(QuasarMeta), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return GPDLA_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -90,30 +74,16 @@ int gpdla_batch_model_spectra(gpdla_context *c, gpdla_batch *b, const gpdla_mode
   const int64_t nsel = rq->num_selected;
   HIP_TRY(hipSetDevice(c->device_id));
   hipStream_t st = c->stream;
-  std::vector<QuasarMeta> meta;
-  if ((rc = spectra_prepare(c, b, rq->meanflux != 0, meta))) return rc;
-
-  std::vector<int64_t> sel((size_t)nsel), off((size_t)nsel + 1, 0);
-  for (int64_t s = 0; s < nsel; ++s) {
-    sel[(size_t)s] = rq->selection ? rq->selection[s] : s;
-    off[(size_t)s + 1] = off[(size_t)s] + meta[(size_t)sel[(size_t)s]].n_u;
-  }
-  const int64_t total = off[(size_t)nsel];
-  std::memcpy(out->offsets, off.data(), ((size_t)nsel + 1) * sizeof(int64_t));
-  if (total > rq->capacity)
-    return fail(GPDLA_ERR_INVALID_ARGUMENT, "the selection has %lld grid pixels, capacity is %lld (offsets are written)",
-                (long long)total, (long long)rq->capacity);
-  if (nsel == 0) return GPDLA_OK;
-
-  std::vector<int64_t> rows((size_t)nsel);
+  GridSelection gs;
+  std::vector<int64_t> rows;
   std::vector<int32_t> status((size_t)nsel);
   AbsorberLists lists;
   Staging sg(st);
-  int64_t *d_sel = nullptr, *d_off = nullptr;
-  if ((rc = sg.put(&d_sel, sel.data(), (size_t)nsel))) return rc;
-  if ((rc = sg.put(&d_off, off.data(), (size_t)nsel + 1))) return rc;
+  if ((rc = gs.open(c, b, rq->meanflux != 0, rq->selection, nsel, rq->capacity, out->offsets, sg)) || nsel == 0) return rc;
+  const std::vector<int64_t> &sel = gs.sel;
+  const int64_t *d_sel = gs.d_sel, *d_off = gs.d_off;
   if ((rc = lists.upload(sg, nsel, rq->absorber_offsets, rq->absorber_z, rq->absorber_nhi))) return rc;
-  const size_t tot = (size_t)total;
+  const size_t tot = (size_t)gs.total;
 
   // P1 (also the absorption the continuum conditions on)
   double *d_map = nullptr;
@@ -126,31 +96,13 @@ int gpdla_batch_model_spectra(gpdla_context *c, gpdla_batch *b, const gpdla_mode
   // P2
   if (want_mom) {
     const int64_t S = b->S;
-    double *d_w = nullptr, *d_table = nullptr, *d_mean = nullptr, *d_var = nullptr, *d_part = nullptr;
-    int64_t *d_rows = nullptr;
+    double *d_w = nullptr, *d_mean = nullptr, *d_var = nullptr, *d_part = nullptr;
     int32_t *d_flag = nullptr;
-    const double *table;
-    if (rq->weights_source == GPDLA_SPECTRA_WEIGHTS_HOST) {
-      if ((rc = sg.put(&d_table, rq->sample_log_likelihoods, (size_t)nsel * S))) return rc;
-      table = d_table;
-      for (int64_t s = 0; s < nsel; ++s) rows[(size_t)s] = s * S;
-    } else {
-      const SampleTable t = resident_samples(b, rq->sub_dla != 0);
-      table = t.table;
-      for (int64_t s = 0; s < nsel; ++s) rows[(size_t)s] = sel[(size_t)s] * t.width;
-    }
-    if ((rc = sg.put(&d_rows, rows.data(), (size_t)nsel))) return rc;
     if ((rc = sg.tmp.alloc(&d_w, (size_t)nsel * S)) || (rc = sg.tmp.alloc(&d_flag, (size_t)nsel)) ||
-        (rc = sg.tmp.alloc(&d_mean, tot)) || (rc = sg.tmp.alloc(&d_var, tot)))
+        (rc = sg.tmp.alloc(&d_mean, tot)) || (rc = sg.tmp.alloc(&d_var, tot)) ||
+        (rc = launch_sample_weights(sg, b, gs, rq->weights_source == GPDLA_SPECTRA_WEIGHTS_HOST ? rq->sample_log_likelihoods : nullptr,
+                                    rq->sub_dla != 0, rows, d_w, d_flag)))
       return rc;
-    SpectraWeightsArgs wa;
-    wa.table = table;
-    wa.row_start = d_rows;
-    wa.S = S;
-    wa.w = d_w;
-    wa.flag = d_flag;
-    hipLaunchKernelGGL(k_spectra_weights, dim3((unsigned)nsel), dim3(256), 0, st, wa);
-    HIP_TRY(hipGetLastError());
 
     const int chunks = (int)((S + kMomWaves * 64 - 1) / (kMomWaves * 64));
     const int64_t stride = ((std::max<int64_t>(b->max_pix, 1) + 15) / 16) * 16;  // n_u <= stored pixels
@@ -197,7 +149,7 @@ int gpdla_batch_model_spectra(gpdla_context *c, gpdla_batch *b, const gpdla_mode
   }
 
   // P3
-  for (int64_t s = 0; s < nsel; ++s) status[(size_t)s] = meta[(size_t)sel[(size_t)s]].status;
+  for (int64_t s = 0; s < nsel; ++s) status[(size_t)s] = gs.meta[(size_t)sel[(size_t)s]].status;
   if (want_cont) {
     double *d_cont = nullptr, *d_flux = nullptr;
     int32_t *d_status = nullptr;

@@ -71,21 +71,16 @@ int gpdla_batch_model_spectra_multi(gpdla_context *c, gpdla_batch *b, const gpdl
   const int64_t nsel = rq->num_selected, S = b->S;
   HIP_TRY(hipSetDevice(c->device_id));
   hipStream_t st = c->stream;
-  std::vector<QuasarMeta> meta;
-  if ((rc = spectra_prepare(c, b, rq->meanflux != 0, meta))) return rc;
-
-  std::vector<int64_t> sel((size_t)nsel), off((size_t)nsel + 1, 0);
-  for (int64_t s = 0; s < nsel; ++s) {
-    sel[(size_t)s] = rq->selection ? rq->selection[s] : s;
-    off[(size_t)s + 1] = off[(size_t)s] + meta[(size_t)sel[(size_t)s]].n_u;
-  }
-  const int64_t total = off[(size_t)nsel];
-  std::memcpy(out->offsets, off.data(), ((size_t)nsel + 1) * sizeof(int64_t));
-  if (total > rq->capacity)
-    return fail(GPDLA_ERR_INVALID_ARGUMENT, "the selection has %lld grid pixels, capacity is %lld (offsets are written)",
-                (long long)total, (long long)rq->capacity);
-  if (nsel == 0) return GPDLA_OK;
-  const size_t tot = (size_t)total, ncols = (size_t)(2 + md);
+  // the host buffers of the asynchronous copies first, then the Staging (its rule)
+  GridSelection gs;
+  std::vector<double> weights;
+  std::vector<int64_t> rows_dla((size_t)nsel), rows_lls((size_t)nsel), rows_base((size_t)nsel);
+  std::vector<int32_t> status((size_t)nsel), flags;
+  Staging sg(st);
+  if ((rc = gs.open(c, b, rq->meanflux != 0, rq->selection, nsel, rq->capacity, out->offsets, sg)) || nsel == 0) return rc;
+  const std::vector<int64_t> &sel = gs.sel;
+  int64_t *d_sel = gs.d_sel, *d_off = gs.d_off;
+  const size_t tot = (size_t)gs.total, ncols = (size_t)(2 + md);
 
   // groups of entries whose partial sums (every model's) fit kSpectraPartialBytes
   const int chunks = (int)((S + kMomWaves * 64 - 1) / (kMomWaves * 64));
@@ -95,7 +90,6 @@ int gpdla_batch_model_spectra_multi(gpdla_context *c, gpdla_batch *b, const gpdl
   if (cap * md * chunks > 2147483647LL) return fail(GPDLA_ERR_UNSUPPORTED, "selection too large for one launch");
 
   // the model weights of the entries
-  std::vector<double> weights;
   if (want_avg) {
     weights.resize((size_t)nsel * ncols);
     if (rq->model_weights) {
@@ -110,24 +104,21 @@ int gpdla_batch_model_spectra_multi(gpdla_context *c, gpdla_batch *b, const gpdl
   }
 
   // where an entry's rows start: in the resident tables, or in the group's staged slice of the host tables
-  std::vector<int64_t> rows_dla((size_t)nsel), rows_lls((size_t)nsel), rows_base((size_t)nsel);
   for (int64_t s = 0; s < nsel; ++s) {
     const int64_t r = resident ? sel[(size_t)s] : s % cap;
     rows_dla[(size_t)s] = r * md * S;
     rows_lls[(size_t)s] = r * S;
     rows_base[(size_t)s] = r * (md - 1) * S;
   }
-  std::vector<int32_t> status((size_t)nsel), flags(nrows * (size_t)nsel, 0);
-  for (int64_t s = 0; s < nsel; ++s) status[(size_t)s] = meta[(size_t)sel[(size_t)s]].status;
+  flags.assign(nrows * (size_t)nsel, 0);
+  for (int64_t s = 0; s < nsel; ++s) status[(size_t)s] = gs.meta[(size_t)sel[(size_t)s]].status;
 
-  Staging sg(st);
-  int64_t *d_sel = nullptr, *d_off = nullptr, *d_rows_dla = nullptr, *d_rows_lls = nullptr, *d_rows_base = nullptr;
+  int64_t *d_rows_dla = nullptr, *d_rows_lls = nullptr, *d_rows_base = nullptr;
   double *d_weights = nullptr, *d_w = nullptr, *d_part = nullptr, *d_planes = nullptr, *d_lls = nullptr, *d_avg = nullptr;
   double *d_tab_dla = nullptr, *d_tab_lls = nullptr;
   uint32_t *d_tab_base = nullptr;
   int32_t *d_flag = nullptr, *d_status = nullptr;
-  if ((rc = sg.put(&d_sel, sel.data(), (size_t)nsel)) || (rc = sg.put(&d_off, off.data(), (size_t)nsel + 1)) ||
-      (rc = sg.put(&d_rows_dla, rows_dla.data(), (size_t)nsel)) || (rc = sg.put(&d_rows_lls, rows_lls.data(), (size_t)nsel)) ||
+  if ((rc = sg.put(&d_rows_dla, rows_dla.data(), (size_t)nsel)) || (rc = sg.put(&d_rows_lls, rows_lls.data(), (size_t)nsel)) ||
       (rc = sg.put(&d_rows_base, rows_base.data(), (size_t)nsel)) ||
       (rc = sg.tmp.alloc(&d_w, nrows * (size_t)cap * S)) || (rc = sg.tmp.alloc(&d_flag, nrows * (size_t)nsel)) ||
       (rc = sg.tmp.alloc(&d_part, nrows * (size_t)cap * per_q)) || (rc = sg.tmp.alloc(&d_planes, 2 * (size_t)md * tot)) ||
@@ -145,14 +136,9 @@ int gpdla_batch_model_spectra_multi(gpdla_context *c, gpdla_batch *b, const gpdl
 
   // the existing single-profile path for one row of the group: weights, moments, combine
   auto single_profile = [&](int row, int64_t g0, int64_t n, const double *table, const int64_t *d_rows, const double *nhi) -> int {
-    SpectraWeightsArgs wa;
-    wa.table = table;
-    wa.row_start = d_rows + g0;
-    wa.S = S;
-    wa.w = d_w + (size_t)row * cap * S;
-    wa.flag = d_flag + (size_t)row * nsel + g0;
-    hipLaunchKernelGGL(k_spectra_weights, dim3((unsigned)n), dim3(256), 0, st, wa);
-    HIP_TRY(hipGetLastError());
+    double *w = d_w + (size_t)row * cap * S;
+    int rc = launch_sample_weights(table, d_rows + g0, S, n, w, d_flag + (size_t)row * nsel + g0, st);
+    if (rc) return rc;
     SpectraMomentsArgs pa;
     pa.meta = b->d_meta;
     pa.lam_pad = b->d_lam;
@@ -160,7 +146,7 @@ int gpdla_batch_model_spectra_multi(gpdla_context *c, gpdla_batch *b, const gpdl
     pa.nhi = nhi;
     pa.perm = c->d_perm;
     pa.sel = d_sel + g0;
-    pa.w = wa.w;
+    pa.w = w;
     pa.S = S;
     pa.num_lines = c->cfg.num_lines;
     pa.s0 = 0;

@@ -135,6 +135,33 @@ def row_kinds(k: int, S: int):
     return ["sweep", "flat", "half_nan"] + [("hot", p) for p in row_hot_positions(k, S)] + list(E.NAN_ROWS)
 
 
+# ---- the batching of the module-level drivers (api.marginal_continuum, api.predictive_flux) ----
+
+BATCHING_NUS = (5, 31, 33, 17, 64)          # five quasars of unequal length
+# a permutation with quasar 2 left out (blocks of 2, 2 at two a batch), and one of all five (2, 2 and a short last block)
+BATCHING_SELECTIONS = {"one_left_out": (3, 0, 4, 1), "all_five": (3, 0, 4, 1, 2)}
+
+
+def batching_case(k: int = 20):
+    """(model, samples, spectra, params, log_priors) of the smallest k = 20 setup (S = 16, 31 lines, mean-flux rows of a
+    multi-DLA run, so that all three components have a table and a posterior) on BATCHING_NUS; ``k`` replaces its rank."""
+    st = dict(setup("k20_S16_31lines_meanflux"), k=k, nus=BATCHING_NUS)
+    model, samples, spectra = build(st)
+    p = params(st)
+    n = len(spectra)
+    log_priors = (np.full(n, np.log(0.85)), np.full(n, np.log(0.05)), np.log(np.full((n, p.max_dlas), 0.1) ** np.arange(1, p.max_dlas + 1)))
+    return model, samples, spectra, p, log_priors
+
+
+def assert_same_results(a: dict, b: dict):
+    """Every returned array bit for bit (NaN equal to NaN), with its dtype and shape."""
+    assert list(a) == list(b)
+    for name in a:
+        x, y = np.asarray(a[name]), np.asarray(b[name])
+        assert x.dtype == y.dtype and x.shape == y.shape, name
+        assert np.array_equal(x, y, equal_nan=x.dtype.kind == "f"), name
+
+
 # ---- the zero-weight skip ----
 
 SKIP_S, SKIP_LIVE = 200, (3, 70, 199)      # z-order positions of the three samples of weight > 0 (blocks 0, 1 and 3 of 4)

@@ -303,6 +303,21 @@ def test_bit_identity_across_launch_groups(tmp_path):
     assert np.isfinite(want["continuum_var"]).all()
 
 
+@pytest.mark.parametrize("which", list(MC.BATCHING_SELECTIONS))
+def test_module_level_results_do_not_depend_on_the_batching(which):
+    """gp.marginal_continuum over five quasars of unequal length in blocks of two (one upload, then reloads; the selection of
+    all five ends on a short block) against the same call with all of them in one batch: every returned array, bit for bit."""
+    model, samples, spectra, p, log_priors = MC.batching_case()
+    results = gp.process_qsos_multiple_dlas_meanflux(model, samples, spectra, log_priors, params=p)
+    kw = dict(params=p, selection=MC.BATCHING_SELECTIONS[which], components=("null", "sub_dla", "dla"), model_weights="posteriors",
+              sample_coefficients=False)
+    blocks = gp.marginal_continuum(model, samples, spectra, results, max_quasars_per_batch=2, **kw)
+    whole = gp.marginal_continuum(model, samples, spectra, results, max_quasars_per_batch=5, **kw)
+    assert set(ALL) <= set(whole) and whole["status"].tolist() == [0] * len(kw["selection"]) and np.isfinite(whole["continuum_var"]).all()
+    np.testing.assert_array_equal(np.diff(whole["offsets"]), [MC.BATCHING_NUS[q] for q in kw["selection"]])
+    MC.assert_same_results(blocks, whole)
+
+
 # ------------------------------------------------------------------------------------------------
 # file to file
 # ------------------------------------------------------------------------------------------------

@@ -12,6 +12,7 @@ import gp_dla_detection_amd as gp
 from gp_dla_detection_amd import synthetic
 from gp_dla_detection_amd.parameters import MultiParameters, Parameters
 
+import marginal_continuum_cases as MC
 import model_spectra_edge_cases as E
 import model_spectra_restatement as R
 import predictive_flux_cases as PC
@@ -334,6 +335,22 @@ def test_bit_identity_across_launch_groups(tmp_path):
     for name in ALL + ("status", "offsets"):
         np.testing.assert_array_equal(got[name], want[name], err_msg=name)
     assert np.isfinite(want["flux_var"]).all()
+
+
+@pytest.mark.parametrize("k, which", [(20, "one_left_out"), (20, "all_five"), (40, "all_five")])
+def test_module_level_results_do_not_depend_on_the_batching(k, which):
+    """gp.predictive_flux over five quasars of unequal length in blocks of two (one upload, then reloads; the selection of all
+    five ends on a short block) against the same call with all of them in one batch: every returned array, bit for bit.
+    k = 40 once: another instantiation of k_mc_contract."""
+    model, samples, spectra, p, log_priors = MC.batching_case(k)
+    results = gp.process_qsos_multiple_dlas_meanflux(model, samples, spectra, log_priors, params=p)
+    kw = dict(params=p, selection=MC.BATCHING_SELECTIONS[which], components=("null", "sub_dla", "dla"), model_weights="posteriors",
+              residuals=True)
+    blocks = gp.predictive_flux(model, samples, spectra, results, max_quasars_per_batch=2, **kw)
+    whole = gp.predictive_flux(model, samples, spectra, results, max_quasars_per_batch=5, **kw)
+    assert set(ALL) <= set(whole) and whole["status"].tolist() == [0] * len(kw["selection"]) and np.isfinite(whole["flux_var"]).all()
+    np.testing.assert_array_equal(np.diff(whole["offsets"]), [MC.BATCHING_NUS[q] for q in kw["selection"]])
+    MC.assert_same_results(blocks, whole)
 
 
 # ------------------------------------------------------------------------------------------------

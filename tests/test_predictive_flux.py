@@ -58,8 +58,12 @@ def test_kernel_constants_of_the_case_lists():
     mc = open(os.path.join(_lib.CSRC, "marginal_continuum_kernels.hpp")).read()
     assert f"constexpr int kMcSolveChunk = {PC.SOLVE_CHUNK};" in mc
     assert "atomic" not in src.replace("atomics", "")     # (the header says there are none)
-    assert "validate_marginal_continuum(" in host          # the request checks are shared, not copied
-    assert "mc_scratch_bytes()" in host and "getenv" not in host and "getenv" not in src
+    # the request checks, the launch groups and their budget are the shared front end's (host_grid.hpp), not copies
+    grid = open(os.path.join(_lib.CSRC, "host_grid.hpp")).read()
+    assert "validate_mixture(" in host and "int validate_mixture(" in grid and "MixturePlan plan(" in host
+    assert "mc_scratch_bytes()" in grid and "getenv" not in host and "getenv" not in src
+    for copied in ("check_selection(", "model_weights[", "mc_scratch_bytes", "McContractArgs", "k_spectra_weights"):
+        assert copied not in host, copied
 
 
 def _request(nsel=2, S=8, **kw):
