@@ -22,6 +22,18 @@ int spectra_prepare(gpdla_context *c, gpdla_batch *b, bool meanflux, std::vector
   return GPDLA_OK;
 }
 
+// What the continuum kernels need to evaluate mu_p and m_p at a pixel (continuum_solve.hpp)
+ContinuumModelArgs continuum_model_args(const gpdla_context *c, bool meanflux) {
+  ContinuumModelArgs g;
+  g.model = c->model;
+  g.lya_wavelength = c->cfg.lya_wavelength;
+  g.prev_tau_0 = c->cfg.prev_tau_0;
+  g.prev_beta = c->cfg.prev_beta;
+  g.meanflux = meanflux ? 1 : 0;
+  g.num_forest_lines = c->cfg.num_forest_lines;
+  return g;
+}
+
 // The selected quasars of a batch and where each one's pixels start in the flat per-pixel outputs (CSR over
 // the unmasked-range grids, n_u pixels each).  Host buffers of asynchronous copies, so it is declared before
 // the Staging it uploads through.

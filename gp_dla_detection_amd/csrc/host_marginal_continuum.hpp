@@ -85,12 +85,7 @@ int gpdla_batch_marginal_continuum(gpdla_context *c, gpdla_batch *b, const gpdla
     fa.z_qsos = b->d_z;
     fa.sel = d_sel;
     fa.out_off = plan.gs.d_off;
-    fa.model = c->model;
-    fa.lya_wavelength = c->cfg.lya_wavelength;
-    fa.prev_tau_0 = c->cfg.prev_tau_0;
-    fa.prev_beta = c->cfg.prev_beta;
-    fa.meanflux = rq->meanflux ? 1 : 0;
-    fa.num_forest_lines = c->cfg.num_forest_lines;
+    fa.g = continuum_model_args(c, rq->meanflux != 0);
     fa.pw = plan.d_pw;
     for (int comp = 0; comp < 2; ++comp) {
       fa.flag[comp] = plan.d_flag[comp];

@@ -45,13 +45,7 @@ int gpdla_batch_predictive_flux(gpdla_context *c, gpdla_batch *b, const gpdla_pr
   for (int comp = 0; comp < 2; ++comp)
     if (plan.reaches(comp) && (rc = sg.tmp.alloc(&d_sums[comp], tot * 4))) return rc;
   if (tables && ((rc = sg.tmp.alloc(&d_list, (size_t)nsub * S)) || (rc = sg.tmp.alloc(&d_count, (size_t)nsub)))) return rc;
-  PfModelArgs g;
-  g.model = c->model;
-  g.lya_wavelength = c->cfg.lya_wavelength;
-  g.prev_tau_0 = c->cfg.prev_tau_0;
-  g.prev_beta = c->cfg.prev_beta;
-  g.meanflux = rq->meanflux ? 1 : 0;
-  g.num_forest_lines = c->cfg.num_forest_lines;
+  const ContinuumModelArgs g = continuum_model_args(c, rq->meanflux != 0);
   // (gpdla_context_set_timing: the kernels of this call are what gpdla_context_last_sweep_ms reports)
   if ((rc = begin_timing(c, st))) return rc;
   for (int64_t s0 = 0; s0 < nsel; s0 += nsub) {

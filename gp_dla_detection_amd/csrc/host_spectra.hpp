@@ -163,12 +163,7 @@ int gpdla_batch_model_spectra(gpdla_context *c, gpdla_batch *b, const gpdla_mode
     ka.sel = d_sel;
     ka.out_off = d_off;
     ka.absorption = lists.have_abs ? d_map : nullptr;
-    ka.model = c->model;
-    ka.lya_wavelength = c->cfg.lya_wavelength;
-    ka.prev_tau_0 = c->cfg.prev_tau_0;
-    ka.prev_beta = c->cfg.prev_beta;
-    ka.meanflux = rq->meanflux ? 1 : 0;
-    ka.num_forest_lines = c->cfg.num_forest_lines;
+    ka.g = continuum_model_args(c, rq->meanflux != 0);
     ka.continuum = d_cont;
     ka.model_flux = d_flux;
     ka.status = d_status;

@@ -10,9 +10,9 @@
 //                   L^-T L^-1 of every sample of weight > 0, one sample per wave; the block's weighted
 //                   partial sums of c_i, Sigma_i and c_i c_i', a not-positive-definite flag, the optional c_i row
 //   k_mc_finish     per selected quasar: the chunk partials in chunk order, the null component (a = 1: the
-//                   accumulation and solve of k_spectra_continuum, restated here so that kernel stays as it
-//                   is), the mixture over (null, sub-DLA table, DLA table), the coefficient outputs and the
-//                   three per-pixel arrays on the unmasked-range grid
+//                   solve k_spectra_continuum calls, continuum_null_solve of continuum_solve.hpp), the
+//                   mixture over (null, sub-DLA table, DLA table), the coefficient outputs and the three
+//                   per-pixel arrays on the unmasked-range grid
 //
 // Every sum runs in a fixed order and nothing is accumulated with atomics: within a wave the samples in
 // index order, the four waves in wave order, the chunks in chunk order, the components in the order
@@ -28,15 +28,6 @@ constexpr int kMcSolveChunk = 64;  // samples (z_DLA positions) per block of k_m
 constexpr int kMcComponents = 3;   // null, sub-DLA table, DLA table
 
 typedef double mc_d4 __attribute__((ext_vector_type(4)));
-
-// (i, j), i >= j, of entry e of a packed lower triangle stored row by row (s_B of k_spectra_continuum)
-__device__ __forceinline__ void mc_unpack(int e, int *pi, int *pj) {
-  int i = (int)((sqrt(8.0 * e + 1.0) - 1.0) * 0.5);
-  while ((i + 1) * (i + 2) / 2 <= e) ++i;
-  while (i * (i + 1) / 2 > e) --i;
-  *pi = i;
-  *pj = e - i * (i + 1) / 2;
-}
 
 // ------------------------------------------------------------------------------------------
 // k_mc_contract<RT, CPW, PT>: 256 threads, NS = 16 RT samples of one quasar (consecutive in the
@@ -155,7 +146,7 @@ __global__ __launch_bounds__(256) void k_mc_contract(McContractArgs a) {
     if (ct < nbt) {
       const int e = ct * 16 + c;
       if (e < nb) {
-        mc_unpack(e, &fi[cc], &fj[cc]);
+        packed_unpack(e, &fi[cc], &fj[cc]);
         ocol[cc] = e;
       }
     } else if (ct < nct) {
@@ -247,7 +238,7 @@ __global__ __launch_bounds__(256) void k_mc_contract(McContractArgs a) {
 // ------------------------------------------------------------------------------------------
 // k_mc_solve: 256 threads, the 64 consecutive z_DLA positions `chunk` of one selected quasar.  Wave 0 lists
 // the positions of weight > 0 in index order; the four waves take them round robin, a sample per
-// wave: L L' = B_i = I + scratch row (column by column, as k_spectra_continuum), X = L^-1 (lane c solves
+// wave: L L' = B_i = I + scratch row (column by column, as continuum_null_solve), X = L^-1 (lane c solves
 // column c), z = X v, c_i = X' z, Sigma_i = X' X.  A sample of weight exactly 0 is never factorised.
 // part[(sl * chunks + chunk) * (k + 2 nb)]: Sum w c_i [k] | Sum w Sigma_i [nb] | Sum w c_i c_i' [nb];
 // notpd[sl * chunks + chunk] != 0: a pivot of a sample of weight > 0 was not positive.
@@ -314,7 +305,7 @@ __device__ __forceinline__ void mc_solve_body(const McSolveArgs &a, double *keep
     const int e = lane + 64 * t;
     ea[t] = eb[t] = -1;
     accW[t] = accV[t] = 0.0;
-    if (e < nb) mc_unpack(e, &ea[t], &eb[t]);
+    if (e < nb) packed_unpack(e, &ea[t], &eb[t]);
   }
   double *Lw = s_L[wave], *Xw = s_X[wave];
   double *v = Lw + nb, *z = Xw + nb;
@@ -352,16 +343,7 @@ __device__ __forceinline__ void mc_solve_body(const McSolveArgs &a, double *keep
       }
     }
     __syncthreads();
-    if (has && lane < k) {  // column `lane` of X = L^-1
-      const int cx = lane;
-      Xw[cx * (cx + 1) / 2 + cx] = 1.0 / Lw[cx * (cx + 1) / 2 + cx];
-      for (int ii = cx + 1; ii < k; ++ii) {
-        const int ri = ii * (ii + 1) / 2;
-        double sum = 0.0;
-        for (int mm = cx; mm < ii; ++mm) sum = fma(Lw[ri + mm], Xw[mm * (mm + 1) / 2 + cx], sum);
-        Xw[ri + cx] = -sum / Lw[ri + ii];
-      }
-    }
+    if (has && lane < k) packed_inverse_column(Lw, Xw, k, lane);  // X = L^-1, a lane per column
     __syncthreads();
     if (has && lane < k) {  // z = X v
       const int ri = lane * (lane + 1) / 2;
@@ -383,11 +365,7 @@ __device__ __forceinline__ void mc_solve_body(const McSolveArgs &a, double *keep
 #pragma unroll
       for (int t = 0; t < kMine; ++t) {
         if (ea[t] < 0) continue;
-        double sig = 0.0;  // Sigma_i[ea][eb] = Sum_{m >= ea} X[m][ea] X[m][eb]
-        for (int mm = ea[t]; mm < k; ++mm) {
-          const int rm = mm * (mm + 1) / 2;
-          sig = fma(Xw[rm + ea[t]], Xw[rm + eb[t]], sig);
-        }
+        const double sig = packed_gram_entry(Xw, k, ea[t], eb[t]);  // Sigma_i[ea][eb]
         accW[t] += wi * sig;
         accV[t] += wi * (v[ea[t]] * v[eb[t]]);
         if constexpr (KEEP) krow[lane + 64 * t] = sig;
@@ -432,12 +410,12 @@ __global__ __launch_bounds__(256) void k_mc_solve(McSolveArgs a) { mc_solve_body
 // ------------------------------------------------------------------------------------------
 // k_mc_finish: one block per selected quasar of a launch group.
 //   sampled component m (sub-DLA table, DLA table) of weight p_m > 0: cbar_m, W_m, S_m = Sum w c c' from
-//   the chunk partials in chunk order; the null component of weight p_0 > 0: B_0, v_0 accumulated, factorised
-//   and solved as k_spectra_continuum does with a = 1, Sigma_0 = B_0^-1 through L^-1, S_0 = c_0 c_0';
+//   the chunk partials in chunk order; the null component of weight p_0 > 0: c_0 from continuum_null_solve with
+//   a = 1 (the function k_spectra_continuum calls), Sigma_0 = B_0^-1 through L^-1, S_0 = c_0 c_0';
 //   c = Sum p_m cbar_m, W = Sum p_m W_m, V = Sum p_m S_m - c c' in component order.
 //   continuum_mean = mu + m_p' c, continuum_var = m_p' (W + V) m_p, continuum_var_between = m_p' V m_p at all n_u
-//   pixels, m_p interpolated (and suppressed) as k_spectra_continuum does.  The pixel-diagonal omega term
-//   is left out as there.
+//   pixels, m_p interpolated (and suppressed) by model_tile_rows, in the arithmetic of k_spectra_continuum.  The
+//   pixel-diagonal omega term is left out as there.
 // status: the quasar's prepare status (1, 3: NaN rows); 4 = some B not positive definite (NaN rows);
 // a component of weight > 0 whose weight row has no weights: NaN rows, status 0.
 // ------------------------------------------------------------------------------------------
@@ -449,12 +427,10 @@ struct McFinishArgs {
   const double *z_qsos;
   const int64_t *sel;
   const int64_t *out_off;
-  ModelDev model;
-  double lya_wavelength, prev_tau_0, prev_beta;
-  int32_t meanflux, num_forest_lines;
+  ContinuumModelArgs g;
   const double *pw;            // [nsel][3] normalised model weights (null, sub-DLA, DLA)
   const int32_t *flag[2];      // [nsel] of the sub-DLA and the DLA weight rows, or nullptr
-  const double *part[2];       // [nsub][chunks][k + 2 nb], or nullptr
+  const double *part[2];      // [nsub][chunks][k + 2 nb], or nullptr
   const int32_t *notpd[2];     // [nsub][chunks]
   int64_t s0;
   int32_t chunks;
@@ -470,14 +446,14 @@ __global__ __launch_bounds__(256) void k_mc_finish(McFinishArgs a) {
   __shared__ double s_X[kMcNb];                // null component: L^-1
   __shared__ double s_c[GPDLA_MAX_K], s_W[kMcNb], s_V[kMcNb];
   __shared__ double s_wt[kContTile], s_ut[kContTile];
-  __shared__ double s_m[kMcPixTile][GPDLA_MAX_K + 1], s_mu[kMcPixTile];
+  __shared__ double s_m[kMcPixTile][GPDLA_MAX_K + 1], s_mu[kMcPixTile], s_mf[kMcPixTile];
   __shared__ double s_piv;
   __shared__ int s_pd, s_none;
   const int tid = threadIdx.x;
   const int64_t sl = blockIdx.x, s = a.s0 + sl;
   const int64_t q = a.sel[s];
   const QuasarMeta m = a.meta[q];
-  const int k = a.model.k, G = a.model.G, nb = k * (k + 1) / 2, plen = k + 2 * nb;
+  const int k = a.g.model.k, nb = k * (k + 1) / 2, plen = k + 2 * nb;
   double *o_mean = a.mean + a.out_off[s], *o_var = a.var + a.out_off[s], *o_btw = a.var_between + a.out_off[s];
   double *o_c = a.coef_mean + s * k, *o_W = a.cov_within + s * nb, *o_V = a.cov_between + s * nb;
   if (m.status != 0) {
@@ -496,109 +472,15 @@ __global__ __launch_bounds__(256) void k_mc_finish(McFinishArgs a) {
   }
   __syncthreads();
 
-  if (p0 > 0.0) {  // the null component: k_spectra_continuum with a = 1
-    const PixelRow *pix = a.pix + m.pix_off;
-    const double *Mi = a.Mi + m.pix_off * k;
-    constexpr int kMine = (kMcNb + GPDLA_MAX_K + 255) / 256;
-    int ei[kMine], ej[kMine];
-    double acc[kMine];
-#pragma unroll
-    for (int t = 0; t < kMine; ++t) {
-      const int e = tid + 256 * t;
-      acc[t] = 0.0;
-      ei[t] = ej[t] = -1;
-      if (e < nb) mc_unpack(e, &ei[t], &ej[t]);
-      else if (e < nb + k) ei[t] = e - nb;
-    }
-    for (int pt0 = 0; pt0 < m.n_u; pt0 += kContTile) {
-      if (tid < kContTile) {
-        const int p = pt0 + tid;
-        double wt = 0.0, ut = 0.0;
-        if (p < m.n_u) {
-          const PixelRow row = pix[p];
-          const double ab = 1.0;
-          const double d = ab * ab * row.omega2 + row.nu;
-          const double r = row.y - ab * row.mu;
-          wt = ab * ab / d;
-          ut = ab * r / d;
-        }
-        s_wt[tid] = wt;
-        s_ut[tid] = ut;
-      }
-      __syncthreads();
-      const int np = min(kContTile, m.n_u - pt0);
-#pragma unroll
-      for (int t = 0; t < kMine; ++t) {
-        if (ei[t] < 0) continue;
-        const double *Mp = Mi + (int64_t)pt0 * k;
-        double sum = acc[t];
-        if (ej[t] >= 0)
-          for (int p = 0; p < np; ++p) sum = fma(Mp[p * k + ei[t]] * s_wt[p], Mp[p * k + ej[t]], sum);
-        else
-          for (int p = 0; p < np; ++p) sum = fma(Mp[p * k + ei[t]], s_ut[p], sum);
-        acc[t] = sum;
-      }
-      __syncthreads();
-    }
-#pragma unroll
-    for (int t = 0; t < kMine; ++t)
-      if (ei[t] >= 0) s_B[tid + 256 * t] = acc[t] + ((ej[t] == ei[t]) ? 1.0 : 0.0);
-    __syncthreads();
-    double *v = s_B + nb;
-    for (int j = 0; j < k; ++j) {
-      const int rj = j * (j + 1) / 2;
-      __syncthreads();
-      if (tid == 0) {
-        double sum = s_B[rj + j];
-        for (int mm = 0; mm < j; ++mm) sum = fma(-s_B[rj + mm], s_B[rj + mm], sum);
-        if (!(sum > 0.0)) s_pd = 0;
-        const double ljj = sqrt(sum);
-        s_B[rj + j] = ljj;
-        s_piv = ljj;
-      }
-      __syncthreads();
-      const double ljj = s_piv;
-      for (int i = j + 1 + tid; i < k; i += 256) {
-        const int ri = i * (i + 1) / 2;
-        double sum = s_B[ri + j];
-        for (int mm = 0; mm < j; ++mm) sum = fma(-s_B[ri + mm], s_B[rj + mm], sum);
-        s_B[ri + j] = sum / ljj;
-      }
-    }
-    __syncthreads();
-    if (tid == 0) {  // c_0 = L'^-1 L^-1 v
-      for (int i = 0; i < k; ++i) {
-        const int ri = i * (i + 1) / 2;
-        double zi = v[i];
-        for (int mm = 0; mm < i; ++mm) zi = fma(-s_B[ri + mm], v[mm], zi);
-        v[i] = zi / s_B[ri + i];
-      }
-      for (int i = k - 1; i >= 0; --i) {
-        double ci = v[i];
-        for (int mm = i + 1; mm < k; ++mm) ci = fma(-s_B[mm * (mm + 1) / 2 + i], v[mm], ci);
-        v[i] = ci / s_B[i * (i + 1) / 2 + i];
-      }
-    }
-    if (tid >= 64 && tid < 64 + k) {  // column cx of X = L^-1 (another wave than the substitution's)
-      const int cx = tid - 64;
-      s_X[cx * (cx + 1) / 2 + cx] = 1.0 / s_B[cx * (cx + 1) / 2 + cx];
-      for (int ii = cx + 1; ii < k; ++ii) {
-        const int ri = ii * (ii + 1) / 2;
-        double sum = 0.0;
-        for (int mm = cx; mm < ii; ++mm) sum = fma(s_B[ri + mm], s_X[mm * (mm + 1) / 2 + cx], sum);
-        s_X[ri + cx] = -sum / s_B[ri + ii];
-      }
-    }
+  if (p0 > 0.0) {  // the null component: a = 1
+    continuum_null_solve<kContTile>(a.pix + m.pix_off, a.Mi + m.pix_off * k, m.n_u, k, nullptr, s_B, s_wt, s_ut, &s_piv, &s_pd, tid);
+    const double *v = s_B + nb;  // c_0
+    if (tid >= 64 && tid < 64 + k) packed_inverse_column(s_B, s_X, k, tid - 64);  // (another wave than the substitution's)
     __syncthreads();
     for (int e = tid; e < nb; e += 256) {
       int ia, ib;
-      mc_unpack(e, &ia, &ib);
-      double sig = 0.0;
-      for (int mm = ia; mm < k; ++mm) {
-        const int rm = mm * (mm + 1) / 2;
-        sig = fma(s_X[rm + ia], s_X[rm + ib], sig);
-      }
-      s_W[e] += p0 * sig;
+      packed_unpack(e, &ia, &ib);
+      s_W[e] += p0 * packed_gram_entry(s_X, k, ia, ib);  // Sigma_0 = B_0^-1
       s_V[e] += p0 * (v[ia] * v[ib]);
     }
     for (int e = tid; e < k; e += 256) s_c[e] += p0 * v[e];
@@ -627,7 +509,7 @@ __global__ __launch_bounds__(256) void k_mc_finish(McFinishArgs a) {
   __syncthreads();
   for (int e = tid; e < nb; e += 256) {
     int ia, ib;
-    mc_unpack(e, &ia, &ib);
+    packed_unpack(e, &ia, &ib);
     s_V[e] = s_V[e] - s_c[ia] * s_c[ib];
   }
   __syncthreads();
@@ -639,41 +521,17 @@ __global__ __launch_bounds__(256) void k_mc_finish(McFinishArgs a) {
   for (int e = tid; e < k; e += 256) o_c[e] = ok ? s_c[e] : NAN;
   if (tid == 0) a.status[s] = s_pd ? 0 : 4;
 
-  // the three per-pixel arrays: the interpolation of k_prepare (process_qsos.m:138-139, multi :287-288)
+  // the three per-pixel arrays, a tile of model rows at a time
   const double *lam = a.lam_pad + m.lam_off + 3;
   const double z_qso = a.z_qsos[q];
   for (int pt0 = 0; pt0 < m.n_u; pt0 += kMcPixTile) {
     __syncthreads();
-    for (int e = tid; e < kMcPixTile * (k + 1); e += 256) {
-      const int pl = e / (k + 1), cm = e - pl * (k + 1);
-      const int p = min(pt0 + pl, m.n_u - 1);
-      const double wl = lam[p];
-      const double rest = wl / (1 + z_qso);
-      int lo = 0, hi = G - 1;
-      if (rest >= a.model.rest[G - 1]) lo = G - 2;
-      else if (rest > a.model.rest[0]) {
-        while (hi - lo > 1) {
-          const int mid = (lo + hi) >> 1;
-          if (a.model.rest[mid] <= rest) lo = mid; else hi = mid;
-        }
-      }
-      const double t = (rest - a.model.rest[lo]) / (a.model.rest[lo + 1] - a.model.rest[lo]);
-      if (cm == k) {
-        s_mu[pl] = a.model.mu[lo] + (a.model.mu[lo + 1] - a.model.mu[lo]) * t;
-      } else {
-        const double m0 = a.model.M[lo + (int64_t)cm * G], m1 = a.model.M[lo + 1 + (int64_t)cm * G];
-        s_m[pl][cm] = m0 + (m1 - m0) * t;
-      }
-    }
+    model_tile_rows(a.g, lam, z_qso, m.n_u, pt0, kMcPixTile, &s_m[0][0], GPDLA_MAX_K + 1, s_mu, s_mf, tid);
     __syncthreads();
     if (tid < kMcPixTile && pt0 + tid < m.n_u) {
       const int p = pt0 + tid;
-      const double mf = a.meanflux ? spectra_mean_flux(lam[p], z_qso, a.lya_wavelength, a.prev_tau_0, a.prev_beta, a.num_forest_lines)
-                                   : 1.0;
-      double *mp = s_m[tid];
-      for (int cm = 0; cm < k; ++cm) mp[cm] = mp[cm] * mf;
+      const double *mp = s_m[tid];
       double val = s_mu[tid];
-      if (a.meanflux) val = val * mf;
       for (int cm = 0; cm < k; ++cm) val = fma(mp[cm], s_c[cm], val);
       double qt = 0.0, qb = 0.0;  // m' (W + V) m and m' V m over the packed triangles, row by row
       for (int ia = 0; ia < k; ++ia) {

@@ -13,9 +13,9 @@
 //                   scratch rows onto [vech(m_p m_p'), off-diagonal entries doubled | m_p] to give
 //                   s_ip = m_p' Sigma_i m_p and m_p' c_i, and the epilogue adds up the four weighted sums
 //                   F1 = Sum w f, F2 = Sum w f^2, FW = Sum w a^2 s, FD = Sum w (a^2 omega2 + nu), f = a (mu + m' c)
-//   k_pf_finish     per selected quasar: the null component (a = 1; c_0, Sigma_0 as k_mc_finish obtains them,
-//                   restated), the mixture over (null, sub-DLA table, DLA table) in that order, the NaN and
-//                   status rules and the five per-pixel arrays
+//   k_pf_finish     per selected quasar: the null component (a = 1; c_0, Sigma_0 from the solve k_mc_finish
+//                   calls, continuum_solve.hpp), the mixture over (null, sub-DLA table, DLA table) in that
+//                   order, the NaN and status rules and the five per-pixel arrays
 //
 // Nothing is accumulated with atomics and every sum runs in a fixed order: a lane adds its samples in the
 // order (list chunk, row tile, result register), the four lanes that share a pixel are added in lane order.  A block
@@ -33,46 +33,6 @@ constexpr int kPfSlab = 16;                   // K-columns a wave requests at a 
 constexpr int kPfCols = kMcNb + GPDLA_MAX_K + 2 * kPfSlab;  // K-columns: vech padded to a slab, then the k entries likewise
 
 __global__ __launch_bounds__(256) void k_pf_solve(McSolveArgs a, double *keep) { mc_solve_body<true>(a, keep); }
-
-// m_p (suppressed under meanflux) and mu_p of the pixels p0 .. p0 + np of a quasar's grid, as k_mc_finish
-// interpolates them: rows[pl * stride + cm], mu[pl].  Pixels past n_u repeat the last one.  All 256 threads.
-struct PfModelArgs {
-  ModelDev model;
-  double lya_wavelength, prev_tau_0, prev_beta;
-  int32_t meanflux, num_forest_lines;
-};
-
-__device__ __forceinline__ void pf_tile_rows(const PfModelArgs &g, const double *lam, double z_qso, int n_u, int p0, int np,
-                                             double *rows, int stride, double *mu, double *mf, int tid) {
-  const int k = g.model.k, G = g.model.G;
-  for (int pl = tid; pl < np; pl += 256) {
-    const int p = min(p0 + pl, n_u - 1);
-    mf[pl] = g.meanflux ? spectra_mean_flux(lam[p], z_qso, g.lya_wavelength, g.prev_tau_0, g.prev_beta, g.num_forest_lines) : 1.0;
-  }
-  __syncthreads();
-  for (int e = tid; e < np * (k + 1); e += 256) {
-    const int pl = e / (k + 1), cm = e - pl * (k + 1);
-    const int p = min(p0 + pl, n_u - 1);
-    const double rest = lam[p] / (1 + z_qso);
-    int lo = 0, hi = G - 1;
-    if (rest >= g.model.rest[G - 1]) lo = G - 2;
-    else if (rest > g.model.rest[0]) {
-      while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (g.model.rest[mid] <= rest) lo = mid; else hi = mid;
-      }
-    }
-    const double t = (rest - g.model.rest[lo]) / (g.model.rest[lo + 1] - g.model.rest[lo]);
-    if (cm == k) {
-      double val = g.model.mu[lo] + (g.model.mu[lo + 1] - g.model.mu[lo]) * t;
-      if (g.meanflux) val = val * mf[pl];
-      mu[pl] = val;
-    } else {
-      const double m0 = g.model.M[lo + (int64_t)cm * G], m1 = g.model.M[lo + 1 + (int64_t)cm * G];
-      rows[pl * stride + cm] = (m0 + (m1 - m0) * t) * mf[pl];
-    }
-  }
-}
 
 // ------------------------------------------------------------------------------------------
 // k_pf_live: one block per selected quasar of a launch group and ONE sampled component.  list[sl * S + j]: the z_DLA
@@ -119,7 +79,7 @@ __global__ __launch_bounds__(256) void k_pf_live(PfLiveArgs a) {
 
 // ------------------------------------------------------------------------------------------
 // k_pf_pixels: 256 threads, the pixels p0 = tile * kPfPixTile .. of one selected quasar and ONE sampled component.
-//   Tile set-up: mu_p and m_p of the tile from the model (pf_tile_rows; not from d_Mi, whose masked rows are 0),
+//   Tile set-up: mu_p and m_p of the tile from the model (model_tile_rows; not from d_Mi, whose masked rows are 0),
 //   the rows with a 1 in column k and a 0 in column k + 1; the K-column table s_ij: column e < nb of the vech part
 //   is (i, j, doubled = i != j), padded to a multiple of kPfSlab with (k + 1, k + 1); then column iv < k of the c part
 //   is (iv, k), padded likewise.  No slab of 4 K-steps straddles the vech | c boundary or runs past the row.
@@ -147,7 +107,7 @@ struct PfPixelsArgs {
   const int64_t *out_off;  // [nsel + 1]
   const double *w;         // [nsel][S] of this component
   const double *pm;        // [nsel] model weight of this component: 0 = not evaluated
-  PfModelArgs g;
+  ContinuumModelArgs g;
   int64_t S;
   int32_t num_lines;
   int64_t s0;
@@ -186,7 +146,7 @@ __global__ __launch_bounds__(256) void k_pf_pixels(PfPixelsArgs a) {
   for (int e = tid; e < nbp + kp; e += 256) {  // (i, j) in 6 bits each, the doubling bit, the scratch column + 1 (0: a zero column)
     int fi = k + 1, fj = k + 1, dbl = 0, ac = -1;
     if (e < nb) {
-      mc_unpack(e, &fi, &fj);
+      packed_unpack(e, &fi, &fj);
       dbl = fi != fj;
       ac = e;
     } else if (e >= nbp && e - nbp < k) {
@@ -197,7 +157,7 @@ __global__ __launch_bounds__(256) void k_pf_pixels(PfPixelsArgs a) {
     s_ij[e] = fi | (fj << 6) | (dbl << 12) | ((ac + 1) << 13);
   }
   for (int e = tid; e < PT * 2; e += 256) s_M[(e >> 1) * KS + k + (e & 1)] = (e & 1) ? 0.0 : 1.0;
-  pf_tile_rows(a.g, lam + 3, a.z_qsos[q], m.n_u, p0, PT, s_M, KS, s_mu, s_mf, tid);
+  model_tile_rows(a.g, lam + 3, a.z_qsos[q], m.n_u, p0, PT, s_M, KS, s_mu, s_mf, tid);
   __syncthreads();
 
   const int r = lane >> 4, c = lane & 15;
@@ -357,8 +317,8 @@ __global__ __launch_bounds__(256) void k_pf_pixels(PfPixelsArgs a) {
 
 // ------------------------------------------------------------------------------------------
 // k_pf_finish: one block per selected quasar of a launch group.
-//   The null component of weight p_0 > 0: B_0, v_0 accumulated, factorised and solved as k_mc_finish does
-//   (restated: that kernel stays as it is), Sigma_0 = B_0^-1 through L^-1; per pixel t_0 = mu + m' c_0,
+//   The null component of weight p_0 > 0: c_0 from continuum_null_solve with a = 1 (the function k_mc_finish and
+//   k_spectra_continuum call), Sigma_0 = B_0^-1 through L^-1; per pixel (model_tile_rows) t_0 = mu + m' c_0,
 //   s_0 = m' Sigma_0 m, and F1 = t_0, F2 = t_0^2, FW = s_0, FD = omega2 + nu.
 //   The mixture in the order (null, sub-DLA, DLA): flux_mean = Sum p_m F1_m, flux_var_within = Sum p_m FW_m,
 //   flux_var_between = max(Sum p_m F2_m - flux_mean^2, 0) (not fused), flux_var = within + between,
@@ -378,7 +338,7 @@ struct PfFinishArgs {
   double min_lambda, max_lambda;
   const int64_t *sel;
   const int64_t *out_off;
-  PfModelArgs g;
+  ContinuumModelArgs g;
   const double *pw;            // [nsel][3] normalised model weights (null, sub-DLA, DLA)
   const int32_t *flag[2];      // [nsel] of the sub-DLA and the DLA weight rows, or nullptr
   const double *sums[2];       // [total][4], or nullptr
@@ -416,109 +376,16 @@ __global__ __launch_bounds__(256) void k_pf_finish(PfFinishArgs a) {
   }
   __syncthreads();
   const PixelRow *pix = a.pix + m.pix_off;
-  double *v = s_B + nb;
+  const double *v = s_B + nb;  // c_0
 
-  if (p0 > 0.0) {  // the null component: k_mc_finish's, which is k_spectra_continuum with a = 1
-    const double *Mi = a.Mi + m.pix_off * k;
-    constexpr int kMine = (kMcNb + GPDLA_MAX_K + 255) / 256;
-    int ei[kMine], ej[kMine];
-    double acc[kMine];
-#pragma unroll
-    for (int t = 0; t < kMine; ++t) {
-      const int e = tid + 256 * t;
-      acc[t] = 0.0;
-      ei[t] = ej[t] = -1;
-      if (e < nb) mc_unpack(e, &ei[t], &ej[t]);
-      else if (e < nb + k) ei[t] = e - nb;
-    }
-    for (int pt0 = 0; pt0 < m.n_u; pt0 += kContTile) {
-      if (tid < kContTile) {
-        const int p = pt0 + tid;
-        double wt = 0.0, ut = 0.0;
-        if (p < m.n_u) {
-          const PixelRow row = pix[p];
-          const double ab = 1.0;
-          const double d = ab * ab * row.omega2 + row.nu;
-          const double rr = row.y - ab * row.mu;
-          wt = ab * ab / d;
-          ut = ab * rr / d;
-        }
-        s_wt[tid] = wt;
-        s_ut[tid] = ut;
-      }
-      __syncthreads();
-      const int np = min(kContTile, m.n_u - pt0);
-#pragma unroll
-      for (int t = 0; t < kMine; ++t) {
-        if (ei[t] < 0) continue;
-        const double *Mp = Mi + (int64_t)pt0 * k;
-        double sum = acc[t];
-        if (ej[t] >= 0)
-          for (int p = 0; p < np; ++p) sum = fma(Mp[p * k + ei[t]] * s_wt[p], Mp[p * k + ej[t]], sum);
-        else
-          for (int p = 0; p < np; ++p) sum = fma(Mp[p * k + ei[t]], s_ut[p], sum);
-        acc[t] = sum;
-      }
-      __syncthreads();
-    }
-#pragma unroll
-    for (int t = 0; t < kMine; ++t)
-      if (ei[t] >= 0) s_B[tid + 256 * t] = acc[t] + ((ej[t] == ei[t]) ? 1.0 : 0.0);
-    __syncthreads();
-    for (int j = 0; j < k; ++j) {
-      const int rj = j * (j + 1) / 2;
-      __syncthreads();
-      if (tid == 0) {
-        double sum = s_B[rj + j];
-        for (int mm = 0; mm < j; ++mm) sum = fma(-s_B[rj + mm], s_B[rj + mm], sum);
-        if (!(sum > 0.0)) s_pd = 0;
-        const double ljj = sqrt(sum);
-        s_B[rj + j] = ljj;
-        s_piv = ljj;
-      }
-      __syncthreads();
-      const double ljj = s_piv;
-      for (int i = j + 1 + tid; i < k; i += 256) {
-        const int ri = i * (i + 1) / 2;
-        double sum = s_B[ri + j];
-        for (int mm = 0; mm < j; ++mm) sum = fma(-s_B[ri + mm], s_B[rj + mm], sum);
-        s_B[ri + j] = sum / ljj;
-      }
-    }
-    __syncthreads();
-    if (tid == 0) {  // c_0 = L'^-1 L^-1 v
-      for (int i = 0; i < k; ++i) {
-        const int ri = i * (i + 1) / 2;
-        double zi = v[i];
-        for (int mm = 0; mm < i; ++mm) zi = fma(-s_B[ri + mm], v[mm], zi);
-        v[i] = zi / s_B[ri + i];
-      }
-      for (int i = k - 1; i >= 0; --i) {
-        double ci = v[i];
-        for (int mm = i + 1; mm < k; ++mm) ci = fma(-s_B[mm * (mm + 1) / 2 + i], v[mm], ci);
-        v[i] = ci / s_B[i * (i + 1) / 2 + i];
-      }
-    }
-    if (tid >= 64 && tid < 64 + k) {  // column cx of X = L^-1 (another wave than the substitution's)
-      const int cx = tid - 64;
-      s_X[cx * (cx + 1) / 2 + cx] = 1.0 / s_B[cx * (cx + 1) / 2 + cx];
-      for (int ii = cx + 1; ii < k; ++ii) {
-        const int ri = ii * (ii + 1) / 2;
-        double sum = 0.0;
-        for (int mm = cx; mm < ii; ++mm) sum = fma(s_B[ri + mm], s_X[mm * (mm + 1) / 2 + cx], sum);
-        s_X[ri + cx] = -sum / s_B[ri + ii];
-      }
-    }
+  if (p0 > 0.0) {  // the null component: a = 1
+    continuum_null_solve<kContTile>(pix, a.Mi + m.pix_off * k, m.n_u, k, nullptr, s_B, s_wt, s_ut, &s_piv, &s_pd, tid);
+    if (tid >= 64 && tid < 64 + k) packed_inverse_column(s_B, s_X, k, tid - 64);  // (another wave than the substitution's)
     __syncthreads();
     for (int e = tid; e < nb; e += 256) {
       int ia, ib;
-      mc_unpack(e, &ia, &ib);
-      double sig = 0.0;
-      for (int mm = ia; mm < k; ++mm) {
-        const int rm = mm * (mm + 1) / 2;
-        sig = fma(s_X[rm + ia], s_X[rm + ib], sig);
-      }
-      s_W[e] = sig;
+      packed_unpack(e, &ia, &ib);
+      s_W[e] = packed_gram_entry(s_X, k, ia, ib);
     }
     __syncthreads();
   }
@@ -543,7 +410,7 @@ __global__ __launch_bounds__(256) void k_pf_finish(PfFinishArgs a) {
   const double z_qso = a.z_qsos[q];
   for (int pt0 = 0; pt0 < m.n_u; pt0 += kMcPixTile) {
     __syncthreads();
-    if (p0 > 0.0) pf_tile_rows(a.g, lam, z_qso, m.n_u, pt0, kMcPixTile, &s_m[0][0], GPDLA_MAX_K + 1, s_mu, s_mf, tid);
+    if (p0 > 0.0) model_tile_rows(a.g, lam, z_qso, m.n_u, pt0, kMcPixTile, &s_m[0][0], GPDLA_MAX_K + 1, s_mu, s_mf, tid);
     __syncthreads();
     if (tid < kMcPixTile && pt0 + tid < m.n_u) {
       const int p = pt0 + tid;

@@ -17,7 +17,7 @@
 // Every sum runs in a fixed order and nothing is accumulated with atomics: outputs are bit-identical
 // from run to run and depend on their own quasar only.
 #pragma once
-#include "multi_kernels.hpp"
+#include "continuum_solve.hpp"
 
 namespace gpdla {
 
@@ -33,22 +33,6 @@ __device__ __forceinline__ double spectra_raw_at(double lambda, double z, double
     total += -g_lines.leading[j] * v;                                            // voigt.c:288
   }
   return exp(N * total);                                                         // voigt.c:291
-}
-
-// multi :267-285 at one observed wavelength (the arithmetic of k_prepare): exp(-Sum_l tau_l (1 + z_l)^beta)
-__device__ __forceinline__ double spectra_mean_flux(double wl, double z_qso, double lya_wavelength, double prev_tau_0,
-                                                    double prev_beta, int num_forest_lines) {
-  const double f_1 = g_lines.osc[0];
-  double total = 0.0;
-  for (int l = 0; l < num_forest_lines; ++l) {
-    const double wl_l = g_lines.wavelength_cm[l] * 1e8;
-    const double z_l = (wl - wl_l) / wl_l;                                       // multi :184-186
-    const double tau_l = prev_tau_0 * g_lines.osc[l] / f_1 * wl_l / lya_wavelength;
-    const double od = tau_l * pow(1 + z_l, prev_beta);                           // multi :275-276
-    if (l > 0 && z_l > z_qso) continue;                                          // multi :279-282
-    total += od;
-  }
-  return exp(-total);                                                            // multi :285
 }
 
 // ------------------------------------------------------------------------------------------
@@ -312,10 +296,14 @@ __global__ __launch_bounds__(256) void k_spectra_combine(SpectraCombineArgs a) {
 //   d = a^2 omega2 + nu,  r = y - a mu,  B = I + M' diag(a^2 / d) M,  c = B^-1 M' (a r / d)
 // which is the posterior mean of the coefficients of the low-rank part of the covariance
 // (log_mvnpdf_low_rank.m's B and its right-hand side, solved instead of folded into the
-// likelihood).  continuum = mu + M c is evaluated at ALL n_u pixels -- a masked pixel's mu and M row
+// likelihood): continuum_null_solve (continuum_solve.hpp), which k_mc_finish and k_pf_finish call with a = 1.
+// continuum = mu + M c is evaluated at ALL n_u pixels -- a masked pixel's mu and M row
 // are interpolated here as k_prepare interpolates a kept one -- and model_flux = a continuum.  The
 // pixel-diagonal omega term has no posterior mean away from the pixel that measured it and is left
 // out.  B not positive definite: NaN rows and status 4.
+// The shapes the edge tests are built around (tests/model_spectra_edge_cases.py): the solve stages the pixel weights
+// kContTile at a time, and thread tid of the 256 accumulates the entries of [vech(B) | v] that the solve enumerates as
+//   const int e = tid + 256 * t;
 // ------------------------------------------------------------------------------------------
 struct SpectraContinuumArgs {
   const QuasarMeta *meta;
@@ -326,25 +314,24 @@ struct SpectraContinuumArgs {
   const int64_t *sel;
   const int64_t *out_off;
   const double *absorption;  // on the output layout, or nullptr
-  ModelDev model;
-  double lya_wavelength, prev_tau_0, prev_beta;
-  int32_t meanflux, num_forest_lines;
+  ContinuumModelArgs g;
   double *continuum, *model_flux;  // either may be nullptr
   int32_t *status;                 // [nsel]
 };
 
-constexpr int kContTile = 128;
+constexpr int kContTile = 128;  // pixels staged at a time by continuum_null_solve, here and in the two finish kernels
 
 __global__ __launch_bounds__(256) void k_spectra_continuum(SpectraContinuumArgs a) {
   constexpr int kNb = GPDLA_MAX_K * (GPDLA_MAX_K + 1) / 2;
-  __shared__ double s_B[kNb + GPDLA_MAX_K];  // packed lower triangle of B, then v (then c)
+  __shared__ double s_B[kNb + GPDLA_MAX_K];  // packed lower triangle of B / L, then v (then c)
   __shared__ double s_wt[kContTile], s_ut[kContTile];
   __shared__ double s_piv;
   __shared__ int s_pd;
   const int s = blockIdx.x, tid = threadIdx.x;
   const int64_t q = a.sel[s];
   const QuasarMeta m = a.meta[q];
-  const int k = a.model.k, G = a.model.G, nb = k * (k + 1) / 2;
+  const ModelDev &model = a.g.model;
+  const int k = model.k, G = model.G;
   const PixelRow *pix = a.pix + m.pix_off;
   const double *Mi = a.Mi + m.pix_off * k;
   const double *absn = a.absorption ? a.absorption + a.out_off[s] : nullptr;
@@ -358,120 +345,24 @@ __global__ __launch_bounds__(256) void k_spectra_continuum(SpectraContinuumArgs 
     if (tid == 0) a.status[s] = m.status;
     return;
   }
-  // the entries of [vech(B) | v] this thread accumulates (at most 4 for k = 40), as (i, j); j < 0: v_i
-  constexpr int kMine = (kNb + GPDLA_MAX_K + 255) / 256;
-  int ei[kMine], ej[kMine];
-  double acc[kMine];
-#pragma unroll
-  for (int t = 0; t < kMine; ++t) {
-    const int e = tid + 256 * t;
-    acc[t] = 0.0;
-    ei[t] = ej[t] = -1;
-    if (e < nb) {
-      int i = (int)((sqrt(8.0 * e + 1.0) - 1.0) * 0.5);
-      while ((i + 1) * (i + 2) / 2 <= e) ++i;
-      while (i * (i + 1) / 2 > e) --i;
-      ei[t] = i;
-      ej[t] = e - i * (i + 1) / 2;
-    } else if (e < nb + k) {
-      ei[t] = e - nb;
-    }
-  }
-  for (int p0 = 0; p0 < m.n_u; p0 += kContTile) {
-    if (tid < kContTile) {
-      const int p = p0 + tid;
-      double wt = 0.0, ut = 0.0;
-      if (p < m.n_u) {
-        const PixelRow row = pix[p];
-        const double ab = absn ? absn[p] : 1.0;
-        const double d = ab * ab * row.omega2 + row.nu;
-        const double r = row.y - ab * row.mu;
-        wt = ab * ab / d;
-        ut = ab * r / d;
-      }
-      s_wt[tid] = wt;
-      s_ut[tid] = ut;
-    }
-    __syncthreads();
-    const int np = min(kContTile, m.n_u - p0);
-#pragma unroll
-    for (int t = 0; t < kMine; ++t) {
-      if (ei[t] < 0) continue;
-      const double *Mp = Mi + (int64_t)p0 * k;
-      double sum = acc[t];
-      if (ej[t] >= 0)
-        for (int p = 0; p < np; ++p) sum = fma(Mp[p * k + ei[t]] * s_wt[p], Mp[p * k + ej[t]], sum);
-      else
-        for (int p = 0; p < np; ++p) sum = fma(Mp[p * k + ei[t]], s_ut[p], sum);
-      acc[t] = sum;
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int t = 0; t < kMine; ++t)
-    if (ei[t] >= 0) s_B[tid + 256 * t] = acc[t] + ((ej[t] == ei[t]) ? 1.0 : 0.0);
   if (tid == 0) s_pd = 1;
-  __syncthreads();
-  // Cholesky of the packed lower triangle, column by column (as k_lowrank_single)
-  double *v = s_B + nb;
-  for (int j = 0; j < k; ++j) {
-    const int rj = j * (j + 1) / 2;
-    __syncthreads();
-    if (tid == 0) {
-      double sum = s_B[rj + j];
-      for (int mm = 0; mm < j; ++mm) sum = fma(-s_B[rj + mm], s_B[rj + mm], sum);
-      if (!(sum > 0.0)) s_pd = 0;
-      const double ljj = sqrt(sum);
-      s_B[rj + j] = ljj;
-      s_piv = ljj;
-    }
-    __syncthreads();
-    const double ljj = s_piv;
-    for (int i = j + 1 + tid; i < k; i += 256) {
-      const int ri = i * (i + 1) / 2;
-      double sum = s_B[ri + j];
-      for (int mm = 0; mm < j; ++mm) sum = fma(-s_B[ri + mm], s_B[rj + mm], sum);
-      s_B[ri + j] = sum / ljj;
-    }
-  }
-  __syncthreads();
-  if (tid == 0) {  // c = L'^-1 L^-1 v
-    for (int i = 0; i < k; ++i) {
-      const int ri = i * (i + 1) / 2;
-      double zi = v[i];
-      for (int mm = 0; mm < i; ++mm) zi = fma(-s_B[ri + mm], v[mm], zi);
-      v[i] = zi / s_B[ri + i];
-    }
-    for (int i = k - 1; i >= 0; --i) {
-      double ci = v[i];
-      for (int mm = i + 1; mm < k; ++mm) ci = fma(-s_B[mm * (mm + 1) / 2 + i], v[mm], ci);
-      v[i] = ci / s_B[i * (i + 1) / 2 + i];
-    }
-    a.status[s] = s_pd ? 0 : 4;
-  }
+  continuum_null_solve<kContTile>(pix, Mi, m.n_u, k, absn, s_B, s_wt, s_ut, &s_piv, &s_pd, tid);
+  if (tid == 0) a.status[s] = s_pd ? 0 : 4;
   __syncthreads();
   const bool pd = s_pd != 0;
-  // mu + M c on the whole grid: the interpolation of k_prepare (process_qsos.m:138-139, multi :287-288)
+  const double *v = s_B + k * (k + 1) / 2;  // c
+  // mu + M c on the whole grid, a thread per pixel: the interpolation of k_prepare (process_qsos.m:138-139, multi :287-288)
   const double *lam = a.lam_pad + m.lam_off + 3;
   const double z_qso = a.z_qsos[q];
   for (int p = tid; p < m.n_u; p += 256) {
     const double wl = lam[p];
-    const double rest = wl / (1 + z_qso);
-    int lo = 0, hi = G - 1;
-    if (rest >= a.model.rest[G - 1]) lo = G - 2;
-    else if (rest > a.model.rest[0]) {
-      while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (a.model.rest[mid] <= rest) lo = mid; else hi = mid;
-      }
-    }
-    const double t = (rest - a.model.rest[lo]) / (a.model.rest[lo + 1] - a.model.rest[lo]);
-    const double mf = a.meanflux ? spectra_mean_flux(wl, z_qso, a.lya_wavelength, a.prev_tau_0, a.prev_beta, a.num_forest_lines)
-                                 : 1.0;
-    double val = a.model.mu[lo] + (a.model.mu[lo + 1] - a.model.mu[lo]) * t;
-    if (a.meanflux) val = val * mf;
+    int lo;
+    const double t = model_bracket(model, wl / (1 + z_qso), &lo);
+    const double mf = a.g.mean_flux(wl, z_qso);
+    double val = model.mu[lo] + (model.mu[lo + 1] - model.mu[lo]) * t;
+    if (a.g.meanflux) val = val * mf;
     for (int c = 0; c < k; ++c) {
-      const double m0 = a.model.M[lo + (int64_t)c * G], m1 = a.model.M[lo + 1 + (int64_t)c * G];
+      const double m0 = model.M[lo + (int64_t)c * G], m1 = model.M[lo + 1 + (int64_t)c * G];
       val = fma((m0 + (m1 - m0) * t) * mf, v[c], val);
     }
     if (!pd) val = NAN;

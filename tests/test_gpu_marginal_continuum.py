@@ -195,10 +195,12 @@ def test_mixing(oracle):
     finally:
         batch.close()
         ctx.close()
-    # (1, 0, 0): the null continuum of the model-spectra kernel, no spread between samples
+    # (1, 0, 0): the null continuum of the model-spectra kernel (one solve, one interpolation: csrc/continuum_solve.hpp), bit
+    # for bit; no spread between samples
     d = MR.deviation(null["continuum_mean"], cond["continuum"])
     print(f"(1, 0, 0) against the null continuum of model_spectra: |delta| {d:.2e}")
-    assert d < 1e-12 and (null["coef_cov_between"] == 0).all() and (null["continuum_var_between"] == 0).all()
+    np.testing.assert_array_equal(null["continuum_mean"], cond["continuum"])
+    assert (null["coef_cov_between"] == 0).all() and (null["continuum_var_between"] == 0).all()
     assert (null["continuum_var"] > 0).all() and null["status"].tolist() == [0] * n
     for name in ALL:
         np.testing.assert_array_equal(default[name], dla_only[name], err_msg=name)

@@ -147,6 +147,9 @@ def test_constants_and_launch_split_mirror_follow_the_source():
     """The tile sizes the case lists are built around, and the arithmetic by which gpdla_batch_model_spectra
     cuts a selection into launches (E.launch_group), are still the library's."""
     kern, multi, mock = _read("spectra_kernels.hpp"), _read("multi_kernels.hpp"), _read("mock_kernels.hpp")
+    solve = _read("continuum_solve.hpp")  # continuum_null_solve: what k_spectra_continuum accumulates and factorises with
+    assert "continuum_null_solve<kContTile>(" in kern[kern.index("void k_spectra_continuum("):]
+    assert "const int e = tid + %d * t;" % E.CONT_THREADS in solve[solve.index("void continuum_null_solve("):]
     host = "".join(open(path).read() for path in _lib.host_sources())
     assert os.path.join(CSRC, "host_spectra.hpp") in _lib.host_sources()
     assert re.search(r"constexpr int kMapTile = %d;" % E.MAP_TILE, kern)
