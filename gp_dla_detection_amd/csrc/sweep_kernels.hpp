@@ -635,6 +635,23 @@ __device__ __forceinline__ void glds16(const double *gsrc, double *lds_wave_base
                : "v"(gsrc), "s"(lds)
                : "memory", "m0");
 }
+// The same copy with the source as a wave-uniform 64-bit base in scalar registers plus a 32-bit byte offset per
+// lane (the instruction's SADDR form).  For a source that advances by a constant from copy to copy under a lane
+// offset that never changes: the advance is then scalar arithmetic and the lane offset is formed once, where
+// glds16 has the caller re-form a 64-bit address per lane (two vector adds) for every copy.
+__device__ __forceinline__ const double *uniform_pointer(const double *p) {  // p is wave-uniform: say so
+  const uint64_t v = (uint64_t)(uintptr_t)p;
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+  return (const double *)(uintptr_t)(((uint64_t)hi << 32) | lo);
+}
+__device__ __forceinline__ void glds16_at(const double *sbase, uint32_t lane_bytes, double *lds_wave_base) {
+  const uint32_t lds = __builtin_amdgcn_readfirstlane(
+      (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void *)lds_wave_base);
+  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
+               :
+               : "v"(lane_bytes), "s"(sbase), "s"(lds)
+               : "memory", "m0");
+}
 // s_waitcnt vmcnt(0) only (gfx9 encoding: expcnt and lgkmcnt fields at their maxima).  The builtin,
 // not inline assembly: the compiler's own wait-count bookkeeping sees it and keeps its
 // conservative vmcnt waits out of the loops that follow.
@@ -1234,11 +1251,18 @@ __device__ __forceinline__ double near_poly(const double *line_tab, double ax) {
 // number of Lyman lines when known at compile time (0: read num_lines at run time).
 __device__ __forceinline__ uint32_t hi_word(double v) { return (uint32_t)__double2hiint(v); }
 
+// What the three-line wing tier leaves for the accurate tier of a voted line (near_lines3): per line
+// s = x^2 + y^2 on the FMA velocity (line j is near where hi_word(s[j]) < hi_word(900.0), the vote's own
+// test) and q = rho T(rho), the line's wing-tier term with cwing[j] left out.
+struct WingLines3 {
+  double s[3], q[3];
+};
+
 // Wing-tier optical-depth sum for the three-line case (Ly-alpha, beta, gamma): FMA-form
 // velocities, ONE reciprocal for the three lines (1/(sa sb sc), then peeled), degree-4 series.
 // Returns Sum_j lead_j y_j [Re w_j sqrt(pi)/y_j]; *near: some line within 30 Doppler widths.
 __device__ __forceinline__ double wing_sum3(double lamP, double msa, double msb, double msc, double cs,
-                                            bool *near) {
+                                            bool *near, WingLines3 *lines = nullptr) {
   const double xa = fma(lamP, msa, -cs), xb = fma(lamP, msb, -cs), xc = fma(lamP, msc, -cs);
   // x^2 + y^2 in one FMA; "near" is then tested on it (a threshold shift of y^2 <= 3e-7 in x^2,
   // immaterial: both tiers are accurate on either side of |x| = 30)
@@ -1258,7 +1282,9 @@ __device__ __forceinline__ double wing_sum3(double lamP, double msa, double msb,
   ta = fma(ta, ra, g_lines.t2[0]); tb = fma(tb, rb, g_lines.t2[1]); tc = fma(tc, rc, g_lines.t2[2]);
   ta = fma(ta, ra, kE1); tb = fma(tb, rb, kE1); tc = fma(tc, rc, kE1);
   ta = fma(ta, ra, 1.0); tb = fma(tb, rb, 1.0); tc = fma(tc, rc, 1.0);
-  return fma(g_lines.cwing[2], rc * tc, fma(g_lines.cwing[1], rb * tb, g_lines.cwing[0] * (ra * ta)));
+  const double qa = ra * ta, qb = rb * tb, qc = rc * tc;
+  if (lines) *lines = WingLines3{{sa, sb, sc}, {qa, qb, qc}};
+  return fma(g_lines.cwing[2], qc, fma(g_lines.cwing[1], qb, g_lines.cwing[0] * qa));
 }
 
 // wing_sum3 with the K-step's OTHER reciprocal riding along: 1/d of the weights (process_qsos.m:192-198
@@ -1271,7 +1297,7 @@ __device__ __forceinline__ double wing_sum3(double lamP, double msa, double msb,
 // (sweep_slim_kernel.hpp spells the same operations as two halves, wing3_front + wing3_back_rcp4: the record classes
 // are bit-identical only while both stay in step -- change them together.)
 __device__ __forceinline__ double wing_sum3_rcp4(double lamP, double msa, double msb, double msc, double cs,
-                                                 bool *near, double d, double *inv_d) {
+                                                 bool *near, double d, double *inv_d, WingLines3 *lines) {
   const double xa = fma(lamP, msa, -cs), xb = fma(lamP, msb, -cs), xc = fma(lamP, msc, -cs);
   const double sa = fma(xa, xa, g_lines.y2[0]), sb = fma(xb, xb, g_lines.y2[1]), sc = fma(xc, xc, g_lines.y2[2]);
   *near = min(min(hi_word(sa), hi_word(sb)), hi_word(sc)) < 0x408C2000u;
@@ -1286,7 +1312,9 @@ __device__ __forceinline__ double wing_sum3_rcp4(double lamP, double msa, double
   ta = fma(ta, ra, g_lines.t2[0]); tb = fma(tb, rb, g_lines.t2[1]); tc = fma(tc, rc, g_lines.t2[2]);
   ta = fma(ta, ra, kE1); tb = fma(tb, rb, kE1); tc = fma(tc, rc, kE1);
   ta = fma(ta, ra, 1.0); tb = fma(tb, rb, 1.0); tc = fma(tc, rc, 1.0);
-  return fma(g_lines.cwing[2], rc * tc, fma(g_lines.cwing[1], rb * tb, g_lines.cwing[0] * (ra * ta)));
+  const double qa = ra * ta, qb = rb * tb, qc = rc * tc;
+  *lines = WingLines3{{sa, sb, sc}, {qa, qb, qc}};
+  return fma(g_lines.cwing[2], qc, fma(g_lines.cwing[1], qb, g_lines.cwing[0] * qa));
 }
 
 constexpr int kRing2 = 33;   // doubled raw-profile ring: 32 slots + 1 pad per sample
@@ -1388,6 +1416,36 @@ __device__ __forceinline__ double total_near(double lamP, double m0, double m1, 
     }
   }
   return total;
+}
+
+// The three-line sum where the wave voted (some lane within 30 Doppler widths of some line): the wing tier's own
+// sum with the accurate tier in the terms that need it and nowhere else.  Line by line, under a wave-uniform
+// vote of the wing tier's own per-line test: the lanes within reach of line j replace its term by
+// sqrt(pi) lead_j Re w_j from the piecewise polynomial, on the reference's two-rounding velocity (voigt.c:287);
+// every other lane, and every line nobody voted for, keeps the wing-tier term it has just computed.  Any
+// number of lines may be voted.  The terms are then summed as the wing tier sums them.  (total_near<3>, which
+// this replaces in the three-line kernels, recomputed all three lines in every lane of a voting wave: the
+// lines are thousands of Doppler widths apart, so two of the three, and the far lanes of the third, were
+// thrown away.)  The two-rounding |x| of a near lane can exceed the FMA form's by an ulp of the velocity;
+// it is held below 32, the end of the table, so the gather stays inside line j's coefficients whatever s says.
+__device__ __forceinline__ double near_lines3(double lamP, double m0, double m1, double m2, const WingLines3 &w) {
+  const double c_light = g_lines.c, inv_s = g_lines.inv_sqrt2_sigma;
+  const double mm[3] = {m0, m1, m2};
+  double coef[3], term[3];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    coef[j] = g_lines.cwing[j];
+    term[j] = w.q[j];
+    const bool near_j = hi_word(w.s[j]) < 0x408C2000u;
+    if (__any(near_j)) {
+      if (near_j) {
+        const double ax = fmin(fabs((lamP * mm[j] - c_light) * inv_s), 0x1.fffffffffffffp+4);  // voigt.c:287
+        coef[j] = 1.7724538509055159 * g_lines.leading[j];
+        term[j] = near_poly(g_lines.near_poly + j * kNearLineDoubles, ax);
+      }
+    }
+  }
+  return fma(coef[2], term[2], fma(coef[1], term[1], coef[0] * term[0]));
 }
 
 // Wing tier for a line count known at run time only: sqrt(pi) Sum_{j<L} lead_j Re w_j by the wing
@@ -1562,9 +1620,10 @@ __global__ __launch_bounds__(WAVES * 64) void k_sweep(SweepArgs a) {
     double v;
     if (LINES == 3) {
       bool near0;
-      v = exp_table_scaled(nscale64 * wing_sum3(lam0, ms_r[0], ms_r[LINES > 1 ? 1 : 0], ms_r[LINES > 2 ? 2 : 0],
-                                                cs, &near0), exp_tab);
-      if (__any(near0)) v = GPDLA_RAW_ACCURATE(lam0);
+      WingLines3 wl;
+      double total = wing_sum3(lam0, ms_r[0], ms_r[LINES > 1 ? 1 : 0], ms_r[LINES > 2 ? 2 : 0], cs, &near0, &wl);
+      if (__any(near0)) total = near_lines3(lam0, mult_r[0], mult_r[LINES > 1 ? 1 : 0], mult_r[LINES > 2 ? 2 : 0], wl);
+      v = exp_table_scaled(nscale64 * total, exp_tab);
     } else {
       v = GPDLA_RAW_ACCURATE(lam0);
     }
@@ -1652,8 +1711,9 @@ __global__ __launch_bounds__(WAVES * 64) void k_sweep(SweepArgs a) {
         // (1) raw profile three K-steps ahead: voigt.c:282-292
         double total;
         bool near;
+        [[maybe_unused]] WingLines3 wl;
         if (LINES == 3) {
-          total = wing_sum3_rcp4(lamP, ms_r[0], ms_r[LINES > 1 ? 1 : 0], ms_r[LINES > 2 ? 2 : 0], cs, &near, d, &inv_d);
+          total = wing_sum3_rcp4(lamP, ms_r[0], ms_r[LINES > 1 ? 1 : 0], ms_r[LINES > 2 ? 2 : 0], cs, &near, d, &inv_d, &wl);
         } else {
           inv_d = fast_rcp(d);
           total = 0.0;
@@ -1667,7 +1727,10 @@ __global__ __launch_bounds__(WAVES * 64) void k_sweep(SweepArgs a) {
         }
         GPDLA_ST(0)  // operand requests + wing-tier optical depth
 #ifndef GPDLA_ABLATE_NOSLOW
-        if (__builtin_expect(__any(near), 0)) total = GPDLA_TOTAL_ACCURATE(lamP);
+        if (__builtin_expect(__any(near), 0)) {
+          if (LINES == 3) total = near_lines3(lamP, mult_r[0], mult_r[LINES > 1 ? 1 : 0], mult_r[LINES > 2 ? 2 : 0], wl);
+          else total = GPDLA_TOTAL_ACCURATE(lamP);
+        }
 #endif
         GPDLA_ST(1)  // accurate tier
         // B fragments of this step: requested only now, so that they are not live across the

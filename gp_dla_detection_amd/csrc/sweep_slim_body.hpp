@@ -65,21 +65,24 @@ __global__ __launch_bounds__(kSlimWaves * 64, 2) void GPDLA_SWEEP_SLIM_KERNEL(GP
   // The block's copy of chunk c's raw records (3584 B): wave w brings record w, 896 B, with its lanes 0..55 -- one
   // copy instruction per wave and chunk, and nothing lands behind the parity's raw buffer (the other parity's tiles
   // or the landing zones follow it at once)
+  // The source of all three copies is this wave's record of the chunk: a block-uniform address in scalar registers
+  // that advances by one chunk per chunk (scalar adds), under lane offsets formed once, here (glds16_at).
   double *const raw_mine = blocks + kSlimSweepTileBuf + wave_s * kSlimRec;
-  const double *const raw_src = rec_base + (size_t)wave_s * kSlimRec + 2 * lane;
-  auto issue_chunk = [&](int c) {
-    if (lane < kSlimRec / 2) glds16(raw_src + (size_t)c * CH * kSlimRec, raw_mine + (c & 1) * kSlimSweepBlock);
+  const double *const my_rec0 = uniform_pointer(rec_base + (size_t)wave_s * kSlimRec);
+  constexpr size_t kChunkDoubles = (size_t)CH * kSlimRec;
+  uint32_t off_raw = 16u * (uint32_t)lane;
+  auto issue_chunk = [&](int c, const double *my_rec) {  // my_rec: this wave's record of chunk c
+    if (lane < kSlimRec / 2) glds16_at(my_rec, off_raw, raw_mine + (c & 1) * kSlimSweepBlock);
   };
-  // This wave's private copy of K-step `wave` of chunk c: its 4 M rows, each laid down twice
+  // This wave's private copy of K-step `wave` of a chunk: its 4 M rows, each laid down twice
   // (lane 16 jj + p fetches doubles 2 (p & 7), 2 (p & 7) + 1 of pixel jj's row), and m[16..19] of
   // the 4 pixels (lanes 0..7).
-  const double *land_src = rec_base + (size_t)wave_s * kSlimRec;
-  const int src_rows = 4 * kSlimExtras + 16 * jj + 2 * (s & 7);
-  const int src_x = kSlimExtras * (lane >> 1) + 4 + 2 * (lane & 1);
-  auto issue_private = [&](int c) {
-    const double *rec = land_src + (size_t)c * CH * kSlimRec;
-    glds16(rec + src_rows, land);
-    if (lane < 8) glds16(rec + src_x, land + 4 * 32);
+  uint32_t off_rows = 8u * (uint32_t)(4 * kSlimExtras + 16 * jj + 2 * (s & 7));
+  uint32_t off_x = 8u * (uint32_t)(kSlimExtras * (lane >> 1) + 4 + 2 * (lane & 1));
+  asm volatile("" : "+v"(off_raw), "+v"(off_rows), "+v"(off_x));  // kept in registers, not re-derived per chunk
+  auto issue_private = [&](const double *my_rec) {
+    glds16_at(my_rec, off_rows, land);
+    if (lane < 8) glds16_at(my_rec, off_x, land + 4 * 32);
   };
   // Expansion of this wave's K-step of the chunk that goes to tile buffer P, tiles [t0, t1): the
   // operands are requested by expand_load (early in a K-step) and multiplied and stored by
@@ -108,21 +111,23 @@ __global__ __launch_bounds__(kSlimWaves * 64, 2) void GPDLA_SWEEP_SLIM_KERNEL(GP
 #pragma unroll
     for (int t = t0; t < t1; ++t) dst[t * 64] = (t == 8 ? x.p8 : x.mc) * x.o[t - t0];
   };
-  // per-lane LDS bases of parity 0: this wave's expansion target, the tile fragments, this lane's
-  // pixel block of a raw record, the u tile of a raw record
-  double *const xd0 = blocks + (size_t)wave_s * kSlimStepTiles + lane;
-  const double *const tb0 = blocks + lane;
-  const double *const mb0 = blocks + kSlimSweepTileBuf + kSlimExtras * jj;
-  const double *const ub0 = blocks + kSlimSweepTileBuf + 4 * kSlimExtras + lane;
   // an address the compiler must keep in a register instead of re-deriving it in every K-step
   auto pinned = [](const double *p) {
     uint32_t v = lds_address(p);
     asm volatile("" : "+v"(v));
     return (double *)(__attribute__((address_space(3))) double *)(uintptr_t)v;
   };
+  // per-lane LDS bases, in registers from here on (a chunk then forms its four parity addresses with one add
+  // each): this wave's expansion target in parity 1 -- a chunk expands into the OTHER parity -- and, of parity
+  // 0, the tile fragments, this lane's pixel block of a raw record, the u tile of a raw record
+  double *const xd1 = pinned(blocks + kSlimSweepBlock + (size_t)wave_s * kSlimStepTiles + lane);
+  double *const xd0 = xd1 - kSlimSweepBlock;  // (the priming's target: chunk 0 is parity 0)
+  const double *const tb0 = pinned(blocks + lane);
+  const double *const mb0 = pinned(blocks + kSlimSweepTileBuf + kSlimExtras * jj);
+  const double *const ub0 = pinned(blocks + kSlimSweepTileBuf + 4 * kSlimExtras + lane);
 
-  issue_private(0);
-  issue_chunk(0);
+  issue_private(my_rec0);
+  issue_chunk(0, my_rec0);
 
   const double c_light = g_lines.c, inv_s = g_lines.inv_sqrt2_sigma;
   [[maybe_unused]] double ms_r[3];
@@ -135,8 +140,9 @@ __global__ __launch_bounds__(kSlimWaves * 64, 2) void GPDLA_SWEEP_SLIM_KERNEL(GP
   auto optical_sum = [&](double lamP) -> double {
     if constexpr (LINES == 3) {
       bool near;
-      double total = wing_sum3(lamP, ms_r[0], ms_r[1], ms_r[2], cs, &near);
-      if (__builtin_expect(__any(near), 0)) total = total_near<3>(lamP, mult_r[0], mult_r[1], mult_r[2], nullptr, 3);
+      WingLines3 wl;
+      double total = wing_sum3(lamP, ms_r[0], ms_r[1], ms_r[2], cs, &near, &wl);
+      if (__builtin_expect(__any(near), 0)) total = near_lines3(lamP, mult_r[0], mult_r[1], mult_r[2], wl);
       return total;
     } else {
       bool near;
@@ -172,7 +178,7 @@ __global__ __launch_bounds__(kSlimWaves * 64, 2) void GPDLA_SWEEP_SLIM_KERNEL(GP
       xd0[t * 64] = (t == 8 ? b8[0] : mc) * (t == 8 ? a8[0] : t == 0 ? mc : t < 8 ? row[t] : bc[t - 9]);
   }
   __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the landing zone has been read ...
-  if (nchunks > 1) issue_private(1);   // ... and may be refilled
+  if (nchunks > 1) issue_private(my_rec0 + kChunkDoubles);   // ... and may be refilled
   glds_wait();
   __syncthreads();
 
@@ -200,17 +206,18 @@ __global__ __launch_bounds__(kSlimWaves * 64, 2) void GPDLA_SWEEP_SLIM_KERNEL(GP
   // that lost: LABBOOK, "Taps and row under the MFMA burst".
   // taps of the next K-step, carried across the chunk barrier too (the ring is this wave's own)
   double n0 = my_ring[0], n1 = my_ring[1], n2 = my_ring[2], n3 = my_ring[3], n4 = my_ring[4], n5 = my_ring[5], n6 = my_ring[6];
-  for (int c = 0; c < nchunks; ++c) {
+  const double *next_rec = my_rec0 + kChunkDoubles;  // this wave's record of chunk c + 1
+  for (int c = 0; c < nchunks; ++c, next_rec += kChunkDoubles) {
     // vmcnt(0): nothing of ours is in flight (see k_sweep).  lgkmcnt(0): no LDS request is open behind the chunk
     // barrier either, but the compiler cannot know that no scalar load of the prologue is (they return out of order),
     // and would make K-step 0's first use of LDS data wait for ALL of that step's requests
     __builtin_amdgcn_s_waitcnt(0x0070);
-    if (c + 1 < nchunks) issue_chunk(c + 1);
+    if (c + 1 < nchunks) issue_chunk(c + 1, next_rec);
     const int par = (c & 1) * kSlimSweepBlock;
     const double *tbuf = pinned(tb0 + par);
     const double *mine0 = pinned(mb0 + par);
     const double *ubuf = pinned(ub0 + par);
-    double *xdst = pinned(xd0 + (kSlimSweepBlock - par));
+    double *xdst = pinned(xd1 - par);
     double lam_next = 0.0;
     double2 n01 = {0.0, 0.0}, n23 = {0.0, 0.0};                                    // its pixel row
 #pragma unroll
@@ -218,7 +225,7 @@ __global__ __launch_bounds__(kSlimWaves * 64, 2) void GPDLA_SWEEP_SLIM_KERNEL(GP
       const int rn = c * CH + tt;
       constexpr int kXS = 3;  // K-steps that carry expansion work
       constexpr int kT0[3] = {0, 5, 9}, kT1[3] = {5, 9, 13};
-      if (tt == kXS && c + 2 < nchunks) issue_private(c + 2);
+      if (tt == kXS && c + 2 < nchunks) issue_private(next_rec + kChunkDoubles);
       if (rn < m.steps) {
         const double *tl = tbuf + (size_t)tt * kSlimStepTiles;
         const double *mine = mine0 + (size_t)tt * kSlimRec;
@@ -259,9 +266,10 @@ __global__ __launch_bounds__(kSlimWaves * 64, 2) void GPDLA_SWEEP_SLIM_KERNEL(GP
         double total;
         if constexpr (LINES == 3) {
           if (tt > 0) wf = wing3_front(lamP, ms_r[0], ms_r[1], ms_r[2], cs, &near);
-          total = wing3_back_rcp4(wf, d, &inv_d);
+          WingLines3 wl;
+          total = wing3_back_rcp4(wf, d, &inv_d, &wl);
 #ifndef SLIM_EXP_NONEAR  // (ablation, results wrong by construction: what the accurate tier costs)
-          if (__builtin_expect(__any(near), 0)) total = total_near<3>(lamP, mult_r[0], mult_r[1], mult_r[2], nullptr, 3);
+          if (__builtin_expect(__any(near), 0)) total = near_lines3(lamP, mult_r[0], mult_r[1], mult_r[2], wl);
 #endif
         } else {
           total = optical_sum(lamP);

@@ -185,7 +185,7 @@ __device__ __forceinline__ WingFront wing3_front(double lamP, double msa, double
   f.pab = f.sa * f.sb, f.pabc = f.pab * f.sc;
   return f;
 }
-__device__ __forceinline__ double wing3_back_rcp4(const WingFront &f, double d, double *inv_d) {
+__device__ __forceinline__ double wing3_back_rcp4(const WingFront &f, double d, double *inv_d, WingLines3 *lines) {
   const double rinv = fast_rcp(f.pabc * d);
   *inv_d = rinv * f.pabc;
   const double r3 = rinv * d;
@@ -196,7 +196,9 @@ __device__ __forceinline__ double wing3_back_rcp4(const WingFront &f, double d, 
   ta = fma(ta, ra, g_lines.t2[0]); tb = fma(tb, rb, g_lines.t2[1]); tc = fma(tc, rc, g_lines.t2[2]);
   ta = fma(ta, ra, kE1); tb = fma(tb, rb, kE1); tc = fma(tc, rc, kE1);
   ta = fma(ta, ra, 1.0); tb = fma(tb, rb, 1.0); tc = fma(tc, rc, 1.0);
-  return fma(g_lines.cwing[2], rc * tc, fma(g_lines.cwing[1], rb * tb, g_lines.cwing[0] * (ra * ta)));
+  const double qa = ra * ta, qb = rb * tb, qc = rc * tc;
+  *lines = WingLines3{{f.sa, f.sb, f.sc}, {qa, qb, qc}};  // for near_lines3, where the wave votes
+  return fma(g_lines.cwing[2], qc, fma(g_lines.cwing[1], qb, g_lines.cwing[0] * qa));
 }
 
 // Epilogue pass of the slim sweep: factor_pass of sweep_kernels.hpp with the spill scattered

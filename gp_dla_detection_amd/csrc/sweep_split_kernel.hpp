@@ -105,8 +105,9 @@ __global__ __launch_bounds__(512) void k_sweep_split(SweepArgs a) {
   auto raw_of = [&](double lamP) -> double {
     double total;
     bool near;
+    [[maybe_unused]] WingLines3 wl;
     if (LINES == 3) {
-      total = wing_sum3(lamP, ms_r[0], ms_r[LINES > 1 ? 1 : 0], ms_r[LINES > 2 ? 2 : 0], cs, &near);
+      total = wing_sum3(lamP, ms_r[0], ms_r[LINES > 1 ? 1 : 0], ms_r[LINES > 2 ? 2 : 0], cs, &near, &wl);
     } else {
       total = 0.0;
       near = false;
@@ -117,8 +118,10 @@ __global__ __launch_bounds__(512) void k_sweep_split(SweepArgs a) {
         total = fma(g_lines.cwing[j], wing_core(x2, g_lines.y2[j]), total);
       }
     }
-    if (__builtin_expect(__any(near), 0))
-      total = total_near<LINES>(lamP, mult_r[0], mult_r[LINES > 1 ? 1 : 0], mult_r[LINES > 2 ? 2 : 0], my_mult, L);
+    if (__builtin_expect(__any(near), 0)) {
+      if (LINES == 3) total = near_lines3(lamP, mult_r[0], mult_r[LINES > 1 ? 1 : 0], mult_r[LINES > 2 ? 2 : 0], wl);
+      else total = total_near<LINES>(lamP, mult_r[0], mult_r[LINES > 1 ? 1 : 0], mult_r[LINES > 2 ? 2 : 0], my_mult, L);
+    }
     return exp_table_scaled(nscale64 * total, exp_tab);
   };
   auto lam_of = [&](int tr) -> double { return lam[min(4 * tr + jj, n_pad - 1)]; };

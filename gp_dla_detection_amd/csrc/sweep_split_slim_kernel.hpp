@@ -282,13 +282,15 @@ __global__ __launch_bounds__(512) void k_sweep_split_slim(Args a) {
   auto raw_of = [&](double lamP) -> double {
     double total;
     bool near;
+    [[maybe_unused]] WingLines3 wl;
     if (LINES == 3) {
-      total = wing_sum3(lamP, ms_r[0], ms_r[LINES > 1 ? 1 : 0], ms_r[LINES > 2 ? 2 : 0], cs, &near);
+      total = wing_sum3(lamP, ms_r[0], ms_r[LINES > 1 ? 1 : 0], ms_r[LINES > 2 ? 2 : 0], cs, &near, &wl);
     } else {
       total = wing_sum_runtime(lamP * inv_opz, cs, L, &near);
     }
     if (__builtin_expect(__any(near), 0)) {
-      if constexpr (LINES > 0) total = total_near<LINES>(lamP, mult_r[0], mult_r[LINES > 1 ? 1 : 0], mult_r[LINES > 2 ? 2 : 0], nullptr, L);
+      if constexpr (LINES == 3) total = near_lines3(lamP, mult_r[0], mult_r[1], mult_r[2], wl);
+      else if constexpr (LINES > 0) total = total_near<LINES>(lamP, mult_r[0], mult_r[LINES > 1 ? 1 : 0], mult_r[LINES > 2 ? 2 : 0], nullptr, L);
       else total = total_near_at(lamP, opz, L);
     }
     return exp_table_scaled(nscale64 * total, exp_tab);
