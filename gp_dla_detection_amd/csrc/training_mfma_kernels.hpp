@@ -7,16 +7,19 @@
 //
 //   d = nu + omega2 (1 - exp(-tau0 (1+z)^beta) + c0)^2,   w = 1/d,   u = y/d          (:22-32)
 //   B_q = I + Sum_p w_qp m_p m_p',   t_q = Sum_p u_qp m_p      contraction over pixels  (:40)
-//   L_q = chol(B_q),  z_q = B_q^-1 t_q,  T_q = B_q^-1 + z_q z_q'   per quasar, k x k    (:42-46)
-//   -log p_q = 1/2 (Sum y^2 w - t_q'z_q + Sum log d + 2 Sum log L_jj + n log 2 pi)      (:48-52)
+//   L_q = chol(B_q),  y_q = L_q^-1 t_q,  z_q = L_q^-T y_q,  T_q = B_q^-1 + z_q z_q'   per quasar   (:42-46)
+//   -log p_q = 1/2 (Sum y^2 w - y_q'y_q + Sum log d + 2 Sum log L_jj + n log 2 pi)      (:48-52)
 //   dM[p,:] = m_p' (Sum_q w_qp T_q) - Sum_q u_qp z_q'          contraction over quasars (:55-56)
-//   core_qp = (K^-1 y)_p^2 - (K^-1)_pp = u^2 - 2 u w (m_p'z_q) + w^2 (m_p'T_q m_p) - w  (:59)
+//   core_qp = (K^-1 y)_p^2 - (K^-1)_pp = (u - w m_p'z_q)^2 - (w - w^2 m_p'B_q^-1 m_p)   (:59)
 //   dlog_omega[p] = -Sum_q an_qp core_qp, dlog_c0 / tau0 / beta = -Sum_qp core_qp da_qp  (:62-74)
 //
 // using K^-1 M = D^-1 M B^-1, M'K^-1 y = z, y'K^-1 y = Sum y^2 w - t'z (identities of the Woodbury
-// form; the as-written k x n matrix C of :44 is never formed).  m'T m is the dot product of
-// vech(m m') with vech(T) (off-diagonals doubled), i.e. the third contraction -- over the
-// k(k+1)/2 + k columns -- and every contraction runs on v_mfma_f64_16x16x4_f64.
+// form; the as-written k x n matrix C of :44 is never formed).  m'B^-1 m is the dot product of
+// vech(m m') with vech(B^-1) (off-diagonals doubled), i.e. the third contraction -- over the
+// k(k+1)/2 + k columns -- and every contraction runs on v_mfma_f64_16x16x4_f64.  (The core contracts
+// B^-1, not T: m'T m - (m'z)^2 gives m'B^-1 m back with log10((m'z)^2 / m'B^-1 m) digits fewer, 3 .. 4
+// at S/N 1000.  And t'z is y'y, z is L^-T y: B^-1 t by the multiplied-out inverse loses cond(B) eps.
+// Both measured against 50-digit arithmetic, tests/test_gpu_training_hard.py.)
 //
 // Kernels (k <= 20: 14 w-tiles + 2 u-tiles of 16 columns; k <= 40: four such tile groups):
 //   k_train_records   [vech(m m') | m] from M in the two B-operand tilings; omega2 = exp(2 log omega)
@@ -26,7 +29,7 @@
 //                     along; split along the pixel axis into partial sums
 //   k_train_factor    per quasar: partials added in split order, Cholesky (64 / KMAX quasars per wave,
 //                     lanes along the rows), B^-1, z, -log p; T_q and z_q in both operand tilings
-//   k_train_core      m'z and m'Tm by MFMA, then the element-wise gradient terms and their sums; its
+//   k_train_core      m'z and m'B^-1 m by MFMA, then the element-wise gradient terms and their sums; its
 //                     result registers hold w and u in the A-operand lane order of the dM contraction,
 //                     which it writes out as whole rows (wB, uB)
 //   k_train_contract  rows x steps MFMA contraction for dM (rows = pixels, steps over quasars), split
@@ -561,7 +564,7 @@ __global__ __launch_bounds__(kTrCWaves * 64, 2) void k_train_build(TrainBuildArg
 // ------------------------------------------------------------------------------------------
 // k_train_factor: 64 / KMAX quasars per wave, lanes along the rows (padded quasars write zero operands).
 // recD: [group][TQ + pad][16 tiles][jj = quasar % 4][col]  B[quasar][column] of [vech(T_q) | z_q]   (dM)
-// recE: [NQ16][Ks][jj = column % 4][s = quasar % 16]       A[quasar][column] of [vech2(T_q) | z_q]  (core)
+// recE: [NQ16][Ks][jj = column % 4][s = quasar % 16]       A[quasar][column] of [vech2(B_q^-1) | z_q]  (core)
 // ------------------------------------------------------------------------------------------
 struct TrainFactorArgs {
   TrainDims d;
@@ -604,7 +607,7 @@ __global__ __launch_bounds__(256, 2) void k_train_factor(TrainFactorArgs a) {
   // the code has no rank-dependent branch.  Column j of the right-looking Cholesky travels through
   // LDS once: every lane publishes a_ij, reads the pivot a_jj and the a_cj (c > j) it needs, and
   // takes ONE reciprocal square root -- l_ij = a_ij / sqrt(a_jj), row_c -= (a_ij / a_jj) a_cj.
-  // L, then L^-1 (column by column), then B^-1 = L^-T L^-1 and z = B^-1 t stay within the wave.
+  // L, then L^-1 (column by column), y = L^-1 t, z = L^-T y and B^-1 = L^-T L^-1 stay within the wave.
   // The two operand tilings of [T_q | z_q] are assembled in LDS (in place: vech(B^-1) overwrites
   // the summed partials, the recE rows the storage of L^-1) and leave the block as contiguous runs.
   using K = TrC<KMAX>;
@@ -724,8 +727,26 @@ __global__ __launch_bounds__(256, 2) void k_train_factor(TrainFactorArgs a) {
       if (i < tri_len(r)) sL[tri_off(r) + i] = x[r];  // (x_r = 0 for r < i: the pad entry is 0)
   }
   wave_lds_sync();
-  // B^-1 = L^-T L^-1: entry (i, c) = Sum_{r >= max(i, c)} Linv[r][i] Linv[r][c]; z = B^-1 t on the way
-  double zacc = 0.0;
+  // y = L^-1 t: lane i takes row i of L^-1 (its own address: no broadcast) and publishes y_i where z
+  // will live; then z_i = Sum_r Linv[r][i] y_r from the column in its registers, and y'y = t'z
+  double yi = 0.0;
+#pragma unroll
+  for (int c = 0; c < KMAX; ++c)
+    if (c <= i) yi = fma(sL[tri_off(i) + c], st[c], yi);
+  if (valid) sz[i] = yi;
+  wave_lds_sync();
+  double zacc = 0.0, yy = 0.0;
+#pragma unroll
+  for (int r = 0; r < KMAX; r += 2) {
+    const double2 yr = *reinterpret_cast<const double2 *>(sz + r);
+    zacc = fma(x[r], yr.x, zacc);
+    zacc = fma(x[r + 1], yr.y, zacc);
+    yy = fma(yr.x, yr.x, yy);
+    yy = fma(yr.y, yr.y, yy);
+  }
+  wave_lds_sync();  // every lane has read y: its storage takes z
+  if (valid) sz[i] = zacc;
+  // B^-1 = L^-T L^-1: entry (i, c) = Sum_{r >= max(i, c)} Linv[r][i] Linv[r][c]
 #pragma unroll
   for (int c0 = 0; c0 < KMAX; c0 += 4) {
     double v[4] = {0.0, 0.0, 0.0, 0.0};
@@ -740,25 +761,17 @@ __global__ __launch_bounds__(256, 2) void k_train_factor(TrainFactorArgs a) {
         v[3] = fma(x[r], l1.y, v[3]);
       }
     }
-    const double2 t0 = *reinterpret_cast<const double2 *>(st + c0), t1 = *reinterpret_cast<const double2 *>(st + c0 + 2);
-    zacc = fma(v[0], t0.x, zacc);
-    zacc = fma(v[1], t0.y, zacc);
-    zacc = fma(v[2], t1.x, zacc);
-    zacc = fma(v[3], t1.y, zacc);
     if (valid && i < k) {
 #pragma unroll
       for (int cc = 0; cc < 4; ++cc)
         if (c0 + cc <= i) sS[i * (i + 1) / 2 + c0 + cc] = v[cc];  // vech(B^-1) over the dead partial sums
     }
   }
-  if (valid) sz[i] = zacc;
   wave_lds_sync();
   if (valid && i == 0) {
-    double tz = 0.0, ld = 0.0;
-    for (int c = 0; c < KMAX; ++c) {
-      tz = fma(st[c], sz[c], tz);
-      ld += s_ld[ql][c];
-    }
+    const double tz = yy;
+    double ld = 0.0;
+    for (int c = 0; c < KMAX; ++c) ld += s_ld[ql][c];
     const double log_2pi = 1.83787706640934534;  // spectrum_loss.m:17
     const double v = 0.5 * ((s_sc[ql][1] - tz) + s_sc[ql][0] + 2 * ld + s_sc[ql][2] * log_2pi);  // :48-52
     const bool good = real && pd && v == v;  // (NaN: a pivot, or a variance d, that was not positive)
@@ -767,18 +780,22 @@ __global__ __launch_bounds__(256, 2) void k_train_factor(TrainFactorArgs a) {
     if (q < nq_pad) a.nlogp[q] = good ? v : 0.0;  // (nlogp is allocated for the padded quasar count)
   }
   __syncthreads();
-  // T = B^-1 + z z' in the two operand tilings (zero for padded / failed quasars): recD rows in
-  // place in s_S, recE rows (off-diagonals doubled: m'T m = Sum_{i>=j} (2 - delta_ij) T_ij m_i m_j)
-  // over the storage of L^-1
+  // The two operand tilings (zero for padded / failed quasars): recD rows [vech(T) | z], T = B^-1 +
+  // z z', in place in s_S; recE rows [vech2(B^-1) | z] (off-diagonals doubled: m'B^-1 m =
+  // Sum_{i>=j} (2 - delta_ij) B^-1_ij m_i m_j) over the storage of L^-1
   for (int e = tid; e < FQ * K::Cols; e += 256) {
     const int qe = e / K::Cols, c = e % K::Cols;
     const bool good = s_good[qe] != 0;
     double v = 0.0;
     if (c < K::W * 16) {
       const int vi = s_vi[c], vj = s_vj[c];
-      if (good && c < nb) v = s_S[qe][c] + s_z[qe][vi] * s_z[qe][vj];
+      double b = 0.0;
+      if (good && c < nb) {
+        b = s_S[qe][c];
+        v = b + s_z[qe][vi] * s_z[qe][vj];
+      }
       s_S[qe][c] = v;
-      if (c < 4 * K::KsW) s_L[qe][c] = vi != vj ? 2.0 * v : v;
+      if (c < 4 * K::KsW) s_L[qe][c] = vi != vj ? 2.0 * b : b;
     } else {
       const int cz = c - K::W * 16;
       if (good && cz < k) v = s_z[qe][cz];
@@ -1107,6 +1124,27 @@ __global__ __launch_bounds__(kTrF16Threads) void k_train_factor16(TrainFactorArg
     }
   }
   __syncthreads();
+  // recE: [g][Ks][jj = column % 4][s = quasar % 16] of [vech2(B^-1) | z], off-diagonals doubled (m'B^-1 m =
+  // Sum_{i>=j} (2 - delta_ij) B^-1_ij m_i m_j): its columns are a prefix of the vech columns, then of z.
+  // Written first, while s_S still holds vech(B^-1) (zero for padded / failed quasars).
+#pragma unroll 6
+  for (int e = tid; e < K::Ks * 4 * FQ; e += NT) {
+    const int qe = e % FQ, kj = e / FQ;  // kj = 4 ks + jj
+    const int64_t qq = q0 + qe;
+    const bool good = s_good[qe] != 0;
+    double v = 0.0;
+    if (kj < 4 * K::KsW) {
+      if (good && kj < nb) {
+        v = s_S[qe][kj];
+        if (s_vi[kj] != s_vj[kj]) v *= 2.0;
+      }
+    } else {
+      const int cz = kj - 4 * K::KsW;
+      if (good && cz < k) v = s_z[qe][cz];
+    }
+    if (qq < nq_pad) a.recE[(qq >> 4) * K::Ks * 64 + (int64_t)kj * 16 + (qq & 15)] = v;
+  }
+  __syncthreads();
   // T = B^-1 + z z' (zero for padded / failed quasars) in place in s_S: the recD rows
   // (one wave does the work four did in k_train_factor: the loops of the shell are unrolled so that
   // their LDS reads and stores are in flight together)
@@ -1134,26 +1172,11 @@ __global__ __launch_bounds__(kTrF16Threads) void k_train_factor16(TrainFactorArg
     const int64_t tq = q0 >> 2;
     if (tq < D.TQ) a.recD[(c >> 4) * a.group_stride + (tq * 16 + (c & 15)) * 64 + (e & 63)] = s_S[jj][16 * c + col];
   }
-  // recE: [g][Ks][jj = column % 4][s = quasar % 16], off-diagonals doubled (m'T m = Sum_{i>=j} (2 - delta_ij)
-  // T_ij m_i m_j): its columns are a prefix of the vech columns, then of z
-#pragma unroll 6
-  for (int e = tid; e < K::Ks * 4 * FQ; e += NT) {
-    const int qe = e % FQ, kj = e / FQ;  // kj = 4 ks + jj
-    const int64_t qq = q0 + qe;
-    double v;
-    if (kj < 4 * K::KsW) {
-      v = s_S[qe][kj];
-      if (s_vi[kj] != s_vj[kj]) v *= 2.0;
-    } else {
-      v = s_S[qe][K::W * 16 + (kj - 4 * K::KsW)];
-    }
-    if (qq < nq_pad) a.recE[(qq >> 4) * K::Ks * 64 + (int64_t)kj * 16 + (qq & 15)] = v;
-  }
 }
 
 // ------------------------------------------------------------------------------------------
 // k_train_core: one wave per (pixel group pt, split gs of the quasar groups).
-// X_qp = m_p' T_q m_p (KsW column steps), Y_qp = m_p' z_q (KsU column steps) by MFMA, then
+// X_qp = m_p' B_q^-1 m_p (KsW column steps), Y_qp = m_p' z_q (KsU column steps) by MFMA, then
 // core_qp and the sums over the wave's quasars: partcol[pt][gs][16] = Sum an core per pixel,
 // partsc[pt][gs][3] = Sum core da for (c0, tau0, beta).
 // ------------------------------------------------------------------------------------------
@@ -1169,7 +1192,7 @@ struct TrainCoreArgs {
 };
 constexpr size_t kTrCoreLds = 2 * TrC<20>::Ks * 64 * sizeof(double);  // k <= 20: two quasar groups' A operands
 
-// The element-wise gradient terms of one (16 quasars x 16 pixels) tile from X = m'Tm and Y = m'z
+// The element-wise gradient terms of one (16 quasars x 16 pixels) tile from X = m'B^-1 m and Y = m'z
 // (result register rr: quasar 16 g + jj + 4 rr, pixel p), accumulated into the wave's sums.
 // Register rr of lane (jj, s) is quasar 4 (4 g + rr) + jj, pixel s: the A-operand lane order of
 // quasar step 4 g + rr of the dM contraction, so w and u leave as whole 512-byte rows of wB / uB
@@ -1215,7 +1238,7 @@ __device__ __forceinline__ void train_core_tile(const TrainCoreArgs &a, int64_t 
       u = w * y;
       const double X = X4[rr], Y = Y4[rr];
       const double kiy = u - w * Y;                             // (K^-1 y)_p, :46
-      const double diag = w - w * w * X + w * w * Y * Y;        // (K^-1)_pp = w - w^2 m'B^-1 m, :59
+      const double diag = w - w * w * X;                        // (K^-1)_pp = w - w^2 m'B^-1 m, :59
       const double core = kiy * kiy - diag;
       col = fma(an, core, col);                                 // :62
       double da = c_0 * om * sf;                                // :65
