@@ -183,6 +183,31 @@ class PredictiveFlux(C.Structure):
                 ("flux_var_between", _dp), ("noise_var", _dp), ("status", _i32p)]
 
 
+class MarginalContinuumMultiRequest(C.Structure):
+    """gpdla_marginal_continuum_multi_request"""
+    _fields_ = [("num_selected", C.c_int64), ("selection", _i64p), ("max_dlas", C.c_int32), ("tables_source", C.c_int32),
+                ("sample_log_likelihoods_dla", _dp), ("base_sample_inds", _u32p), ("sample_log_likelihoods_lls", _dp),
+                ("model_weights", _dp), ("meanflux", C.c_int32), ("capacity", C.c_int64)]
+
+
+class MarginalContinuumMulti(C.Structure):
+    """gpdla_marginal_continuum_multi"""
+    _fields_ = [("offsets", _i64p), ("continuum_mean", _dp), ("continuum_var", _dp), ("continuum_var_between", _dp),
+                ("coef_mean", _dp), ("coef_cov_within", _dp), ("coef_cov_between", _dp), ("status", _i32p),
+                ("model_flags", _u32p)]
+
+
+class PredictiveFluxMultiRequest(C.Structure):
+    """gpdla_predictive_flux_multi_request"""
+    _fields_ = list(MarginalContinuumMultiRequest._fields_)
+
+
+class PredictiveFluxMulti(C.Structure):
+    """gpdla_predictive_flux_multi"""
+    _fields_ = [("offsets", _i64p), ("flux_mean", _dp), ("flux_var", _dp), ("flux_var_within", _dp),
+                ("flux_var_between", _dp), ("noise_var", _dp), ("status", _i32p), ("model_flags", _u32p)]
+
+
 class MockRequest(C.Structure):
     """gpdla_mock_request"""
     _fields_ = [("seed", C.c_uint64), ("absorber_offsets", _i64p), ("absorber_z", _dp), ("absorber_nhi", _dp),
@@ -355,6 +380,14 @@ SYMBOLS = [
     ("gpdla_batch_marginal_continuum", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(MarginalContinuumRequest),
                                                  C.POINTER(MarginalContinuum)]),
     ("gpdla_predictive_flux_validate", C.c_int, [C.POINTER(PredictiveFluxRequest), C.c_int64, C.c_int64, C.c_int]),
+    ("gpdla_marginal_continuum_multi_validate", C.c_int, [C.POINTER(MarginalContinuumMultiRequest), C.c_int64, C.c_int64, C.c_int,
+                                                          C.c_int, C.c_int]),
+    ("gpdla_batch_marginal_continuum_multi", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(MarginalContinuumMultiRequest),
+                                                       C.POINTER(MarginalContinuumMulti)]),
+    ("gpdla_predictive_flux_multi_validate", C.c_int, [C.POINTER(PredictiveFluxMultiRequest), C.c_int64, C.c_int64, C.c_int,
+                                                       C.c_int, C.c_int]),
+    ("gpdla_batch_predictive_flux_multi", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(PredictiveFluxMultiRequest),
+                                                    C.POINTER(PredictiveFluxMulti)]),
     ("gpdla_batch_predictive_flux", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(PredictiveFluxRequest),
                                               C.POINTER(PredictiveFlux)]),
     ("gpdla_debug_profiles_ms", C.c_int, [C.c_void_p, C.c_void_p, _dp]),

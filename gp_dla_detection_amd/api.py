@@ -479,6 +479,37 @@ class Batch:
         return self._grid_product("model_spectra", rq, sel, _lib.ModelSpectra(),
                                   lambda total: {name: total for p in set(products) for name in names[p]})
 
+    def _multi_tables(self, rq, tables, nsel: int, keep: list) -> int:
+        """Fill ``tables_source`` and the three table pointers of a multi-model request from ``tables`` ("resident" or a
+        dict of host tables, as :meth:`model_spectra_multi` takes them); the arrays the request points into are appended to
+        ``keep``.  Returns the tables' ``max_dlas``."""
+        S = self.num_samples
+        if isinstance(tables, str):
+            if tables != "resident":
+                raise ValueError("tables: 'resident' or a dict of host tables")
+            rq.tables_source = _lib.SPECTRA_WEIGHTS_RESIDENT
+            return self.max_dlas
+        rq.tables_source = _lib.SPECTRA_WEIGHTS_HOST
+        dla = np.ascontiguousarray(tables["sample_log_likelihoods_dla"], dtype=np.float64)
+        if dla.ndim != 3 or dla.shape[0] != nsel or dla.shape[2] != S:
+            raise _lib.GpdlaError(-1, f"sample_log_likelihoods_dla must be [nsel, max_dlas, S] = ({nsel}, max_dlas, {S}), got {dla.shape}")
+        md = dla.shape[1]
+        keep.append(dla)
+        rq.sample_log_likelihoods_dla = dla.ctypes.data_as(_dp)
+        if tables.get("sample_log_likelihoods_lls") is not None:
+            lls = np.ascontiguousarray(tables["sample_log_likelihoods_lls"], dtype=np.float64)
+            if lls.shape != (nsel, S):
+                raise _lib.GpdlaError(-1, f"sample_log_likelihoods_lls must be [nsel, S] = {(nsel, S)}, got {lls.shape}")
+            keep.append(lls)
+            rq.sample_log_likelihoods_lls = lls.ctypes.data_as(_dp)
+        if tables.get("base_sample_inds") is not None:
+            base = np.ascontiguousarray(tables["base_sample_inds"], dtype=np.uint32)
+            if base.shape != (nsel, md - 1, S):
+                raise _lib.GpdlaError(-1, f"base_sample_inds must be [nsel, max_dlas-1, S] = {(nsel, md - 1, S)}, got {base.shape}")
+            keep.append(base)
+            rq.base_sample_inds = base.ctypes.data_as(C.POINTER(C.c_uint32))
+        return md
+
     def model_spectra_multi(self, selection=None, tables="resident", model_weights=None, models=None,
                             products=("models", "average"), meanflux: bool | None = None, sub_dla: bool = True) -> dict:
         """The per-pixel absorption of a multi-DLA run averaged over the samples of every model and over
@@ -499,35 +530,12 @@ class Batch:
         Returns those with ``offsets [nsel + 1]``, ``status [nsel]`` and ``model_flags [nsel]`` (bit n-1: model
         DLA(n) has no weight; bit 30: the sub-DLA model)."""
         sel = self._selection(selection)
-        nsel, S = sel.size, self.num_samples
+        nsel = sel.size
         rq = _lib.ModelSpectraMultiRequest()
         rq.num_selected = nsel
         rq.selection = sel.ctypes.data_as(_i64p)
         keep = [sel]
-        if isinstance(tables, str):
-            if tables != "resident":
-                raise ValueError("tables: 'resident' or a dict of host tables")
-            rq.tables_source, md = _lib.SPECTRA_WEIGHTS_RESIDENT, self.max_dlas
-        else:
-            rq.tables_source = _lib.SPECTRA_WEIGHTS_HOST
-            dla = np.ascontiguousarray(tables["sample_log_likelihoods_dla"], dtype=np.float64)
-            if dla.ndim != 3 or dla.shape[0] != nsel or dla.shape[2] != S:
-                raise _lib.GpdlaError(-1, f"sample_log_likelihoods_dla must be [nsel, max_dlas, S] = ({nsel}, max_dlas, {S}), got {dla.shape}")
-            md = dla.shape[1]
-            keep.append(dla)
-            rq.sample_log_likelihoods_dla = dla.ctypes.data_as(_dp)
-            if tables.get("sample_log_likelihoods_lls") is not None:
-                lls = np.ascontiguousarray(tables["sample_log_likelihoods_lls"], dtype=np.float64)
-                if lls.shape != (nsel, S):
-                    raise _lib.GpdlaError(-1, f"sample_log_likelihoods_lls must be [nsel, S] = {(nsel, S)}, got {lls.shape}")
-                keep.append(lls)
-                rq.sample_log_likelihoods_lls = lls.ctypes.data_as(_dp)
-            if tables.get("base_sample_inds") is not None:
-                base = np.ascontiguousarray(tables["base_sample_inds"], dtype=np.uint32)
-                if base.shape != (nsel, md - 1, S):
-                    raise _lib.GpdlaError(-1, f"base_sample_inds must be [nsel, max_dlas-1, S] = {(nsel, md - 1, S)}, got {base.shape}")
-                keep.append(base)
-                rq.base_sample_inds = base.ctypes.data_as(C.POINTER(C.c_uint32))
+        md = self._multi_tables(rq, tables, nsel, keep)
         rq.max_dlas = md
         first, last = (1, md) if models is None else ((int(models), int(models)) if np.isscalar(models) else
                                                       (int(models[0]), int(models[-1])))
@@ -684,6 +692,74 @@ class Batch:
         sel, keep = self._mixture_request(rq, selection, weights, components, model_weights, meanflux)
         out = self._grid_product("predictive_flux", rq, sel, _lib.PredictiveFlux(),
                                  lambda total: {name: total for name in PREDICTIVE_FLUX_ARRAYS})
+        del keep
+        if residuals:
+            y, kept = self.grid_flux(sel)
+            out.update(predictive_residuals(out, y, kept))
+        return out
+
+    # ---- marginal continuum and predictive flux over all models of a multi-DLA run ----
+
+    def _mixture_multi_request(self, rq, selection, tables, model_weights, meanflux):
+        """Fill a multi-model mixture request; returns (selection, max_dlas, the arrays the request points into)."""
+        sel = self._selection(selection)
+        nsel = sel.size
+        rq.num_selected = nsel
+        rq.selection = sel.ctypes.data_as(_i64p)
+        keep = [sel]
+        md = self._multi_tables(rq, tables, nsel, keep)
+        rq.max_dlas = md
+        if model_weights is not None:
+            w = np.ascontiguousarray(model_weights, dtype=np.float64)
+            if w.shape != (nsel, 2 + md):
+                raise _lib.GpdlaError(-1, f"model_weights must be [nsel, 2 + max_dlas] = {(nsel, 2 + md)}, got {w.shape}")
+            keep.append(w)
+            rq.model_weights = w.ctypes.data_as(_dp)
+        rq.meanflux = int(bool(self.max_dlas) if meanflux is None else bool(meanflux))
+        return sel, md, keep
+
+    def marginal_continuum_multi(self, selection=None, tables="resident", model_weights=None, meanflux: bool | None = None) -> dict:
+        """:meth:`marginal_continuum` over ALL models of a multi-DLA run (gpdla_batch_marginal_continuum_multi; the
+        definitions are in include/gpdla.h): the components are (null, sub-DLA, DLA(1), .., DLA(max_dlas)), and sample i
+        of model DLA(n) absorbs with the product of the n profiles of its slots, gathered through ``base_sample_inds`` as
+        :meth:`model_spectra_multi` gathers them.
+
+        ``tables``: ``"resident"`` or the dict of host tables of :meth:`model_spectra_multi`.
+        ``model_weights``: ``[nsel, 2 + max_dlas]`` as (null, sub-DLA, DLA(1..max_dlas)), each row normalised by its sum, or
+        None: the resident ``model_posteriors`` (resident tables only).  A negative or infinite entry is refused; a row
+        with a NaN (the reference's early exit) gives NaN rows and ``SPECTRA_AVERAGE_UNDEFINED`` in ``status`` --
+        :func:`renormalised_model_posteriors` makes weights that include such quasars.
+        Returns what :meth:`marginal_continuum` returns (no ``sample_coefficients``) and ``model_flags [nsel]``: bit n-1 --
+        model DLA(n) carries weight for the quasar and its table row has none (NaN rows, status 0); bit 30: the sub-DLA
+        table."""
+        rq = _lib.MarginalContinuumMultiRequest()
+        sel, _md, keep = self._mixture_multi_request(rq, selection, tables, model_weights, meanflux)
+        nsel, k = sel.size, self.ctx.k
+        nb = k * (k + 1) // 2
+        rows = {"coef_mean": (nsel, k), "coef_cov_within": (nsel, nb), "coef_cov_between": (nsel, nb)}
+        flags = np.zeros(nsel, dtype=np.uint32)
+        st = _lib.MarginalContinuumMulti()
+        st.model_flags = flags.ctypes.data_as(C.POINTER(C.c_uint32))
+        out = self._grid_product("marginal_continuum_multi", rq, sel, st,
+                                 lambda total: {**{name: total for name in MARGINAL_CONTINUUM_ARRAYS}, **rows},
+                                 self.max_dlas, int(self._multi_processed))
+        out["model_flags"] = flags
+        del keep
+        return out
+
+    def predictive_flux_multi(self, selection=None, tables="resident", model_weights=None, meanflux: bool | None = None,
+                              residuals: bool = False) -> dict:
+        """:meth:`predictive_flux` over ALL models of a multi-DLA run (gpdla_batch_predictive_flux_multi): the components,
+        ``tables``, ``model_weights`` and ``model_flags`` of :meth:`marginal_continuum_multi`, the arrays and the
+        ``residuals`` of :meth:`predictive_flux`."""
+        rq = _lib.PredictiveFluxMultiRequest()
+        sel, _md, keep = self._mixture_multi_request(rq, selection, tables, model_weights, meanflux)
+        flags = np.zeros(sel.size, dtype=np.uint32)
+        st = _lib.PredictiveFluxMulti()
+        st.model_flags = flags.ctypes.data_as(C.POINTER(C.c_uint32))
+        out = self._grid_product("predictive_flux_multi", rq, sel, st, lambda total: {name: total for name in PREDICTIVE_FLUX_ARRAYS},
+                                 self.max_dlas, int(self._multi_processed))
+        out["model_flags"] = flags
         del keep
         if residuals:
             y, kept = self.grid_flux(sel)
@@ -1619,10 +1695,50 @@ def _mixture_inputs(results, components, model_weights, sample_rows):
     return components, sampled, model_weights, sample_rows
 
 
+def _mixture_multi(method: str, flat, rows, model, samples, spectra, results, p, sel, model_weights, multi_rows, device,
+                   max_quasars_per_batch, **kw) -> dict:
+    """:func:`marginal_continuum` / :func:`predictive_flux` with ``multi_models``: ``Batch.<method>`` block by block on the
+    three tables of the selected quasars (``multi_rows(idx)``, default: those of ``results``), ``flat`` per-pixel arrays and
+    ``rows`` per-quasar arrays stitched in selection order."""
+    if not isinstance(p, MultiParameters):
+        raise ValueError("multi_models needs MultiParameters (a multi-DLA run)")
+    if multi_rows is None:
+        if results is None or "base_sample_inds" not in results or np.asarray(results["sample_log_likelihoods_dla"]).ndim != 3:
+            raise ValueError("multi_models needs results with base_sample_inds and sample_log_likelihoods_dla [nq, max_dlas, S]")
+        multi_rows = lambda idx: {name: np.asarray(results[name])[idx] for name in  # noqa: E731
+                                  ("sample_log_likelihoods_dla", "base_sample_inds", "sample_log_likelihoods_lls")}
+    if model_weights is None or (isinstance(model_weights, str) and model_weights == "posteriors"):
+        if results is None:
+            raise ValueError("multi_models needs model_weights or results")
+        model_weights = results["model_posteriors"]
+    elif isinstance(model_weights, str):
+        raise ValueError("model_weights: 'posteriors', an array [nq, 2 + max_dlas] or None")
+    model_weights = np.asarray(model_weights, dtype=np.float64)
+    per = _block_size(max_quasars_per_batch, spectra, sel, model, samples)
+    out = {"selection": sel, "offsets": np.zeros(sel.size + 1, dtype=np.int64), "status": np.zeros(sel.size, dtype=np.int32),
+           "model_flags": np.zeros(sel.size, dtype=np.uint32)}
+    parts = {name: [] for name in tuple(flat) + tuple(rows)}
+    with closing(_resident_blocks(model, samples, spectra, sel, p, device, per)) as blocks:
+        for lo, hi, idx, batch in blocks:
+            res = getattr(batch, method)(tables=multi_rows(idx), model_weights=model_weights[idx], **kw)
+            _stitch(out, lo, hi, res)
+            out["model_flags"][lo:hi] = res["model_flags"]
+            for name in parts:
+                parts[name].append(res[name])
+    k = np.asarray(model["M"]).shape[1]
+    empty = {"coef_mean": (0, k), "coef_cov_within": (0, k * (k + 1) // 2), "coef_cov_between": (0, k * (k + 1) // 2)}
+    for name in parts:
+        if parts[name]:
+            out[name] = np.concatenate(parts[name], axis=0)
+        else:
+            out[name] = np.zeros(empty.get(name, 0), dtype=np.int64 if name == "num_kept" else np.float64)
+    return out
+
+
 def marginal_continuum(model: dict, samples: dict, spectra, results: dict | None = None,
                        params: Parameters | None = None, selection=None, components=("dla",), model_weights=None,
                        sample_coefficients: bool = False, sample_rows=None, device: int = 0,
-                       max_quasars_per_batch: int | None = None) -> dict:
+                       max_quasars_per_batch: int | None = None, multi_models: bool = False, multi_rows=None) -> dict:
     """The marginal continuum (:meth:`Batch.marginal_continuum`) of the selected quasars of a processed run,
     batched like :func:`model_spectra`: nothing is swept again, the posterior weights come from the saved
     sample log-likelihoods.
@@ -1635,10 +1751,22 @@ def marginal_continuum(model: dict, samples: dict, spectra, results: dict | None
     model DLA(1) of ``[nq, max_dlas, S]``) and ``sample_log_likelihoods_lls`` of ``results``;
     ``sample_rows(idx, name) -> [len(idx), S]`` (``name`` ``"dla"`` or ``"sub_dla"``) supplies the rows
     instead (a file streamed block by block).  Returns ``selection``, ``offsets``, ``status`` and the arrays of
-    :meth:`Batch.marginal_continuum` in selection order; results do not depend on the batching."""
+    :meth:`Batch.marginal_continuum` in selection order; results do not depend on the batching.
+
+    ``multi_models``: the mixture over ALL models of a multi-DLA run instead (:meth:`Batch.marginal_continuum_multi`):
+    ``components`` and ``sample_rows`` are ignored, ``results`` must carry ``base_sample_inds``, the 3-D
+    ``sample_log_likelihoods_dla`` and ``sample_log_likelihoods_lls`` -- or ``multi_rows(idx)`` returns the dict of those
+    three for quasars ``idx`` -- and ``model_weights`` is ``[nq, 2 + max_dlas]`` over ALL quasars (default and
+    ``"posteriors"``: ``results["model_posteriors"]``; :func:`renormalised_model_posteriors` includes the quasars of the
+    reference's early exit).  The result also carries ``model_flags``; ``sample_coefficients`` are not offered."""
     p = params or Parameters()
     spectra = list(spectra)
     sel = np.arange(len(spectra), dtype=np.int64) if selection is None else np.asarray(selection, dtype=np.int64).reshape(-1)
+    if multi_models:
+        if sample_coefficients:
+            raise ValueError("sample_coefficients are not offered with multi_models")
+        return _mixture_multi("marginal_continuum_multi", MARGINAL_CONTINUUM_ARRAYS, MARGINAL_CONTINUUM_ROWS[:3], model, samples,
+                              spectra, results, p, sel, model_weights, multi_rows, device, max_quasars_per_batch)
     components, sampled, model_weights, sample_rows = _mixture_inputs(results, components, model_weights, sample_rows)
     S = np.asarray(samples["offset_samples"]).size
     k = np.asarray(model["M"]).shape[1]
@@ -1692,17 +1820,21 @@ def predictive_residuals(pf: dict, flux, kept) -> dict:
 def predictive_flux(model: dict, samples: dict, spectra, results: dict | None = None,
                     params: Parameters | None = None, selection=None, components=("dla",), model_weights=None,
                     residuals: bool = False, sample_rows=None, device: int = 0,
-                    max_quasars_per_batch: int | None = None) -> dict:
+                    max_quasars_per_batch: int | None = None, multi_models: bool = False, multi_rows=None) -> dict:
     """The posterior predictive flux (:meth:`Batch.predictive_flux`) of the selected quasars of a processed run,
     batched like :func:`marginal_continuum`, whose arguments these are: nothing is swept again, the posterior weights
     come from the saved sample log-likelihoods; ``model_weights="posteriors"`` mixes by
     :func:`posterior_model_weights`.  ``residuals``: also the in-sample replicate ``residual`` per pixel and
     ``chi2``, ``num_kept`` per quasar (conservative; not leave-one-out).  Returns ``selection``, ``offsets``,
     ``status`` and the arrays of :meth:`Batch.predictive_flux` in selection order; results do not depend on the
-    batching."""
+    batching.  ``multi_models``, ``multi_rows``: as :func:`marginal_continuum` (:meth:`Batch.predictive_flux_multi`)."""
     p = params or Parameters()
     spectra = list(spectra)
     sel = np.arange(len(spectra), dtype=np.int64) if selection is None else np.asarray(selection, dtype=np.int64).reshape(-1)
+    if multi_models:
+        names = PREDICTIVE_FLUX_ARRAYS + (PREDICTIVE_FLUX_RESIDUALS if residuals else ())
+        return _mixture_multi("predictive_flux_multi", names, PREDICTIVE_FLUX_ROWS if residuals else (), model, samples, spectra,
+                              results, p, sel, model_weights, multi_rows, device, max_quasars_per_batch, residuals=residuals)
     components, sampled, model_weights, sample_rows = _mixture_inputs(results, components, model_weights, sample_rows)
     per = _block_size(max_quasars_per_batch, spectra, sel, model, samples)
     out = {"selection": sel, "offsets": np.zeros(sel.size + 1, dtype=np.int64), "status": np.zeros(sel.size, dtype=np.int32)}

@@ -895,8 +895,9 @@ def save_marginal_continuum(path: str, mc: dict, **run_metadata) -> None:
     :func:`save_model_spectra`: ``quasar_ind`` (1-based), ``num_pixels`` and ``status`` as columns, the three
     per-pixel arrays as ragged N x 1 cell arrays, ``coef_mean`` [N x k], ``coef_cov_within`` and
     ``coef_cov_between`` [N x k (k + 1) / 2] (packed lower triangles, row by row) and, when present,
-    ``model_weights`` [N x 3] as matrices and ``sample_coefficients`` as a cell of [S x k] matrices.
-    :func:`load_model_spectra` reads it."""
+    ``model_weights`` [N x 3] as matrices and ``sample_coefficients`` as a cell of [S x k] matrices.  With
+    ``multi_models`` the same cells hold the mixture over all models, ``model_weights`` is [N x (2 + max_dlas)] and
+    ``model_flags`` is an extra column.  :func:`load_model_spectra` reads it."""
     off = np.asarray(mc["offsets"], dtype=np.int64)
     nsel = off.size - 1
     w = _MatWriter(path)
@@ -916,6 +917,8 @@ def save_marginal_continuum(path: str, mc: dict, **run_metadata) -> None:
         if "sample_coefficients" in mc:
             v = np.asarray(mc["sample_coefficients"], dtype=np.float64)
             w.put("sample_coefficients", [np.ascontiguousarray(v[i]) for i in range(nsel)])
+        if "model_flags" in mc:     # multi_models
+            w.put("model_flags", np.asarray(mc["model_flags"], dtype=np.float64))
     finally:
         w.close()
 
@@ -929,7 +932,8 @@ def save_predictive_flux(path: str, pf: dict, **run_metadata) -> None:
     """What :func:`api.predictive_flux` returns as a ``-v7.3`` file, in the layout of :func:`save_marginal_continuum`:
     ``quasar_ind`` (1-based), ``num_pixels`` and ``status`` as columns, the five per-pixel arrays (and ``residual``
     when present) as ragged N x 1 cell arrays, ``chi2`` and ``num_kept`` as columns and ``model_weights`` [N x 3] as a
-    matrix when present.  :func:`load_predictive_flux` reads it."""
+    matrix when present ([N x (2 + max_dlas)], with ``model_flags`` as an extra column, for ``multi_models``).
+    :func:`load_predictive_flux` reads it."""
     off = np.asarray(pf["offsets"], dtype=np.int64)
     nsel = off.size - 1
     w = _MatWriter(path)
@@ -948,6 +952,8 @@ def save_predictive_flux(path: str, pf: dict, **run_metadata) -> None:
                 w.put(name, np.asarray(pf[name], dtype=np.float64))
         if "model_weights" in pf:
             w.put("model_weights", np.ascontiguousarray(pf["model_weights"], dtype=np.float64))
+        if "model_flags" in pf:     # multi_models
+            w.put("model_flags", np.asarray(pf["model_flags"], dtype=np.float64))
     finally:
         w.close()
 

@@ -165,12 +165,50 @@ def _run_mixture(call, preloaded, catalog, model_file, samples_file, processed, 
     return res, is_multi, components
 
 
+def _run_mixture_multi(call, preloaded, catalog, model_file, samples_file, processed, p_dla, indices, model_weights, device,
+                       max_quasars_per_batch, **more):
+    """``--multi-models`` of ``--marginal-continuum`` and ``--predictive-flux``: the selection of a multi-DLA processed file,
+    its spectra, its three tables streamed by :func:`multi_row_reader` (as ``--multi-models`` of the moments streams them)
+    and ``call(..., multi_models=True)``.  ``model_weights``: ``"posteriors"`` (the file's ``model_posteriors``) or
+    ``"equal"`` (equal over all ``2 + max_dlas`` components).  Returns the result with its selection and model_weights."""
+    results = {k: np.asarray(v, dtype=np.float64).reshape(-1) if k.startswith("p_") else v
+               for k, v in io.loadmat73(processed, ["model_posteriors", "p_dlas", "test_ind"]).items()}
+    mp = np.asarray(results["model_posteriors"], dtype=np.float64)
+    if mp.shape[1] <= 2:
+        raise ValueError("--multi-models needs a multi-DLA processed file")
+    sel = select(results, p_dla, indices)
+    z_qsos = np.asarray(io.load_catalog(catalog, ("z_qsos",))["z_qsos"], dtype=np.float64)
+    test_ind = np.asarray(results["test_ind"]).reshape(-1).astype(bool) if "test_ind" in results else None
+    run_pos = np.flatnonzero(test_ind) if test_ind is not None else np.arange(z_qsos.size)
+    spectra_sel = io.load_preloaded_qsos(preloaded, z_qsos, run_pos[sel])
+    model, samples = io.load_learned_model(model_file), io.load_dla_samples(samples_file)
+    weights = mp[sel] if model_weights == "posteriors" else np.ones((sel.size, mp.shape[1]))
+    multi_rows, close = multi_row_reader(processed)
+    try:  # the loaded list holds the selected quasars only: positions 0 .. len(sel) - 1 map to sel
+        res = call(model, samples, spectra_sel, None, params=MultiParameters(max_dlas=mp.shape[1] - 2), model_weights=weights,
+                   multi_models=True, multi_rows=lambda idx: multi_rows(sel[idx]), device=device,
+                   max_quasars_per_batch=max_quasars_per_batch, **more)
+    finally:
+        close()
+    res["selection"] = sel
+    res["model_weights"] = weights
+    return res
+
+
 def run_marginal_continuum(preloaded: str, catalog: str, model_file: str, samples_file: str, processed: str, out: str,
                            p_dla: float | None = None, indices=None, components=("dla",), model_weights="posteriors",
-                           multi: bool | None = None, device: int = 0, max_quasars_per_batch: int | None = None) -> dict:
+                           multi: bool | None = None, device: int = 0, max_quasars_per_batch: int | None = None,
+                           multi_models: bool = False) -> dict:
     """``--marginal-continuum``: :func:`api.marginal_continuum` of the selected quasars of a processed file, its
     sample tables streamed like the moments' rows, written by :func:`io.save_marginal_continuum`.
-    ``model_weights``: ``"posteriors"`` (p_no_dlas, p_lls or 0, p_dlas of the file) or ``"equal"``."""
+    ``model_weights``: ``"posteriors"`` (p_no_dlas, p_lls or 0, p_dlas of the file) or ``"equal"``.
+    ``multi_models`` (``--multi-models``): the mixture over all models of a multi-DLA file (DESIGN.md 4.25);
+    ``components`` is ignored, ``model_weights`` is the file's ``model_posteriors`` or equal over all of them."""
+    if multi_models:
+        res = _run_mixture_multi(api.marginal_continuum, preloaded, catalog, model_file, samples_file, processed, p_dla, indices,
+                                 model_weights, device, max_quasars_per_batch)
+        io.save_marginal_continuum(out, res, processed_file=str(processed), multi_dla=np.float64(1), multi_models=np.float64(1))
+        return res
     res, is_multi, components = _run_mixture(api.marginal_continuum, preloaded, catalog, model_file, samples_file, processed,
                                              p_dla, indices, components, model_weights, multi, device, max_quasars_per_batch)
     io.save_marginal_continuum(out, res, processed_file=str(processed), multi_dla=np.float64(is_multi),
@@ -181,10 +219,15 @@ def run_marginal_continuum(preloaded: str, catalog: str, model_file: str, sample
 def run_predictive_flux(preloaded: str, catalog: str, model_file: str, samples_file: str, processed: str, out: str,
                         p_dla: float | None = None, indices=None, components=("dla",), model_weights="posteriors",
                         residuals: bool = False, multi: bool | None = None, device: int = 0,
-                        max_quasars_per_batch: int | None = None) -> dict:
+                        max_quasars_per_batch: int | None = None, multi_models: bool = False) -> dict:
     """``--predictive-flux``: :func:`api.predictive_flux` of the selected quasars of a processed file, its sample
     tables streamed like the moments' rows, written by :func:`io.save_predictive_flux`.  The arguments are those of
     :func:`run_marginal_continuum`; ``residuals``: also the in-sample replicate residuals (``--residuals``)."""
+    if multi_models:
+        res = _run_mixture_multi(api.predictive_flux, preloaded, catalog, model_file, samples_file, processed, p_dla, indices,
+                                 model_weights, device, max_quasars_per_batch, residuals=residuals)
+        io.save_predictive_flux(out, res, processed_file=str(processed), multi_dla=np.float64(1), multi_models=np.float64(1))
+        return res
     res, is_multi, components = _run_mixture(api.predictive_flux, preloaded, catalog, model_file, samples_file, processed,
                                              p_dla, indices, components, model_weights, multi, device, max_quasars_per_batch,
                                              residuals=residuals)
@@ -203,7 +246,8 @@ def main(argv=None) -> int:
     ap.add_argument("--moments-sub-dla", action="store_true", help="weight the sub-DLA sample table")
     ap.add_argument("--multi-models", action="store_true",
                     help="a multi-DLA processed file: also the moments of every model DLA(1..max_dlas) and of the "
-                         "sub-DLA model, and the absorption averaged over the models by model_posteriors")
+                         "sub-DLA model, and the absorption averaged over the models by model_posteriors; with "
+                         "--marginal-continuum / --predictive-flux: the mixture over ALL models (DESIGN.md 4.25)")
     ap.add_argument("--marginal-continuum", action="store_true",
                     help="write the marginal continuum instead (DESIGN.md 4.23): its posterior mean and variance over "
                          "the sample tables and the models")
@@ -213,9 +257,11 @@ def main(argv=None) -> int:
     ap.add_argument("--residuals", action="store_true",
                     help="--predictive-flux: also the in-sample replicate residuals, chi2 and num_kept")
     ap.add_argument("--components", type=str, default="dla",
-                    help="--marginal-continuum, --predictive-flux: any of null,sub_dla,dla")
+                    help="--marginal-continuum, --predictive-flux: any of null,sub_dla,dla (ignored with --multi-models: "
+                         "every model is a component)")
     ap.add_argument("--model-weights", choices=("posteriors", "equal"), default="posteriors",
-                    help="--marginal-continuum, --predictive-flux: mix the components by the file's posteriors, or equally")
+                    help="--marginal-continuum, --predictive-flux: mix the components by the file's posteriors, or equally "
+                         "(--multi-models: model_posteriors, or equal over all 2 + max_dlas components)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--max-quasars-per-batch", type=int, default=None)
     a = ap.parse_args(argv)
@@ -223,13 +269,14 @@ def main(argv=None) -> int:
     if a.predictive_flux:
         res = run_predictive_flux(a.preloaded, a.catalog, a.model, a.samples, a.processed, a.out, p_dla=a.p_dla, indices=idx,
                                   components=tuple(x for x in a.components.split(",") if x), model_weights=a.model_weights,
-                                  residuals=a.residuals, device=a.device, max_quasars_per_batch=a.max_quasars_per_batch)
+                                  residuals=a.residuals, device=a.device, max_quasars_per_batch=a.max_quasars_per_batch,
+                                  multi_models=a.multi_models)
         print(f"wrote {a.out}: {res['selection'].size} quasars, {int(res['offsets'][-1])} grid pixels")
         return 0
     if a.marginal_continuum:
         res = run_marginal_continuum(a.preloaded, a.catalog, a.model, a.samples, a.processed, a.out, p_dla=a.p_dla, indices=idx,
                                      components=tuple(x for x in a.components.split(",") if x), model_weights=a.model_weights,
-                                     device=a.device, max_quasars_per_batch=a.max_quasars_per_batch)
+                                     device=a.device, max_quasars_per_batch=a.max_quasars_per_batch, multi_models=a.multi_models)
         print(f"wrote {a.out}: {res['selection'].size} quasars, {int(res['offsets'][-1])} grid pixels")
         return 0
     res = run(a.preloaded, a.catalog, a.model, a.samples, a.processed, a.out, p_dla=a.p_dla, indices=idx,

@@ -1390,6 +1390,104 @@ int gpdla_predictive_flux_validate(const gpdla_predictive_flux_request *request,
 int gpdla_batch_predictive_flux(gpdla_context *ctx, gpdla_batch *batch, const gpdla_predictive_flux_request *request,
                                 gpdla_predictive_flux *out);
 
+/* ---------------------------------------------------------------------------------------------
+ * Marginal continuum and posterior predictive flux over ALL models of a multi-DLA run.
+ * Additive: GPDLA_ABI_VERSION is unchanged.  fp64 throughout; tests/marginal_continuum_multi_restatement.py and
+ * tests/predictive_flux_multi_restatement.py state the same in NumPy.
+ *
+ * Every definition of gpdla_batch_marginal_continuum and gpdla_batch_predictive_flux above holds unchanged: the
+ * prepared rows, d_i, B_i, v_i, c_i, Sigma_i; cbar, W, V; per pixel t_ip, s_ip, f_ip, F1, F2, FW, FD; the
+ * pixel-diagonal term left out; masked pixels treated as kept ones except for noise_var.  Two things change.
+ *
+ * 1. Components, in this order: null; the sub-DLA table; DLA(1), .., DLA(max_dlas).  For model DLA(n), sample i:
+ *   profile  a_i = A_{n,i}(p) = Prod_{j=1..n} c_{s_j(i)}(p) of gpdla_batch_model_spectra_multi, word for word: the
+ *            slots s_1(i) = i, s_j(i) = base_sample_inds[q][j-2][i] - 1, the product of the BROADENED profiles
+ *            (z, N of nhi_samples) in slot order;
+ *   weight   that entry's: w_i = exp(l_i - max l) / Sum from row sample_log_likelihoods_dla[q][n-1][.], a NaN l_i
+ *            weighs 0, a sample one of whose slots j >= 2 has base index 0 ("never drawn") is read as NaN.
+ *   The sub-DLA table and DLA(1) are the two sampled components of the entries above, bit for bit.
+ * 2. Model weights: model_weights [num_selected][2 + max_dlas] in the order (P_null, P_lls, P_1 .. P_md), or NULL: the
+ *   batch's resident model_posteriors (resident tables only).  Each row is normalised by its sum; the sums over the
+ *   models run in component order.  A row with a negative or infinite entry, or without a positive finite sum, is
+ *   refused.  A row with a NaN entry is NOT refused (the reference's early exit leaves whole model_posteriors rows
+ *   NaN): that quasar gets NaN rows and GPDLA_SPECTRA_AVERAGE_UNDEFINED in its status.
+ *
+ * A component of weight exactly 0 is not evaluated; a sample of weight exactly 0 is never touched (its column
+ * density may be NaN).  status: the quasar's sweep status (1, 3: NaN rows); 4 = a B_i of positive weight, or B_0, is
+ * not positive definite (NaN rows); GPDLA_SPECTRA_AVERAGE_UNDEFINED as above.  A component of positive weight whose
+ * weight row has no weights (all NaN, all -inf, a +inf, every sample consuming a base index of 0) gives NaN rows
+ * and status 0, and is named in model_flags[s]: bit n-1 for DLA(n), GPDLA_SPECTRA_MULTI_FLAG_LLS for the sub-DLA
+ * table.  A component the quasar does not weigh is never flagged.  A conditioned batch is refused.
+ * sample_coefficients are not offered.
+ *
+ * Sums run in a fixed order without atomics (samples in list / index order, waves in wave order, chunks in chunk
+ * order, components in component order): outputs are bit-identical for any selection order and launch grouping
+ * and for the resident and the host form of the same tables.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct {
+  int64_t num_selected;
+  const int64_t *selection;          /* [num_selected] quasars of the batch; NULL = 0 .. num_selected-1 */
+  int32_t max_dlas;                  /* models of the tables: 1 .. GPDLA_POSTERIOR_MAX_MODELS */
+  int32_t tables_source;             /* GPDLA_SPECTRA_WEIGHTS_RESIDENT (after gpdla_batch_process_multi) or _HOST */
+  const double *sample_log_likelihoods_dla;  /* host: [num_selected][max_dlas][S], where a row weighs a DLA(n) */
+  const uint32_t *base_sample_inds;          /* host: [num_selected][max_dlas-1][S], 1-based, 0 = never drawn,
+                                                where a row weighs a DLA(n >= 2) */
+  const double *sample_log_likelihoods_lls;  /* host: [num_selected][S], where a row weighs the sub-DLA table */
+  const double *model_weights;       /* host [num_selected][2 + max_dlas], or NULL: the resident model_posteriors
+                                        (refused for host tables) */
+  int32_t meanflux;                  /* != 0: prepared rows of the mean-flux model */
+  int64_t capacity;                  /* entries of each per-pixel output array */
+} gpdla_marginal_continuum_multi_request;
+typedef struct {
+  int64_t *offsets;                  /* [num_selected + 1]; required */
+  double *continuum_mean, *continuum_var, *continuum_var_between; /* per pixel; any may be NULL */
+  double *coef_mean;                 /* [num_selected][k] or NULL */
+  double *coef_cov_within, *coef_cov_between; /* [num_selected][k (k + 1) / 2] or NULL */
+  int32_t *status;                   /* [num_selected] or NULL */
+  uint32_t *model_flags;             /* [num_selected] or NULL */
+} gpdla_marginal_continuum_multi;
+typedef struct {
+  int64_t num_selected;
+  const int64_t *selection;
+  int32_t max_dlas;
+  int32_t tables_source;
+  const double *sample_log_likelihoods_dla;
+  const uint32_t *base_sample_inds;
+  const double *sample_log_likelihoods_lls;
+  const double *model_weights;
+  int32_t meanflux;
+  int64_t capacity;
+} gpdla_predictive_flux_multi_request; /* the fields of gpdla_marginal_continuum_multi_request */
+typedef struct {
+  int64_t *offsets;                  /* [num_selected + 1]; required */
+  double *flux_mean, *flux_var, *flux_var_within, *flux_var_between, *noise_var; /* per pixel; any may be NULL */
+  int32_t *status;                   /* [num_selected] or NULL */
+  uint32_t *model_flags;             /* [num_selected] or NULL */
+} gpdla_predictive_flux_multi;
+/* The checks the two entries make before their first device call, for a batch of num_quasars quasars uploaded for
+ * batch_max_dlas models (0: a single-DLA batch) that has (batch_processed != 0) or has not run
+ * gpdla_batch_process_multi: max_dlas outside 1 .. GPDLA_POSTERIOR_MAX_MODELS, a selection index outside the batch,
+ * a resident source on a single-DLA batch, on a batch of another max_dlas or on one that has not been processed,
+ * host tables without model_weights, a host table that a weighted component needs and that is missing, a host base
+ * index above num_samples, a negative or infinite model weight or a row (without a NaN) without a positive finite
+ * sum, no lls_nhi_samples while the sub-DLA column carries weight (without model_weights: always).  Return GPDLA_OK
+ * or GPDLA_ERR_INVALID_ARGUMENT.  Need no GPU. */
+int gpdla_marginal_continuum_multi_validate(const gpdla_marginal_continuum_multi_request *request, int64_t num_quasars,
+                                            int64_t num_samples, int has_lls_nhi_samples, int batch_max_dlas,
+                                            int batch_processed);
+int gpdla_predictive_flux_multi_validate(const gpdla_predictive_flux_multi_request *request, int64_t num_quasars,
+                                         int64_t num_samples, int has_lls_nhi_samples, int batch_max_dlas,
+                                         int batch_processed);
+/* The selected quasars are taken in groups whose scratch rows fit 512 MiB; host tables are staged a group at a time;
+ * results do not depend on the grouping.  With gpdla_context_set_timing enabled, gpdla_context_last_sweep_ms reports
+ * the kernels of the call (weights, contract, solve, live list, pixels, finish). */
+int gpdla_batch_marginal_continuum_multi(gpdla_context *ctx, gpdla_batch *batch,
+                                         const gpdla_marginal_continuum_multi_request *request,
+                                         gpdla_marginal_continuum_multi *out);
+int gpdla_batch_predictive_flux_multi(gpdla_context *ctx, gpdla_batch *batch,
+                                      const gpdla_predictive_flux_multi_request *request,
+                                      gpdla_predictive_flux_multi *out);
+
 #ifdef __cplusplus
 }
 #endif
