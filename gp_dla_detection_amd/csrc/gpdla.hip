@@ -36,7 +36,6 @@
 #include "spectra_multi_kernels.hpp"
 #include "marginal_continuum_kernels.hpp"
 #include "predictive_flux_kernels.hpp"
-#include "mixture_multi_kernels.hpp"
 #include "mock_kernels.hpp"
 #include "sample_kernels.hpp"
 #include "preload_kernels.hpp"

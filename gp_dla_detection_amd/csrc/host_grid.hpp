@@ -118,12 +118,15 @@ size_t mc_scratch_bytes() {
   return kMcScratchBytes;
 }
 
+// ma.nslots < 2: k_mc_contract on ma.c; else k_mc_contract_multi for the model DLA(ma.nslots)
 template <int RT, int CPW, int PT>
-int launch_mc_contract(const McContractArgs &ca, int64_t n, int64_t S, hipStream_t st) {
-  McContractArgs args = ca;
-  args.chunks = (int32_t)((S + 16 * RT - 1) / (16 * RT));
-  if (n * args.chunks > 2147483647LL) return fail(GPDLA_ERR_UNSUPPORTED, "selection too large for one launch");
-  hipLaunchKernelGGL((k_mc_contract<RT, CPW, PT>), dim3((unsigned)(n * args.chunks)), dim3(256), 0, st, args);
+int launch_mc_contract(const McContractMultiArgs &ma, int64_t n, int64_t S, hipStream_t st) {
+  McContractMultiArgs args = ma;
+  args.c.chunks = (int32_t)((S + 16 * RT - 1) / (16 * RT));
+  if (n * args.c.chunks > 2147483647LL) return fail(GPDLA_ERR_UNSUPPORTED, "selection too large for one launch");
+  const dim3 grid((unsigned)(n * args.c.chunks));
+  if (args.nslots >= 2) hipLaunchKernelGGL((k_mc_contract_multi<RT, CPW, PT>), grid, dim3(256), 0, st, args);
+  else hipLaunchKernelGGL((k_mc_contract<RT, CPW, PT>), grid, dim3(256), 0, st, args.c);
   HIP_TRY(hipGetLastError());
   return GPDLA_OK;
 }
@@ -182,85 +185,214 @@ int validate_mixture(const MixtureRequest &rq, int64_t nq, int64_t S, bool has_l
   return GPDLA_OK;
 }
 
-// A mixture over the sample tables and the models, from the request its entry has validated down to the launch
-// groups: the refusals that need the batch, the selection, the normalised model weights, the posterior weights
-// of each table the mixture reaches, and the scratch rows of k_mc_contract.  The entry then loops
-//   for (s0 = 0; s0 < nsel; s0 += nsub) { n = min(nsub, nsel - s0); per reached table: contract(comp, s0, n), own kernels }
-// comp 0 is the sub-DLA table, comp 1 the DLA table.  Host buffers first, the Staging last (its rule).
+// What a MixturePlan is built from, once its entry has validated the request.  The mixture has the null component
+// and 1 + md sampled ones: comp 0 is the sub-DLA table, comp n model DLA(n), whose sample i absorbs with the product
+// of n profiles gathered through the base rows (n >= 2).  The single-DLA entries have md = 1 and no base rows.
+struct MixtureSpec {
+  int64_t num_selected;
+  const int64_t *selection;
+  int md;
+  bool resident;                    // the tables are the batch's, on the device; else the caller's, [num_selected] quasars
+  const double *lls, *dla;          // quasar r's rows start at lls + r * lls_stride ([S]) and dla + r * dla_stride ([md][S])
+  int64_t lls_stride, dla_stride;
+  const uint32_t *base;             // [.][md - 1][S]
+  const double *model_weights;      // host [num_selected][2 + md]; nullptr: `posteriors`, the device's [nq][2 + md]
+  const double *posteriors;         // gathered by entry, or (nullptr as well) the row (0, .., 0, 1)
+  bool meanflux;
+  int64_t capacity;
+};
+
+// of a single-DLA entry; `tables` as validate_mixture gave them (no table is looked up for a mixture that reaches none)
+MixtureSpec mixture_spec(const gpdla_batch *b, const MixtureRequest &rq, int tables) {
+  MixtureSpec sp = {};
+  sp.num_selected = rq.num_selected;
+  sp.selection = rq.selection;
+  sp.md = 1;
+  sp.resident = rq.weights_source != GPDLA_SPECTRA_WEIGHTS_HOST;
+  if (sp.resident && tables) {
+    const SampleTable lls = resident_samples(b, true), dla = resident_samples(b, false);
+    sp.lls = lls.table, sp.lls_stride = lls.width;
+    sp.dla = dla.table, sp.dla_stride = dla.width;
+  } else {
+    sp.lls = rq.sample_log_likelihoods_lls, sp.dla = rq.sample_log_likelihoods_dla;
+    sp.lls_stride = sp.dla_stride = b->S;
+  }
+  sp.model_weights = rq.model_weights;
+  sp.meanflux = rq.meanflux != 0;
+  sp.capacity = rq.capacity;
+  return sp;
+}
+
+// A mixture over the sample tables and the models, from the validated request down to the launch groups: the
+// selection, the normalised model weights, the scratch rows of k_mc_contract and, group by group, the staged slice of
+// host tables and the posterior weights of every component the mixture reaches.  The two products loop
+//   for (s0 = 0; s0 < nsel; s0 += nsub) { n = min(nsub, nsel - s0); begin_group(s0, n);
+//                                         per reached comp: contract(comp, s0, n), own kernels; finish }
+// Everything a kernel of a group indexes by entry is handed to it from the group's first entry on, so the weights and
+// the staged slice are the group's own, as in host_spectra_multi.hpp.  The scratch table is ONE group-sized buffer,
+// reused component after component.  Host buffers first, the Staging last (its rule).
 struct MixturePlan {
   gpdla_context *c;
   gpdla_batch *b;
-  const int tables;
+  const MixtureSpec sp;
   hipStream_t st = nullptr;
+  int md = 0, ncomp = 0;              // ncomp = 1 + md sampled components
+  unsigned reach = 0;                 // bit comp: some row weighs the component
   int64_t nsel = 0, S = 0, nsub = 0;  // nsub: quasars a launch group
   int k = 0, nb = 0, ncol = 0;        // nb: packed triangle of B; ncol: a scratch row, [vech(B) | v]
   int chunks = 0;                     // kMcSolveChunk samples each
   size_t tot = 1;                     // max(gs.total, 1)
+  ContinuumModelArgs g;
   GridSelection gs;
-  std::vector<double> pw, pcol[2];    // [nsel][3] rows normalised by their sums; a reached component's column
-  std::vector<int64_t> rows[2];
-  std::vector<int32_t> status;        // [nsel]: where the entry fetches its status
+  std::vector<double> pw, pcol, post;  // [nsel][2 + md] normalised; [ncomp][nsel] columns, 0 for an undefined row
+  std::vector<int64_t> rows_dla, rows_lls, rows_base;
+  std::vector<int32_t> status, flags;
   Staging sg;
-  double *d_pw = nullptr, *d_w[2] = {nullptr, nullptr}, *d_pm[2] = {nullptr, nullptr}, *d_scratch = nullptr;
-  int32_t *d_flag[2] = {nullptr, nullptr}, *d_notpd[2] = {nullptr, nullptr};
+  double *d_pw = nullptr, *d_pcol = nullptr, *d_w = nullptr, *d_scratch = nullptr, *d_tab_dla = nullptr, *d_tab_lls = nullptr;
+  uint32_t *d_tab_base = nullptr;
+  int64_t *d_rows_dla = nullptr, *d_rows_lls = nullptr, *d_rows_base = nullptr;
+  int32_t *d_flag = nullptr, *d_notpd = nullptr;
+  const double *tab_dla = nullptr, *tab_lls = nullptr;
+  const uint32_t *tab_base = nullptr;
 
-  MixturePlan(gpdla_context *ctx, gpdla_batch *batch, int reached) : c(ctx), b(batch), tables(reached), sg(ctx->stream) {}
-  bool reaches(int comp) const { return (tables & (1 << comp)) != 0; }
+  MixturePlan(gpdla_context *ctx, gpdla_batch *batch, const MixtureSpec &spec) : c(ctx), b(batch), sp(spec), sg(ctx->stream) {}
+  bool reaches(int comp) const { return (reach >> comp) & 1u; }
+  double *w(int comp) const { return d_w + (size_t)comp * nsub * S; }                  // [ncomp][nsub][S]
+  const double *pm(int comp, int64_t s0) const { return d_pcol + (size_t)comp * nsel + s0; }
+  int32_t *notpd(int comp) const { return d_notpd + (size_t)comp * nsub * chunks; }  // [ncomp][nsub][chunks]
+  const double *nhi(int comp) const { return comp == 0 ? c->d_lls_nhi : c->d_nhi; }
 
   // nsel == 0: GPDLA_OK with the offsets written and nothing else done (the entry returns)
-  int open(const MixtureRequest &rq, int64_t *offsets_out) {
-    int rc = check_unchanged(c, b, true);
-    if (rc) return rc;
-    if (tables && rq.weights_source == GPDLA_SPECTRA_WEIGHTS_RESIDENT && (rc = check_processed(b, "resident weights: "))) return rc;
-    nsel = rq.num_selected, S = b->S;
+  int open(int64_t *offsets_out) {
+    int rc;
+    md = sp.md, ncomp = 1 + md;
+    nsel = sp.num_selected, S = b->S;
     k = c->model.k, nb = k * (k + 1) / 2, ncol = nb + k;
     if (k > GPDLA_MAX_K) return fail(GPDLA_ERR_UNSUPPORTED, "k = %d > %d", k, GPDLA_MAX_K);
     HIP_TRY(hipSetDevice(c->device_id));
     st = c->stream;
-    if ((rc = gs.open(c, b, rq.meanflux != 0, rq.selection, nsel, rq.capacity, offsets_out, sg)) || nsel == 0) return rc;
+    g = continuum_model_args(c, sp.meanflux);
+    if ((rc = gs.open(c, b, sp.meanflux, sp.selection, nsel, sp.capacity, offsets_out, sg)) || nsel == 0) return rc;
     tot = (size_t)std::max<int64_t>(gs.total, 1);
+    const size_t ncols = (size_t)(2 + md);
 
-    // model weights, each row normalised by its sum; per component as a column for the sample kernels
-    pw.resize((size_t)nsel * 3);
+    // model weights: the caller's rows, the resident model_posteriors gathered by entry, or the last component alone;
+    // each row normalised by its sum, added in component order; a row with a NaN stays NaN
+    pw.assign((size_t)nsel * ncols, 0.0);
+    if (sp.model_weights) {
+      std::memcpy(pw.data(), sp.model_weights, pw.size() * sizeof(double));
+    } else if (sp.posteriors) {
+      post.resize((size_t)b->nq * ncols);
+      HIP_TRY(hipMemcpyAsync(post.data(), sp.posteriors, post.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      for (int64_t s = 0; s < nsel; ++s)
+        std::memcpy(pw.data() + (size_t)s * ncols, post.data() + (size_t)gs.sel[(size_t)s] * ncols, ncols * sizeof(double));
+    } else {
+      for (int64_t s = 0; s < nsel; ++s) pw[(size_t)s * ncols + ncols - 1] = 1.0;
+    }
+    pcol.assign((size_t)ncomp * nsel, 0.0);
     for (int64_t s = 0; s < nsel; ++s) {
-      double p[3] = {0.0, 0.0, 1.0};
-      if (rq.model_weights) std::memcpy(p, rq.model_weights + 3 * s, sizeof p);
-      const double sum = p[0] + p[1] + p[2];
-      for (int mm = 0; mm < 3; ++mm) pw[(size_t)s * 3 + mm] = p[mm] / sum;
+      double *p = pw.data() + (size_t)s * ncols;
+      double sum = 0.0;
+      for (size_t mm = 0; mm < ncols; ++mm) sum += p[mm];
+      // (the resident posteriors are not the caller's to get refused: a row that is no distribution is undefined)
+      const bool good = sum > 0.0 && std::isfinite(sum);
+      for (size_t mm = 0; mm < ncols; ++mm) p[mm] = good ? p[mm] / sum : (double)NAN;
+      if (!good) continue;
+      for (int comp = 0; comp < ncomp; ++comp) {
+        pcol[(size_t)comp * nsel + s] = p[1 + comp];
+        if (p[1 + comp] > 0.0) reach |= 1u << comp;
+      }
     }
+    if ((reach & 1u) && !c->d_lls_nhi) return fail(GPDLA_ERR_INVALID_ARGUMENT, "the sub-DLA component needs lls_nhi_samples in the context's samples");
     status.resize((size_t)nsel);
-    if ((rc = sg.put(&d_pw, pw.data(), (size_t)nsel * 3))) return rc;
-
-    // the posterior weights of each table the mixture reaches (k_spectra_weights, as model spectra)
-    const bool host = rq.weights_source == GPDLA_SPECTRA_WEIGHTS_HOST;
-    for (int comp = 0; comp < 2; ++comp) {
-      if (!reaches(comp)) continue;
-      pcol[comp].resize((size_t)nsel);
-      for (int64_t s = 0; s < nsel; ++s) pcol[comp][(size_t)s] = pw[(size_t)s * 3 + 1 + comp];
-      const double *host_table = !host ? nullptr : comp == 0 ? rq.sample_log_likelihoods_lls : rq.sample_log_likelihoods_dla;
-      if ((rc = sg.put(&d_pm[comp], pcol[comp].data(), (size_t)nsel)) || (rc = sg.tmp.alloc(&d_w[comp], (size_t)nsel * S)) ||
-          (rc = sg.tmp.alloc(&d_flag[comp], (size_t)nsel)) ||
-          (rc = launch_sample_weights(sg, b, gs, host_table, comp == 0, rows[comp], d_w[comp], d_flag[comp])))
-        return rc;
-    }
+    flags.assign((size_t)ncomp * nsel, 0);
+    if ((rc = sg.put(&d_pw, pw.data(), pw.size())) || (rc = sg.put(&d_pcol, pcol.data(), pcol.size()))) return rc;
 
     // launch groups: the scratch rows of a group's quasars fit the budget
     chunks = (int)((S + kMcSolveChunk - 1) / kMcSolveChunk);
     nsub = nsel;
-    if (tables) {
+    if (reach) {
       const size_t per_q = (size_t)S * ncol * sizeof(double);
       nsub = std::min<int64_t>(nsel, std::max<int64_t>(1, (int64_t)(mc_scratch_bytes() / per_q)));
       if (nsub * chunks > 2147483647LL) return fail(GPDLA_ERR_UNSUPPORTED, "selection too large for one launch");
-      if ((rc = sg.tmp.alloc(&d_scratch, (size_t)nsub * S * ncol))) return rc;
-      for (int comp = 0; comp < 2; ++comp)
-        if (reaches(comp) && (rc = sg.tmp.alloc(&d_notpd[comp], (size_t)nsub * chunks))) return rc;
+      if ((rc = sg.tmp.alloc(&d_scratch, (size_t)nsub * S * ncol)) || (rc = sg.tmp.alloc(&d_notpd, (size_t)ncomp * nsub * chunks)) ||
+          (rc = sg.tmp.alloc(&d_w, (size_t)ncomp * nsub * S)))
+        return rc;
+    }
+    if ((rc = sg.tmp.alloc(&d_flag, (size_t)ncomp * nsel))) return rc;
+    HIP_TRY(hipMemsetAsync(d_flag, 0, (size_t)ncomp * nsel * sizeof(int32_t), st));
+
+    // where an entry's rows start: in the resident tables, or in the group's staged slice of the host tables
+    // (bit 0: the sub-DLA table; any higher bit: the DLA table; from bit 2 on: the base rows, which models n >= 2 alone read)
+    const bool need_lls = reach & 1u, need_dla = reach & ~1u, need_base = reach >> 2;
+    rows_dla.resize((size_t)nsel), rows_lls.resize((size_t)nsel), rows_base.resize(need_base ? (size_t)nsel : 0);
+    for (int64_t s = 0; s < nsel; ++s) {
+      const int64_t r = sp.resident ? gs.sel[(size_t)s] : s % nsub;
+      rows_dla[(size_t)s] = r * sp.dla_stride;
+      rows_lls[(size_t)s] = r * sp.lls_stride;
+      if (need_base) rows_base[(size_t)s] = r * (md - 1) * S;
+    }
+    if ((rc = sg.put(&d_rows_dla, rows_dla.data(), (size_t)nsel)) || (rc = sg.put(&d_rows_lls, rows_lls.data(), (size_t)nsel)) ||
+        (need_base && (rc = sg.put(&d_rows_base, rows_base.data(), (size_t)nsel))))
+      return rc;
+    if (!sp.resident && ((need_dla && (rc = sg.tmp.alloc(&d_tab_dla, (size_t)nsub * sp.dla_stride))) ||
+                         (need_lls && (rc = sg.tmp.alloc(&d_tab_lls, (size_t)nsub * sp.lls_stride))) ||
+                         (need_base && (rc = sg.tmp.alloc(&d_tab_base, (size_t)nsub * (md - 1) * S)))))
+      return rc;
+    tab_dla = sp.resident ? sp.dla : d_tab_dla;
+    tab_lls = sp.resident ? sp.lls : d_tab_lls;
+    tab_base = sp.resident ? sp.base : d_tab_base;
+    return GPDLA_OK;
+  }
+
+  // the group's slice of the caller's tables, then the posterior weights of every reached component of its quasars
+  int begin_group(int64_t s0, int64_t n) {
+    if (!reach) return GPDLA_OK;
+    int rc;
+    if (!sp.resident) {
+      if (reach & ~1u)
+        HIP_TRY(hipMemcpyAsync(d_tab_dla, sp.dla + (size_t)s0 * sp.dla_stride, (size_t)n * sp.dla_stride * sizeof(double),
+                               hipMemcpyHostToDevice, st));
+      if (reach & 1u)
+        HIP_TRY(hipMemcpyAsync(d_tab_lls, sp.lls + (size_t)s0 * sp.lls_stride, (size_t)n * sp.lls_stride * sizeof(double),
+                               hipMemcpyHostToDevice, st));
+      if (reach >> 2)
+        HIP_TRY(hipMemcpyAsync(d_tab_base, sp.base + (size_t)s0 * (md - 1) * S, (size_t)n * (md - 1) * S * sizeof(uint32_t),
+                               hipMemcpyHostToDevice, st));
+    }
+    if (reaches(0) && (rc = launch_sample_weights(tab_lls, d_rows_lls + s0, S, n, w(0), d_flag + s0, st))) return rc;
+    // DLA(1): row 0 of the quasar's [md][S] table
+    if (reaches(1) && (rc = launch_sample_weights(tab_dla, d_rows_dla + s0, S, n, w(1), d_flag + nsel + s0, st))) return rc;
+    int n_lo = 0, n_hi = 0;
+    for (int nn = 2; nn <= md; ++nn)
+      if (reaches(nn)) {
+        if (!n_lo) n_lo = nn;
+        n_hi = nn;
+      }
+    if (n_lo) {
+      SpectraWeightsMultiArgs wa;
+      wa.table = tab_dla;
+      wa.row_start = d_rows_dla + s0;
+      wa.base = tab_base;
+      wa.base_start = d_rows_base + s0;
+      wa.S = S;
+      wa.cap = nsub;
+      wa.flag_stride = nsel;
+      wa.n_lo = n_lo;
+      wa.n_hi = n_hi;
+      wa.w = d_w;
+      wa.flag = d_flag + s0;
+      hipLaunchKernelGGL(k_spectra_weights_multi, dim3((unsigned)(n * (n_hi - n_lo + 1))), dim3(256), 0, st, wa);
+      HIP_TRY(hipGetLastError());
     }
     return GPDLA_OK;
   }
 
-  // k_mc_contract: the scratch rows of table comp for quasars [s0, s0 + n) of the selection
+  // k_mc_contract(_multi): the scratch rows of component comp for quasars [s0, s0 + n) of the selection
   int contract(int comp, int64_t s0, int64_t n) const {
-    McContractArgs ca;
+    McContractMultiArgs ma;
+    McContractArgs &ca = ma.c;
     ca.meta = b->d_meta;
     ca.pix = b->d_pix;
     ca.Mi = b->d_Mi;
@@ -268,19 +400,110 @@ struct MixturePlan {
     ca.offset_samples = c->d_offset;
     ca.nhi = nhi(comp);
     ca.perm = c->d_perm;
-    ca.sel = gs.d_sel;
-    ca.w = d_w[comp];
-    ca.pm = d_pm[comp];
+    ca.sel = gs.d_sel + s0;
+    ca.w = w(comp);
+    ca.pm = pm(comp, s0);
     ca.S = S;
     ca.num_lines = c->cfg.num_lines;
     ca.k = k;
-    ca.s0 = s0;
+    ca.s0 = 0;
     ca.chunks = 0;
     ca.scratch = d_scratch;
+    ma.base = tab_base;
+    ma.base_start = d_rows_base + s0;
+    ma.nslots = comp;  // (0, 1: one profile a sample, k_mc_contract itself)
     // k <= 20: 16 column tiles, 64 samples a block; k <= 40: 55 column tiles, 16 samples a block
-    return k <= 20 ? launch_mc_contract<4, 4, 32>(ca, n, S, st) : launch_mc_contract<1, 14, 64>(ca, n, S, st);
+    return k <= 20 ? launch_mc_contract<4, 4, 32>(ma, n, S, st) : launch_mc_contract<1, 14, 64>(ma, n, S, st);
   }
-  const double *nhi(int comp) const { return comp == 0 ? c->d_lls_nhi : c->d_nhi; }
+
+  McSolveArgs solve_args(int comp, int64_t s0) const {
+    McSolveArgs sa;
+    sa.meta = b->d_meta;
+    sa.perm = c->d_perm;
+    sa.sel = gs.d_sel + s0;
+    sa.w = w(comp);
+    sa.pm = pm(comp, s0);
+    sa.S = S;
+    sa.k = k;
+    sa.chunks = chunks;
+    sa.scratch = d_scratch;
+    sa.part = nullptr;
+    sa.notpd = notpd(comp);
+    sa.sample_coef = nullptr;
+    return sa;
+  }
+
+  PfLiveArgs live_args(int comp, int64_t s0, int32_t *d_list, int32_t *d_count) const {
+    PfLiveArgs la;
+    la.meta = b->d_meta;
+    la.perm = c->d_perm;
+    la.sel = gs.d_sel + s0;
+    la.w = w(comp);
+    la.pm = pm(comp, s0);
+    la.S = S;
+    la.list = d_list;
+    la.count = d_count;
+    return la;
+  }
+
+  // (.p alone for k_pf_pixels: comp < 2)
+  PfPixelsMultiArgs pixels_args(int comp, int64_t s0, int64_t tiles, const int32_t *d_list, const int32_t *d_count, double *d_sums) const {
+    PfPixelsMultiArgs ma;
+    PfPixelsArgs &pa = ma.p;
+    pa.meta = b->d_meta;
+    pa.pix = b->d_pix;
+    pa.lam_pad = b->d_lam;
+    pa.z_qsos = b->d_z;
+    pa.offset_samples = c->d_offset;
+    pa.nhi = nhi(comp);
+    pa.perm = c->d_perm;
+    pa.sel = gs.d_sel + s0;
+    pa.out_off = gs.d_off + s0;
+    pa.w = w(comp);
+    pa.pm = pm(comp, s0);
+    pa.g = g;
+    pa.S = S;
+    pa.num_lines = c->cfg.num_lines;
+    pa.s0 = 0;
+    pa.tiles = (int32_t)tiles;
+    pa.scratch = d_scratch;
+    pa.list = d_list;
+    pa.count = d_count;
+    pa.sums = d_sums;
+    ma.base = tab_base;
+    ma.base_start = d_rows_base + s0;
+    ma.nslots = comp;
+    return ma;
+  }
+
+  MixtureArgs mixture_args(int64_t s0) const {
+    MixtureArgs mx;
+    mx.pw = d_pw + (size_t)s0 * (2 + md);
+    mx.flag = d_flag + s0;
+    mx.notpd = d_notpd;
+    mx.flag_stride = nsel;
+    mx.notpd_stride = nsub * chunks;
+    mx.sampled = ncomp;
+    mx.chunks = chunks;
+    return mx;
+  }
+
+  // after the last group: the status of every entry and which of ITS components of positive weight had no weights
+  int close(int32_t *d_status, int32_t *status_out, uint32_t *flags_out) {
+    int rc;
+    if ((rc = sg.fetch(status.data(), d_status, (size_t)nsel)) || (rc = sg.fetch(flags.data(), d_flag, flags.size()))) return rc;
+    HIP_TRY(hipStreamSynchronize(st));
+    if (status_out) std::memcpy(status_out, status.data(), (size_t)nsel * sizeof(int32_t));
+    if (flags_out)
+      for (int64_t s = 0; s < nsel; ++s) {
+        uint32_t word = 0;
+        for (int comp = 0; comp < ncomp; ++comp)
+          if (flags[(size_t)comp * nsel + s] && pcol[(size_t)comp * nsel + s] > 0.0)
+            word |= comp == 0 ? GPDLA_SPECTRA_MULTI_FLAG_LLS : 1u << (comp - 1);
+        flags_out[s] = word;
+      }
+    return GPDLA_OK;
+  }
 };
 
 }  // namespace

@@ -1,5 +1,6 @@
 // host_marginal_continuum.hpp -- the marginal continuum: the GP posterior mean and
-// variance of the low-rank continuum over the sample tables and the models, on a resident batch.
+// variance of the low-rank continuum over the sample tables and the models, on a resident batch.  The multi-DLA
+// entry (4.25, host_mixture_multi.hpp) runs the same group loop, run_marginal_continuum.
 // Kernels: marginal_continuum_kernels.hpp.
 #pragma once
 
@@ -14,6 +15,72 @@ int validate_marginal_continuum(const gpdla_marginal_continuum_request *rq, int6
     return fail(GPDLA_ERR_INVALID_ARGUMENT, "sample_coefficients are those of ONE sampled component: the model weights reach %s",
                 *tables_out == 3 ? "both tables" : "none");
   return GPDLA_OK;
+}
+
+// The product of an opened plan into the caller's arrays (out.offsets are written already; any other may be null).
+// sample_coefficients: [nsel][S][k] of the ONE sampled component the plan reaches, or nullptr.
+int run_marginal_continuum(MixturePlan &plan, const gpdla_marginal_continuum_multi &out, double *sample_coefficients) {
+  gpdla_context *c = plan.c;
+  const gpdla_batch *b = plan.b;
+  Staging &sg = plan.sg;
+  hipStream_t st = plan.st;
+  const int64_t nsel = plan.nsel, S = plan.S, nsub = plan.nsub, total = plan.gs.total;
+  const int k = plan.k, nb = plan.nb, plen = k + 2 * nb, chunks = plan.chunks;
+  const size_t tot = plan.tot, part_stride = (size_t)nsub * chunks * plen;
+  int rc;
+
+  double *d_mean = nullptr, *d_var = nullptr, *d_btw = nullptr, *d_c = nullptr, *d_W = nullptr, *d_V = nullptr, *d_part = nullptr,
+         *d_sc = nullptr;
+  int32_t *d_status = nullptr;
+  if ((rc = sg.tmp.alloc(&d_mean, tot)) || (rc = sg.tmp.alloc(&d_var, tot)) || (rc = sg.tmp.alloc(&d_btw, tot)) ||
+      (rc = sg.tmp.alloc(&d_c, (size_t)nsel * k)) || (rc = sg.tmp.alloc(&d_W, (size_t)nsel * nb)) ||
+      (rc = sg.tmp.alloc(&d_V, (size_t)nsel * nb)) || (rc = sg.tmp.alloc(&d_status, (size_t)nsel)) ||
+      (plan.reach && (rc = sg.tmp.alloc(&d_part, (size_t)plan.ncomp * part_stride))))
+    return rc;
+  if (sample_coefficients && (rc = sg.tmp.alloc(&d_sc, (size_t)nsel * S * k))) return rc;
+  // (gpdla_context_set_timing: the kernels of this loop are what gpdla_context_last_sweep_ms reports)
+  if ((rc = begin_timing(c, st))) return rc;
+  for (int64_t s0 = 0; s0 < nsel; s0 += nsub) {
+    const int64_t n = std::min(nsub, nsel - s0);
+    if ((rc = plan.begin_group(s0, n))) return rc;
+    for (int comp = 0; comp < plan.ncomp; ++comp) {
+      if (!plan.reaches(comp)) continue;
+      if ((rc = plan.contract(comp, s0, n))) return rc;
+      McSolveArgs sa = plan.solve_args(comp, s0);
+      sa.part = d_part + (size_t)comp * part_stride;
+      sa.sample_coef = d_sc ? d_sc + (size_t)s0 * S * k : nullptr;
+      hipLaunchKernelGGL(k_mc_solve, dim3((unsigned)(n * chunks)), dim3(256), 0, st, sa);
+      HIP_TRY(hipGetLastError());
+    }
+    McFinishArgs fa;
+    fa.meta = b->d_meta;
+    fa.pix = b->d_pix;
+    fa.Mi = b->d_Mi;
+    fa.lam_pad = b->d_lam;
+    fa.z_qsos = b->d_z;
+    fa.sel = plan.gs.d_sel + s0;
+    fa.out_off = plan.gs.d_off + s0;
+    fa.g = plan.g;
+    fa.mix = plan.mixture_args(s0);
+    fa.part = d_part;
+    fa.part_stride = (int64_t)part_stride;
+    fa.mean = d_mean;
+    fa.var = d_var;
+    fa.var_between = d_btw;
+    fa.coef_mean = d_c + (size_t)s0 * k;
+    fa.cov_within = d_W + (size_t)s0 * nb;
+    fa.cov_between = d_V + (size_t)s0 * nb;
+    fa.status = d_status + s0;
+    hipLaunchKernelGGL(k_mc_finish, dim3((unsigned)n), dim3(256), 0, st, fa);
+    HIP_TRY(hipGetLastError());
+  }
+  if ((rc = end_timing(c, st))) return rc;
+  if ((rc = sg.fetch(out.continuum_mean, d_mean, (size_t)total)) || (rc = sg.fetch(out.continuum_var, d_var, (size_t)total)) ||
+      (rc = sg.fetch(out.continuum_var_between, d_btw, (size_t)total)) || (rc = sg.fetch(out.coef_mean, d_c, (size_t)nsel * k)) ||
+      (rc = sg.fetch(out.coef_cov_within, d_W, (size_t)nsel * nb)) || (rc = sg.fetch(out.coef_cov_between, d_V, (size_t)nsel * nb)) ||
+      (rc = sg.fetch(sample_coefficients, d_sc, (size_t)nsel * S * k)))
+    return rc;
+  return plan.close(d_status, out.status, out.model_flags);
 }
 
 }  // namespace
@@ -31,89 +98,14 @@ int gpdla_batch_marginal_continuum(gpdla_context *c, gpdla_batch *b, const gpdla
   int rc = check_batch_pair(c, b, rq && out && out->offsets);
   int tables = 0;
   if (rc || (rc = check_unconditioned(b, "marginal continuum")) ||
-      (rc = validate_marginal_continuum(rq, b->nq, b->S, c->d_lls_nhi != nullptr, &tables)))
+      (rc = validate_marginal_continuum(rq, b->nq, b->S, c->d_lls_nhi != nullptr, &tables)) || (rc = check_unchanged(c, b, true)) ||
+      (tables && rq->weights_source == GPDLA_SPECTRA_WEIGHTS_RESIDENT && (rc = check_processed(b, "resident weights: "))))
     return rc;
-  MixturePlan plan(c, b, tables);
-  if ((rc = plan.open(MixtureRequest(*rq), out->offsets)) || plan.nsel == 0) return rc;
-  Staging &sg = plan.sg;
-  hipStream_t st = plan.st;
-  const int64_t nsel = plan.nsel, S = plan.S, nsub = plan.nsub, total = plan.gs.total;
-  const int k = plan.k, nb = plan.nb, plen = k + 2 * nb, chunks = plan.chunks;
-  const size_t tot = plan.tot;
-  const int64_t *d_sel = plan.gs.d_sel;
-
-  double *d_mean = nullptr, *d_var = nullptr, *d_btw = nullptr, *d_c = nullptr, *d_W = nullptr, *d_V = nullptr, *d_sc = nullptr;
-  double *d_part[2] = {nullptr, nullptr};
-  int32_t *d_status = nullptr;
-  if ((rc = sg.tmp.alloc(&d_mean, tot)) || (rc = sg.tmp.alloc(&d_var, tot)) || (rc = sg.tmp.alloc(&d_btw, tot)) ||
-      (rc = sg.tmp.alloc(&d_c, (size_t)nsel * k)) || (rc = sg.tmp.alloc(&d_W, (size_t)nsel * nb)) ||
-      (rc = sg.tmp.alloc(&d_V, (size_t)nsel * nb)) || (rc = sg.tmp.alloc(&d_status, (size_t)nsel)))
-    return rc;
-  const bool want_sc = rq->sample_coefficients && out->sample_coefficients;
-  if (want_sc && (rc = sg.tmp.alloc(&d_sc, (size_t)nsel * S * k))) return rc;
-  for (int comp = 0; comp < 2; ++comp)
-    if (plan.reaches(comp) && (rc = sg.tmp.alloc(&d_part[comp], (size_t)nsub * chunks * plen))) return rc;
-  // (gpdla_context_set_timing: the three kernels of this call are what gpdla_context_last_sweep_ms reports)
-  if ((rc = begin_timing(c, st))) return rc;
-  for (int64_t s0 = 0; s0 < nsel; s0 += nsub) {
-    const int64_t n = std::min(nsub, nsel - s0);
-    for (int comp = 0; comp < 2; ++comp) {
-      if (!plan.reaches(comp)) continue;
-      if ((rc = plan.contract(comp, s0, n))) return rc;
-      McSolveArgs sa;
-      sa.meta = b->d_meta;
-      sa.perm = c->d_perm;
-      sa.sel = d_sel;
-      sa.w = plan.d_w[comp];
-      sa.pm = plan.d_pm[comp];
-      sa.S = S;
-      sa.k = k;
-      sa.s0 = s0;
-      sa.chunks = chunks;
-      sa.scratch = plan.d_scratch;
-      sa.part = d_part[comp];
-      sa.notpd = plan.d_notpd[comp];
-      sa.sample_coef = want_sc ? d_sc : nullptr;
-      hipLaunchKernelGGL(k_mc_solve, dim3((unsigned)(n * chunks)), dim3(256), 0, st, sa);
-      HIP_TRY(hipGetLastError());
-    }
-    McFinishArgs fa;
-    fa.meta = b->d_meta;
-    fa.pix = b->d_pix;
-    fa.Mi = b->d_Mi;
-    fa.lam_pad = b->d_lam;
-    fa.z_qsos = b->d_z;
-    fa.sel = d_sel;
-    fa.out_off = plan.gs.d_off;
-    fa.g = continuum_model_args(c, rq->meanflux != 0);
-    fa.pw = plan.d_pw;
-    for (int comp = 0; comp < 2; ++comp) {
-      fa.flag[comp] = plan.d_flag[comp];
-      fa.part[comp] = d_part[comp];
-      fa.notpd[comp] = plan.d_notpd[comp];
-    }
-    fa.s0 = s0;
-    fa.chunks = chunks;
-    fa.mean = d_mean;
-    fa.var = d_var;
-    fa.var_between = d_btw;
-    fa.coef_mean = d_c;
-    fa.cov_within = d_W;
-    fa.cov_between = d_V;
-    fa.status = d_status;
-    hipLaunchKernelGGL(k_mc_finish, dim3((unsigned)n), dim3(256), 0, st, fa);
-    HIP_TRY(hipGetLastError());
-  }
-  if ((rc = end_timing(c, st))) return rc;
-  if ((rc = sg.fetch(out->continuum_mean, d_mean, (size_t)total)) || (rc = sg.fetch(out->continuum_var, d_var, (size_t)total)) ||
-      (rc = sg.fetch(out->continuum_var_between, d_btw, (size_t)total)) || (rc = sg.fetch(out->coef_mean, d_c, (size_t)nsel * k)) ||
-      (rc = sg.fetch(out->coef_cov_within, d_W, (size_t)nsel * nb)) || (rc = sg.fetch(out->coef_cov_between, d_V, (size_t)nsel * nb)) ||
-      (rc = sg.fetch(plan.status.data(), d_status, (size_t)nsel)))
-    return rc;
-  if (want_sc && (rc = sg.fetch(out->sample_coefficients, d_sc, (size_t)nsel * S * k))) return rc;
-  HIP_TRY(hipStreamSynchronize(st));
-  if (out->status) std::memcpy(out->status, plan.status.data(), (size_t)nsel * sizeof(int32_t));
-  return GPDLA_OK;
+  MixturePlan plan(c, b, mixture_spec(b, MixtureRequest(*rq), tables));
+  if ((rc = plan.open(out->offsets)) || plan.nsel == 0) return rc;
+  const gpdla_marginal_continuum_multi arrays = {out->offsets, out->continuum_mean, out->continuum_var, out->continuum_var_between,
+                                                 out->coef_mean, out->coef_cov_within, out->coef_cov_between, out->status, nullptr};
+  return run_marginal_continuum(plan, arrays, rq->sample_coefficients ? out->sample_coefficients : nullptr);
 } GPDLA_NO_THROW
 
 }  // extern "C"

@@ -1,31 +1,39 @@
-// marginal_continuum_kernels.hpp -- device side of the "marginal continuum" subsystem (DESIGN.md 4.23):
+// marginal_continuum_kernels.hpp -- device side of the "marginal continuum" subsystem (DESIGN.md 4.23, 4.25):
 // the GP posterior mean and variance of the low-rank continuum, averaged over the sample table(s) and
-// over the models instead of conditioned on one absorber list (k_spectra_continuum).
+// over the models instead of conditioned on one absorber list (k_spectra_continuum).  The
+// components of the mixture are the null model and a run-time number of sampled ones: the sub-DLA table and
+// DLA(1), .., DLA(max_dlas); the single-DLA entries run it with two (the sub-DLA table, the DLA table).
 //
-//   k_mc_contract   per (selected quasar, chunk of samples in z_DLA order): the Voigt stage of
+//   k_mc_contract   per (quasar of the launch group, chunk of samples in z_DLA order): the Voigt stage of
 //                   k_spectra_moments fused with the contraction of the two per-sample weight vectors
 //                   a^2/d and a (y - a mu)/d onto [vech(m_p m_p') | m_p] on v_mfma_f64_16x16x4_f64;
 //                   writes [vech(M' diag(a^2/d) M) | M'(a r/d)] per sample to a scratch table
-//   k_mc_solve      per (selected quasar, 64 samples): B_i = I + ..., packed Cholesky, L^-1, c_i, Sigma_i =
+//   k_mc_contract_multi  k_mc_contract for one model DLA(n), n >= 2: sample i absorbs with the product of the n
+//                   broadened profiles of its slots (the gather of 4.21), formed by a slot loop INSIDE the tile.  A body
+//                   of its own, a copy of k_mc_contract outside the Voigt stage: a shared body was measured slower
+//                   (DESIGN.md 4.25), so a fix to one of the two has to be made in the other
+//   k_mc_solve      per (quasar, 64 samples): B_i = I + ..., packed Cholesky, L^-1, c_i, Sigma_i =
 //                   L^-T L^-1 of every sample of weight > 0, one sample per wave; the block's weighted
 //                   partial sums of c_i, Sigma_i and c_i c_i', a not-positive-definite flag, the optional c_i row
-//   k_mc_finish     per selected quasar: the chunk partials in chunk order, the null component (a = 1: the
+//   k_mc_finish     per quasar: the chunk partials in chunk order, the null component (a = 1: the
 //                   solve k_spectra_continuum calls, continuum_null_solve of continuum_solve.hpp), the
-//                   mixture over (null, sub-DLA table, DLA table), the coefficient outputs and the three
-//                   per-pixel arrays on the unmasked-range grid
+//                   mixture over (null, sampled components in their order), the coefficient outputs and the
+//                   three per-pixel arrays on the unmasked-range grid
 //
+// Every kernel is handed the pointers of its launch group (the s0 of k_mc_contract is 0): entry sl of the group is
+// sel[sl], w[sl], pm[sl], ...
 // Every sum runs in a fixed order and nothing is accumulated with atomics: within a wave the samples in
-// index order, the four waves in wave order, the chunks in chunk order, the components in the order
-// (null, sub-DLA, DLA).  A block depends on its own (quasar, chunk) only, so outputs are bit-identical
+// index order, the four waves in wave order, the chunks in chunk order, the components in component order.
+// A block depends on its own (quasar, chunk) only, so outputs are bit-identical
 // for any selection order, any launch grouping and either source of the weights.
 #pragma once
-#include "spectra_kernels.hpp"
+#include "spectra_multi_kernels.hpp"
 
 namespace gpdla {
 
 constexpr int kMcNb = GPDLA_MAX_K * (GPDLA_MAX_K + 1) / 2;
 constexpr int kMcSolveChunk = 64;  // samples (z_DLA positions) per block of k_mc_solve
-constexpr int kMcComponents = 3;   // null, sub-DLA table, DLA table
+constexpr int kMixMaxSampled = 1 + GPDLA_POSTERIOR_MAX_MODELS;  // sampled components at most: sub-DLA table, DLA(1) .. DLA(max)
 
 typedef double mc_d4 __attribute__((ext_vector_type(4)));
 
@@ -236,6 +244,211 @@ __global__ __launch_bounds__(256) void k_mc_contract(McContractArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------
+// k_mc_contract_multi<RT, CPW, PT>: the decomposition, the contraction and the scratch layout of k_mc_contract.
+//   Voigt stage: for slot j = 1 .. nslots (block-uniform: a launch is one model) the lane reads the index of its
+//   gathered sample (slot 1: the sample itself; slot j: base[(j - 2) S + i] - 1), forms that sample's multipliers,
+//   evaluates the raw values of its sub-run plus the 6 of halo, broadens with the taps in ascending order and
+//   multiplies the result into the running product, which lives in the lane's OWN s_wt entries (no barrier between
+//   slots, no register per slot).  Each slot takes the accurate tier under its own __any(near).  After the last slot
+//   the product is turned into (a^2/d, a r/d) in place.
+//   A sample that consumes a base index of 0 has weight 0 (k_spectra_weights_multi); its lane gathers ITS OWN
+//   sample for that slot, so no index is formed from the 0, and its row is written and never read.
+// ------------------------------------------------------------------------------------------
+struct McContractMultiArgs {
+  McContractArgs c;           // c.w, c.pm: of this model; c.nhi: nhi_samples
+  const uint32_t *base;       // base rows of entry s start at base + base_start[s]: [max_dlas - 1][S], 1-based, 0 = never drawn
+  const int64_t *base_start;  // [nsel]
+  int32_t nslots;             // n of DLA(n), >= 2
+};
+
+template <int RT, int CPW, int PT>
+__global__ __launch_bounds__(256) void k_mc_contract_multi(McContractMultiArgs am) {
+  const McContractArgs &a = am.c;
+  constexpr int NS = 16 * RT, NSUB = 256 / NS, PPS = PT / NSUB, KS = GPDLA_MAX_K + 2;
+  static_assert(PPS >= 1 && PPS * NSUB == PT && PT % 4 == 0, "tile shape");
+  __shared__ double s_exp[kExpTab];
+  __shared__ double s_wt[PT * NS], s_ut[PT * NS];
+  __shared__ double s_M[PT * KS];
+  __shared__ int s_any;
+
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int64_t sl = blockIdx.x / a.chunks;
+  const int chunk = blockIdx.x - sl * a.chunks;
+  const int64_t s = a.s0 + sl;
+  const QuasarMeta m = a.meta[a.sel[s]];
+  if (m.status != 0 || a.pm[s] == 0.0) return;  // (the whole block)
+  const int smp = tid % NS, sub = tid / NS;
+  const int64_t pos = (int64_t)chunk * NS + smp;
+  const bool live = pos < a.S;
+  const int64_t i = a.perm[pos < a.S ? pos : a.S - 1];
+  const double wgt = live ? a.w[s * a.S + i] : 0.0;
+  if (tid == 0) s_any = 0;
+  for (int e = tid; e < kExpTab; e += 256) s_exp[e] = exp2((double)e * (1.0 / kExpTab));
+  __syncthreads();
+  if (wgt > 0.0) s_any = 1;
+  __syncthreads();
+  if (!s_any) return;
+
+  const int k = a.k, nb = k * (k + 1) / 2, ncol = nb + k;
+  const int nbt = (nb + 15) / 16, nct = nbt + (k + 15) / 16;
+  const int L = a.num_lines, nslots = am.nslots;
+  const double c_light = g_lines.c, inv_s = g_lines.inv_sqrt2_sigma;
+  const double cs = c_light * inv_s;
+  const uint32_t *base = am.base + am.base_start[s] + i;
+  const double *lam = a.lam_pad + m.lam_off;
+  const int n_pad = m.n_u + 6;
+  const double t0 = g_lines.taps[0], t1 = g_lines.taps[1], t2 = g_lines.taps[2], t3 = g_lines.taps[3],
+               t4 = g_lines.taps[4], t5 = g_lines.taps[5], t6 = g_lines.taps[6];
+
+  // this lane's B-operand columns: (fi, fj) index the LDS copy of an Mi row, F = row[fi] * row[fj]
+  const int r = lane >> 4, c = lane & 15;
+  int fi[CPW], fj[CPW], ocol[CPW];
+  bool isv[CPW], valid[CPW];
+  mc_d4 acc[CPW][RT];
+#pragma unroll
+  for (int cc = 0; cc < CPW; ++cc) {
+    const int ct = wave + 4 * cc;
+    fi[cc] = fj[cc] = k + 1;
+    ocol[cc] = -1;
+    valid[cc] = ct < nct;
+    isv[cc] = ct >= nbt;
+    if (ct < nbt) {
+      const int e = ct * 16 + c;
+      if (e < nb) {
+        packed_unpack(e, &fi[cc], &fj[cc]);
+        ocol[cc] = e;
+      }
+    } else if (ct < nct) {
+      const int iv = (ct - nbt) * 16 + c;
+      if (iv < k) {
+        fi[cc] = iv;
+        fj[cc] = k;
+        ocol[cc] = nb + iv;
+      }
+    }
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) acc[cc][rt] = mc_d4{0.0, 0.0, 0.0, 0.0};
+  }
+
+  const PixelRow *pix = a.pix + m.pix_off;
+  const double *Mi = a.Mi + m.pix_off * k;
+  for (int p0 = 0; p0 < m.n_u; p0 += PT) {
+    // the Mi rows of the tile, with the 1 and the 0
+    for (int e = tid; e < PT * (k + 2); e += 256) {
+      const int pl = e / (k + 2), cm = e - pl * (k + 2);
+      const int p = p0 + pl;
+      double val = cm == k ? 1.0 : 0.0;
+      if (cm < k && p < m.n_u) val = Mi[(int64_t)p * k + cm];
+      s_M[pl * KS + cm] = val;
+    }
+    // Voigt stage: the product over the slots, in slot order, in this lane's s_wt entries
+    const int pp = p0 + sub * PPS;
+    for (int j = 1; j <= nslots; ++j) {
+      int64_t sj = i;  // slot 1: the sample itself
+      if (j > 1) {
+        const uint32_t b1 = base[(int64_t)(j - 2) * a.S];
+        sj = b1 ? (int64_t)b1 - 1 : i;  // (never drawn: the weight is 0)
+      }
+      const double z_dla = m.min_z_dla + (m.max_z_dla - m.min_z_dla) * a.offset_samples[sj];
+      double mult[3], ms[3];
+#pragma unroll
+      for (int l = 0; l < 3; ++l) {
+        mult[l] = g_lines.c / (g_lines.wavelength_cm[l] * (1 + z_dla)) / 1e8;  // voigt.c:278-279
+        ms[l] = mult[l] * inv_s;
+      }
+      const double inv_opz = 1.0 / (1 + z_dla);
+      const double nscale = -a.nhi[sj] * g_lines.inv_sqrt2pi_sigma * kInvSqrtPi * kExpScale;
+      auto raw = [&](int P) -> double {  // voigt.c:282-291 for slot j's sample at padded pixel P (as k_mc_contract)
+        const double lamP = lam[min(P, n_pad - 1)];
+        double total;
+        bool near = false;
+        if (L == 3) total = wing_sum3(lamP, ms[0], ms[1], ms[2], cs, &near);
+        else total = wing_sum_runtime(lamP * inv_opz, cs, L, &near);
+        if (__any(near)) {  // accurate tier, wave-uniformly
+          if (L == 3) {
+            total = 0.0;
+            for (int l = 0; l < 3; ++l) {
+              const double ax = fabs((lamP * mult[l] - c_light) * inv_s);
+              total += ax < 30.0 ? 1.7724538509055159 * g_lines.leading[l] *
+                                       near_poly(g_lines.near_poly + l * kNearLineDoubles, ax)
+                                 : g_lines.cwing[l] * wing_core(ax * ax, g_lines.y2[l]);
+            }
+          } else {
+            total = total_near_at(lamP, 1 + z_dla, L);
+          }
+        }
+        return exp_table_scaled(nscale * total, s_exp);
+      };
+      double a0 = raw(pp), a1 = raw(pp + 1), a2 = raw(pp + 2), a3 = raw(pp + 3), a4 = raw(pp + 4), a5 = raw(pp + 5), a6;
+#pragma unroll
+      for (int u = 0; u < PPS; ++u) {
+        a6 = raw(pp + u + 6);
+        double ab = a0 * t0;  // voigt.c:297-299, taps in ascending order
+        ab = fma(a1, t1, ab);
+        ab = fma(a2, t2, ab);
+        ab = fma(a3, t3, ab);
+        ab = fma(a4, t4, ab);
+        ab = fma(a5, t5, ab);
+        ab = fma(a6, t6, ab);
+        a0 = a1; a1 = a2; a2 = a3; a3 = a4; a4 = a5; a5 = a6;
+        double *slot = s_wt + (sub * PPS + u) * NS + smp;
+        *slot = (j == 1) ? ab : *slot * ab;  // multi :342-351, in slot order
+      }
+    }
+    // the two weights, in place
+#pragma unroll
+    for (int u = 0; u < PPS; ++u) {
+      const int p = pp + u;
+      const double ab = s_wt[(sub * PPS + u) * NS + smp];
+      double wt = 0.0, ut = 0.0;
+      if (p < m.n_u) {
+        const PixelRow row = pix[p];
+        const double d = ab * ab * row.omega2 + row.nu;
+        const double rr = row.y - ab * row.mu;
+        wt = ab * ab / d;
+        ut = ab * rr / d;
+      }
+      s_wt[(sub * PPS + u) * NS + smp] = wt;
+      s_ut[(sub * PPS + u) * NS + smp] = ut;
+    }
+    __syncthreads();
+    // contraction: PT / 4 K-steps of 4 pixels
+    for (int st = 0; st < PT / 4; ++st) {
+      const int pl = 4 * st + r;
+      double aw[RT], au[RT];
+#pragma unroll
+      for (int rt = 0; rt < RT; ++rt) {
+        aw[rt] = s_wt[pl * NS + rt * 16 + c];
+        au[rt] = s_ut[pl * NS + rt * 16 + c];
+      }
+      const double *Mrow = s_M + pl * KS;
+#pragma unroll
+      for (int cc = 0; cc < CPW; ++cc) {
+        if (!valid[cc]) continue;  // (wave-uniform)
+        const double f = Mrow[fi[cc]] * Mrow[fj[cc]];
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt)
+          acc[cc][rt] = __builtin_amdgcn_mfma_f64_16x16x4f64(isv[cc] ? au[rt] : aw[rt], f, acc[cc][rt], 0, 0, 0);
+      }
+    }
+    __syncthreads();
+  }
+  // result register rr of row tile rt: sample rt * 16 + (lane >> 4) + 4 rr, column tile's column lane & 15
+  double *out = a.scratch + (sl * a.S) * (int64_t)ncol;
+#pragma unroll
+  for (int cc = 0; cc < CPW; ++cc) {
+    if (!valid[cc] || ocol[cc] < 0) continue;
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) {
+        const int64_t po = (int64_t)chunk * NS + rt * 16 + r + 4 * rr;
+        if (po < a.S) out[po * ncol + ocol[cc]] = acc[cc][rt][rr];
+      }
+  }
+}
+
+// ------------------------------------------------------------------------------------------
 // k_mc_solve: 256 threads, the 64 consecutive z_DLA positions `chunk` of one selected quasar.  Wave 0 lists
 // the positions of weight > 0 in index order; the four waves take them round robin, a sample per
 // wave: L L' = B_i = I + scratch row (column by column, as continuum_null_solve), X = L^-1 (lane c solves
@@ -247,16 +460,15 @@ struct McSolveArgs {
   const QuasarMeta *meta;
   const int32_t *perm;
   const int64_t *sel;
-  const double *w;      // [nsel][S]
-  const double *pm;     // [nsel]
+  const double *w;      // [n][S]
+  const double *pm;     // [n]
   int64_t S;
   int32_t k;
-  int64_t s0;
   int32_t chunks;       // ceil(S / kMcSolveChunk)
   const double *scratch;
   double *part;
   int32_t *notpd;
-  double *sample_coef;  // [nsel][S][k] in sample order, or nullptr
+  double *sample_coef;  // [n][S][k] in sample order, or nullptr
 };
 
 // KEEP (the predictive flux): the sample's scratch row, consumed by then, is overwritten in place
@@ -271,15 +483,14 @@ __device__ __forceinline__ void mc_solve_body(const McSolveArgs &a, double *keep
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int64_t sl = blockIdx.x / a.chunks;
   const int chunk = blockIdx.x - sl * a.chunks;
-  const int64_t s = a.s0 + sl;
-  const QuasarMeta m = a.meta[a.sel[s]];
+  const QuasarMeta m = a.meta[a.sel[sl]];
   const int k = a.k, nb = k * (k + 1) / 2, ncol = nb + k, plen = k + 2 * nb;
   double *part = KEEP ? nullptr : a.part + (sl * a.chunks + chunk) * (int64_t)plen;
-  const bool off = m.status != 0 || a.pm[s] == 0.0;
+  const bool off = m.status != 0 || a.pm[sl] == 0.0;
   if (wave == 0) {
     const int64_t pos = (int64_t)chunk * kMcSolveChunk + lane;
     const int64_t i = a.perm[pos < a.S ? pos : a.S - 1];
-    const bool live = !off && pos < a.S && a.w[s * a.S + i] > 0.0;
+    const bool live = !off && pos < a.S && a.w[sl * a.S + i] > 0.0;
     const unsigned long long mask = __ballot(live);
     if (live) s_live[__popcll(mask & ((1ull << lane) - 1ull))] = (int)(pos - (int64_t)chunk * kMcSolveChunk);
     if (lane == 0) {
@@ -287,7 +498,7 @@ __device__ __forceinline__ void mc_solve_body(const McSolveArgs &a, double *keep
       s_bad = 0;
     }
     if (a.sample_coef && pos < a.S && !live)
-      for (int cidx = 0; cidx < k; ++cidx) a.sample_coef[(s * a.S + i) * k + cidx] = NAN;
+      for (int cidx = 0; cidx < k; ++cidx) a.sample_coef[(sl * a.S + i) * k + cidx] = NAN;
   }
   __syncthreads();
   const int nl = s_nlive;
@@ -315,7 +526,7 @@ __device__ __forceinline__ void mc_solve_body(const McSolveArgs &a, double *keep
     const bool has = idx < nl;
     const int64_t pos = (int64_t)chunk * kMcSolveChunk + (has ? s_live[idx] : s_live[0]);
     const int64_t i = a.perm[pos];
-    const double wi = a.w[s * a.S + i];
+    const double wi = a.w[sl * a.S + i];
     const double *row = a.scratch + (sl * a.S + pos) * (int64_t)ncol;
     double *krow = KEEP ? keep + (sl * a.S + pos) * (int64_t)ncol : nullptr;
     if (has) {
@@ -357,7 +568,7 @@ __device__ __forceinline__ void mc_solve_body(const McSolveArgs &a, double *keep
       for (int ii = lane; ii < k; ++ii) sum = fma(Xw[ii * (ii + 1) / 2 + lane], z[ii], sum);
       v[lane] = sum;
       accC += wi * sum;
-      if (a.sample_coef) a.sample_coef[(s * a.S + i) * k + lane] = sum;
+      if (a.sample_coef) a.sample_coef[(sl * a.S + i) * k + lane] = sum;
       if constexpr (KEEP) krow[nb + lane] = sum;
     }
     __syncthreads();
@@ -408,8 +619,29 @@ __device__ __forceinline__ void mc_solve_body(const McSolveArgs &a, double *keep
 __global__ __launch_bounds__(256) void k_mc_solve(McSolveArgs a) { mc_solve_body<false>(a, nullptr); }
 
 // ------------------------------------------------------------------------------------------
-// k_mc_finish: one block per selected quasar of a launch group.
-//   sampled component m (sub-DLA table, DLA table) of weight p_m > 0: cbar_m, W_m, S_m = Sum w c c' from
+// What the two finish kernels share: entry s of a launch group mixes the null component and `sampled` sampled
+// components (the single-DLA entries: the sub-DLA table, the DLA table; the multi entries: the sub-DLA table, DLA(1), ..,
+// DLA(max_dlas)).  pw[s][1 + sampled] are the normalised model weights; a row with a NaN entry is UNDEFINED (NaN rows,
+// kSpectraAverageUndefined; the single-DLA entries refuse such a row).  flag[comp * flag_stride + s] != 0: the
+// component's weight row has no weights.  notpd[comp * notpd_stride + s * chunks + ch].
+// ------------------------------------------------------------------------------------------
+struct MixtureArgs {
+  const double *pw;
+  const int32_t *flag;
+  const int32_t *notpd;
+  int64_t flag_stride, notpd_stride;
+  int32_t sampled, chunks;
+};
+
+__device__ __forceinline__ bool mixture_row_undefined(const double *P, int sampled) {
+  bool undefined = false;
+  for (int mm = 0; mm <= sampled; ++mm) undefined = undefined || P[mm] != P[mm];
+  return undefined;
+}
+
+// ------------------------------------------------------------------------------------------
+// k_mc_finish: one block per quasar of a launch group; all pointers are the group's: entry s is block s.
+//   sampled component m of weight p_m > 0: cbar_m, W_m, S_m = Sum w c c' from
 //   the chunk partials in chunk order; the null component of weight p_0 > 0: c_0 from continuum_null_solve with
 //   a = 1 (the function k_spectra_continuum calls), Sigma_0 = B_0^-1 through L^-1, S_0 = c_0 c_0';
 //   c = Sum p_m cbar_m, W = Sum p_m W_m, V = Sum p_m S_m - c c' in component order.
@@ -418,6 +650,7 @@ __global__ __launch_bounds__(256) void k_mc_solve(McSolveArgs a) { mc_solve_body
 //   pixel-diagonal omega term is left out as there.
 // status: the quasar's prepare status (1, 3: NaN rows); 4 = some B not positive definite (NaN rows);
 // a component of weight > 0 whose weight row has no weights: NaN rows, status 0.
+// part[comp * part_stride + (s * chunks + ch) * (k + 2 nb)].
 // ------------------------------------------------------------------------------------------
 struct McFinishArgs {
   const QuasarMeta *meta;
@@ -428,15 +661,12 @@ struct McFinishArgs {
   const int64_t *sel;
   const int64_t *out_off;
   ContinuumModelArgs g;
-  const double *pw;            // [nsel][3] normalised model weights (null, sub-DLA, DLA)
-  const int32_t *flag[2];      // [nsel] of the sub-DLA and the DLA weight rows, or nullptr
-  const double *part[2];      // [nsub][chunks][k + 2 nb], or nullptr
-  const int32_t *notpd[2];     // [nsub][chunks]
-  int64_t s0;
-  int32_t chunks;
-  double *mean, *var, *var_between;           // flat, out_off
-  double *coef_mean, *cov_within, *cov_between;  // [nsel][k], [nsel][nb], [nsel][nb]
-  int32_t *status;                            // [nsel]
+  MixtureArgs mix;
+  const double *part;
+  int64_t part_stride;
+  double *mean, *var, *var_between;              // flat, out_off
+  double *coef_mean, *cov_within, *cov_between;  // [n][k], [n][nb], [n][nb]
+  int32_t *status;                               // [n]
 };
 
 constexpr int kMcPixTile = 64;
@@ -450,20 +680,22 @@ __global__ __launch_bounds__(256) void k_mc_finish(McFinishArgs a) {
   __shared__ double s_piv;
   __shared__ int s_pd, s_none;
   const int tid = threadIdx.x;
-  const int64_t sl = blockIdx.x, s = a.s0 + sl;
+  const int64_t s = blockIdx.x;
   const int64_t q = a.sel[s];
   const QuasarMeta m = a.meta[q];
   const int k = a.g.model.k, nb = k * (k + 1) / 2, plen = k + 2 * nb;
+  const double *P = a.mix.pw + s * (int64_t)(1 + a.mix.sampled);
   double *o_mean = a.mean + a.out_off[s], *o_var = a.var + a.out_off[s], *o_btw = a.var_between + a.out_off[s];
   double *o_c = a.coef_mean + s * k, *o_W = a.cov_within + s * nb, *o_V = a.cov_between + s * nb;
-  if (m.status != 0) {
+  const bool undefined = m.status == 0 && mixture_row_undefined(P, a.mix.sampled);
+  if (m.status != 0 || undefined) {
     for (int p = tid; p < m.n_u; p += 256) o_mean[p] = o_var[p] = o_btw[p] = NAN;
     for (int e = tid; e < nb; e += 256) o_W[e] = o_V[e] = NAN;
     for (int e = tid; e < k; e += 256) o_c[e] = NAN;
-    if (tid == 0) a.status[s] = m.status;
+    if (tid == 0) a.status[s] = undefined ? kSpectraAverageUndefined : m.status;
     return;
   }
-  const double p0 = a.pw[s * 3];
+  const double p0 = P[0];
   for (int e = tid; e < nb; e += 256) s_W[e] = s_V[e] = 0.0;
   for (int e = tid; e < k; e += 256) s_c[e] = 0.0;
   if (tid == 0) {
@@ -487,24 +719,25 @@ __global__ __launch_bounds__(256) void k_mc_finish(McFinishArgs a) {
     __syncthreads();
   }
 
-  for (int comp = 0; comp < 2; ++comp) {  // the sub-DLA table, then the DLA table
-    const double pm = a.pw[s * 3 + 1 + comp];
+  for (int comp = 0; comp < a.mix.sampled; ++comp) {  // the sampled components in their order
+    const double pm = P[1 + comp];
     if (!(pm > 0.0)) continue;
-    if (a.flag[comp][s] != 0) {
+    if (a.mix.flag[comp * a.mix.flag_stride + s] != 0) {
       if (tid == 0) s_none = 1;
       continue;
     }
-    const int64_t first = sl * a.chunks;
-    const int nch = a.chunks;
+    const int64_t first = s * a.mix.chunks;
+    const int nch = a.mix.chunks;
+    const double *part = a.part + comp * a.part_stride;
     for (int e = tid; e < plen; e += 256) {
       double sum = 0.0;
-      for (int ch = 0; ch < nch; ++ch) sum += a.part[comp][(first + ch) * plen + e];
+      for (int ch = 0; ch < nch; ++ch) sum += part[(first + ch) * plen + e];
       if (e < k) s_c[e] += pm * sum;
       else if (e < k + nb) s_W[e - k] += pm * sum;
       else s_V[e - k - nb] += pm * sum;
     }
-    for (int ch = tid; ch < a.chunks; ch += 256)
-      if (a.notpd[comp][first + ch] != 0) s_pd = 0;
+    for (int ch = tid; ch < nch; ch += 256)
+      if (a.mix.notpd[comp * a.mix.notpd_stride + first + ch] != 0) s_pd = 0;
   }
   __syncthreads();
   for (int e = tid; e < nb; e += 256) {

@@ -3,7 +3,7 @@
 // sample table(s) and the models.  It needs the per-pixel cross term of a_i and c_i, which none of the
 // products of 4.12, 4.21 and 4.23 carries.
 //
-//   k_mc_contract   (marginal_continuum_kernels.hpp, unchanged) fills the scratch rows [vech(B_i - I) | v_i]
+//   k_mc_contract(_multi)  (marginal_continuum_kernels.hpp) fills the scratch rows [vech(B_i - I) | v_i]
 //   k_pf_solve      the solve of k_mc_solve (one device body, mc_solve_body<KEEP = true>): every sample of
 //                   weight > 0 overwrites its scratch row in place with [vech(Sigma_i) | c_i]; a
 //                   not-positive-definite flag per block; no partial sums
@@ -13,10 +13,14 @@
 //                   scratch rows onto [vech(m_p m_p'), off-diagonal entries doubled | m_p] to give
 //                   s_ip = m_p' Sigma_i m_p and m_p' c_i, and the epilogue adds up the four weighted sums
 //                   F1 = Sum w f, F2 = Sum w f^2, FW = Sum w a^2 s, FD = Sum w (a^2 omega2 + nu), f = a (mu + m' c)
+//   k_pf_pixels_multi  k_pf_pixels for one model DLA(n), n >= 2: a_ip is the product over the sample's n slots,
+//                   kept slot by slot in the lane's a_ip entries of LDS (as k_mc_contract_multi); a body of its own
 //   k_pf_finish     per selected quasar: the null component (a = 1; c_0, Sigma_0 from the solve k_mc_finish
-//                   calls, continuum_solve.hpp), the mixture over (null, sub-DLA table, DLA table) in that
-//                   order, the NaN and status rules and the five per-pixel arrays
+//                   calls, continuum_solve.hpp), the mixture over (null, the sampled components in their order:
+//                   MixtureArgs), the NaN and status rules and the five per-pixel arrays
 //
+// Every kernel is handed the pointers of its launch group (the s0 of k_pf_pixels is 0): entry sl of the group is
+// sel[sl], w[sl], out_off[sl], ...
 // Nothing is accumulated with atomics and every sum runs in a fixed order: a lane adds its samples in the
 // order (list chunk, row tile, result register), the four lanes that share a pixel are added in lane order.  A block
 // depends on its own (quasar, pixel tile) only, so outputs are bit-identical for any selection order, any launch
@@ -43,24 +47,23 @@ struct PfLiveArgs {
   const QuasarMeta *meta;
   const int32_t *perm;
   const int64_t *sel;
-  const double *w;   // [nsel][S]
-  const double *pm;  // [nsel]
+  const double *w;   // [n][S]
+  const double *pm;  // [n]
   int64_t S;
-  int64_t s0;
-  int32_t *list;     // [nsub][S]
-  int32_t *count;    // [nsub]
+  int32_t *list;     // [n][S]
+  int32_t *count;    // [n]
 };
 
 __global__ __launch_bounds__(256) void k_pf_live(PfLiveArgs a) {
   __shared__ int s_cnt[4];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int64_t sl = blockIdx.x, s = a.s0 + sl;
-  const QuasarMeta m = a.meta[a.sel[s]];
-  const bool off = m.status != 0 || a.pm[s] == 0.0;
+  const int64_t sl = blockIdx.x;
+  const QuasarMeta m = a.meta[a.sel[sl]];
+  const bool off = m.status != 0 || a.pm[sl] == 0.0;
   int done = 0;  // live positions before this stretch (block-uniform)
   for (int64_t t0 = 0; t0 < a.S; t0 += 256) {
     const int64_t pos = t0 + tid;
-    const bool live = !off && pos < a.S && a.w[s * a.S + a.perm[pos < a.S ? pos : a.S - 1]] > 0.0;
+    const bool live = !off && pos < a.S && a.w[sl * a.S + a.perm[pos < a.S ? pos : a.S - 1]] > 0.0;
     const unsigned long long bal = __ballot(live);
     const int pre = __popcll(bal & ((1ull << lane) - 1ull));
     __syncthreads();  // (the previous stretch's s_cnt has been read)
@@ -316,15 +319,234 @@ __global__ __launch_bounds__(256) void k_pf_pixels(PfPixelsArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------
+// k_pf_pixels_multi: k_pf_pixels for one model DLA(n), n >= 2 -- the tile set-up, the live list (of this model),
+// the contraction and the epilogue as there; in the Voigt stage a lane is a live sample and the product over its
+// slots is kept in its a_ip entries of s_a, slot by slot, as k_mc_contract_multi keeps it in s_wt.
+// ------------------------------------------------------------------------------------------
+struct PfPixelsMultiArgs {
+  PfPixelsArgs p;             // p.w, p.pm, p.list, p.count: of this model; p.nhi: nhi_samples
+  const uint32_t *base;
+  const int64_t *base_start;  // [nsel]
+  int32_t nslots;
+};
+
+__global__ __launch_bounds__(256) void k_pf_pixels_multi(PfPixelsMultiArgs am) {
+  const PfPixelsArgs &a = am.p;
+  constexpr int RT = kPfRowTiles, NS = kPfSamples, PT = kPfPixTile, PPS = PT / (256 / NS), KS = GPDLA_MAX_K + 2;
+  static_assert(NS == 64 && PT == 64 && PPS * (256 / NS) == PT, "a lane is a sample, a wave a 16-pixel column tile");
+  __shared__ double s_exp[kExpTab];
+  __shared__ double s_a[PT * NS];  // a_ip as [pixel][sample]; at the end the lane partials
+  __shared__ double s_M[PT * KS];
+  __shared__ double s_mu[PT], s_mf[PT], s_w[NS];
+  __shared__ int s_ij[kPfCols];
+
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int64_t sl = blockIdx.x / a.tiles;
+  const int tile = blockIdx.x - sl * a.tiles;
+  const int64_t s = a.s0 + sl;
+  const int64_t q = a.sel[s];
+  const QuasarMeta m = a.meta[q];
+  const int p0 = tile * PT;
+  if (m.status != 0 || a.pm[s] == 0.0 || p0 >= m.n_u) return;  // (the whole block)
+
+  const int k = a.g.model.k, nb = k * (k + 1) / 2, ncol = nb + k;
+  const int nbp = (nb + kPfSlab - 1) & ~(kPfSlab - 1), kp = (k + kPfSlab - 1) & ~(kPfSlab - 1);
+  const int L = a.num_lines, nslots = am.nslots;
+  const double *lam = a.lam_pad + m.lam_off;
+  const int n_pad = m.n_u + 6;
+
+  for (int e = tid; e < kExpTab; e += 256) s_exp[e] = exp2((double)e * (1.0 / kExpTab));
+  for (int e = tid; e < nbp + kp; e += 256) {  // (i, j) in 6 bits each, the doubling bit, the scratch column + 1 (0: a zero column)
+    int fi = k + 1, fj = k + 1, dbl = 0, ac = -1;
+    if (e < nb) {
+      packed_unpack(e, &fi, &fj);
+      dbl = fi != fj;
+      ac = e;
+    } else if (e >= nbp && e - nbp < k) {
+      fi = e - nbp;
+      fj = k;
+      ac = nb + fi;
+    }
+    s_ij[e] = fi | (fj << 6) | (dbl << 12) | ((ac + 1) << 13);
+  }
+  for (int e = tid; e < PT * 2; e += 256) s_M[(e >> 1) * KS + k + (e & 1)] = (e & 1) ? 0.0 : 1.0;
+  model_tile_rows(a.g, lam + 3, a.z_qsos[q], m.n_u, p0, PT, s_M, KS, s_mu, s_mf, tid);
+  __syncthreads();
+
+  const int r = lane >> 4, c = lane & 15;
+  const int smp = tid % NS, sub = tid / NS;
+  const int myp = p0 + wave * 16 + c;  // this lane's pixel in the accumulator layout
+  const bool pin = myp < m.n_u;
+  PixelRow prow = {0.0, 0.0, 0.0, 0.0};
+  if (pin) prow = a.pix[m.pix_off + myp];
+  const double mu_p = s_mu[wave * 16 + c];
+  const double *Mrow = s_M + (wave * 16 + c) * KS;
+  const double *rows = a.scratch + (sl * a.S) * (int64_t)ncol;
+  const uint32_t *base_q = am.base + am.base_start[s];
+  const double c_light = g_lines.c, inv_s = g_lines.inv_sqrt2_sigma;
+  const double cs = c_light * inv_s;
+  const double t0 = g_lines.taps[0], t1 = g_lines.taps[1], t2 = g_lines.taps[2], t3 = g_lines.taps[3],
+               t4 = g_lines.taps[4], t5 = g_lines.taps[5], t6 = g_lines.taps[6];
+  double F1 = 0.0, F2 = 0.0, FW = 0.0, FD = 0.0;
+
+  const int nlive = a.count[sl];
+  const int32_t *list = a.list + sl * a.S;
+  const int nchunks = (nlive + NS - 1) / NS;
+  for (int chunk = 0; chunk < nchunks; ++chunk) {
+    const int idx = chunk * NS + smp;
+    const bool live = idx < nlive;
+    const int64_t i = a.perm[list[live ? idx : 0]];
+    const double wgt = live ? a.w[s * a.S + i] : 0.0;
+    __syncthreads();  // (the previous chunk's epilogue has read s_a and s_w)
+
+    const int pp = p0 + sub * PPS;
+    for (int j = 1; j <= nslots; ++j) {
+      int64_t sj = i;  // slot 1: the sample itself
+      if (j > 1) {
+        const uint32_t b1 = base_q[(int64_t)(j - 2) * a.S + i];
+        sj = b1 ? (int64_t)b1 - 1 : i;  // (never drawn: not on the live list; a lane past its end repeats a live sample)
+      }
+      const double z_dla = m.min_z_dla + (m.max_z_dla - m.min_z_dla) * a.offset_samples[sj];
+      double mult[3], ms[3];
+#pragma unroll
+      for (int l = 0; l < 3; ++l) {
+        mult[l] = g_lines.c / (g_lines.wavelength_cm[l] * (1 + z_dla)) / 1e8;  // voigt.c:278-279
+        ms[l] = mult[l] * inv_s;
+      }
+      const double inv_opz = 1.0 / (1 + z_dla);
+      const double nscale = -a.nhi[sj] * g_lines.inv_sqrt2pi_sigma * kInvSqrtPi * kExpScale;
+      auto raw = [&](int P) -> double {  // voigt.c:282-291 for slot j's sample at padded pixel P (as k_pf_pixels)
+        const double lamP = lam[min(P, n_pad - 1)];
+        double total;
+        bool near = false;
+        if (L == 3) total = wing_sum3(lamP, ms[0], ms[1], ms[2], cs, &near);
+        else total = wing_sum_runtime(lamP * inv_opz, cs, L, &near);
+        if (__any(near)) {  // accurate tier, wave-uniformly
+          if (L == 3) {
+            total = 0.0;
+            for (int l = 0; l < 3; ++l) {
+              const double ax = fabs((lamP * mult[l] - c_light) * inv_s);
+              total += ax < 30.0 ? 1.7724538509055159 * g_lines.leading[l] *
+                                       near_poly(g_lines.near_poly + l * kNearLineDoubles, ax)
+                                 : g_lines.cwing[l] * wing_core(ax * ax, g_lines.y2[l]);
+            }
+          } else {
+            total = total_near_at(lamP, 1 + z_dla, L);
+          }
+        }
+        return exp_table_scaled(nscale * total, s_exp);
+      };
+      double a0 = raw(pp), a1 = raw(pp + 1), a2 = raw(pp + 2), a3 = raw(pp + 3), a4 = raw(pp + 4), a5 = raw(pp + 5), a6;
+#pragma unroll 4
+      for (int u = 0; u < PPS; ++u) {
+        a6 = raw(pp + u + 6);
+        double ab = a0 * t0;  // voigt.c:297-299, taps in ascending order
+        ab = fma(a1, t1, ab);
+        ab = fma(a2, t2, ab);
+        ab = fma(a3, t3, ab);
+        ab = fma(a4, t4, ab);
+        ab = fma(a5, t5, ab);
+        ab = fma(a6, t6, ab);
+        a0 = a1; a1 = a2; a2 = a3; a3 = a4; a4 = a5; a5 = a6;
+        double *slot = s_a + (sub * PPS + u) * NS + smp;
+        *slot = (j == 1) ? ab : *slot * ab;  // multi :342-351, in slot order
+      }
+    }
+    if (sub == 0) s_w[smp] = wgt > 0.0 ? wgt : 0.0;
+    __syncthreads();
+
+    // contraction: (nbp + kp) / 16 slabs of 4 K-steps, as k_pf_pixels
+    const double *arow[RT];
+    mc_d4 accS[RT], accT[RT];
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+      const int po = chunk * NS + rt * 16 + c;
+      arow[rt] = rows + (int64_t)list[po < nlive ? po : 0] * ncol;
+      accS[rt] = mc_d4{0.0, 0.0, 0.0, 0.0};
+      accT[rt] = mc_d4{0.0, 0.0, 0.0, 0.0};
+    }
+    struct Slab {
+      double av[4][RT], fv[4];
+    };
+    auto request = [&](int col0, Slab &sb) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int ent = s_ij[col0 + 4 * r + u];
+        double f = Mrow[ent & 63] * Mrow[(ent >> 6) & 63];
+        if (ent & 4096) f = 2.0 * f;
+        sb.fv[u] = f;
+        const int ac = (ent >> 13) - 1;
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt) sb.av[u][rt] = ac >= 0 ? arow[rt][ac] : 0.0;
+      }
+    };
+    const int nslab_s = nbp / kPfSlab, nslab = (nbp + kp) / kPfSlab;
+    Slab cur, nxt;
+    request(0, cur);
+    for (int sb = 0; sb < nslab; ++sb) {
+      if (sb + 1 < nslab) request((sb + 1) * kPfSlab, nxt);
+      if (sb < nslab_s) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+          for (int rt = 0; rt < RT; ++rt) accS[rt] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur.av[u][rt], cur.fv[u], accS[rt], 0, 0, 0);
+      } else {
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+          for (int rt = 0; rt < RT; ++rt) accT[rt] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur.av[u][rt], cur.fv[u], accT[rt], 0, 0, 0);
+      }
+      cur = nxt;
+    }
+    // epilogue
+    const double *ap = s_a + (wave * 16 + c) * NS;
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) {
+        const int sm = rt * 16 + r + 4 * rr;
+        const double wv = s_w[sm];
+        if (wv > 0.0) {
+          const double ab = ap[sm];
+          const double f = ab * (mu_p + accT[rt][rr]);
+          const double a2 = ab * ab;
+          F1 += wv * f;
+          F2 += wv * (f * f);
+          FW += wv * (a2 * accS[rt][rr]);
+          FD += wv * (a2 * prow.omega2 + prow.nu);
+        }
+      }
+  }
+  // the four lanes of a pixel in lane order
+  __syncthreads();
+  double *red = s_a + ((wave * 4 + r) * 16 + c) * 4;
+  red[0] = F1;
+  red[1] = F2;
+  red[2] = FW;
+  red[3] = FD;
+  __syncthreads();
+  if (r == 0 && pin) {
+    double *out = a.sums + (a.out_off[s] + myp) * 4;
+    for (int j = 0; j < 4; ++j) {
+      double sum = s_a[((wave * 4 + 0) * 16 + c) * 4 + j];
+      for (int rr = 1; rr < 4; ++rr) sum += s_a[((wave * 4 + rr) * 16 + c) * 4 + j];
+      out[j] = sum;
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------
 // k_pf_finish: one block per selected quasar of a launch group.
 //   The null component of weight p_0 > 0: c_0 from continuum_null_solve with a = 1 (the function k_mc_finish and
 //   k_spectra_continuum call), Sigma_0 = B_0^-1 through L^-1; per pixel (model_tile_rows) t_0 = mu + m' c_0,
 //   s_0 = m' Sigma_0 m, and F1 = t_0, F2 = t_0^2, FW = s_0, FD = omega2 + nu.
-//   The mixture in the order (null, sub-DLA, DLA): flux_mean = Sum p_m F1_m, flux_var_within = Sum p_m FW_m,
+//   The mixture in component order (MixtureArgs): flux_mean = Sum p_m F1_m, flux_var_within = Sum p_m FW_m,
 //   flux_var_between = max(Sum p_m F2_m - flux_mean^2, 0) (not fused), flux_var = within + between,
 //   noise_var = Sum p_m FD_m on kept pixels, NaN on masked ones.
 // status: the quasar's prepare status (1, 3: NaN rows); 4 = some B not positive definite (NaN rows);
 // a component of weight > 0 whose weight row has no weights: NaN rows, status 0.
+// sel, out_off, mix and status are those of the launch group; sums[comp * sums_stride + (out_off[s] + p) * 4 + .] and
+// the five outputs are indexed by the selection's own offsets.
 // ------------------------------------------------------------------------------------------
 struct PfFinishArgs {
   const QuasarMeta *meta;
@@ -339,14 +561,11 @@ struct PfFinishArgs {
   const int64_t *sel;
   const int64_t *out_off;
   ContinuumModelArgs g;
-  const double *pw;            // [nsel][3] normalised model weights (null, sub-DLA, DLA)
-  const int32_t *flag[2];      // [nsel] of the sub-DLA and the DLA weight rows, or nullptr
-  const double *sums[2];       // [total][4], or nullptr
-  const int32_t *notpd[2];     // [nsub][chunks]
-  int64_t s0;
-  int32_t chunks;
+  MixtureArgs mix;
+  const double *sums;
+  int64_t sums_stride;
   double *mean, *var, *var_within, *var_between, *noise_var;  // flat, out_off
-  int32_t *status;                                            // [nsel]
+  int32_t *status;                                            // [n]
 };
 
 __global__ __launch_bounds__(256) void k_pf_finish(PfFinishArgs a) {
@@ -358,18 +577,20 @@ __global__ __launch_bounds__(256) void k_pf_finish(PfFinishArgs a) {
   __shared__ double s_piv;
   __shared__ int s_pd, s_none, s_cnt[4];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int64_t sl = blockIdx.x, s = a.s0 + sl;
+  const int64_t s = blockIdx.x;
   const int64_t q = a.sel[s];
   const QuasarMeta m = a.meta[q];
   const int k = a.g.model.k, nb = k * (k + 1) / 2;
   const int64_t o = a.out_off[s];
-  if (m.status != 0) {
+  const double *P = a.mix.pw + s * (int64_t)(1 + a.mix.sampled);
+  const bool undefined = m.status == 0 && mixture_row_undefined(P, a.mix.sampled);
+  if (m.status != 0 || undefined) {
     for (int p = tid; p < m.n_u; p += 256)
       a.mean[o + p] = a.var[o + p] = a.var_within[o + p] = a.var_between[o + p] = a.noise_var[o + p] = NAN;
-    if (tid == 0) a.status[s] = m.status;
+    if (tid == 0) a.status[s] = undefined ? kSpectraAverageUndefined : m.status;
     return;
   }
-  const double p0 = a.pw[s * 3];
+  const double p0 = P[0];
   if (tid == 0) {
     s_pd = 1;
     s_none = 0;
@@ -390,17 +611,20 @@ __global__ __launch_bounds__(256) void k_pf_finish(PfFinishArgs a) {
     __syncthreads();
   }
 
-  double pmv[2] = {0.0, 0.0};
-  for (int comp = 0; comp < 2; ++comp) {  // the sub-DLA table, then the DLA table
-    const double pm = a.pw[s * 3 + 1 + comp];
+  double pmv[kMixMaxSampled];
+#pragma unroll
+  for (int comp = 0; comp < kMixMaxSampled; ++comp) {  // the sampled components in their order
+    pmv[comp] = 0.0;
+    if (comp >= a.mix.sampled) continue;
+    const double pm = P[1 + comp];
     if (!(pm > 0.0)) continue;
-    if (a.flag[comp][s] != 0) {
+    if (a.mix.flag[comp * a.mix.flag_stride + s] != 0) {
       if (tid == 0) s_none = 1;
       continue;
     }
     pmv[comp] = pm;
-    for (int ch = tid; ch < a.chunks; ch += 256)
-      if (a.notpd[comp][sl * a.chunks + ch] != 0) s_pd = 0;
+    for (int ch = tid; ch < a.mix.chunks; ch += 256)
+      if (a.mix.notpd[comp * a.mix.notpd_stride + s * a.mix.chunks + ch] != 0) s_pd = 0;
   }
   __syncthreads();
   const bool ok = s_pd != 0 && s_none == 0;
@@ -433,9 +657,10 @@ __global__ __launch_bounds__(256) void k_pf_finish(PfFinishArgs a) {
         wi += p0 * qs;
         nd += p0 * (row.omega2 + row.nu);
       }
-      for (int comp = 0; comp < 2; ++comp) {
+#pragma unroll
+      for (int comp = 0; comp < kMixMaxSampled; ++comp) {
         if (!(pmv[comp] > 0.0)) continue;
-        const double *F = a.sums[comp] + (o + p) * 4;
+        const double *F = a.sums + comp * a.sums_stride + (o + p) * 4;
         m1 += pmv[comp] * F[0];
         m2 += pmv[comp] * F[1];
         wi += pmv[comp] * F[2];

@@ -1317,8 +1317,8 @@ typedef struct {
  * sample_coefficients with both tables or none.  Returns GPDLA_OK or GPDLA_ERR_INVALID_ARGUMENT.  Needs no GPU. */
 int gpdla_marginal_continuum_validate(const gpdla_marginal_continuum_request *request, int64_t num_quasars,
                                       int64_t num_samples, int has_lls_nhi_samples);
-/* With gpdla_context_set_timing enabled, gpdla_context_last_sweep_ms reports the k_mc_contract, k_mc_solve and
- * k_mc_finish launches of the call. */
+/* With gpdla_context_set_timing enabled, gpdla_context_last_sweep_ms reports the launch groups of the call: per
+ * group the staging of a host table's slice, k_spectra_weights, k_mc_contract, k_mc_solve and k_mc_finish. */
 int gpdla_batch_marginal_continuum(gpdla_context *ctx, gpdla_batch *batch, const gpdla_marginal_continuum_request *request,
                                    gpdla_marginal_continuum *out);
 
@@ -1385,8 +1385,9 @@ typedef struct {
  * GPDLA_ERR_INVALID_ARGUMENT.  Needs no GPU. */
 int gpdla_predictive_flux_validate(const gpdla_predictive_flux_request *request, int64_t num_quasars,
                                    int64_t num_samples, int has_lls_nhi_samples);
-/* With gpdla_context_set_timing enabled, gpdla_context_last_sweep_ms reports the k_mc_contract, k_pf_solve,
- * k_pf_live, k_pf_pixels and k_pf_finish launches of the call. */
+/* With gpdla_context_set_timing enabled, gpdla_context_last_sweep_ms reports the launch groups of the call: per
+ * group the staging of a host table's slice, k_spectra_weights, k_mc_contract, k_pf_solve, k_pf_live, k_pf_pixels and
+ * k_pf_finish. */
 int gpdla_batch_predictive_flux(gpdla_context *ctx, gpdla_batch *batch, const gpdla_predictive_flux_request *request,
                                 gpdla_predictive_flux *out);
 

@@ -1,5 +1,5 @@
 """The shapes, base-index patterns and weight rows at which the marginal continuum and the predictive flux over all models
-of a multi-DLA run (csrc/mixture_multi_kernels.hpp, csrc/host_mixture_multi.hpp) can go wrong, as case
+of a multi-DLA run (csrc/marginal_continuum_kernels.hpp, csrc/predictive_flux_kernels.hpp, csrc/host_mixture_multi.hpp) can go wrong, as case
 lists and builders shared by tests/test_mixture_multi.py (CPU) and tests/test_gpu_mixture_multi.py.  A plain module beside
 marginal_continuum_cases.py and model_spectra_multi_cases.py, whose builders it reuses.
 

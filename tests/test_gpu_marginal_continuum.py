@@ -303,6 +303,11 @@ def test_bit_identity_across_launch_groups(tmp_path):
     for name in ALL + ("sample_coefficients", "status", "offsets"):
         np.testing.assert_array_equal(got[name], want[name], err_msg=name)
     assert np.isfinite(want["continuum_var"]).all()
+    # host tables (null, sub-DLA and DLA under an unsorted selection): staged one launch group at a time
+    for name in ALL + ("status", "offsets"):
+        np.testing.assert_array_equal(got["host_" + name], want["host_" + name], err_msg="host_" + name)
+    assert np.isfinite(want["host_continuum_var"]).all() and want["host_status"].tolist() == [0] * 5
+    np.testing.assert_array_equal(np.diff(want["host_offsets"]), [worker.NUS[q] for q in worker.HOST_SELECTION])
 
 
 @pytest.mark.parametrize("which", list(MC.BATCHING_SELECTIONS))

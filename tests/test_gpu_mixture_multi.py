@@ -1,5 +1,5 @@
 """GPU checks of the marginal continuum and the predictive flux over all models of a multi-DLA run (DESIGN.md 4.25;
-csrc/mixture_multi_kernels.hpp, csrc/host_mixture_multi.hpp) against the NumPy-and-oracle restatements
+csrc/marginal_continuum_kernels.hpp, csrc/predictive_flux_kernels.hpp, csrc/host_mixture_multi.hpp) against the NumPy-and-oracle restatements
 tests/marginal_continuum_multi_restatement.py and tests/predictive_flux_multi_restatement.py in their DENSE form, at the
 shapes of tests/mixture_multi_cases.py.  Tolerances against the restatement are not fixed in advance: per product family
 ``R.continuum_tolerance`` of the restatement's own dense-vs-Woodbury disagreement on the same case (10 x, floored at 1e-12,
