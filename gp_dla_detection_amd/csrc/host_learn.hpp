@@ -8,7 +8,7 @@ int64_t learn_splits(int64_t work, int64_t per_split, int64_t max_splits) {
   return std::max<int64_t>(1, std::min<int64_t>(max_splits, (work + per_split - 1) / per_split));
 }
 
-// mean (mode 0) or std (mode 1) of the columns of x over the quasars with w != 0 (w NULL: all)
+// mean (mode 0; mode 2: 0 where nobody counts) or std (mode 1) of the columns of x over the quasars with w != 0 (w NULL: all)
 int learn_column_pass(const gpdla_training *t, const double *x, const double *w, int mode, double *part,
                       int32_t nsplit, double *out, double *count) {
   LearnColArgs a;
@@ -189,7 +189,8 @@ int gpdla_training_pca_covariance(gpdla_training *t, int complete_rows, double *
   if (complete_rows) {  // the complete rows' own column mean (pca 'rows','complete' centres what it keeps)
     const int32_t cs = (int32_t)learn_splits(nq, 64, 64);
     if ((rc = tmp.alloc(&d_cmean, (size_t)ld)) || (rc = tmp.alloc(&d_cpart, (size_t)cs * 3 * ld))) return rc;
-    if ((rc = learn_column_pass(t, t->d_flux, d_flags, 0, d_cpart, cs, d_cmean, nullptr))) return rc;
+    // (mode 2: without a complete row the covariance is the empty sum over n_c - 1 = -1, not NaN)
+    if ((rc = learn_column_pass(t, t->d_flux, d_flags, 2, d_cpart, cs, d_cmean, nullptr))) return rc;
   }
   LearnGramArgs g;
   g.x = t->d_flux;

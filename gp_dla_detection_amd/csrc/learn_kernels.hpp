@@ -158,7 +158,9 @@ __global__ __launch_bounds__(256) void k_learn_colsum(LearnColArgs a) {
 }
 
 // mode 0: mean[p] = sum / count (NaN without entries); mode 1: std[p] with n - 1 (nanstd, :87; 0 for
-// one entry, NaN for none).  count[p] = the number of entries.  Pixels in [G, ld) get mean 0.
+// one entry, NaN for none); mode 2: the mean, 0 without entries (the offset of k_learn_gram, which
+// multiplies (x - offset) by a weight of 0 there: a NaN offset would turn the empty sum 0 into NaN).
+// count[p] = the number of entries.  Pixels in [G, ld) get mean 0.
 struct LearnColFinishArgs {
   const double *part;
   int64_t G, ld;
@@ -178,7 +180,7 @@ __global__ __launch_bounds__(256) void k_learn_colfinish(LearnColFinishArgs a) {
   }
   double r;
   if (p >= a.G) r = 0.0;
-  else if (a.mode == 0) r = c > 0.0 ? s1 / c : __builtin_nan("");
+  else if (a.mode != 1) r = c > 0.0 ? s1 / c : (a.mode == 2 ? 0.0 : __builtin_nan(""));
   else r = c > 1.0 ? sqrt((s2 - s1 * (s1 / c)) / (c - 1.0)) : (c == 1.0 ? 0.0 : __builtin_nan(""));
   a.out[p] = r;
   if (a.count) a.count[p] = c;

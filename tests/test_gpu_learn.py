@@ -51,6 +51,7 @@ def restated(csr, p, meanflux):
 
 def assert_close_nan(a, b, rtol):
     assert np.array_equal(np.isnan(a), np.isnan(b)), "NaN patterns differ"
+    assert np.array_equal(np.isposinf(a), np.isposinf(b)) and np.array_equal(np.isneginf(a), np.isneginf(b)), "+-inf differ"
     fin = np.isfinite(b)
     err = np.abs(a[fin] - b[fin]) / np.maximum(np.abs(b[fin]), 1e-300)
     assert err.max(initial=0.0) <= rtol, err.max()
@@ -109,6 +110,7 @@ def test_covariance_matches_the_restatement(nq, G, big_set):
             assert np.array_equal(cov, cov.T, equal_nan=True)
             assert np.array_equal(N, rN)
             assert np.array_equal(np.isnan(cov), np.isnan(rcov))
+            assert np.array_equal(np.isposinf(cov), np.isposinf(rcov)) and np.array_equal(np.isneginf(cov), np.isneginf(rcov))
             fin = np.isfinite(rcov)
             if fin.any():  # (one complete row of 17 at G = 1217: 0 / 0 everywhere)
                 assert np.abs(cov[fin] - rcov[fin]).max() <= 1e-11 * np.abs(rcov[fin]).max()
