@@ -9,9 +9,9 @@
 //                   a^2/d and a (y - a mu)/d onto [vech(m_p m_p') | m_p] on v_mfma_f64_16x16x4_f64;
 //                   writes [vech(M' diag(a^2/d) M) | M'(a r/d)] per sample to a scratch table
 //   k_mc_contract_multi  k_mc_contract for one model DLA(n), n >= 2: sample i absorbs with the product of the n
-//                   broadened profiles of its slots (the gather of 4.21), formed by a slot loop INSIDE the tile.  A body
-//                   of its own, a copy of k_mc_contract outside the Voigt stage: a shared body was measured slower
-//                   (DESIGN.md 4.25), so a fix to one of the two has to be made in the other
+//                   broadened profiles of its slots (the gather of 4.21), formed by a slot loop INSIDE the tile.  The
+//                   two are one text, mc_contract_body.hpp, included under the two names with a switch for the
+//                   Voigt stage; the line sum and the tap fold are those of sampled_profile.hpp
 //   k_mc_solve      per (quasar, 64 samples): B_i = I + ..., packed Cholesky, L^-1, c_i, Sigma_i =
 //                   L^-T L^-1 of every sample of weight > 0, one sample per wave; the block's weighted
 //                   partial sums of c_i, Sigma_i and c_i c_i', a not-positive-definite flag, the optional c_i row
@@ -42,7 +42,7 @@ typedef double mc_d4 __attribute__((ext_vector_type(4)));
 // context's z_DLA order), PT pixels a tile.
 //   Voigt stage (the arithmetic of k_spectra_moments): thread t takes sample t % NS and the sub-run
 //   of PT / (256 / NS) pixels t / NS of the tile; seven raw values in registers, the accurate tier by
-//   whole waves under __any(near).  RT = 4: a lane is a sample and a wave is a quarter of the tile.
+//   whole waves (sampled_line_sum).  RT = 4: a lane is a sample and a wave is a quarter of the tile.
 //   The two weights of (sample, pixel) go to LDS as the A operands, [pixel][sample].
 //   Contraction: D[sample][column] += Sum_p A[sample][p] F[p][column].  The columns are nbt = ceil(nb / 16)
 //   tiles of vech(m_p m_p') (weight a^2/d) followed by ceil(k / 16) tiles of m_p (weight a r/d); wave w owns
@@ -71,185 +71,13 @@ struct McContractArgs {
   double *scratch;
 };
 
-template <int RT, int CPW, int PT>
-__global__ __launch_bounds__(256) void k_mc_contract(McContractArgs a) {
-  constexpr int NS = 16 * RT, NSUB = 256 / NS, PPS = PT / NSUB, KS = GPDLA_MAX_K + 2;
-  static_assert(PPS >= 1 && PPS * NSUB == PT && PT % 4 == 0, "tile shape");
-  __shared__ double s_exp[kExpTab];
-  __shared__ double s_wt[PT * NS], s_ut[PT * NS];
-  __shared__ double s_M[PT * KS];
-  __shared__ int s_any;
-
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int64_t sl = blockIdx.x / a.chunks;
-  const int chunk = blockIdx.x - sl * a.chunks;
-  const int64_t s = a.s0 + sl;
-  const QuasarMeta m = a.meta[a.sel[s]];
-  if (m.status != 0 || a.pm[s] == 0.0) return;  // (the whole block)
-  const int smp = tid % NS, sub = tid / NS;
-  const int64_t pos = (int64_t)chunk * NS + smp;
-  const bool live = pos < a.S;
-  const int64_t i = a.perm[pos < a.S ? pos : a.S - 1];
-  const double wgt = live ? a.w[s * a.S + i] : 0.0;
-  if (tid == 0) s_any = 0;
-  for (int e = tid; e < kExpTab; e += 256) s_exp[e] = exp2((double)e * (1.0 / kExpTab));
-  __syncthreads();
-  if (wgt > 0.0) s_any = 1;
-  __syncthreads();
-  if (!s_any) return;
-
-  const int k = a.k, nb = k * (k + 1) / 2, ncol = nb + k;
-  const int nbt = (nb + 15) / 16, nct = nbt + (k + 15) / 16;
-  const int L = a.num_lines;
-  const double z_dla = m.min_z_dla + (m.max_z_dla - m.min_z_dla) * a.offset_samples[i];
-  const double c_light = g_lines.c, inv_s = g_lines.inv_sqrt2_sigma;
-  double mult[3], ms[3];
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    mult[j] = g_lines.c / (g_lines.wavelength_cm[j] * (1 + z_dla)) / 1e8;  // voigt.c:278-279
-    ms[j] = mult[j] * inv_s;
-  }
-  const double cs = c_light * inv_s;
-  const double inv_opz = 1.0 / (1 + z_dla);
-  const double nscale = -a.nhi[i] * g_lines.inv_sqrt2pi_sigma * kInvSqrtPi * kExpScale;
-  const double *lam = a.lam_pad + m.lam_off;
-  const int n_pad = m.n_u + 6;
-  const double t0 = g_lines.taps[0], t1 = g_lines.taps[1], t2 = g_lines.taps[2], t3 = g_lines.taps[3],
-               t4 = g_lines.taps[4], t5 = g_lines.taps[5], t6 = g_lines.taps[6];
-
-  auto raw = [&](int P) -> double {  // voigt.c:282-291 for this thread's sample at padded pixel P (as k_spectra_moments)
-    const double lamP = lam[min(P, n_pad - 1)];
-    double total;
-    bool near = false;
-    if (L == 3) total = wing_sum3(lamP, ms[0], ms[1], ms[2], cs, &near);
-    else total = wing_sum_runtime(lamP * inv_opz, cs, L, &near);
-    if (__any(near)) {  // accurate tier, wave-uniformly
-      if (L == 3) {
-        total = 0.0;
-        for (int j = 0; j < 3; ++j) {
-          const double ax = fabs((lamP * mult[j] - c_light) * inv_s);
-          total += ax < 30.0 ? 1.7724538509055159 * g_lines.leading[j] *
-                                   near_poly(g_lines.near_poly + j * kNearLineDoubles, ax)
-                             : g_lines.cwing[j] * wing_core(ax * ax, g_lines.y2[j]);
-        }
-      } else {
-        total = total_near_at(lamP, 1 + z_dla, L);
-      }
-    }
-    return exp_table_scaled(nscale * total, s_exp);
-  };
-
-  // this lane's B-operand columns: (fi, fj) index the LDS copy of an Mi row, F = row[fi] * row[fj]
-  const int r = lane >> 4, c = lane & 15;
-  int fi[CPW], fj[CPW], ocol[CPW];
-  bool isv[CPW], valid[CPW];
-  mc_d4 acc[CPW][RT];
-#pragma unroll
-  for (int cc = 0; cc < CPW; ++cc) {
-    const int ct = wave + 4 * cc;
-    fi[cc] = fj[cc] = k + 1;
-    ocol[cc] = -1;
-    valid[cc] = ct < nct;
-    isv[cc] = ct >= nbt;
-    if (ct < nbt) {
-      const int e = ct * 16 + c;
-      if (e < nb) {
-        packed_unpack(e, &fi[cc], &fj[cc]);
-        ocol[cc] = e;
-      }
-    } else if (ct < nct) {
-      const int iv = (ct - nbt) * 16 + c;
-      if (iv < k) {
-        fi[cc] = iv;
-        fj[cc] = k;
-        ocol[cc] = nb + iv;
-      }
-    }
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) acc[cc][rt] = mc_d4{0.0, 0.0, 0.0, 0.0};
-  }
-
-  const PixelRow *pix = a.pix + m.pix_off;
-  const double *Mi = a.Mi + m.pix_off * k;
-  for (int p0 = 0; p0 < m.n_u; p0 += PT) {
-    // the Mi rows of the tile, with the 1 and the 0
-    for (int e = tid; e < PT * (k + 2); e += 256) {
-      const int pl = e / (k + 2), cm = e - pl * (k + 2);
-      const int p = p0 + pl;
-      double val = cm == k ? 1.0 : 0.0;
-      if (cm < k && p < m.n_u) val = Mi[(int64_t)p * k + cm];
-      s_M[pl * KS + cm] = val;
-    }
-    // Voigt stage and the two weights
-    const int pp = p0 + sub * PPS;
-    double a0 = raw(pp), a1 = raw(pp + 1), a2 = raw(pp + 2), a3 = raw(pp + 3), a4 = raw(pp + 4), a5 = raw(pp + 5), a6;
-#pragma unroll
-    for (int u = 0; u < PPS; ++u) {
-      a6 = raw(pp + u + 6);
-      double ab = a0 * t0;  // voigt.c:297-299, taps in ascending order
-      ab = fma(a1, t1, ab);
-      ab = fma(a2, t2, ab);
-      ab = fma(a3, t3, ab);
-      ab = fma(a4, t4, ab);
-      ab = fma(a5, t5, ab);
-      ab = fma(a6, t6, ab);
-      a0 = a1; a1 = a2; a2 = a3; a3 = a4; a4 = a5; a5 = a6;
-      const int p = pp + u;
-      double wt = 0.0, ut = 0.0;
-      if (p < m.n_u) {
-        const PixelRow row = pix[p];
-        const double d = ab * ab * row.omega2 + row.nu;
-        const double rr = row.y - ab * row.mu;
-        wt = ab * ab / d;
-        ut = ab * rr / d;
-      }
-      s_wt[(sub * PPS + u) * NS + smp] = wt;
-      s_ut[(sub * PPS + u) * NS + smp] = ut;
-    }
-    __syncthreads();
-    // contraction: PT / 4 K-steps of 4 pixels
-    for (int st = 0; st < PT / 4; ++st) {
-      const int pl = 4 * st + r;
-      double aw[RT], au[RT];
-#pragma unroll
-      for (int rt = 0; rt < RT; ++rt) {
-        aw[rt] = s_wt[pl * NS + rt * 16 + c];
-        au[rt] = s_ut[pl * NS + rt * 16 + c];
-      }
-      const double *Mrow = s_M + pl * KS;
-#pragma unroll
-      for (int cc = 0; cc < CPW; ++cc) {
-        if (!valid[cc]) continue;  // (wave-uniform)
-        const double f = Mrow[fi[cc]] * Mrow[fj[cc]];
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt)
-          acc[cc][rt] = __builtin_amdgcn_mfma_f64_16x16x4f64(isv[cc] ? au[rt] : aw[rt], f, acc[cc][rt], 0, 0, 0);
-      }
-    }
-    __syncthreads();
-  }
-  // result register rr of row tile rt: sample rt * 16 + (lane >> 4) + 4 rr, column tile's column lane & 15
-  double *out = a.scratch + (sl * a.S) * (int64_t)ncol;
-#pragma unroll
-  for (int cc = 0; cc < CPW; ++cc) {
-    if (!valid[cc] || ocol[cc] < 0) continue;
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr) {
-        const int64_t po = (int64_t)chunk * NS + rt * 16 + r + 4 * rr;
-        if (po < a.S) out[po * ncol + ocol[cc]] = acc[cc][rt][rr];
-      }
-  }
-}
-
 // ------------------------------------------------------------------------------------------
 // k_mc_contract_multi<RT, CPW, PT>: the decomposition, the contraction and the scratch layout of k_mc_contract.
 //   Voigt stage: for slot j = 1 .. nslots (block-uniform: a launch is one model) the lane reads the index of its
 //   gathered sample (slot 1: the sample itself; slot j: base[(j - 2) S + i] - 1), forms that sample's multipliers,
 //   evaluates the raw values of its sub-run plus the 6 of halo, broadens with the taps in ascending order and
 //   multiplies the result into the running product, which lives in the lane's OWN s_wt entries (no barrier between
-//   slots, no register per slot).  Each slot takes the accurate tier under its own __any(near).  After the last slot
+//   slots, no register per slot).  Each slot takes the accurate tier under its own vote of the wave.  After the last slot
 //   the product is turned into (a^2/d, a r/d) in place.
 //   A sample that consumes a base index of 0 has weight 0 (k_spectra_weights_multi); its lane gathers ITS OWN
 //   sample for that slot, so no index is formed from the 0, and its row is written and never read.
@@ -261,191 +89,20 @@ struct McContractMultiArgs {
   int32_t nslots;             // n of DLA(n), >= 2
 };
 
+// The body of both kernels is mc_contract_body.hpp, a header WITHOUT an include guard that is included twice.
+template <int RT, int CPW, int PT>
+__global__ __launch_bounds__(256) void k_mc_contract(McContractArgs a) {
+#define GPDLA_MC_CONTRACT_MULTI 0
+#include "mc_contract_body.hpp"
+#undef GPDLA_MC_CONTRACT_MULTI
+}
+
 template <int RT, int CPW, int PT>
 __global__ __launch_bounds__(256) void k_mc_contract_multi(McContractMultiArgs am) {
   const McContractArgs &a = am.c;
-  constexpr int NS = 16 * RT, NSUB = 256 / NS, PPS = PT / NSUB, KS = GPDLA_MAX_K + 2;
-  static_assert(PPS >= 1 && PPS * NSUB == PT && PT % 4 == 0, "tile shape");
-  __shared__ double s_exp[kExpTab];
-  __shared__ double s_wt[PT * NS], s_ut[PT * NS];
-  __shared__ double s_M[PT * KS];
-  __shared__ int s_any;
-
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int64_t sl = blockIdx.x / a.chunks;
-  const int chunk = blockIdx.x - sl * a.chunks;
-  const int64_t s = a.s0 + sl;
-  const QuasarMeta m = a.meta[a.sel[s]];
-  if (m.status != 0 || a.pm[s] == 0.0) return;  // (the whole block)
-  const int smp = tid % NS, sub = tid / NS;
-  const int64_t pos = (int64_t)chunk * NS + smp;
-  const bool live = pos < a.S;
-  const int64_t i = a.perm[pos < a.S ? pos : a.S - 1];
-  const double wgt = live ? a.w[s * a.S + i] : 0.0;
-  if (tid == 0) s_any = 0;
-  for (int e = tid; e < kExpTab; e += 256) s_exp[e] = exp2((double)e * (1.0 / kExpTab));
-  __syncthreads();
-  if (wgt > 0.0) s_any = 1;
-  __syncthreads();
-  if (!s_any) return;
-
-  const int k = a.k, nb = k * (k + 1) / 2, ncol = nb + k;
-  const int nbt = (nb + 15) / 16, nct = nbt + (k + 15) / 16;
-  const int L = a.num_lines, nslots = am.nslots;
-  const double c_light = g_lines.c, inv_s = g_lines.inv_sqrt2_sigma;
-  const double cs = c_light * inv_s;
-  const uint32_t *base = am.base + am.base_start[s] + i;
-  const double *lam = a.lam_pad + m.lam_off;
-  const int n_pad = m.n_u + 6;
-  const double t0 = g_lines.taps[0], t1 = g_lines.taps[1], t2 = g_lines.taps[2], t3 = g_lines.taps[3],
-               t4 = g_lines.taps[4], t5 = g_lines.taps[5], t6 = g_lines.taps[6];
-
-  // this lane's B-operand columns: (fi, fj) index the LDS copy of an Mi row, F = row[fi] * row[fj]
-  const int r = lane >> 4, c = lane & 15;
-  int fi[CPW], fj[CPW], ocol[CPW];
-  bool isv[CPW], valid[CPW];
-  mc_d4 acc[CPW][RT];
-#pragma unroll
-  for (int cc = 0; cc < CPW; ++cc) {
-    const int ct = wave + 4 * cc;
-    fi[cc] = fj[cc] = k + 1;
-    ocol[cc] = -1;
-    valid[cc] = ct < nct;
-    isv[cc] = ct >= nbt;
-    if (ct < nbt) {
-      const int e = ct * 16 + c;
-      if (e < nb) {
-        packed_unpack(e, &fi[cc], &fj[cc]);
-        ocol[cc] = e;
-      }
-    } else if (ct < nct) {
-      const int iv = (ct - nbt) * 16 + c;
-      if (iv < k) {
-        fi[cc] = iv;
-        fj[cc] = k;
-        ocol[cc] = nb + iv;
-      }
-    }
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) acc[cc][rt] = mc_d4{0.0, 0.0, 0.0, 0.0};
-  }
-
-  const PixelRow *pix = a.pix + m.pix_off;
-  const double *Mi = a.Mi + m.pix_off * k;
-  for (int p0 = 0; p0 < m.n_u; p0 += PT) {
-    // the Mi rows of the tile, with the 1 and the 0
-    for (int e = tid; e < PT * (k + 2); e += 256) {
-      const int pl = e / (k + 2), cm = e - pl * (k + 2);
-      const int p = p0 + pl;
-      double val = cm == k ? 1.0 : 0.0;
-      if (cm < k && p < m.n_u) val = Mi[(int64_t)p * k + cm];
-      s_M[pl * KS + cm] = val;
-    }
-    // Voigt stage: the product over the slots, in slot order, in this lane's s_wt entries
-    const int pp = p0 + sub * PPS;
-    for (int j = 1; j <= nslots; ++j) {
-      int64_t sj = i;  // slot 1: the sample itself
-      if (j > 1) {
-        const uint32_t b1 = base[(int64_t)(j - 2) * a.S];
-        sj = b1 ? (int64_t)b1 - 1 : i;  // (never drawn: the weight is 0)
-      }
-      const double z_dla = m.min_z_dla + (m.max_z_dla - m.min_z_dla) * a.offset_samples[sj];
-      double mult[3], ms[3];
-#pragma unroll
-      for (int l = 0; l < 3; ++l) {
-        mult[l] = g_lines.c / (g_lines.wavelength_cm[l] * (1 + z_dla)) / 1e8;  // voigt.c:278-279
-        ms[l] = mult[l] * inv_s;
-      }
-      const double inv_opz = 1.0 / (1 + z_dla);
-      const double nscale = -a.nhi[sj] * g_lines.inv_sqrt2pi_sigma * kInvSqrtPi * kExpScale;
-      auto raw = [&](int P) -> double {  // voigt.c:282-291 for slot j's sample at padded pixel P (as k_mc_contract)
-        const double lamP = lam[min(P, n_pad - 1)];
-        double total;
-        bool near = false;
-        if (L == 3) total = wing_sum3(lamP, ms[0], ms[1], ms[2], cs, &near);
-        else total = wing_sum_runtime(lamP * inv_opz, cs, L, &near);
-        if (__any(near)) {  // accurate tier, wave-uniformly
-          if (L == 3) {
-            total = 0.0;
-            for (int l = 0; l < 3; ++l) {
-              const double ax = fabs((lamP * mult[l] - c_light) * inv_s);
-              total += ax < 30.0 ? 1.7724538509055159 * g_lines.leading[l] *
-                                       near_poly(g_lines.near_poly + l * kNearLineDoubles, ax)
-                                 : g_lines.cwing[l] * wing_core(ax * ax, g_lines.y2[l]);
-            }
-          } else {
-            total = total_near_at(lamP, 1 + z_dla, L);
-          }
-        }
-        return exp_table_scaled(nscale * total, s_exp);
-      };
-      double a0 = raw(pp), a1 = raw(pp + 1), a2 = raw(pp + 2), a3 = raw(pp + 3), a4 = raw(pp + 4), a5 = raw(pp + 5), a6;
-#pragma unroll
-      for (int u = 0; u < PPS; ++u) {
-        a6 = raw(pp + u + 6);
-        double ab = a0 * t0;  // voigt.c:297-299, taps in ascending order
-        ab = fma(a1, t1, ab);
-        ab = fma(a2, t2, ab);
-        ab = fma(a3, t3, ab);
-        ab = fma(a4, t4, ab);
-        ab = fma(a5, t5, ab);
-        ab = fma(a6, t6, ab);
-        a0 = a1; a1 = a2; a2 = a3; a3 = a4; a4 = a5; a5 = a6;
-        double *slot = s_wt + (sub * PPS + u) * NS + smp;
-        *slot = (j == 1) ? ab : *slot * ab;  // multi :342-351, in slot order
-      }
-    }
-    // the two weights, in place
-#pragma unroll
-    for (int u = 0; u < PPS; ++u) {
-      const int p = pp + u;
-      const double ab = s_wt[(sub * PPS + u) * NS + smp];
-      double wt = 0.0, ut = 0.0;
-      if (p < m.n_u) {
-        const PixelRow row = pix[p];
-        const double d = ab * ab * row.omega2 + row.nu;
-        const double rr = row.y - ab * row.mu;
-        wt = ab * ab / d;
-        ut = ab * rr / d;
-      }
-      s_wt[(sub * PPS + u) * NS + smp] = wt;
-      s_ut[(sub * PPS + u) * NS + smp] = ut;
-    }
-    __syncthreads();
-    // contraction: PT / 4 K-steps of 4 pixels
-    for (int st = 0; st < PT / 4; ++st) {
-      const int pl = 4 * st + r;
-      double aw[RT], au[RT];
-#pragma unroll
-      for (int rt = 0; rt < RT; ++rt) {
-        aw[rt] = s_wt[pl * NS + rt * 16 + c];
-        au[rt] = s_ut[pl * NS + rt * 16 + c];
-      }
-      const double *Mrow = s_M + pl * KS;
-#pragma unroll
-      for (int cc = 0; cc < CPW; ++cc) {
-        if (!valid[cc]) continue;  // (wave-uniform)
-        const double f = Mrow[fi[cc]] * Mrow[fj[cc]];
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt)
-          acc[cc][rt] = __builtin_amdgcn_mfma_f64_16x16x4f64(isv[cc] ? au[rt] : aw[rt], f, acc[cc][rt], 0, 0, 0);
-      }
-    }
-    __syncthreads();
-  }
-  // result register rr of row tile rt: sample rt * 16 + (lane >> 4) + 4 rr, column tile's column lane & 15
-  double *out = a.scratch + (sl * a.S) * (int64_t)ncol;
-#pragma unroll
-  for (int cc = 0; cc < CPW; ++cc) {
-    if (!valid[cc] || ocol[cc] < 0) continue;
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr) {
-        const int64_t po = (int64_t)chunk * NS + rt * 16 + r + 4 * rr;
-        if (po < a.S) out[po * ncol + ocol[cc]] = acc[cc][rt][rr];
-      }
-  }
+#define GPDLA_MC_CONTRACT_MULTI 1
+#include "mc_contract_body.hpp"
+#undef GPDLA_MC_CONTRACT_MULTI
 }
 
 // ------------------------------------------------------------------------------------------

@@ -17,7 +17,7 @@
 #pragma once
 #include <type_traits>
 
-#include "sweep_kernels.hpp"
+#include "sampled_profile.hpp"
 
 namespace gpdla {
 
@@ -52,18 +52,6 @@ struct ProfilesArgs {
 constexpr int kProfTile = 16;   // pixels per transposed store
 constexpr int kProfWaves = 4;   // waves per block (4 x 2 x 64 x 17 doubles of LDS: two blocks per CU)
 
-#ifdef PROF_EXP_RHOTABLE
-// Cost probe (round 5, results WRONG by construction): the three-line wing sum as ONE piecewise
-// polynomial of rho = lambda / (1 + z_DLA) -- the sum depends on lambda and z_DLA only through rho
-// (voigt.c:278-290) -- binned geometrically around the nearest line centre, 16 bins per octave of
-// |rho - lambda_j| from 2^-4 to 2^9 Angstrom on either side of each of the three lines, degree 7:
-// 1248 rows of 8 coefficients (80 KB).  The table holds zeros: the probe measures what the look-up
-// COSTS in k_profiles (index arithmetic, four 16-byte gathers per lane at the addresses a real table
-// would be read at, the local coordinate, Horner) against the 42 instructions of wing_sum3.
-constexpr int kRhoBinsPerSide = 13 * 16;
-__device__ double g_rho_probe[6 * kRhoBinsPerSide * 8];
-#endif
-
 __global__ __launch_bounds__(kProfWaves * 64) void k_profiles(ProfilesArgs a) {
   __shared__ double s_exp[kExpTab];  // 2^(j/64), the table behind exp_table()
   __shared__ double s_out[kProfWaves][2][64][kProfTile + 1];
@@ -91,9 +79,6 @@ __global__ __launch_bounds__(kProfWaves * 64) void k_profiles(ProfilesArgs a) {
   }
   const double cs = c_light * inv_s;
   const double inv_opz = 1.0 / (1 + z_dla);  // (run-time line counts: wing_sum_runtime)
-#ifdef PROF_EXP_RHOTABLE
-  const double inv1pz = inv_opz;
-#endif
   // (pre-scaled exp, sweep_kernels.hpp)
   const double nscale_a = -a.nhi_samples[i] * g_lines.inv_sqrt2pi_sigma * kInvSqrtPi * kExpScale;
   const double nscale_b = -a.lls_nhi_samples[i] * g_lines.inv_sqrt2pi_sigma * kInvSqrtPi * kExpScale;
@@ -106,51 +91,7 @@ __global__ __launch_bounds__(kProfWaves * 64) void k_profiles(ProfilesArgs a) {
 
   auto line_sum = [&](int P) -> double {  // voigt.c:282-290 for this lane's z_DLA at padded pixel P
     const double lamP = lam[min(P, n_pad - 1)];  // wave-uniform address
-    double total = 0.0;
-    bool near = false;
-    if (L == 3) {
-#ifdef PROF_EXP_RHOTABLE
-      const double rho = lamP * inv1pz;  // rest wavelength at the absorber, Angstrom
-      const bool ab = rho > 1120.6962, bc = rho > 999.12955;  // midpoints of Ly-alpha / beta / gamma
-      const double lc = ab ? 1215.6701 : bc ? 1025.7223 : 972.5368;
-      const int lsel = ab ? 0 : bc ? 1 : 2;
-      const double dd = rho - lc, ad = fabs(dd);
-      near = ad < 1.3e-3 * lc;  // |x| < 30: 30 sqrt2 sigma / c of the line's wavelength
-      const uint32_t hi = hi_word(ad);
-      int bin = (int)(hi >> 16) - (1019 << 4);  // exponent and the top four mantissa bits: 16 bins per octave from 2^-4
-      bin = min(max(bin, 0), kRhoBinsPerSide - 1);
-      const int row = (lsel * 2 + (dd < 0.0 ? 1 : 0)) * kRhoBinsPerSide + bin;
-      const double2 *cp = reinterpret_cast<const double2 *>(g_rho_probe + row * 8);
-      const double2 c01 = cp[0], c23 = cp[1], c45 = cp[2], c67 = cp[3];
-      // the position inside the bin, [0, 1): the mantissa bits below the bin's
-      const double tf = __hiloint2double((int)((hi & 0xFFFFu) | 0x3FF00000u), __double2loint(ad)) - 1.0;
-      double t = fma(c67.y, tf, c67.x);
-      t = fma(t, tf, c45.y);
-      t = fma(t, tf, c45.x);
-      t = fma(t, tf, c23.y);
-      t = fma(t, tf, c23.x);
-      t = fma(t, tf, c01.y);
-      total = fma(t, tf, c01.x);
-#else
-      total = wing_sum3(lamP, ms[0], ms[1], ms[2], cs, &near);
-#endif
-    } else {  // a run-time line count: the wing tier of k_sweep_slim<0> (four lines at a time from rho = lambda / (1 + z))
-      total = wing_sum_runtime(lamP * inv_opz, cs, L, &near);
-    }
-    if (__any(near)) {  // accurate tier: per-line piecewise polynomials (near_tables.hpp), as in k_sweep
-      if (L == 3) {
-        total = 0.0;
-        for (int j = 0; j < 3; ++j) {
-          const double ax = fabs((lamP * mult[j] - c_light) * inv_s);
-          total += ax < 30.0 ? 1.7724538509055159 * g_lines.leading[j] *
-                                   near_poly(g_lines.near_poly + j * kNearLineDoubles, ax)
-                             : g_lines.cwing[j] * wing_core(ax * ax, g_lines.y2[j]);
-        }
-      } else {
-        total = total_near_at(lamP, 1 + z_dla, L);
-      }
-    }
-    return total;
+    return sampled_line_sum(lamP, mult, ms, cs, inv_opz, z_dla, L);
   };
   // the two raw profiles at padded pixel P (voigt.c:291)
 #define GPDLA_PROF_RAW(P, ra, rb)                          \
@@ -181,22 +122,8 @@ __global__ __launch_bounds__(kProfWaves * 64) void k_profiles(ProfilesArgs a) {
 #pragma unroll
     for (int tt = 0; tt < kProfTile; ++tt) {
       GPDLA_PROF_RAW(p0 + tt + 6, a6, b6);
-      double acc = a0 * t0;  // voigt.c:297-299, taps in ascending order
-      acc = fma(a1, t1, acc);
-      acc = fma(a2, t2, acc);
-      acc = fma(a3, t3, acc);
-      acc = fma(a4, t4, acc);
-      acc = fma(a5, t5, acc);
-      acc = fma(a6, t6, acc);
-      s_out[wave][0][lane][tt] = acc;
-      acc = b0 * t0;
-      acc = fma(b1, t1, acc);
-      acc = fma(b2, t2, acc);
-      acc = fma(b3, t3, acc);
-      acc = fma(b4, t4, acc);
-      acc = fma(b5, t5, acc);
-      acc = fma(b6, t6, acc);
-      s_out[wave][1][lane][tt] = acc;
+      s_out[wave][0][lane][tt] = tap_fold(a0, a1, a2, a3, a4, a5, a6, t0, t1, t2, t3, t4, t5, t6);
+      s_out[wave][1][lane][tt] = tap_fold(b0, b1, b2, b3, b4, b5, b6, t0, t1, t2, t3, t4, t5, t6);
       a0 = a1; a1 = a2; a2 = a3; a3 = a4; a4 = a5; a5 = a6;
       b0 = b1; b1 = b2; b2 = b3; b3 = b4; b4 = b5; b5 = b6;
     }

@@ -18,6 +18,7 @@
 // from run to run and depend on their own quasar only.
 #pragma once
 #include "continuum_solve.hpp"
+#include "sampled_profile.hpp"
 
 namespace gpdla {
 
@@ -143,116 +144,11 @@ struct SpectraMomentsArgs {
 
 constexpr int kMomWaves = 4;
 
+// The body is spectra_moments_body.hpp, which k_spectra_moments_multi (spectra_multi_kernels.hpp) includes as well.
 __global__ __launch_bounds__(kMomWaves * 64) void k_spectra_moments(SpectraMomentsArgs a) {
-  __shared__ double s_exp[kExpTab];
-  __shared__ double s_out[kMomWaves][64][kProfTile + 1];
-  __shared__ double s_w[kMomWaves][64];
-  __shared__ double s_part[2][kMomWaves][2][kProfTile];
-
-  for (int e = threadIdx.x; e < kExpTab; e += kMomWaves * 64) s_exp[e] = exp2((double)e * (1.0 / kExpTab));
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int64_t sl = blockIdx.x / a.chunks;       // selected quasar of this launch
-  const int chunk = blockIdx.x - sl * a.chunks;
-  const int64_t s = a.s0 + sl;
-  const QuasarMeta m = a.meta[a.sel[s]];
-  if (m.status != 0) return;  // (the whole block: no sample redshifts; k_spectra_combine writes NaN)
-  const int L = a.num_lines;
-  const int64_t pos = (int64_t)chunk * (kMomWaves * 64) + wave * 64 + lane;
-  const bool live = pos < a.S;
-  const int64_t i = a.perm[live ? pos : a.S - 1];
-  s_w[wave][lane] = live ? a.w[s * a.S + i] : 0.0;
-  __syncthreads();
-  const double z_dla = m.min_z_dla + (m.max_z_dla - m.min_z_dla) * a.offset_samples[i];
-  const double c_light = g_lines.c, inv_s = g_lines.inv_sqrt2_sigma;
-  double mult[3], ms[3];
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    mult[j] = g_lines.c / (g_lines.wavelength_cm[j] * (1 + z_dla)) / 1e8;  // voigt.c:278-279
-    ms[j] = mult[j] * inv_s;
-  }
-  const double cs = c_light * inv_s;
-  const double inv_opz = 1.0 / (1 + z_dla);
-  const double nscale = -a.nhi[i] * g_lines.inv_sqrt2pi_sigma * kInvSqrtPi * kExpScale;
-  const double *lam = a.lam_pad + m.lam_off;
-  const int n_pad = m.n_u + 6;
-  const double t0 = g_lines.taps[0], t1 = g_lines.taps[1], t2 = g_lines.taps[2], t3 = g_lines.taps[3],
-               t4 = g_lines.taps[4], t5 = g_lines.taps[5], t6 = g_lines.taps[6];
-
-  auto raw = [&](int P) -> double {  // voigt.c:282-291 for this lane's sample at padded pixel P (as k_profiles)
-    const double lamP = lam[min(P, n_pad - 1)];  // wave-uniform address
-    double total;
-    bool near = false;
-    if (L == 3) total = wing_sum3(lamP, ms[0], ms[1], ms[2], cs, &near);
-    else total = wing_sum_runtime(lamP * inv_opz, cs, L, &near);
-    if (__any(near)) {  // accurate tier, wave-uniformly
-      if (L == 3) {
-        total = 0.0;
-        for (int j = 0; j < 3; ++j) {
-          const double ax = fabs((lamP * mult[j] - c_light) * inv_s);
-          total += ax < 30.0 ? 1.7724538509055159 * g_lines.leading[j] *
-                                   near_poly(g_lines.near_poly + j * kNearLineDoubles, ax)
-                             : g_lines.cwing[j] * wing_core(ax * ax, g_lines.y2[j]);
-        }
-      } else {
-        total = total_near_at(lamP, 1 + z_dla, L);
-      }
-    }
-    return exp_table_scaled(nscale * total, s_exp);
-  };
-
-  // the 16 weights of the rows this lane adds up (rows 4 e + g)
-  const int g = lane >> 4, tt = lane & 15;
-  double wr[16];
-#pragma unroll
-  for (int e = 0; e < 16; ++e) wr[e] = s_w[wave][4 * e + g];
-
-  double a0 = raw(0), a1 = raw(1), a2 = raw(2), a3 = raw(3), a4 = raw(4), a5 = raw(5), a6;
-  double *part = a.part + ((sl * a.chunks + chunk) * 2) * a.stride;
-  int buf = 0;
-  for (int p0 = 0; p0 < m.n_u; p0 += kProfTile, buf ^= 1) {
-#pragma unroll
-    for (int u = 0; u < kProfTile; ++u) {
-      a6 = raw(p0 + u + 6);
-      double acc = a0 * t0;  // voigt.c:297-299, taps in ascending order
-      acc = fma(a1, t1, acc);
-      acc = fma(a2, t2, acc);
-      acc = fma(a3, t3, acc);
-      acc = fma(a4, t4, acc);
-      acc = fma(a5, t5, acc);
-      acc = fma(a6, t6, acc);
-      s_out[wave][lane][u] = acc;
-      a0 = a1; a1 = a2; a2 = a3; a3 = a4; a4 = a5; a5 = a6;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    double m1 = 0.0, m2 = 0.0;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const double b = 1.0 - s_out[wave][4 * e + g][tt];
-      const double t = wr[e] * b;
-      m1 += t;
-      m2 = fma(t, b, m2);
-    }
-    m1 += __shfl_xor(m1, 16);
-    m2 += __shfl_xor(m2, 16);
-    m1 += __shfl_xor(m1, 32);
-    m2 += __shfl_xor(m2, 32);
-    if (lane < kProfTile) {
-      s_part[buf][wave][0][lane] = m1;
-      s_part[buf][wave][1][lane] = m2;
-    }
-    // one barrier a tile: s_part is double-buffered (wave 0 reads buffer `buf` of tile t while the
-    // other waves can at most be writing buffer `buf ^ 1` of tile t + 1), and it also orders this
-    // wave's reads of s_out before its writes of the next tile
-    __syncthreads();
-    if (threadIdx.x < 2 * kProfTile) {
-      const int mom = threadIdx.x >> 4, t = threadIdx.x & 15;
-      double sum = s_part[buf][0][mom][t];
-#pragma unroll
-      for (int w = 1; w < kMomWaves; ++w) sum += s_part[buf][w][mom][t];
-      if (p0 + t < m.n_u) part[mom * a.stride + p0 + t] = sum;
-    }
-  }
+#define GPDLA_SPECTRA_MOMENTS_MULTI 0
+#include "spectra_moments_body.hpp"
+#undef GPDLA_SPECTRA_MOMENTS_MULTI
 }
 
 // ------------------------------------------------------------------------------------------

@@ -11,7 +11,9 @@
 //                            partial sums of every model
 //
 // Model DLA(1) and the sub-DLA model are k_spectra_moments' (spectra_kernels.hpp); every model's chunks are
-// combined by k_spectra_combine.  Sums run in a fixed order, nothing is accumulated with atomics and an
+// combined by k_spectra_combine.  The two moments kernels include one body (spectra_moments_body.hpp,
+// DESIGN.md 4.26); the two weights kernels are written out twice, because the softmax as one function over a value(i)
+// functor reorders k_spectra_weights' instructions (same section).  Sums run in a fixed order, nothing is accumulated with atomics and an
 // entry is reduced on its own: outputs are bit-identical from run to run and for any grouping.
 #pragma once
 #include "spectra_kernels.hpp"
@@ -71,7 +73,7 @@ __global__ __launch_bounds__(256) void k_spectra_weights_multi(SpectraWeightsMul
 // are evaluated at the tile's 22 padded pixels (the six carried raw values are recomputed: 22 / 16 of the
 // line sums, nothing kept per slot in registers or LDS), broadened with the taps in ascending order and
 // multiplied into the lane's own s_out row in slot order -- a lane owns its row until the transpose, so
-// this needs no barrier.  Each slot takes the accurate tier under its own __any(near): the own samples of
+// this needs no barrier.  Each slot takes the accurate tier under its own vote of the wave: the own samples of
 // a wave are neighbours in z_DLA, the gathered ones are wherever the resampling put them.
 // A sample of weight 0 (a NaN log-likelihood, a slot never drawn) is evaluated like any other and drops
 // out of the sums; its missing slot reads sample 0.
@@ -94,125 +96,11 @@ struct SpectraMomentsMultiArgs {
   double *part;
 };
 
+// The body is spectra_moments_body.hpp, the one k_spectra_moments (spectra_kernels.hpp) includes.
 __global__ __launch_bounds__(kMomWaves * 64) void k_spectra_moments_multi(SpectraMomentsMultiArgs a) {
-  __shared__ double s_exp[kExpTab];
-  __shared__ double s_out[kMomWaves][64][kProfTile + 1];
-  __shared__ double s_w[kMomWaves][64];
-  __shared__ double s_part[2][kMomWaves][2][kProfTile];
-
-  for (int e = threadIdx.x; e < kExpTab; e += kMomWaves * 64) s_exp[e] = exp2((double)e * (1.0 / kExpTab));
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int nm = a.n_hi - a.n_lo + 1;
-  const int64_t item = blockIdx.x / a.chunks;     // (entry, model)
-  const int chunk = (int)(blockIdx.x - item * a.chunks);
-  const int64_t sl = item / nm;
-  const int n = a.n_lo + (int)(item - sl * nm);
-  const QuasarMeta m = a.meta[a.sel[sl]];
-  // (the whole block: no sample redshifts, or no weight -- k_spectra_combine writes NaN without reading)
-  if (m.status != 0 || a.flag[(int64_t)n * a.flag_stride + sl] != 0) return;
-  const int L = a.num_lines;
-  const int64_t pos = (int64_t)chunk * (kMomWaves * 64) + wave * 64 + lane;
-  const bool live = pos < a.S;
-  const int64_t i = a.perm[live ? pos : a.S - 1];
-  s_w[wave][lane] = live ? a.w[((int64_t)n * a.cap + sl) * a.S + i] : 0.0;
-  __syncthreads();
-  const double c_light = g_lines.c, inv_s = g_lines.inv_sqrt2_sigma;
-  const double cs = c_light * inv_s;
-  const uint32_t *base = a.base + a.base_start[sl] + i;
-  const double *lam = a.lam_pad + m.lam_off;
-  const int n_pad = m.n_u + 6;
-  const double t0 = g_lines.taps[0], t1 = g_lines.taps[1], t2 = g_lines.taps[2], t3 = g_lines.taps[3],
-               t4 = g_lines.taps[4], t5 = g_lines.taps[5], t6 = g_lines.taps[6];
-
-  // lane (g, t) adds up rows 4 e + g of pixel t; their 16 weights stay in s_w (read again every tile: next to
-  // n x 22 line sums the 16 LDS reads are nothing, and 32 registers are not held across the slot loop)
-  const int g = lane >> 4, tt = lane & 15;
-
-  double *part = a.part + ((((int64_t)n * a.cap + sl) * a.chunks + chunk) * 2) * a.stride;
-  int buf = 0;
-  for (int p0 = 0; p0 < m.n_u; p0 += kProfTile, buf ^= 1) {
-    for (int j = 1; j <= n; ++j) {
-      int64_t sj = i;                                 // slot 1: the sample itself
-      if (j > 1) {
-        const uint32_t b1 = base[(int64_t)(j - 2) * a.S];
-        sj = b1 ? (int64_t)b1 - 1 : 0;                // (never drawn: the weight is 0)
-      }
-      const double z_dla = m.min_z_dla + (m.max_z_dla - m.min_z_dla) * a.offset_samples[sj];
-      double mult[3], ms[3];
-#pragma unroll
-      for (int l = 0; l < 3; ++l) {
-        mult[l] = g_lines.c / (g_lines.wavelength_cm[l] * (1 + z_dla)) / 1e8;  // voigt.c:278-279
-        ms[l] = mult[l] * inv_s;
-      }
-      const double inv_opz = 1.0 / (1 + z_dla);
-      const double nscale = -a.nhi[sj] * g_lines.inv_sqrt2pi_sigma * kInvSqrtPi * kExpScale;
-
-      auto raw = [&](int P) -> double {  // voigt.c:282-291 for slot j's sample at padded pixel P (as k_spectra_moments)
-        const double lamP = lam[min(P, n_pad - 1)];  // wave-uniform address
-        double total;
-        bool near = false;
-        if (L == 3) total = wing_sum3(lamP, ms[0], ms[1], ms[2], cs, &near);
-        else total = wing_sum_runtime(lamP * inv_opz, cs, L, &near);
-        if (__any(near)) {  // accurate tier, wave-uniformly
-          if (L == 3) {
-            total = 0.0;
-            for (int l = 0; l < 3; ++l) {
-              const double ax = fabs((lamP * mult[l] - c_light) * inv_s);
-              total += ax < 30.0 ? 1.7724538509055159 * g_lines.leading[l] *
-                                       near_poly(g_lines.near_poly + l * kNearLineDoubles, ax)
-                                 : g_lines.cwing[l] * wing_core(ax * ax, g_lines.y2[l]);
-            }
-          } else {
-            total = total_near_at(lamP, 1 + z_dla, L);
-          }
-        }
-        return exp_table_scaled(nscale * total, s_exp);
-      };
-
-      double a0 = raw(p0), a1 = raw(p0 + 1), a2 = raw(p0 + 2), a3 = raw(p0 + 3), a4 = raw(p0 + 4), a5 = raw(p0 + 5), a6;
-#pragma unroll
-      for (int u = 0; u < kProfTile; ++u) {
-        a6 = raw(p0 + u + 6);
-        double acc = a0 * t0;  // voigt.c:297-299, taps in ascending order
-        acc = fma(a1, t1, acc);
-        acc = fma(a2, t2, acc);
-        acc = fma(a3, t3, acc);
-        acc = fma(a4, t4, acc);
-        acc = fma(a5, t5, acc);
-        acc = fma(a6, t6, acc);
-        s_out[wave][lane][u] = (j == 1) ? acc : s_out[wave][lane][u] * acc;  // multi :342-351, in slot order
-        a0 = a1; a1 = a2; a2 = a3; a3 = a4; a4 = a5; a5 = a6;
-      }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    double m1 = 0.0, m2 = 0.0;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const double b = 1.0 - s_out[wave][4 * e + g][tt];
-      const double t = s_w[wave][4 * e + g] * b;
-      m1 += t;
-      m2 = fma(t, b, m2);
-    }
-    m1 += __shfl_xor(m1, 16);
-    m2 += __shfl_xor(m2, 16);
-    m1 += __shfl_xor(m1, 32);
-    m2 += __shfl_xor(m2, 32);
-    if (lane < kProfTile) {
-      s_part[buf][wave][0][lane] = m1;
-      s_part[buf][wave][1][lane] = m2;
-    }
-    // one barrier a tile, as in k_spectra_moments: s_part is double-buffered, and the barrier orders this
-    // wave's reads of s_out before its writes of the next tile
-    __syncthreads();
-    if (threadIdx.x < 2 * kProfTile) {
-      const int mom = threadIdx.x >> 4, t = threadIdx.x & 15;
-      double sum = s_part[buf][0][mom][t];
-#pragma unroll
-      for (int w = 1; w < kMomWaves; ++w) sum += s_part[buf][w][mom][t];
-      if (p0 + t < m.n_u) part[mom * a.stride + p0 + t] = sum;
-    }
-  }
+#define GPDLA_SPECTRA_MOMENTS_MULTI 1
+#include "spectra_moments_body.hpp"
+#undef GPDLA_SPECTRA_MOMENTS_MULTI
 }
 
 // ------------------------------------------------------------------------------------------

@@ -44,6 +44,7 @@ def test_header_declares_the_entries_and_the_bindings_load(lib):
 
 def test_kernel_constants_of_the_case_lists():
     src = open(os.path.join(_lib.CSRC, "marginal_continuum_kernels.hpp")).read()
+    src += open(os.path.join(_lib.CSRC, "mc_contract_body.hpp")).read()      # the body of k_mc_contract(_multi)
     host = open(os.path.join(_lib.CSRC, "host_grid.hpp")).read()      # MixturePlan::contract, which the predictive flux shares
     assert f"constexpr int kMcSolveChunk = {MC.SOLVE_CHUNK};" in src and f"constexpr int kMcPixTile = {MC.FINISH_TILE};" in src
     lo, hi = MC.CONTRACT[20], MC.CONTRACT[40]

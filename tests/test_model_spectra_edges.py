@@ -147,6 +147,7 @@ def test_constants_and_launch_split_mirror_follow_the_source():
     """The tile sizes the case lists are built around, and the arithmetic by which gpdla_batch_model_spectra
     cuts a selection into launches (E.launch_group), are still the library's."""
     kern, multi, mock = _read("spectra_kernels.hpp"), _read("multi_kernels.hpp"), _read("mock_kernels.hpp")
+    kern += _read("spectra_moments_body.hpp")  # the body k_spectra_moments includes
     solve = _read("continuum_solve.hpp")  # continuum_null_solve: what k_spectra_continuum accumulates and factorises with
     assert "continuum_null_solve<kContTile>(" in kern[kern.index("void k_spectra_continuum("):]
     assert "const int e = tid + %d * t;" % E.CONT_THREADS in solve[solve.index("void continuum_null_solve("):]

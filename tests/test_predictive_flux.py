@@ -52,6 +52,7 @@ def test_header_declares_the_entries_and_the_bindings_load(lib):
 
 def test_kernel_constants_of_the_case_lists():
     src = open(os.path.join(_lib.CSRC, "predictive_flux_kernels.hpp")).read()
+    src += open(os.path.join(_lib.CSRC, "pf_pixels_body.hpp")).read()      # the body of k_pf_pixels(_multi)
     host = open(os.path.join(_lib.CSRC, "host_predictive_flux.hpp")).read()
     assert f"constexpr int kPfRowTiles = {PC.SAMPLES // 16};" in src and "constexpr int kPfSamples = 16 * kPfRowTiles;" in src
     assert f"constexpr int kPfPixTile = {PC.PIXEL_TILE};" in src
