@@ -5,10 +5,11 @@
 //   k_refine_boxes    one block of 256 threads per selected quasar.  From a source table (the first
 //                     pass's l_i with the global offset / log N tables, or the previous level's lambda_j
 //                     with the unit points mapped through the previous box): pass 1 the NaN-aware
-//                     maximum, pass 2 the extrema of z and log N over A = {l >= max - delta}, pass 3 the
-//                     sum of exp(l - max) over the samples strictly outside the new box.  Writes the box,
-//                     a copy of the quasar's QuasarMeta whose search range is the box (the batch's own
-//                     meta is not touched), and the evidence term (max, scaled sum) of what lies outside.
+//                     maximum, pass 2 the extrema of z and log N over A = {l >= max - delta}, passes 3 and 4
+//                     the maximum m of the samples strictly outside the new box and their sum of
+//                     exp(l - m).  Writes the box, a copy of the quasar's QuasarMeta whose search range is
+//                     the box (the batch's own meta is not touched), and the evidence term (m, scaled sum)
+//                     of what lies outside.
 //   the boxed sweep   k_sweep_slim_boxed<LINES> / k_sweep_split_slim<LINES, 0, BoxedSweepArgs>: the shipped
 //                     kernels with one prologue line changed (N = exp10(n_lo + (n_hi - n_lo) v)).
 //   k_refine_finish   one block per quasar: lambda_j = l'_j + log p_N(n'_j), its maximum, first argmax
@@ -115,12 +116,23 @@ __global__ __launch_bounds__(256) void k_refine_boxes(RefineBoxArgs a) {
   const double z_lo = fmax(pz_lo, z0 - padz), z_hi = fmin(pz_hi, z1 + padz);
   const double n_lo = fmax(pn_lo, n0 - padn), n_hi = fmin(pn_hi, n1 + padn);
 
-  CompSum out;
+  // the term's own maximum: the samples outside the box, not the level's.  On a narrow posterior the level's
+  // maximum lies inside the box and thousands above everything outside: exp(l - mx) is 0 for every sample the
+  // term sums, and a term that is 0 next to its own shift takes Z_ref with it (k_refine_finish).
+  double omx = -inf;
   for (int64_t i = tid; i < S; i += 256) {
     const double l = row[i];
     const double z = pz_lo + pdz * a.su[i], n = a.level ? pn_lo + pdn * a.sv[i] : a.sv[i];
-    if (l == l && (z < z_lo || z > z_hi || n < n_lo || n > n_hi)) out.add(exp(l - mx));
+    if (l == l && (z < z_lo || z > z_hi || n < n_lo || n > n_hi)) omx = fmax(omx, l);
   }
+  omx = post_block_max(omx, red);
+  CompSum out;
+  if (omx > -inf)   // (else nothing outside, or -inf only: the term is (-inf, 0))
+    for (int64_t i = tid; i < S; i += 256) {
+      const double l = row[i];
+      const double z = pz_lo + pdz * a.su[i], n = a.level ? pn_lo + pdn * a.sv[i] : a.sv[i];
+      if (l == l && (z < z_lo || z > z_hi || n < n_lo || n > n_hi)) out.add(exp(l - omx));
+    }
   const double sum = post_block_sum(out.value(), red);
   if (tid == 0) {
     box[4 * a.level + 0] = z_lo;
@@ -138,7 +150,7 @@ __global__ __launch_bounds__(256) void k_refine_boxes(RefineBoxArgs a) {
       scaled = (V * pdn) * scaled;
     }
     double *t = a.terms + (q * kRefineTerms + a.level) * 2;
-    t[0] = mx;
+    t[0] = omx;
     t[1] = scaled;
     a.status[q] = 0;
   }
@@ -231,12 +243,16 @@ __global__ __launch_bounds__(256) void k_refine_finish(RefineFinishArgs a) {
     double *t = a.terms + q * kRefineTerms * 2;
     t[2 * (a.level + 1) + 0] = mx;
     t[2 * (a.level + 1) + 1] = (V * dn) * (sum / (double)S);
-    // Z_ref = Sum_l exp(m_l) s_l over the a.level + 2 terms, with the one shift M = max m_l
-    double M = t[0];
-    for (int l = 1; l <= a.level + 1; ++l) M = fmax(M, t[2 * l]);
+    // Z_ref = Sum_l exp(m_l) s_l over those of the a.level + 2 terms that are not 0, with the one shift M = the
+    // largest m_l among them (a term of s_l = 0 -- nothing outside its box, or a box of no volume -- has no say
+    // in the shift: exp(m_l - M) may overflow next to its 0)
+    double M = -inf;
+    for (int l = 0; l <= a.level + 1; ++l)
+      if (t[2 * l + 1] > 0.0) M = fmax(M, t[2 * l]);
     double tot = 0.0;
-    for (int l = 0; l <= a.level + 1; ++l) tot = tot + exp(t[2 * l] - M) * t[2 * l + 1];
-    const double log_z = M + log(tot);
+    for (int l = 0; l <= a.level + 1; ++l)
+      if (t[2 * l + 1] > 0.0) tot = tot + exp(t[2 * l] - M) * t[2 * l + 1];
+    const double log_z = M + log(tot);   // (no term at all: -inf + -inf)
     double *out = a.scal + q * kRefineScalars;
     out[0] = log_z;
     out[1] = a.lp_dla[q] + log_z;

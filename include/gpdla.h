@@ -1018,12 +1018,16 @@ double gpdla_debug_last_summaries_ms(void);
  *
  * Refined evidence: with V_l = (z_hi - z_lo) / (max_z - min_z) of box l (1 where max_z == min_z) and
  * W_l = n_hi - n_lo, Z_ref = Sum_{t = 0 .. L} exp(m_t) s_t with
- *   t = 0:           m = max l_i,              s = (Sum over i outside box 1 of exp(l_i - m)) / S,
- *   t = 1 .. L - 1:  m = max lambda_j (level t), s = (V_t W_t) ((Sum over j outside box t + 1 of exp(lambda_j - m)) / S'),
+ *   t = 0:           m = max of l_i over i outside box 1,  s = (Sum over i outside box 1 of exp(l_i - m)) / S,
+ *   t = 1 .. L - 1:  m = max of lambda_j (level t) over j outside box t + 1,
+ *                    s = (V_t W_t) ((Sum over j outside box t + 1 of exp(lambda_j - m)) / S'),
  *   t = L:           m = max lambda_j (level L), s = (V_L W_L) ((Sum over all j of exp(lambda_j - m)) / S'),
- * "outside" meaning z or n strictly beyond an edge and NaN contributing 0; the terms are added in this
- * order as exp(m_t - M) s_t with the one shift M = max m_t, and log_likelihoods_dla_refined = M + log of
- * that sum; log_posteriors_dla_refined adds the batch's log_priors_dla.  The batch's own results and model
+ * "outside" meaning z or n strictly beyond an edge and NaN contributing 0.  Every term is shifted by the maximum of
+ * the samples it sums, not of its level: on a narrow posterior the level's maximum lies inside the next box,
+ * thousands above everything outside it.  A term with nothing outside its box (or -inf only) is m = -inf, s = 0.
+ * The terms with s_t > 0 are added in this order as exp(m_t - M) s_t with the one shift M = the largest m_t among
+ * them (a term of 0 has no say in the shift), and log_likelihoods_dla_refined = M + log of that sum (-inf where no
+ * term is left); log_posteriors_dla_refined adds the batch's log_priors_dla.  The batch's own results and model
  * posteriors are not touched.
  *
  * Refined MAP: the first j of largest lambda_j at level L: MAP_z_dlas_refined = z'_j, MAP_log_nhis_refined

@@ -54,10 +54,15 @@ def log_prior(n, prior, N_lo, N_hi, dtype=np.float64):
         return np.log(p)
 
 
-def _outside_sum(l, mx, outside, dtype):
+def _outside_term(l, outside, dtype):
+    """(m, Sum exp(l - m)) over the samples outside the box, m their own maximum; (-inf, 0) where there is none, or
+    -inf only"""
     l = np.asarray(l, dtype=np.float64)
     take = outside & ~np.isnan(l)
-    return np.sum(np.exp((l[take] - mx).astype(dtype)), dtype=dtype) if take.any() else dtype(0.0)
+    m = np.max(l[take]) if take.any() else -np.inf
+    if not m > -np.inf:
+        return -np.inf, dtype(0.0)
+    return m, np.sum(np.exp((l[take] - m).astype(dtype)), dtype=dtype)
 
 
 def refine_row(l, offsets, lnhi, min_z, max_z, status, u, v, sweep, levels=2, delta=12.5, pad=2.0, prior=None,
@@ -84,11 +89,12 @@ def refine_row(l, offsets, lnhi, min_z, max_z, status, u, v, sweep, levels=2, de
         if got is None:
             return out
         box, mx, outside = got
-        scaled = _outside_sum(src_l, mx, outside, dtype) / dtype(len(src_l))
+        omx, scaled = _outside_term(src_l, outside, dtype)
+        scaled = scaled / dtype(len(src_l))
         if lev:
             V = 1.0 if prior_dz == 0.0 else (parent[1] - parent[0]) / prior_dz
             scaled = dtype(V * (parent[3] - parent[2])) * scaled
-        terms.append((mx, scaled))
+        terms.append((omx, scaled))
         out["boxes"][lev] = box
         z = box[0] + (box[1] - box[0]) * u
         n = box[2] + (box[3] - box[2]) * v
@@ -108,7 +114,8 @@ def refine_row(l, offsets, lnhi, min_z, max_z, status, u, v, sweep, levels=2, de
     V = 1.0 if prior_dz == 0.0 else (box[1] - box[0]) / prior_dz
     total = np.sum(np.exp(lam[ok] - mx), dtype=dtype)
     terms.append((mx, dtype(V * (box[3] - box[2])) * (total / dtype(Sr))))
-    M = max(float(m) for m, _ in terms)
+    terms = [(m, s) for m, s in terms if s > 0]   # a term of 0 has no say in the shift
+    M = max((float(m) for m, _ in terms), default=-np.inf)
     tot = dtype(0.0)
     for m, s in terms:
         tot = tot + np.exp(dtype(m) - dtype(M)) * s
