@@ -19,7 +19,7 @@ DEFAULT_LIB_PATH = os.path.join(CSRC, "libgpdla.so")
 def lib_path() -> str:
     """The library load() opens: GPDLA_LIB_PATH if set (read at call time, so a child process may
     set it after this module was imported), else the in-tree product library.  GPDLA_LIB_PATH is a
-    diagnostic override: ablation builds made by tools/ab_build.sh / tools/ablate.sh;
+    diagnostic override: library variants made by tools/ab_build.sh;
     libgpdla_legacy.so for the bit-identity tests."""
     return os.environ.get("GPDLA_LIB_PATH") or DEFAULT_LIB_PATH
 
@@ -32,7 +32,7 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-s
                "-std=c++17", "-no-hip-rt", "-Wno-inline-asm"]
 
 #: the second library: the same source with the superseded kernels and their environment switches
-#: compiled in (csrc/host_legacy.hpp, GPDLA_WITH_LEGACY).  Only bit-identity tests and A/B tools load it,
+#: compiled in (csrc/host_legacy.hpp, GPDLA_WITH_LEGACY).  Only bit-identity and launch-group tests load it,
 #: through GPDLA_LIB_PATH; nothing in the package does.
 LEGACY_LIB_PATH = os.path.join(CSRC, "libgpdla_legacy.so")
 
@@ -475,8 +475,9 @@ def build(force: bool = False, verbose: bool = False) -> str:
 
 def build_legacy(force: bool = False, verbose: bool = False) -> str:
     """Compile libgpdla_legacy.so: csrc/gpdla.hip with -DGPDLA_WITH_LEGACY, which turns the hooks of
-    csrc/host_legacy.hpp on (the pre-expanded-record sweeps, the round-1/-3 training kernels and the
-    GPDLA_* environment switches that select them)."""
+    csrc/host_legacy.hpp on: the pre-expanded-record sweeps behind GPDLA_EXPANDED_RECORDS, the
+    GPDLA_MC_SCRATCH_BYTES budget of the launch-group tests, and the round-1 training kernel behind
+    GPDLA_TRAIN_LEGACY."""
     return _build(LEGACY_LIB_PATH, ["-DGPDLA_WITH_LEGACY"], force, verbose)
 
 

@@ -13,7 +13,7 @@
 //
 // __device__ __forceinline__ only: a kernel keeps its own __shared__ arrays and passes pointers.
 #pragma once
-#include "multi_kernels.hpp"
+#include "batch_types.hpp"
 
 namespace gpdla {
 

@@ -13,7 +13,7 @@
 //
 // These tiers serve gpdla_voigt (k_voigt_raw) directly and, evaluated in long double on the host,
 // are what near_tables.hpp fits its per-line polynomials to.  The sweep kernels evaluate the wing
-// formula (economised, sweep_kernels.hpp) branch-free for every (pixel, line) and, under a
+// formula (economised, voigt_tiers.hpp) branch-free for every (pixel, line) and, under a
 // wave-uniform vote when some lane is within 30 Doppler widths of a line centre (about 11 pixels
 // per line; samples are processed in z order so those lanes coincide), those polynomials.
 #pragma once

@@ -25,11 +25,16 @@
 
 #include "../../include/gpdla.h"
 #include "../../include/gpdla_lyman_series.h"
+#include "prepare_kernels.hpp"
+#include "evidence_kernels.hpp"
 #include "multi_kernels.hpp"
+#include "sweep_expanded_kernel.hpp"
 #include "sweep_multi_slim_kernel.hpp"
 #include "sweep_slim_kernel.hpp"
-#include "sweep_split_kernel.hpp"
 #include "sweep_split_slim_kernel.hpp"
+#ifdef GPDLA_WITH_LEGACY
+#include "superseded_kernels.hpp"
+#endif
 #include "learn_kernels.hpp"
 #include "stats_kernels.hpp"
 #include "spectra_kernels.hpp"

@@ -1,15 +1,14 @@
 // host_legacy.hpp -- everything that only libgpdla_legacy.so has.  Superseded kernels and the
 // environment switches that select them live in that SECOND library: the same translation unit
 // built with -DGPDLA_WITH_LEGACY (gp_dla_detection_amd/_lib.py: build_legacy), loaded through
-// GPDLA_LIB_PATH by tests/test_gpu_record_classes.py, tools/ab*.sh and tools/check_training_legacy.py
-// for bit-identity tests and A/B timing.  The product library reads no environment variable: no
-// stray variable can select a slower kernel, and the superseded kernels are not in its code object.
+// GPDLA_LIB_PATH by tests/test_gpu_record_classes.py, the launch-group tests and tools/check_training_legacy.py.
+// The product library reads no environment variable: no stray variable can select a slower kernel,
+// and the superseded kernels (superseded_kernels.hpp) are not in its code object.
 //   GPDLA_EXPANDED_RECORDS  the sweeps on pre-expanded records (k_sweep / k_sweep_split / k_sweep_multi*)
-//   GPDLA_SPLIT_LEGACY      20 < k <= 40 with every wave of a group repeating the Voigt / weight arithmetic
-//   GPDLA_TRAIN_SPLITS      "H,H2,GS": the three splits of the training objective
-//   GPDLA_TRAIN_FACTOR_LDS  k_train_factor<40> (LDS broadcasts) instead of k_train_factor16<40>
-//   GPDLA_TRAIN_LEGACY      the round-1 training kernel (one block per slot of quasars)
-// The product functions reach this file through the six legacy_* hooks below (declared in host_sweep.hpp and
+//   GPDLA_MC_SCRATCH_BYTES  the scratch budget that cuts a selection into launch groups (host_grid.hpp)
+//   GPDLA_TRAIN_LEGACY      the round-1 training kernel (one block per slot of quasars, training_kernels.hpp): its
+//                           three kernels are not templates, so they stand in the product code object as well
+// The product functions reach this file through the four legacy_* hooks below (declared in host_sweep.hpp and
 // host_training.hpp); the product library's versions, at the end, do nothing.
 #pragma once
 
@@ -17,76 +16,45 @@ namespace {
 
 #ifdef GPDLA_WITH_LEGACY
 
-#define GPDLA_LEGACY_SWITCH(name, var) static const bool name = std::getenv(var) != nullptr
-
-RecordClass legacy_record_class(int k, RecordClass product) {
-  GPDLA_LEGACY_SWITCH(expanded, "GPDLA_EXPANDED_RECORDS");
-  GPDLA_LEGACY_SWITCH(split_legacy, "GPDLA_SPLIT_LEGACY");
-  return expanded || (k > 20 && split_legacy) ? kRecExpanded : product;
+RecordClass legacy_record_class(int, RecordClass product) {
+  static const bool expanded = std::getenv("GPDLA_EXPANDED_RECORDS") != nullptr;
+  return expanded ? kRecExpanded : product;
 }
 
 // fp64 on pre-expanded records.  k <= 20: the compact class of k_sweep; 20 < k <= 40: the same tiles
-// split over the 4 waves of a sample group, every wave repeating the Voigt / weight arithmetic
-// (GPDLA_SPLIT_LEGACY, k_sweep) or all four sharing that pipeline (k_sweep_split)
+// split over the 4 waves of a sample group, all four sharing the Voigt / weight pipeline (k_sweep_split)
 template <int KMAX>
 int legacy_sweep(gpdla_context *c, gpdla_batch *b, const SweepArgs &args) {
   const bool three = args.num_lines == 3;
   if constexpr (KMAX == 20) {
     return three ? launch_sweep_expanded<double, 8, 14, 1, 8, 13, 3>(c, b, args) : launch_sweep_expanded<double, 8, 14, 1, 4, 13, 0>(c, b, args);
   } else {
-    GPDLA_LEGACY_SWITCH(split_legacy, "GPDLA_SPLIT_LEGACY");
-    if (split_legacy)
-      return three ? launch_sweep_expanded<double, 8, 14, 4, 2, 52, 3>(c, b, args) : launch_sweep_expanded<double, 8, 14, 4, 1, 52, 0>(c, b, args);
     const size_t lds = std::max(sweep_split_lds_doubles(three ? 0 : args.num_lines), kExpTab + kSplitEpilogueDoubles) * sizeof(double);
     if (lds > 160 * 1024) return fail(GPDLA_ERR_UNSUPPORTED, "split sweep needs %zu B of LDS", lds);
     return launch_sweep_kernel(c, three ? &k_sweep_split<3> : &k_sweep_split<0>, 512, lds, 2 * kSamplesPerWave, b->nq, args);
   }
 }
 
-// The multi-DLA passes on pre-expanded records: k_sweep_multi_split (20 < k <= 40: the roles of a
-// sample group share the gathers and weights) or k_sweep_multi (k <= 20, and GPDLA_SPLIT_LEGACY)
-template <int NTW, int TS, int CH, int TW>
-int legacy_sweep_multi_expanded(gpdla_context *c, gpdla_batch *b, const SweepMultiArgs &args) {
-  constexpr int groups = kSweepWaves / TS;
-  const size_t RD = (size_t)record_doubles(b->ntiles, 0);
-  // stage buffers during the loop; the epilogue reuses the array for its factorisation rows
-  const size_t lds = std::max(2 * (size_t)CH * RD,
-                              (size_t)groups * EpilogueShape<TW, TS>::SPP * EpilogueShape<TW, TS>::stride(logical_tiles(b->ntiles))) * sizeof(double);
-  if (lds > 160 * 1024) return fail(GPDLA_ERR_UNSUPPORTED, "multi sweep needs %zu B of LDS", lds);
-  return dispatch_nd(args.mode, [&](auto nd) {
-    return launch_sweep_kernel(c, &k_sweep_multi<NTW, TS, CH, TW, decltype(nd)::value>, 512, lds, groups * kSamplesPerWave, args.nq_sub, args);
-  });
-}
-
+// The multi-DLA passes on pre-expanded records: k_sweep_multi (k <= 20) or k_sweep_multi_split
+// (20 < k <= 40: the roles of a sample group share the gathers and weights)
 template <class Args>
 int legacy_sweep_multi(gpdla_context *c, gpdla_batch *b, const Args &args) {
-  GPDLA_LEGACY_SWITCH(split_legacy, "GPDLA_SPLIT_LEGACY");
-  if (b->k > 20 && !split_legacy) {
+  if (b->k > 20) {
     const size_t lds = std::max(sweep_multi_split_lds_doubles(), kSplitEpilogueDoubles) * sizeof(double);
     if (lds > 160 * 1024) return fail(GPDLA_ERR_UNSUPPORTED, "multi split sweep needs %zu B of LDS", lds);
     return dispatch_nd(args.mode, [&](auto nd) {
       return launch_sweep_kernel(c, &k_sweep_multi_split<decltype(nd)::value>, 512, lds, 2 * kSamplesPerWave, args.nq_sub, args);
     });
   }
-  return b->k <= 20 ? legacy_sweep_multi_expanded<14, 1, 8, 13>(c, b, args) : legacy_sweep_multi_expanded<14, 4, 1, 52>(c, b, args);
-}
-
-void legacy_train_splits(TrainDims *d) {
-  static const char *splits = std::getenv("GPDLA_TRAIN_SPLITS");
-  int h = 0, h2 = 0, gs = 0;
-  if (splits && std::sscanf(splits, "%d,%d,%d", &h, &h2, &gs) == 3 && h > 0 && h2 > 0 && gs > 0 && h <= 64 &&
-      h2 <= 256 && gs <= 256) {
-    d->H = h;
-    d->H2 = h2;
-    d->GS = gs;
-  }
-}
-
-template <int KMAX>
-bool legacy_train_factor(dim3 grid, hipStream_t st, const TrainFactorArgs &fa) {
-  GPDLA_LEGACY_SWITCH(factor_lds, "GPDLA_TRAIN_FACTOR_LDS");
-  if (factor_lds) hipLaunchKernelGGL(k_train_factor<KMAX>, grid, dim3(256), 0, st, fa);
-  return factor_lds;
+  constexpr int NTW = 14, CH = 8, TW = 13;
+  const size_t RD = (size_t)record_doubles(b->ntiles, 0);
+  // stage buffers during the loop; the epilogue reuses the array for its factorisation rows
+  const size_t lds = std::max(2 * (size_t)CH * RD,
+                              (size_t)kSweepWaves * EpilogueShape<TW, 1>::SPP * EpilogueShape<TW, 1>::stride(logical_tiles(b->ntiles))) * sizeof(double);
+  if (lds > 160 * 1024) return fail(GPDLA_ERR_UNSUPPORTED, "multi sweep needs %zu B of LDS", lds);
+  return dispatch_nd(args.mode, [&](auto nd) {
+    return launch_sweep_kernel(c, &k_sweep_multi<NTW, 1, CH, TW, decltype(nd)::value>, 512, lds, kSweepWaves * kSamplesPerWave, args.nq_sub, args);
+  });
 }
 
 // GPDLA_TRAIN_LEGACY (diagnostic cross-check): one block per slot of quasars, each slot adding into
@@ -147,7 +115,7 @@ int legacy_objective_round1(gpdla_training *t, const double *x, int k, double *f
 }
 
 bool legacy_training_objective(gpdla_training *t, const double *x, int k, double *f, double *g, int *rc) {
-  GPDLA_LEGACY_SWITCH(round1, "GPDLA_TRAIN_LEGACY");
+  static const bool round1 = std::getenv("GPDLA_TRAIN_LEGACY") != nullptr;
   if (round1) *rc = legacy_objective_round1(t, x, k, f, g);
   return round1;
 }
@@ -163,9 +131,6 @@ template <class Args>
 int legacy_sweep_multi(gpdla_context *, gpdla_batch *, const Args &) {
   return fail(GPDLA_ERR_UNSUPPORTED, "the multi-DLA sweeps on pre-expanded records are in libgpdla_legacy.so only");
 }
-void legacy_train_splits(TrainDims *) {}
-template <int KMAX>
-bool legacy_train_factor(dim3, hipStream_t, const TrainFactorArgs &) { return false; }
 bool legacy_training_objective(gpdla_training *, const double *, int, double *, double *, int *) { return false; }
 
 #endif

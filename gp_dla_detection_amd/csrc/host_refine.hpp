@@ -5,7 +5,7 @@
 // refined evidence (k_refined_posteriors).
 #pragma once
 
-static_assert(GPDLA_REFINE_MAX_LEVELS == gpdla::kRefineMaxLevels, "gpdla.h and sweep_kernels.hpp disagree");
+static_assert(GPDLA_REFINE_MAX_LEVELS == gpdla::kRefineMaxLevels, "gpdla.h and sweep_primitives.hpp disagree");
 
 namespace {
 
@@ -73,7 +73,7 @@ int refine_reserve(gpdla_batch *b, int64_t Sr) {
 }
 
 // The boxed sweep of `count` quasars (rows) at one level; the launch shapes of launch_sweep
-int launch_boxed_sweep(gpdla_context *c, gpdla_batch *b, RecordClass cls, int64_t count, const BoxedSweepArgs &args) {
+int launch_boxed_sweep(gpdla_context *c, gpdla_batch *, RecordClass cls, int64_t count, const BoxedSweepArgs &args) {
   const bool three = args.num_lines == 3;
   if (cls == kRecSlim20)
     return launch_sweep_kernel(c, three ? &k_sweep_slim_boxed<3> : &k_sweep_slim_boxed<0>, kSlimWaves * 64,

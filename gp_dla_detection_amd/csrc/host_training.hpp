@@ -12,7 +12,7 @@ struct gpdla_training {
   double *d_x = nullptr, *d_g = nullptr, *d_omega2 = nullptr, *d_f = nullptr;
   int32_t *d_flag = nullptr;
   int64_t x_capacity = 0;
-  // one-block-per-slot path (k > 20, GPDLA_TRAIN_LEGACY): per-slot copies of [g | f], summed in order
+  // one-block-per-slot path (GPDLA_TRAIN_LEGACY of libgpdla_legacy.so): per-slot copies of [g | f], summed in order
   double *d_slots = nullptr;
   int64_t slots_capacity = 0;
   // workspace of the matrix-core path (training_mfma_kernels.hpp): its sizes do not depend on k.
@@ -136,13 +136,8 @@ int gpdla_training_create(int device_id, int64_t nq, int64_t G, const double *fl
 
 namespace {
 
-// What libgpdla_legacy.so adds to training (host_legacy.hpp; the product library's versions do nothing
-// and return false): other splits for train_dims, k_train_factor<40> in place of k_train_factor16<40>
-// (true: launched; a template for the reason given in host_sweep.hpp), the round-1 objective in place
-// of the matrix-core one (true: *rc is its result).
-void legacy_train_splits(TrainDims *d);
-template <int KMAX>
-bool legacy_train_factor(dim3 grid, hipStream_t st, const TrainFactorArgs &fa);
+// What libgpdla_legacy.so adds to training (host_legacy.hpp; the product library's version does nothing and
+// returns false): the round-1 objective in place of the matrix-core one (true: *rc is its result).
 bool legacy_training_objective(gpdla_training *t, const double *x, int k, double *f, double *g, int *rc);
 
 TrainDims train_dims(const gpdla_training *t, int k) {
@@ -162,12 +157,11 @@ TrainDims train_dims(const gpdla_training *t, int k) {
     d.GS = 24 * kTrWidePB;  // k_train_core_wide: ceil(77 / PB) pixel-group blocks x GS / 4 = 468 blocks at PB = 2
     // four tile groups make the contraction grids four times larger, so they need fewer splits to fill
     // the chip -- and every split is a copy of the partial sums through HBM (246 MB at H = 6, 242 MB at
-    // H2 = 24): 79 x 4 x 3 = 948 and 20 x 4 x 12 = 960 blocks.  Measured (tools/train_knobs.sh 40, two
-    // rounds): 6,24 -> 1.122 ms; 3,24 -> 1.075; 6,12 -> 1.077; 3,12 -> 1.03; 3,8 / 3,6 the same; 2,x worse.
+    // H2 = 24): 79 x 4 x 3 = 948 and 20 x 4 x 12 = 960 blocks.  Measured at k = 40, two rounds (H,H2):
+    // 6,24 -> 1.122 ms; 3,24 -> 1.075; 6,12 -> 1.077; 3,12 -> 1.03; 3,8 / 3,6 the same; 2,x worse.
     d.H = 3;
     d.H2 = 12;
   }
-  legacy_train_splits(&d);
   d.H = (int32_t)std::max<int64_t>(d.H, (d.PG + kTrBuildMaxChunks - 1) / kTrBuildMaxChunks);  // a split's omega2 table fits its LDS
   d.GS = (d.GS + 3) / 4 * 4;  // k_train_core_wide: four splits per block
   return d;
@@ -223,8 +217,7 @@ int training_enqueue_mfma(gpdla_training *t, int k, hipStream_t st) {
   // k <= 40: the per-quasar algebra in registers (k_train_factor16); k <= 20 keeps the round-3 kernel
   const dim3 factor_grid((unsigned)((d.NQ16 * 16 + TrF<KMAX>::FQ - 1) / TrF<KMAX>::FQ));
   if constexpr (KMAX == 40) {
-    if (!legacy_train_factor<KMAX>(factor_grid, st, fa))
-      hipLaunchKernelGGL(k_train_factor16<KMAX>, factor_grid, dim3(kTrF16Threads), 0, st, fa);
+    hipLaunchKernelGGL(k_train_factor16<KMAX>, factor_grid, dim3(kTrF16Threads), 0, st, fa);
   } else {
     hipLaunchKernelGGL(k_train_factor<KMAX>, factor_grid, dim3(256), 0, st, fa);
   }

@@ -40,7 +40,7 @@ constexpr int kLearnStage = 4096;    // rest wavelengths of one spectrum staged 
 // Line wavelengths: set_parameters_multi.m:77 holds all_transition_wavelengths in cm, and
 // learn_qso_model_meanflux.m:67 and :113 combine them with Angstrom quantities.  Read literally,
 // every line's 1 + z would be ~3e8 and every flux would be divided by exp(-huge) = 0; as the sweep
-// does for the same mixed-unit code of the multi-DLA driver (sweep_kernels.hpp, wavelength_cm *
+// does for the same mixed-unit code of the multi-DLA driver (prepare_kernels.hpp, wavelength_cm *
 // 1e8), the host passes the table in Angstrom (line_wl) and tau0_j = prev_tau_0 f_j / f_lya *
 // lambda_j / lambda_lya computed from it (line_tau0).
 // ------------------------------------------------------------------------------------------

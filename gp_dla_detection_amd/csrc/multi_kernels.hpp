@@ -6,10 +6,12 @@
 // sample index alone, so the 2 S distinct profiles of a quasar (S DLA + S sub-DLA column densities,
 // multi :365-368) are computed ONCE (k_profiles) into HBM -- 288 GB holds them for hundreds of
 // quasars at a time -- and the sweeps of the 1 + max_dlas models gather and multiply them
-// (k_sweep_multi), feeding the same MFMA contraction and Cholesky epilogue as the single-DLA sweep.
+// (k_sweep_multi_slim, k_sweep_split_slim), feeding the same MFMA contraction and Cholesky epilogue as the
+// single-DLA sweep.
 //
 //   k_profiles        voigt.c:278-299 for every (quasar, DLA|LLS, sample)
-//   k_sweep_multi     multi :340-381   (the parfor body)
+//   SweepMultiArgs    multi :340-381   (the parfor body: sweep_multi_slim_kernel.hpp, sweep_split_slim_kernel.hpp;
+//                                      on pre-expanded records, superseded_kernels.hpp)
 //   k_multi_evidence  multi :386-445   separation mask, nanmax/nanmean evidence, Occam terms, MAP
 //   k_multi_resample  multi :467-472   weighted resampling (documented counter-based RNG; the
 //                                      reference uses MATLAB's rng('default') + randsample)
@@ -79,7 +81,7 @@ __global__ __launch_bounds__(kProfWaves * 64) void k_profiles(ProfilesArgs a) {
   }
   const double cs = c_light * inv_s;
   const double inv_opz = 1.0 / (1 + z_dla);  // (run-time line counts: wing_sum_runtime)
-  // (pre-scaled exp, sweep_kernels.hpp)
+  // (pre-scaled exp, voigt_tiers.hpp)
   const double nscale_a = -a.nhi_samples[i] * g_lines.inv_sqrt2pi_sigma * kInvSqrtPi * kExpScale;
   const double nscale_b = -a.lls_nhi_samples[i] * g_lines.inv_sqrt2pi_sigma * kInvSqrtPi * kExpScale;
   const double *lam = a.lam_pad + m.lam_off;
@@ -154,11 +156,6 @@ __global__ __launch_bounds__(kProfWaves * 64) void k_profiles(ProfilesArgs a) {
   }
 }
 
-// ------------------------------------------------------------------------------------------
-// k_sweep_multi: the parfor body of multi :340-381 for one model.
-// mode 0: LLS profiles (multi :365-380); mode nd >= 1: product of nd DLA profiles.
-// Slot S of the mode-1 pass is the null model (multi :296-298).
-// ------------------------------------------------------------------------------------------
 struct SweepMultiArgs {
   const QuasarMeta *meta;
   const double *records;
@@ -173,427 +170,6 @@ struct SweepMultiArgs {
   double *sample_ll_lls;       // [nq][S]
   double *ll_no_dla;           // [nq]
 };
-
-// ND: number of profiles a sample multiplies (1 for the LLS model and the one-DLA model), known at
-// compile time so that the ND gathers of a K-step are issued back to back ahead of the MFMA burst
-// (with a run-time count each gather sat behind a branch and was waited for before the next).
-template <int NTW, int TS, int kChunkSteps, int TW, int ND>
-__global__ __launch_bounds__(512) void k_sweep_multi(SweepMultiArgs a) {
-  extern __shared__ double smem[];
-  constexpr int GROUPS = kSweepWaves / TS;
-  constexpr int NT = NTW * TS;
-  constexpr int RD = NT * 64 + record_extras(NT);
-  constexpr bool kCompact = tiles_compact(NT);
-  const int64_t xj = blockIdx.x >> 3;
-  const int64_t ql = 8 * (xj / a.blocks_per_quasar) + (blockIdx.x & 7);
-  const int bq = (int)(xj % a.blocks_per_quasar);
-  if (ql >= a.nq_sub) return;
-  const int64_t q = a.q0 + ql;
-  const QuasarMeta m = a.meta[q];
-  if (m.status != 0 || a.alive[q] == 0) return;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int group = wave / TS, role = wave % TS;
-  const int s = lane & 15, jj = lane >> 4;
-  double *stage = smem;  // [2][kChunkSteps][RD]
-
-  const int64_t slot0 = (int64_t)bq * (GROUPS * kSamplesPerWave) + group * kSamplesPerWave;
-  const int64_t slot = slot0 + s;
-  const bool is_sample = slot < a.S;
-  const bool is_null = !is_sample;
-  const int64_t i = is_sample ? slot : 0;
-  constexpr int nd = ND;  // a.mode == 0 ? 1 : a.mode
-  // rows of the profile table this lane multiplies (multi :342-351)
-  // An index outside [1, S] (0 = "never drawn": the rows the reference leaves zero after its early
-  // exit, multi :116, :460-464) is never followed: the sample's likelihood becomes NaN.
-  const double *rows[4];
-  rows[0] = a.prof + ((ql * 2 + (a.mode == 0 ? 1 : 0)) * a.S + i) * a.stride;
-  int chain_ok = 1;
-#pragma unroll
-  for (int j = 1; j < 4; ++j) {
-    int64_t kk = i;
-    if (j < nd) {
-      kk = (int64_t)a.base_inds[((int64_t)q * (a.max_dlas - 1) + (j - 1)) * a.S + i] - 1;
-      if (kk < 0 || kk >= a.S) {
-        chain_ok = 0;
-        kk = i;
-      }
-    }
-    rows[j] = a.prof + ((ql * 2) * a.S + kk) * a.stride;
-  }
-  const double *rec_base = a.records + m.rec_off * (int64_t)RD;
-  const int nrec = m.steps + 1;
-  const int nchunks = (nrec + kChunkSteps - 1) / kChunkSteps;
-  static_assert((kChunkSteps * RD) % 128 == 0, "a chunk is a whole number of KiB");
-  const int wave_s = __builtin_amdgcn_readfirstlane(wave);
-  const uint32_t stage_lds = __builtin_amdgcn_readfirstlane(lds_address(stage));
-  auto issue_chunk = [&](int c) {  // (see glds_chunk in sweep_kernels.hpp)
-    glds_chunk<kChunkSteps * RD / 128, kSweepWaves>(rec_base + (size_t)c * kChunkSteps * RD,
-                                                    stage_lds + (uint32_t)(c & 1) * (uint32_t)(kChunkSteps * RD * 8), wave_s, lane);
-  };
-  issue_chunk(0);
-  d4 acc[NTW];
-#pragma unroll
-  for (int c = 0; c < NTW; ++c) acc[c] = d4{0.0, 0.0, 0.0, 0.0};
-  double quad_sum = 0.0, dprod = 1.0;
-  double xw[kXW] = {0.0, 0.0}, xu[kXU] = {0.0, 0.0, 0.0, 0.0};  // compact class: columns kept off the MFMA
-  int dexp = 0;
-  const int tile0 = role * NTW;
-
-  // absorption of pixel p for this lane's sample: product of the gathered profiles.  The gather
-  // reads HBM (the profile table is 243 MB per quasar) and a K-step of this kernel is short -- 14
-  // MFMAs and ~35 vector instructions, ~1 us per wave -- so the values are requested kAhead K-steps
-  // before they are used: with a single step of lookahead every K-step waited for its own gather
-  // (PMC, round 2: the matrix pipe busy 65 % of the time with 16 % of it idle on both waves).
-  constexpr int kAhead = 3;
-  double raw0_product;
-  auto gather = [&](int p, double (&r)[ND]) {
-#pragma unroll
-    for (int j = 0; j < ND; ++j) r[j] = rows[j][p];
-  };
-  auto product = [&](const double (&r)[ND]) -> double {
-    double v = r[0];
-#pragma unroll
-    for (int j = 1; j < ND; ++j) v *= r[j];
-    return is_null ? 1.0 : v;
-  };
-  const int p_last = 4 * m.steps + jj;  // rows are padded to 4*(steps+1) entries
-  double raw[kAhead][ND];               // raw[i]: gathered for K-step (t + 1 + i) mod kAhead at use
-  {
-    double r0[ND];
-    gather(jj, r0);
-#pragma unroll
-    for (int i = 0; i < kAhead; ++i) gather(min(4 * (1 + i) + jj, p_last), raw[i]);
-    raw0_product = product(r0);
-  }
-  double a_next = raw0_product;  // step 0
-  glds_wait();
-  __syncthreads();
-  if (nchunks > 1) issue_chunk(1);
-
-  double w_cur, u_cur, bop[NTW];
-  double xpr[kXW] = {0.0, 0.0}, upr[kXU] = {0.0, 0.0, 0.0, 0.0};  // compact class: this step's VALU columns
-#define GPDLA_MPREP(rec, absorb_in)                                                       \
-  {                                                                                       \
-    const double *extra_ = (rec) + NT * 64;                                               \
-    const double *mine_ = extra_ + extras_row(NT, 1) * jj;                                \
-    if (kCompact) {                                                                       \
-      _Pragma("unroll") for (int x = 0; x < kXW; ++x) xpr[x] = mine_[kExtrasXW + x];      \
-      _Pragma("unroll") for (int x = 0; x < kXU; ++x) upr[x] = mine_[kExtrasXU + x];      \
-    }                                                                                     \
-    const double absorb_ = (absorb_in);                                                   \
-    const double py_ = mine_[0], pmu_ = mine_[1], pom_ = mine_[2], pnu_ = mine_[3];       \
-    const double r_ = fma(-absorb_, pmu_, py_);      /* multi :355 */                     \
-    const double a2_ = absorb_ * absorb_;                                                 \
-    const double d_ = fma(pom_, a2_, pnu_);          /* multi :357, :361 */               \
-    const double inv_d_ = fast_rcp(d_);                                                   \
-    w_cur = a2_ * inv_d_;                                                                 \
-    u_cur = absorb_ * r_ * inv_d_;                                                        \
-    quad_sum = fma(r_ * r_, inv_d_, quad_sum);                                            \
-    dprod *= d_;                                                                          \
-    dexp += __builtin_amdgcn_frexp_exp(dprod);                                            \
-    dprod = __builtin_amdgcn_frexp_mant(dprod);                                           \
-    const double *bt_ = (rec) + (size_t)tile0 * 64 + lane;                                \
-    _Pragma("unroll") for (int cc = 0; cc < NTW; ++cc) bop[cc] = bt_[(size_t)cc * 64];    \
-  }
-  GPDLA_MPREP(stage, a_next)
-  // one K-step; I = t mod kAhead selects the gather slot at compile time (the loop is unrolled
-  // kAhead times so that the slots rotate without register moves)
-  auto kstep = [&](auto I, int t) {
-    constexpr int i = decltype(I)::value;
-    const int rn = t + 1;
-    const int cn = rn / kChunkSteps;
-    if (rn % kChunkSteps == 0) {
-      glds_wait();  // chunk cn (issued one chunk ago) has landed
-      __syncthreads();
-      if (cn + 1 < nchunks) issue_chunk(cn + 1);
-    }
-    const double *rec = stage + ((size_t)(cn & 1) * kChunkSteps + (rn % kChunkSteps)) * RD;
-    a_next = product(raw[i]);                                    // K-step rn, requested kAhead steps ago
-    gather(min(4 * (rn + kAhead) + jj, p_last), raw[i]);         // K-step rn + kAhead
-    const double wa = w_cur, ua = u_cur;
-#pragma unroll
-    for (int cc = 0; cc < NTW; ++cc)
-    {
-      constexpr int kTail = TS == 1 ? 0 : NT - TW;
-      const double a_tail = role == TS - 1 ? ua : wa;
-      const double aop = TS == 1 ? (cc < TW ? wa : ua) : (cc < NTW - kTail ? wa : a_tail);
-      acc[cc] = __builtin_amdgcn_mfma_f64_16x16x4f64(aop, bop[cc], acc[cc], 0, 0, 0);
-    }
-    if (kCompact) {
-#pragma unroll
-      for (int x = 0; x < kXW; ++x) xw[x] = fma(wa, xpr[x], xw[x]);
-#pragma unroll
-      for (int x = 0; x < kXU; ++x) xu[x] = fma(ua, upr[x], xu[x]);
-    }
-    GPDLA_MPREP(rec, a_next)
-  };
-  static_assert(kAhead == 3, "the loop below is unrolled three times");
-  for (int t = 0; t < m.steps; t += kAhead) {
-    kstep(std::integral_constant<int, 0>{}, t);
-    if (t + 1 < m.steps) kstep(std::integral_constant<int, 1>{}, t + 1);
-    if (t + 2 < m.steps) kstep(std::integral_constant<int, 2>{}, t + 2);
-  }
-#undef GPDLA_MPREP
-  __syncthreads();
-  double logd_sum = log(dprod) + (double)dexp * 0.6931471805599453;
-  quad_sum += __shfl_xor(quad_sum, 16);
-  quad_sum += __shfl_xor(quad_sum, 32);
-  logd_sum += __shfl_xor(logd_sum, 16);
-  logd_sum += __shfl_xor(logd_sum, 32);
-  if (kCompact) {
-#pragma unroll
-    for (int x = 0; x < kXW; ++x) {
-      xw[x] += __shfl_xor(xw[x], 16);
-      xw[x] += __shfl_xor(xw[x], 32);
-    }
-#pragma unroll
-    for (int x = 0; x < kXU; ++x) {
-      xu[x] += __shfl_xor(xu[x], 16);
-      xu[x] += __shfl_xor(xu[x], 32);
-    }
-  }
-
-  using ES = EpilogueShape<TW, TS>;
-  double *Eg = stage + (size_t)group * ES::SPP * ES::stride(logical_tiles(NT));
-#pragma unroll
-  for (int p = 0; p < ES::PASSES; ++p) {
-    int sigma;
-    bool writer;
-    const double ll = factor_pass<double, NTW, TS, TW>(acc, xw, xu, p, Eg, lane, role, tile0, a.k, quad_sum,
-                                                       logd_sum, m.n_kept, &sigma, &writer);
-    const int64_t slot_s = slot0 + sigma;
-    const bool ok_s = __shfl(chain_ok, sigma) != 0;  // lane sigma (jj = 0) holds sample sigma's flag
-    if (writer) {
-      if (slot_s < a.S) {
-        if (a.mode == 0) a.sample_ll_lls[q * a.S + slot_s] = ll + m.ll_bias - a.log_S;     // multi :376-378
-        else a.sample_ll_dla[(q * a.max_dlas + (a.mode - 1)) * a.S + slot_s] = ok_s ? ll + m.ll_bias - a.log_S : NAN;  // :359-361
-      } else if (slot_s == a.S && a.mode == 1) {
-        a.ll_no_dla[q] = ll + m.ll_bias;                                                    // multi :296-298
-      }
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------------
-// k_sweep_multi_split: k_sweep_multi for 20 < k <= 40 with the k_sweep_split pipeline
-// (sweep_split_kernel.hpp).  56 accumulator tiles do not fit one wave, so four waves ("roles") share
-// a group of 16 samples and take 14 tiles each.  In k_sweep_multi<14, 4, ...> every one of the four
-// gathered the group's profile values and formed the weights itself -- the HBM gathers of the
-// profile table four times over -- and the block met at a barrier every K-step.  Here role r
-// gathers and weighs only the K-steps t = r (mod 4), into a double-buffered (w, u) table in LDS,
-// and every role reads (w, u) of each K-step for its 14 MFMAs; one loop iteration is 4 K-steps (two
-// 2-step record chunks).  The profile values of step 4 (it + 2) + r are requested at the top of
-// iteration it and multiplied at the end of iteration it + 1: two iterations (8 K-steps) of latency
-// hiding for the HBM gather.
-// ------------------------------------------------------------------------------------------
-__host__ __device__ constexpr size_t sweep_multi_split_lds_doubles() {
-  constexpr int RD = 56 * 64 + record_extras(56);
-  return 2 * 2 * (size_t)RD + 2 * 2 * 2 * 4 * 64 + 2 * 4 * 2 * 16;  // stage | (w, u) | per-role partial sums
-}
-
-template <int ND>
-__global__ __launch_bounds__(512) void k_sweep_multi_split(SweepMultiArgs a) {
-  extern __shared__ double smem[];
-  constexpr int WAVES = 8, TS = 4, NTW = 14, NT = 56, TW = 52, CH = 2;
-  constexpr int RD = NT * 64 + record_extras(NT);
-  const int64_t xj = blockIdx.x >> 3;
-  const int64_t ql = 8 * (xj / a.blocks_per_quasar) + (blockIdx.x & 7);
-  const int bq = (int)(xj % a.blocks_per_quasar);
-  if (ql >= a.nq_sub) return;
-  const int64_t q = a.q0 + ql;
-  const QuasarMeta m = a.meta[q];
-  if (m.status != 0 || a.alive[q] == 0) return;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int group = wave >> 2, role = wave & 3;
-  const int s = lane & 15, jj = lane >> 4;
-
-  double *stage = smem;                                    // [2][CH][RD]
-  double *wu = stage + (size_t)2 * CH * RD;                // [2 parity][2 groups][2][4 steps][64]
-  double *red = wu + 2 * 2 * 2 * 4 * 64;                   // [2 groups][4 roles][2][16]
-
-  const int64_t slot0 = (int64_t)bq * (2 * kSamplesPerWave) + group * kSamplesPerWave;
-  const int64_t slot = slot0 + s;
-  const bool is_sample = slot < a.S;
-  const bool is_null = !is_sample;
-  const int64_t i = is_sample ? slot : 0;
-  // rows of the profile table this lane multiplies (multi :342-351); see k_sweep_multi
-  const double *rows[4];
-  rows[0] = a.prof + ((ql * 2 + (a.mode == 0 ? 1 : 0)) * a.S + i) * a.stride;
-  int chain_ok = 1;
-#pragma unroll
-  for (int j = 1; j < 4; ++j) {
-    int64_t kk = i;
-    if (j < ND) {
-      kk = (int64_t)a.base_inds[((int64_t)q * (a.max_dlas - 1) + (j - 1)) * a.S + i] - 1;
-      if (kk < 0 || kk >= a.S) {
-        chain_ok = 0;
-        kk = i;
-      }
-    }
-    rows[j] = a.prof + ((ql * 2) * a.S + kk) * a.stride;
-  }
-  const PixelRow *pix = a.pix + m.pix_off;
-  const double *rec_base = a.records + m.rec_off * (int64_t)RD;
-  const int nchunks = (m.steps + CH - 1) / CH;
-  const int niter = (m.steps + 3) / 4;
-  static_assert((CH * RD) % 128 == 0, "a chunk is a whole number of KiB");
-  const int wave_s = __builtin_amdgcn_readfirstlane(wave);
-  const uint32_t stage_lds = __builtin_amdgcn_readfirstlane(lds_address(stage));
-  auto issue_chunk = [&](int c) {
-    glds_chunk<CH * RD / 128, WAVES>(rec_base + (size_t)c * CH * RD, stage_lds + (uint32_t)(c & 1) * (uint32_t)(CH * RD * 8),
-                                     wave_s, lane);
-  };
-  issue_chunk(0);
-
-  const int p_last = 4 * m.steps + jj;  // rows are padded to 4 (steps + 1) entries
-  auto gather = [&](int t, double (&r)[ND]) {
-    const int p = min(4 * t + jj, p_last);
-#pragma unroll
-    for (int j = 0; j < ND; ++j) r[j] = rows[j][p];
-  };
-  auto pix_of = [&](int t) -> PixelRow { return pix[4 * min(t, m.steps) + jj]; };  // row `steps` is neutral
-  double quad_sum = 0.0, dprod = 1.0;
-  int dexp = 0;
-  auto weights_of = [&](int t, const PixelRow &px, const double (&r)[ND], double *w_out, double *u_out) {
-    double absorb = r[0];
-#pragma unroll
-    for (int j = 1; j < ND; ++j) absorb *= r[j];
-    if (is_null) absorb = 1.0;
-    const double rr = fma(-absorb, px.mu, px.y);   // multi :355
-    const double a2 = absorb * absorb;
-    const double d = fma(px.omega2, a2, px.nu);    // multi :357, :361
-    const double inv_d = fast_rcp(d);
-    *w_out = a2 * inv_d;
-    *u_out = absorb * rr * inv_d;
-    if (t < m.steps) {  // (steps beyond the last are never consumed; keep them out of the sums)
-      quad_sum = fma(rr * rr, inv_d, quad_sum);
-      dprod *= d;
-      dexp += __builtin_amdgcn_frexp_exp(dprod);
-      dprod = __builtin_amdgcn_frexp_mant(dprod);
-    }
-  };
-  auto wu_slot = [&](int par, int which, int step) -> double * {
-    return wu + ((((size_t)par * 2 + group) * 2 + which) * 4 + step) * 64 + lane;
-  };
-
-  // prime: (w, u) of K-steps 0..3 (role r: step r); profile values of step 4 + r in flight
-  double g_cur[ND], g_next[ND];
-  {
-    double g0[ND], w0, u0;
-    gather(role, g0);
-    gather(4 + role, g_cur);
-    weights_of(role, pix_of(role), g0, &w0, &u0);
-    *wu_slot(0, 0, role) = w0;
-    *wu_slot(0, 1, role) = u0;
-  }
-  d4 acc[NTW];
-#pragma unroll
-  for (int c = 0; c < NTW; ++c) acc[c] = d4{0.0, 0.0, 0.0, 0.0};
-  const int tile0 = role * NTW;
-  constexpr int kTail = NT - TW;  // the last role's last 4 tiles take u
-
-  glds_wait();  // chunk 0 landed
-  __syncthreads();
-
-  for (int it = 0; it < niter; ++it) {
-    const int par = it & 1;
-    const int t_w = 4 * (it + 1) + role;
-    PixelRow px_w;
-#pragma unroll
-    for (int hc = 0; hc < 2; ++hc) {
-      const int c = 2 * it + hc;
-      if (c < nchunks) {  // block-uniform
-        __builtin_amdgcn_s_waitcnt(0x0F70);  // (see k_sweep: free here, keeps compiler waits out of the K-steps)
-        if (c + 1 < nchunks) issue_chunk(c + 1);
-        if (hc == 0) {
-          px_w = pix_of(t_w);
-          gather(t_w + 4, g_next);  // for the W stage of the NEXT iteration
-        }
-        const double *buf = stage + (size_t)hc * CH * RD;  // chunk c lives in buffer c & 1 = hc
-#pragma unroll
-        for (int tt = 0; tt < CH; ++tt) {
-          const int rn = c * CH + tt;
-          if (rn < m.steps) {
-            const int st = 2 * hc + tt;  // step within the iteration
-            const double w = *wu_slot(par, 0, st), u = *wu_slot(par, 1, st);
-            const double *bt = buf + (size_t)tt * RD + (size_t)tile0 * 64 + lane;
-            double bop[NTW];
-#pragma unroll
-            for (int cc = 0; cc < NTW; ++cc) bop[cc] = bt[(size_t)cc * 64];
-            const double a_tail = role == TS - 1 ? u : w;
-#pragma unroll
-            for (int cc = 0; cc < NTW; ++cc)
-              acc[cc] = __builtin_amdgcn_mfma_f64_16x16x4f64(cc < NTW - kTail ? w : a_tail, bop[cc], acc[cc], 0, 0, 0);
-          }
-        }
-        if (hc == 1) {  // stage W of this role for the next iteration
-          double w1, u1;
-          weights_of(t_w, px_w, g_cur, &w1, &u1);
-          *wu_slot(par ^ 1, 0, role) = w1;
-          *wu_slot(par ^ 1, 1, role) = u1;
-#pragma unroll
-          for (int j = 0; j < ND; ++j) g_cur[j] = g_next[j];
-        }
-        glds_wait();
-        __syncthreads();
-      } else if (hc == 1) {
-        __syncthreads();  // odd number of chunks: keep the barrier structure uniform
-      }
-    }
-  }
-
-  double logd_sum = log(dprod) + (double)dexp * 0.6931471805599453;
-  quad_sum += __shfl_xor(quad_sum, 16);
-  quad_sum += __shfl_xor(quad_sum, 32);
-  logd_sum += __shfl_xor(logd_sum, 16);
-  logd_sum += __shfl_xor(logd_sum, 32);
-  if (jj == 0) {
-    red[((group * 4 + role) * 2 + 0) * 16 + s] = quad_sum;
-    red[((group * 4 + role) * 2 + 1) * 16 + s] = logd_sum;
-  }
-  __syncthreads();
-  quad_sum = 0.0;
-  logd_sum = 0.0;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    quad_sum += red[((group * 4 + r) * 2 + 0) * 16 + s];
-    logd_sum += red[((group * 4 + r) * 2 + 1) * 16 + s];
-  }
-  __syncthreads();
-
-  // epilogue: all four roles factor, 32 lanes per sample (as k_sweep_split)
-  using ES = EpilogueShape<TW, TS>;
-  constexpr int ncols = ES::stride(logical_tiles(NT));
-  constexpr int voff = TW * 16;
-  double *Eg = stage + (size_t)group * ES::SPP * ncols;
-#pragma unroll
-  for (int p = 0; p < 2; ++p) {
-    __syncthreads();
-    double *e = Eg + (size_t)(jj * 2) * ncols;
-#pragma unroll
-    for (int cc = 0; cc < NTW; ++cc) {
-      const int tile = tile0 + cc;
-      const int col0 = tile < TW ? tile * 16 : voff + (tile - TW) * 16;
-      e[col0 + s] = acc[cc][2 * p];
-      e[ncols + col0 + s] = acc[cc][2 * p + 1];
-    }
-    __syncthreads();
-    const int rho = 2 * role + (lane >> 5);
-    const int sigma = (rho >> 1) + 4 * (2 * p + (rho & 1));  // Mat<double>::sample_of(jj, reg)
-    const double q_s = __shfl(quad_sum, sigma), ld_s = __shfl(logd_sum, sigma);
-    const bool ok_s = __shfl(chain_ok, sigma) != 0;
-    const double ll = factor_lds<2, 32>(Eg + (size_t)rho * ncols, lane & 31, a.k, voff, q_s, ld_s, m.n_kept);
-    const int64_t slot_s = slot0 + sigma;
-    if ((lane & 31) == 0) {
-      if (slot_s < a.S) {
-        if (a.mode == 0) a.sample_ll_lls[q * a.S + slot_s] = ll + m.ll_bias - a.log_S;     // multi :376-378
-        else a.sample_ll_dla[(q * a.max_dlas + (a.mode - 1)) * a.S + slot_s] = ok_s ? ll + m.ll_bias - a.log_S : NAN;  // :359-361
-      } else if (slot_s == a.S && a.mode == 1) {
-        a.ll_no_dla[q] = ll + m.ll_bias;                                                    // multi :296-298
-      }
-    }
-  }
-}
 
 // ------------------------------------------------------------------------------------------
 // Block-wide helpers (256 threads).

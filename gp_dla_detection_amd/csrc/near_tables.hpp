@@ -6,7 +6,7 @@
 // Why tables: inside |x| < 30 the asymptotic wing formula is not accurate enough and Re w needs the
 // series / trapezoid tiers of faddeeva.hpp (130 / 1200 instructions, divergent).  In the sweep
 // kernel that meant a call with all accumulators live in ~5 % of the K-steps, 8.5 % of the run
-// time (tools/ablate.sh) plus the chunk barrier waiting for whichever wave drew it.  A degree-11
+// time (LABBOOK.md, round 1) plus the chunk barrier waiting for whichever wave drew it.  A degree-11
 // polynomial per interval costs ~35 instructions, inline.
 //
 // Layout: kNearIntervals = 64 intervals of width 1/8 on [0, 8) (Gaussian core), then 48 of width
@@ -158,7 +158,7 @@ inline void near_locate(double ax, int *idx, double *t) {
   }
 }
 
-// Host evaluation of one line's table (the device does the same Horner, sweep_kernels.hpp).
+// Host evaluation of one line's table (the device does the same Horner, voigt_tiers.hpp).
 inline double near_poly_host(const double *line_tab, double ax) {
   int idx;
   double t;

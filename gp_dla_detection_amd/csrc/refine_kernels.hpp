@@ -28,7 +28,7 @@
 
 #include "posterior_kernels.hpp"
 #include "sample_kernels.hpp"
-#include "sweep_kernels.hpp"
+#include "sweep_primitives.hpp"  // kRefineMaxLevels, kRefineBoxStride
 
 #pragma clang fp contract(off)
 

@@ -5,7 +5,7 @@
 // of its own and hands them in: with them formed in here the compiled kernels change (tools/isa_diff.py), with them
 // handed in every kernel compiles to the instructions it had with the text written out.
 #pragma once
-#include "sweep_kernels.hpp"
+#include "voigt_tiers.hpp"
 
 namespace gpdla {
 

@@ -121,8 +121,8 @@ __global__ __launch_bounds__(512) void k_sweep_multi_slim(SweepMultiArgs a) {
 
   // profile values: requested kAhead K-steps before they are multiplied (the gather reads HBM)
   const int p_last = 4 * m.steps + jj;  // rows are padded to 4 (steps + 1) entries
-  // The loads are issued as inline assembly and waited for by hand (MSLIM_EXP_CLOADS: plain C++
-  // loads, for A/B).  With compiler-visible loads every K-step began with s_waitcnt vmcnt(0): the
+  // The loads are issued as inline assembly and waited for by hand.  With compiler-visible loads
+  // every K-step began with s_waitcnt vmcnt(0): the
   // K-steps are separate basic blocks (each is guarded by rn < steps) with untracked LDS-DMA
   // instructions between them, and the compiler's wait-count pass then no longer knows how many of
   // its loads are in flight -- so a gather was waited for ONE K-step after its issue, not four.
@@ -131,21 +131,13 @@ __global__ __launch_bounds__(512) void k_sweep_multi_slim(SweepMultiArgs a) {
   auto gather = [&](int p, double (&r)[ND]) {
 #pragma unroll
     for (int j = 0; j < ND; ++j) {
-#if defined(MSLIM_EXP_NOGATHER)
-      r[j] = 1.0 + 1e-9 * p;  // ablation: no profile loads at all (results wrong by construction)
-#elif defined(MSLIM_EXP_CLOADS)
-      r[j] = rows[j][p];
-#else
       asm volatile("global_load_dwordx2 %0, %1, off" : "=v"(r[j]) : "v"(rows[j] + p));
-#endif
     }
   };
   auto gathered = [&](double (&r)[ND]) {  // the values requested kAhead K-steps ago have arrived
-#if !defined(MSLIM_EXP_CLOADS) && !defined(MSLIM_EXP_NOGATHER)
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"((kAhead - 1) * ND) : "memory");
 #pragma unroll
     for (int j = 0; j < ND; ++j) asm volatile("" : "+v"(r[j]));  // (orders every later use behind the wait)
-#endif
   };
   double raw[kAhead][ND];
 #pragma unroll
@@ -191,11 +183,7 @@ __global__ __launch_bounds__(512) void k_sweep_multi_slim(SweepMultiArgs a) {
       // short chunk followed by another chunk -- on which a gather slot is consumed with fewer than
       // (kAhead - 1) ND younger requests behind it: paths that never execute, but that the static check
       // of the hand-counted waits (tools/check_vmem_hazard.py) cannot tell from real ones.
-#ifdef MSLIM_EXP_GUARD_EACH  // (A/B: the round-4 form, every K-step guarded by itself)
-      if (rn < m.steps)
-#else
       if (rn >= m.steps) goto k_loop_done;
-#endif
       {
         const double *tl = tbuf + (size_t)tt * kSlimStepTiles;
         const double *mine = mine0 + (size_t)tt * kSlimRec;
@@ -204,13 +192,8 @@ __global__ __launch_bounds__(512) void k_sweep_multi_slim(SweepMultiArgs a) {
         const double py = p01.x, pmu = p01.y, pom = p23.x, pnu = p23.y;
         double bop[14];
 #pragma unroll
-#ifdef MSLIM_EXP_NOBOP  // ablation: no fragment reads (results wrong by construction)
-        for (int cc = 0; cc < 14; ++cc) bop[cc] = 1.0 + 1e-9 * (cc + lane);
-        asm volatile("" ::"v"(tl));
-#else
         for (int cc = 0; cc < kSlimTilesW; ++cc) bop[cc] = tl[cc * 64];
         bop[13] = ubuf[(size_t)tt * kSlimRec];  // m[0..15] of the 4 pixels in lane order: the u tile
-#endif
         // absorption of pixel 4 rn + jj: product of the gathered profiles (multi :342-351); then the
         // request for K-step rn + kAhead into the slot just consumed
         gathered(raw[tt % kAhead]);
@@ -255,15 +238,9 @@ __global__ __launch_bounds__(512) void k_sweep_multi_slim(SweepMultiArgs a) {
     // chunk's first four steps: vmcnt counts in order, so "at most (8 - kXS) ND operations outstanding"
     // is exactly "everything up to the landing-zone copy has completed".  (A plain vmcnt(0) here made
     // every wave sit out an HBM gather latency once per chunk.)  In the last chunk nothing was copied.
-#ifndef MSLIM_EXP_WAITALL
     __builtin_amdgcn_s_waitcnt(vmcnt_imm((CH - 4) * ND));
     asm volatile("" ::: "memory");
-#else
-    glds_wait();
-#endif
-#ifndef MSLIM_EXP_NOBAR  // (ablation: no chunk barrier; results wrong by construction)
     __syncthreads();  // ... everyone's tiles of the next chunk are written; this chunk's buffers are free
-#endif
   }
 
 k_loop_done:
@@ -271,14 +248,12 @@ k_loop_done:
   // assembly, so the compiler does not know that their destination registers are still awaited and
   // hands them to the epilogue: a load landing late would overwrite whatever lives there by then.
   // Drain them before anything else reuses a register.
-#if !defined(MSLIM_EXP_CLOADS) && !defined(MSLIM_EXP_NOGATHER)
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll
   for (int t = 0; t < kAhead; ++t) {
 #pragma unroll
     for (int j = 0; j < ND; ++j) asm volatile("" : "+v"(raw[t][j]));  // (the registers stay theirs up to here)
   }
-#endif
   // a short last chunk has jumped over its chunk-end barrier: the epilogue below reuses the LDS the
   // other waves' last K-steps read (all waves of a block sweep the same quasar and leave the same way)
   glds_wait();
@@ -305,15 +280,7 @@ k_loop_done:
   for (int p = 0; p < ES::PASSES; ++p) {
     int sigma;
     bool writer;
-#ifdef MSLIM_EXP_NOEPI  // ablation: no factorisation (results wrong by construction)
-    sigma = (lane >> 4) + 4 * (2 * p + ((lane >> 3) & 1));
-    writer = (lane & 7) == 0;
-    double ll = quad_sum + logd_sum + xw[0] + xu[p];
-#pragma unroll
-    for (int cc = 0; cc < 14; ++cc) ll += acc[cc][2 * p] + acc[cc][2 * p + 1];  // (every accumulator stays live)
-#else
     const double ll = slim_factor_pass(acc, xw, xu, p, Eg, lane, a.k, quad_sum, logd_sum, m.n_kept, &sigma, &writer);
-#endif
     const int64_t slot_s = slot0 + sigma;
     const bool ok_s = __shfl(chain_ok, sigma) != 0;  // lane sigma (jj = 0) holds sample sigma's flag
     if (writer) {

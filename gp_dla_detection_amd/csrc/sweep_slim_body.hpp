@@ -268,9 +268,7 @@ __global__ __launch_bounds__(kSlimWaves * 64, 2) void GPDLA_SWEEP_SLIM_KERNEL(GP
           if (tt > 0) wf = wing3_front(lamP, ms_r[0], ms_r[1], ms_r[2], cs, &near);
           WingLines3 wl;
           total = wing3_back_rcp4(wf, d, &inv_d, &wl);
-#ifndef SLIM_EXP_NONEAR  // (ablation, results wrong by construction: what the accurate tier costs)
           if (__builtin_expect(__any(near), 0)) total = near_lines3(lamP, mult_r[0], mult_r[1], mult_r[2], wl);
-#endif
         } else {
           total = optical_sum(lamP);
           inv_d = fast_rcp(d);

@@ -1,7 +1,7 @@
 // sweep_slim_kernel.hpp -- the fp64 sweep for k <= 20, three Lyman lines (the production case), on
 // SLIM step records: the B-operand tiles vech(m m') are formed inside the sweep.
 //
-// k_sweep (sweep_kernels.hpp) streams, per K-step of 4 pixels, a pre-expanded record of 14 MFMA
+// k_sweep (sweep_expanded_kernel.hpp) streams, per K-step of 4 pixels, a pre-expanded record of 14 MFMA
 // B-operand tiles: 7680 B of HBM per step, 2.9 MB per quasar, 2.9 GB per 1000 quasars -- 18 times
 // the algorithmic traffic, 59 GB for one DR12Q shard.  Only 4 x (20 + 5) of those 960 doubles are
 // information: the 4 interpolated M rows, the 4 pixel rows and the wavelengths.  Here a step record
@@ -47,7 +47,9 @@
 #pragma once
 #include <type_traits>
 
-#include "sweep_kernels.hpp"
+#include "epilogue_factor.hpp"
+#include "prepare_kernels.hpp"  // BuildRecordsArgs
+#include "voigt_tiers.hpp"
 
 namespace gpdla {
 
@@ -201,7 +203,7 @@ __device__ __forceinline__ double wing3_back_rcp4(const WingFront &f, double d, 
   return fma(g_lines.cwing[2], qc, fma(g_lines.cwing[1], qb, g_lines.cwing[0] * qa));
 }
 
-// Epilogue pass of the slim sweep: factor_pass of sweep_kernels.hpp with the spill scattered
+// Epilogue pass of the slim sweep: factor_pass of epilogue_factor.hpp with the spill scattered
 // through the column map (tile, column) -> packed-triangle position.
 __device__ __forceinline__ double slim_factor_pass(const d4 (&acc)[14], const double (&xw)[kXW],
                                                    const double (&xu)[kXU], int p, double *Eg, int lane, int k,

@@ -2,7 +2,7 @@
 // tiles vech(m m') are formed inside the sweep (process_qsos.m:185-199; multi-DLA driver
 // multi_dlas/process_qsos_multiple_dlas_meanflux.m:340-381).
 //
-// k_sweep_split / k_sweep_multi_split (sweep_split_kernel.hpp, multi_kernels.hpp) stream, per K-step of
+// k_sweep_split / k_sweep_multi_split (superseded_kernels.hpp) stream, per K-step of
 // 4 pixels, a pre-expanded record of 56 MFMA B-operand tiles: 29 696 B of HBM per step, of which
 // 4 x 40 doubles are information (r03 PMC: 331 x the algorithmic traffic), in 2-step chunks because
 // two of them fill the LDS -- one block barrier per 2 K-steps and one chunk of copy lead, which the
@@ -30,22 +30,18 @@
 //     The multi-DLA form gathers profile values in place of stage R.
 //
 //   * Epilogue.  The 32 Cholesky factorisations of a block run in registers, one sample per 16-lane
-//     DPP row, four per wave, in one round (factor_rows16, sweep_kernels.hpp); LDS only transposes
+//     DPP row, four per wave, in one round (factor_rows16, epilogue_factor.hpp); LDS only transposes
 //     the accumulators into rows.
 //
 // Results are bit-identical to the pre-expanded kernels': the same products, the same MFMA sequence
-// per column, the same operations in the epilogue.  (S40_EXP_*: ablation and A/B switches of
-// diagnostic builds, tools/ab_build.sh; NO* results are wrong by construction, S40_EXP_PAIRED and
-// S40_EXP_LDSEPI select this round's earlier epilogues.)
+// per column, the same operations in the epilogue.
 #pragma once
 #include <type_traits>
 
-#include "multi_kernels.hpp"
-#include "sweep_split_kernel.hpp"
-
-#ifndef S40_EPI_PW
-#define S40_EPI_PW 4  // columns per panel of factor_paired (-DS40_EXP_PAIRED)
-#endif
+#include "epilogue_factor.hpp"
+#include "multi_kernels.hpp"    // SweepMultiArgs
+#include "prepare_kernels.hpp"  // BuildRecordsArgs
+#include "voigt_tiers.hpp"
 
 namespace gpdla {
 // s_waitcnt immediate for "vmcnt(n), nothing else" (gfx9 encoding: vmcnt in bits 3:0 and 15:14, expcnt
@@ -242,7 +238,7 @@ __global__ __launch_bounds__(512) void k_sweep_split_slim(Args a) {
     if (tid < kExpTab) exp_tab[tid] = exp2((double)tid * (1.0 / kExpTab));
     lam = a.lam_pad + m.lam_off;
     n_pad = m.n_u + 6;
-    nscale64 = -nhi * g_lines.inv_sqrt2pi_sigma * kInvSqrtPi * kExpScale;  // (pre-scaled exp, sweep_kernels.hpp)
+    nscale64 = -nhi * g_lines.inv_sqrt2pi_sigma * kInvSqrtPi * kExpScale;  // (pre-scaled exp, voigt_tiers.hpp)
     inv_s = g_lines.inv_sqrt2_sigma;
 #pragma unroll
     for (int j = 0; j < (LINES > 0 ? LINES : 0); ++j) ms_r[j] = mult_r[j] * inv_s;
@@ -253,7 +249,7 @@ __global__ __launch_bounds__(512) void k_sweep_split_slim(Args a) {
 
   static_assert((CH * kS40Rec) % 128 == 0, "a chunk is a whole number of KiB");
   const uint32_t stage_lds = __builtin_amdgcn_readfirstlane(lds_address(stage));
-  auto issue_chunk = [&](int c) {  // (see glds_chunk in sweep_kernels.hpp)
+  auto issue_chunk = [&](int c) {  // (see glds_chunk in sweep_primitives.hpp)
     glds_chunk<CH * kS40Rec / 128, 8>(rec_base + (size_t)c * CH * kS40Rec,
                                       stage_lds + (uint32_t)(c & 1) * (uint32_t)(CH * kS40Rec * 8), wave_s, lane);
   };
@@ -419,35 +415,20 @@ __global__ __launch_bounds__(512) void k_sweep_split_slim(Args a) {
 #pragma unroll
           for (int cc = 0; cc < NTW; ++cc) {
             opa[cc] = lds_at(pa[cc], off);
-#ifndef S40_EXP_NOMUL
             opb[cc] = lds_at(pb[cc], off);
-#endif
           }
           __builtin_amdgcn_sched_barrier(0);  // all 18 reads requested before the first product waits
 #pragma unroll
           for (int cc = 0; cc < NTW; ++cc) {
-#ifdef S40_EXP_NOMUL
-            bop[cc] = opa[cc];
-#else
             bop[cc] = opa[cc] * opb[cc];
-#endif
           }
-#ifdef S40_EXP_NOMFMA
-#pragma unroll
-          for (int cc = 0; cc < NTW; ++cc) {
-            asm volatile("" ::"v"(bop[cc]));
-            if (cc < 1) acc0[cc][0] += (cc < 3 ? w0 : t0) * bop[cc] + w1 * t1;
-          }
-#else
 #pragma unroll
           for (int cc = 0; cc < NTW; ++cc) {
             acc0[cc] = __builtin_amdgcn_mfma_f64_16x16x4f64(cc < 3 ? w0 : t0, bop[cc], acc0[cc], 0, 0, 0);
             acc1[cc] = __builtin_amdgcn_mfma_f64_16x16x4f64(cc < 3 ? w1 : t1, bop[cc], acc1[cc], 0, 0, 0);
           }
-#endif
         }
       }
-#ifndef S40_EXP_NOWR
       double w1, u1;
       if constexpr (kMulti) {
         weigh(t_w, px_w, absorb_gathered(g_buf[PAR][h]), &w1, &u1);
@@ -457,17 +438,12 @@ __global__ __launch_bounds__(512) void k_sweep_split_slim(Args a) {
       *wu_at(PAR ^ 1, group, 0, 4 * h + role) = w1;
       *wu_at(PAR ^ 1, group, 1, 4 * h + role) = u1;
       if constexpr (!kMulti) my_ring[(4 * t_r + jj) & 127] = raw_of(lam_r);
-#else
-      asm volatile("" ::"v"(px_w.y), "v"(lam_r));
-#endif
     }
     // the chunk copy has landed.  Multi-DLA: the ND gathers of the second half are younger than the
     // copy and stay in flight (the wait for that half's pixel row has already drained everything older)
     __builtin_amdgcn_s_waitcnt(vmcnt_imm(kMulti ? ND : 0));
     asm volatile("" ::: "memory");
-#ifndef S40_EXP_NOBAR
     __syncthreads();
-#endif
   };
   for (int it = 0; it < niter; it += 2) {
     iteration(std::integral_constant<int, 0>{}, it);
@@ -504,7 +480,6 @@ __global__ __launch_bounds__(512) void k_sweep_split_slim(Args a) {
   for (int cc = 0; cc < NTW; ++cc) at[cc] = s40_pos(wave_s * NTW + cc, s);
   double *Eg = stage;
   double *e0 = Eg + (size_t)(jj * 2) * ncols, *e1 = e0 + (size_t)ES::SPP * ncols;
-#if !defined(S40_EXP_LDSEPI) && !defined(S40_EXP_PAIRED) && !defined(S40_EXP_NOEPI)
   // The accumulators pass through LDS in two rounds of 16 samples (32 x 861 doubles do not fit) only
   // to be transposed into rows: after round p the waves of roles 2p, 2p + 1 take four of its samples
   // each -- one per 16-lane row, all k + 1 rows of a sample in registers (load_rows16) -- and once
@@ -554,69 +529,6 @@ __global__ __launch_bounds__(512) void k_sweep_split_slim(Args a) {
       }
     }
   }
-#else  // the round-4 predecessors, for A/B: two passes of 16 samples, 32 lanes per sample, factored next to LDS
-  __syncthreads();  // the loop's buffers are dead
-#pragma unroll
-  for (int cc = 0; cc < NTW; ++cc) {
-    e0[at[cc]] = acc0[cc][0];
-    e0[ncols + at[cc]] = acc0[cc][1];
-    e1[at[cc]] = acc1[cc][0];
-    e1[ncols + at[cc]] = acc1[cc][1];
-  }
-  // ONE copy of the factorisation's straight-line code (4 to 6 thousand instructions).  The first
-  // pass's spill is peeled off above, so only the second pass's result registers (56 of the 112) are
-  // live while the first pass factors; with the 48 row entries per lane factor_paired keeps that
-  // still fits the register file -- nothing of the epilogue may go to scratch: 100 bytes per lane
-  // and block would already double the kernel's HBM traffic
-#ifdef S40_EXP_UNROLLP
-#pragma unroll
-#else
-#pragma nounroll
-#endif
-  for (int p = 0; p < 2; ++p) {
-    if (p == 1) {
-      __syncthreads();  // first pass factored
-#pragma unroll
-      for (int cc = 0; cc < NTW; ++cc) {
-        e0[at[cc]] = acc0[cc][2];
-        e0[ncols + at[cc]] = acc0[cc][3];
-        e1[at[cc]] = acc1[cc][2];
-        e1[ncols + at[cc]] = acc1[cc][3];
-      }
-    }
-    __syncthreads();
-    const int rho = 2 * role + (lane >> 5);
-    const int sigma = (rho >> 1) + 4 * (2 * p + (rho & 1));  // Mat<double>::sample_of(jj, reg)
-    const double q_s = __shfl(quad_sum, sigma), ld_s = __shfl(logd_sum, sigma);
-#ifdef S40_EXP_NOEPI
-    const double ll = q_s + ld_s + Eg[(size_t)(group * ES::SPP + rho) * ncols + (lane & 31)];
-#elif defined(S40_EXP_LDSEPI)
-    const double ll = factor_lds<2, 32>(Eg + (size_t)(group * ES::SPP + rho) * ncols, lane & 31, a.k, voff, q_s, ld_s,
-                                        m.n_kept);
-#else
-    const double ll = factor_paired<40, S40_EPI_PW>(Eg + (size_t)(group * ES::SPP + rho) * ncols, lane & 31, a.k, voff, q_s, ld_s,
-                                        m.n_kept);
-#endif
-    const int64_t slot_s = slot0 + sigma;
-    if constexpr (kMulti) {
-      const bool ok_s = __shfl(chain_ok, sigma) != 0;
-      if ((lane & 31) == 0) {
-        if (slot_s < a.S) {
-          if (a.mode == 0) a.sample_ll_lls[q * a.S + slot_s] = ll + m.ll_bias - a.log_S;     // multi :376-378
-          else a.sample_ll_dla[(q * a.max_dlas + (a.mode - 1)) * a.S + slot_s] = ok_s ? ll + m.ll_bias - a.log_S : NAN;  // :359-361
-        } else if (slot_s == a.S && a.mode == 1) {
-          a.ll_no_dla[q] = ll + m.ll_bias;                                                    // multi :296-298
-        }
-      }
-    } else {
-      const int32_t sample_s = __shfl(sample, sigma);
-      if ((lane & 31) == 0) {
-        if (slot_s < a.S) a.sample_ll[(int64_t)q * a.S + sample_s] = ll + m.ll_bias;
-        else if (slot_s == a.S) a.ll_no_dla[q] = ll + m.ll_bias;
-      }
-    }
-  }
-#endif
 }
 
 }  // namespace gpdla

@@ -11,13 +11,15 @@
 // slot, slot + S, ... in order and adds each one's gradient into the slot's own copy of g (every
 // address is touched by one thread of the block, always the same one), and k_training_reduce sums
 // the slots in order -- round 1 accumulated g with fp64 atomics, whose order changed the last bits
-// from run to run.  Used for 20 < k <= 40 (the matrix-core path of training_mfma_kernels.hpp
-// takes k <= 20) and as its cross-check (GPDLA_TRAIN_LEGACY=1).
+// from run to run.  The matrix-core path of training_mfma_kernels.hpp serves every k <= 40; these
+// kernels are launched by libgpdla_legacy.so alone, as its cross-check (GPDLA_TRAIN_LEGACY=1).  They are
+// not templates, so the product code object holds them too: taking the file out changes the product's
+// set of kernels, which the instruction-text check of DESIGN.md 4.27 does not allow a refactor to do.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "sweep_kernels.hpp"
+#include "sweep_primitives.hpp"
 
 namespace gpdla {
 

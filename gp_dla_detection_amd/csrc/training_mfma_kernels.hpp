@@ -39,7 +39,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "sweep_kernels.hpp"
+#include "epilogue_factor.hpp"
 
 namespace gpdla {
 
@@ -259,11 +259,7 @@ constexpr size_t kTrBuildLds = kTrContractLds + (16 * kTrBuildMaxChunks + kTrMax
 template <int NW>
 constexpr int train_group_tiles() {
   static_assert(TrK<40>::W == 52 && TrK<40>::U == 3 && TrK<20>::W + TrK<20>::U == 16, "tile counts of the two rank classes");
-#ifdef TR_EXP_ALLTILES  // (A/B: the rounds-3/4 form, MFMAs on the padding tiles too)
-  return 16;
-#else
   return NW == 4 ? 4 + TrK<40>::U : 16;
-#endif
 }
 template <int NW>
 __device__ __forceinline__ void train_contract_body(const TrainContractArgs &a, double *smem, int tg) {
@@ -282,7 +278,7 @@ __device__ __forceinline__ void train_contract_body(const TrainContractArgs &a, 
   for (int c = 0; c < NT; ++c) acc[c] = d4{0.0, 0.0, 0.0, 0.0};
   const double *aw = a.Aw + ((active ? r : 0) * a.steps) * 64 + lane, *au = a.Au + ((active ? r : 0) * a.steps) * 64 + lane;
   const double *brec = a.Brec + tg * a.group_stride;
-  // whole chunks, copied as per-wave spans (glds_chunk, sweep_kernels.hpp); a chunk that runs past
+  // whole chunks, copied as per-wave spans (glds_chunk, sweep_primitives.hpp); a chunk that runs past
   // t1 reads the following steps' records or the kTrChunk records of padding behind the group
   static_assert((kTrChunk * kTrGroupD) % 128 == 0, "a chunk is a whole number of KiB");
   const int wave_s = __builtin_amdgcn_readfirstlane(wave);
@@ -312,9 +308,7 @@ __device__ __forceinline__ void train_contract_body(const TrainContractArgs &a, 
       uc[tt] = un[tt];
     }
     glds_wait();      // chunk c landed (this wave's part) ...
-#ifndef TR_EXP_NOBAR
     __syncthreads();  // ... and everyone's; the other buffer's readers are done
-#endif
     if (c + 1 < nchunks) {
       load_a(c + 1);
       issue_chunk(c + 1);
@@ -326,11 +320,7 @@ __device__ __forceinline__ void train_contract_body(const TrainContractArgs &a, 
       if (tt < csteps) {
         double b[NT];
 #pragma unroll
-#ifdef TR_EXP_NOLDS
-        for (int cc = 0; cc < NT; ++cc) b[cc] = wc[tt] + cc;
-#else
         for (int cc = 0; cc < NT; ++cc) b[cc] = buf[(size_t)(tt * 16 + cc) * 64];
-#endif
 #pragma unroll
         for (int cc = 0; cc < NT; ++cc)
           acc[cc] = __builtin_amdgcn_mfma_f64_16x16x4f64(cc < nw ? wc[tt] : uc[tt], b[cc], acc[cc], 0, 0, 0);
@@ -339,9 +329,6 @@ __device__ __forceinline__ void train_contract_body(const TrainContractArgs &a, 
   }
   glds_wait();  // nothing is in flight here (the last chunk issued no copy); says so to tools/check_vmem_hazard.py
   if (!active) return;
-#ifdef TR_EXP_NOSTORE
-  if (acc[0][0] == acc[0][0]) return;
-#endif
   // result register rr of tile c: row (lane >> 4) + 4 rr, column 16 (16 tg + c) + (lane & 15)
   double *o = a.out + ((r * a.nsplit + h) * 16) * (int64_t)a.cols + 256 * tg;
   const int jj = lane >> 4, s = lane & 15;
@@ -469,20 +456,12 @@ __device__ __forceinline__ void train_build_body(const TrainBuildArgs &a, double
     esum += ex;
   };
   for (int c = 0; c < nchunks; ++c) {
-#ifdef TR_EXP_BUILD_EARLYCOPY  // (A/B: rounds 3-4, the next chunk's copy issued at the top of the chunk)
-    // chunk c landed (this wave's part): its copy is older than the (at most six) raw loads in flight
-    __builtin_amdgcn_s_waitcnt(0x0F76);  // vmcnt(6)
-    asm volatile("" ::: "memory");
-    __syncthreads();  // ... and everyone's; the other buffer's readers are done
-    if (c + 1 < nchunks) issue_chunk(c + 1);
-#else
     // chunk c landed (this wave's part): its copy was issued in the MIDDLE of the previous chunk, behind
     // that chunk's requests for this chunk's first two pixels and in front of those for the last two
     // (three loads): only those may still be in flight
     __builtin_amdgcn_s_waitcnt(0x0F73);  // vmcnt(3)
     asm volatile("" ::: "memory");
     __syncthreads();  // ... and everyone's; the other buffer's readers are done
-#endif
     const double *buf = smem + (size_t)(c & 1) * kTrChunk * kTrGroupD + lane;
     const double *omc = om_s + 16 * c + 4 * jj;
     const bool more = c + 1 < nchunks;
@@ -496,7 +475,6 @@ __device__ __forceinline__ void train_build_body(const TrainBuildArgs &a, double
       if (e == 1) element(f01.y, z01.y, n01.y, omc[1], (nl_cur >> 8) & 0xFF, w, u);
       if (e == 2) {
         element(f23.x, z23.x, n23.x, omc[2], (nl_cur >> 16) & 0xFF, w, u);
-#ifndef TR_EXP_BUILD_EARLYCOPY
         // The next chunk's record copy is issued HERE: behind the compiler's waits for this chunk's raw
         // values.  The compiler counts only its own loads, so with the inline-assembly copy issued at
         // the top of the chunk (rounds 3-4) its vmcnt(2) / vmcnt(0) in front of element 0 also waited
@@ -507,7 +485,6 @@ __device__ __forceinline__ void train_build_body(const TrainBuildArgs &a, double
         // was measured as well: no gain, 281 us.)
         __builtin_amdgcn_sched_barrier(0);
         if (more) issue_chunk(c + 1);
-#endif
       }
       if (e == 3) element(f23.y, z23.y, n23.y, omc[3], nl_cur >> 24, w, u);
       __builtin_amdgcn_sched_barrier(0);
@@ -826,7 +803,7 @@ __global__ __launch_bounds__(256, 2) void k_train_factor(TrainFactorArgs a) {
 // Cholesky as broadcast LDS reads -- ~1250 of them per quasar, the pattern that bounds the old sweep
 // epilogues (48 cycles per instruction with eight waves per CU, tools/dpp_f64_probe.hip).  Here a
 // quasar sits on the 16 lanes of ONE DPP row, four quasars per wave, rows dealt as in Rows16
-// (sweep_kernels.hpp: lane l owns rows l < 9, 9 + l and 25 + l; row 40 is t), and every cross-lane
+// (epilogue_factor.hpp: lane l owns rows l < 9, 9 + l and 25 + l; row 40 is t), and every cross-lane
 // operand is a register of the same row, broadcast by v_fmac_f64_dpp:
 //   Cholesky      left-looking, the pivot row's entries from their owner (as factor_rows16); the
 //                 augmented row t comes out as y = L^-1 t, its running diagonal as -y'y = -t'z
@@ -1070,12 +1047,8 @@ __global__ __launch_bounds__(kTrF16Threads) void k_train_factor16(TrainFactorArg
         for (int u = 0; u < 7; ++u)
 #pragma unroll
           for (int hh = 0; hh < 4; ++hh) {
-#ifdef TF16_EXP_NOLOAD  // ablation: no partial sums read (results wrong by construction)
-            pv[u][hh] = 1e-6 * (u + hh);
-#else
             const bool on = onq && tid + NT * (7 * half + u) < Used && h0 + hh < D.H;
             pv[u][hh] = on ? base[NT * (7 * half + u) + (int64_t)(h0 + hh) * 16 * K::Cols] : 0.0;
-#endif
           }
 #pragma unroll
         for (int u = 0; u < 7; ++u)
@@ -1106,14 +1079,7 @@ __global__ __launch_bounds__(kTrF16Threads) void k_train_factor16(TrainFactorArg
     const bool real = q < D.nq;
     double tz, two_ld;
     bool pd;
-#ifdef TF16_EXP_NOFACTOR  // ablation: no factorisation (results wrong by construction)
-    tz = s_S[ql][l];
-    two_ld = 0.0;
-    pd = true;
-    if (l < 8) s_z[ql][l] = tz;
-#else
     train_factor16<KMAX>(s_S[ql], s_z[ql], l, k, &tz, &two_ld, &pd);
-#endif
     if (l == 0) {
       const double log_2pi = 1.83787706640934534;  // spectrum_loss.m:17
       const double v = 0.5 * ((s_sc[ql][1] - tz) + s_sc[ql][0] + two_ld + s_sc[ql][2] * log_2pi);  // :48-52
@@ -1304,7 +1270,7 @@ __global__ __launch_bounds__(256, 2) void k_train_core(TrainCoreArgs a) {
   static_assert((K::Ks * 64) % 128 == 0, "a quasar group's operands are a whole number of KiB");
   const int wave_s = __builtin_amdgcn_readfirstlane(wave);
   const uint32_t smem_lds = __builtin_amdgcn_readfirstlane(lds_address(smem));
-  auto issue_group = [&](int64_t g) {  // (glds_chunk, sweep_kernels.hpp)
+  auto issue_group = [&](int64_t g) {  // (glds_chunk, sweep_primitives.hpp)
     glds_chunk<K::Ks * 64 / 128, 4>(a.recE + g * K::Ks * 64, smem_lds + (uint32_t)((g - g0) & 1) * (uint32_t)(K::Ks * 64 * 8),
                                     wave_s, lane);
   };
@@ -1418,11 +1384,7 @@ __global__ __launch_bounds__(256, 2) void k_train_core_wide(TrainCoreArgs a) {
   };
   auto load_a = [&](int n, double (&dst)[CH]) {
     const int it = n / NCH, c = n - it * NCH;
-#ifdef TR_EXP_AHOT  // ablation (results wrong by construction): every wave re-reads ONE quasar group's operand -- an L2-hot A stream
-    const double *re = a.recE + (size_t)c * CH * 64 + lane + 0 * it;
-#else
     const double *re = a.recE + group_of(it) * K::Ks * 64 + (size_t)c * CH * 64 + lane;
-#endif
 #pragma unroll
     for (int j = 0; j < CH; ++j) dst[j] = re[j * 64];
   };
@@ -1443,9 +1405,7 @@ __global__ __launch_bounds__(256, 2) void k_train_core_wide(TrainCoreArgs a) {
     const int it = n / NCH, c = n - it * NCH;
     const bool live = g0 + it < g1;
     glds_wait();      // chunk n of the shared operands landed (this wave's part); so did cur
-#ifndef TR_EXP_WIDE_NOBAR  // (ablation: no chunk barrier; results wrong by construction)
     __syncthreads();  // ... everyone's; the other buffer's readers are done
-#endif
     if (n + 1 < total) {
       issue(n + 1);
       load_a(n + 1, nxt);

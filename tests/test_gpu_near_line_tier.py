@@ -1,4 +1,4 @@
-"""The accurate Voigt tier of the three-line sweeps, taken line by line (near_lines3 in csrc/sweep_kernels.hpp): in a
+"""The accurate Voigt tier of the three-line sweeps, taken line by line (near_lines3 in csrc/voigt_tiers.hpp): in a
 K-step whose wave votes, only the lanes within 30 Doppler widths of a line replace that line's term, by the
 piecewise polynomial on the reference's velocity (voigt.c:282-289); every other lane and line keeps its wing-tier
 term.  k_sweep_slim<3> and, through one refine level, k_sweep_slim_boxed<3> against the CPU oracle:

@@ -1,10 +1,10 @@
 """Static checks of the shipped ISA for hazards the compiler cannot see behind inline assembly.
 
 * tools/check_dpp_hazard.py: the DPP read hazard around the v_fmac_f64_dpp / v_mov_b64_dpp of the
-  register epilogues (csrc/sweep_kernels.hpp) -- VALU write -> DPP read, VALU write of EXEC -> DPP,
+  register epilogues (csrc/epilogue_factor.hpp) -- VALU write -> DPP read, VALU write of EXEC -> DPP,
   matrix-pipe write -> DPP read -- walked backwards over the control-flow graph (branch targets too).
 * tools/check_vmem_hazard.py: the hand-issued vector-memory operations (the profile gathers of
-  csrc/sweep_multi_slim_kernel.hpp, the global -> LDS copies of csrc/sweep_kernels.hpp): no
+  csrc/sweep_multi_slim_kernel.hpp, the global -> LDS copies of csrc/sweep_primitives.hpp): no
   destination register touched before a covering `s_waitcnt vmcnt(n)`, nothing outstanding at
   s_endpgm, every hand-written vmcnt literal exactly what the instruction stream needs.
 

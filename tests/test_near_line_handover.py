@@ -1,4 +1,4 @@
-"""The three-line optical-depth sum of a voted K-step (near_lines3 in csrc/sweep_kernels.hpp), restated in Python
+"""The three-line optical-depth sum of a voted K-step (near_lines3 in csrc/voigt_tiers.hpp), restated in Python
 floats in the kernel's operation order and compared with 50-digit sums of sqrt(pi) lead_j Re w(x_j + i y_j)
 (voigt.c:282-289).  No GPU.
 
@@ -65,7 +65,7 @@ def lib():
 
 @pytest.fixture(scope="module")
 def wing():
-    with open(os.path.join(_lib.CSRC, "sweep_kernels.hpp")) as f:
+    with open(os.path.join(_lib.CSRC, "voigt_tiers.hpp")) as f:
         found = dict(re.findall(r"\b(kE\d) = (0x1\.[0-9a-f]+p[+-]\d+)", f.read()))
     return {name: float.fromhex(v) for name, v in found.items()}
 

@@ -1,5 +1,5 @@
 """The two short series of the sweeps' profile arithmetic, as shipped: the coefficients are read out of
-csrc/sweep_kernels.hpp and both series are evaluated the way the kernels evaluate them (fp64, one rounding per
+csrc/voigt_tiers.hpp and both series are evaluated the way the kernels evaluate them (fp64, one rounding per
 FMA, the kernels' Horner order), then compared with 50-digit mpmath values.
 
  - the wing tier (wing_core / wing_sum3 / wing_sum3_rcp4 and the halves in csrc/sweep_slim_kernel.hpp):
@@ -43,7 +43,7 @@ def source(name):
 
 @pytest.fixture(scope="module")
 def wing():
-    found = dict(re.findall(r"\b(kE\d) = (0x1\.[0-9a-f]+p[+-]\d+)", source("sweep_kernels.hpp")))
+    found = dict(re.findall(r"\b(kE\d) = (0x1\.[0-9a-f]+p[+-]\d+)", source("voigt_tiers.hpp")))
     print("shipped wing coefficients:", found)
     assert sorted(found) == ["kE1", "kE2", "kE3", "kE4"], "the wing series is of degree 4"
     return {name: float.fromhex(v) for name, v in found.items()}
@@ -52,7 +52,7 @@ def wing():
 @pytest.fixture(scope="module")
 def exp_poly():
     """c1..c5 of exp_table_end_scaled, formed as its constexpr line forms them"""
-    text = source("sweep_kernels.hpp")
+    text = source("voigt_tiers.hpp")
     body = text[text.index("double exp_table_end_scaled("):]
     body = body[:body.index("\n}\n")]
     L = float(re.search(r"constexpr double L = ([0-9.e+-]+);", body).group(1))
@@ -73,8 +73,8 @@ def test_both_spellings_are_in_step():
     assert not re.search(r"\bkE\d = ", slim)
     for name in ("kE1", "kE3", "wing_lead"):   # (kE4 is wing_lead's, kE2 rides in LineTable::t2)
         assert re.search(rf"\b{name}\b", slim), name
-    assert "kE5" not in slim and "kE5" not in source("sweep_kernels.hpp")
-    one = source("sweep_kernels.hpp")
+    assert "kE5" not in slim and "kE5" not in source("voigt_tiers.hpp")
+    one = source("voigt_tiers.hpp")
     one = one[one.index("double exp_table_end_scaled("):]
     two = slim[slim.index("double exp_series_scaled("):]
     pick = lambda s: re.findall(r"constexpr double (?:L|c1) = [^;]+;|asm\(\"v_fma_f64[^;]+;", s[:s.index("\n}\n")])

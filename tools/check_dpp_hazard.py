@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Checks a gfx950 ISA dump (hipcc -save-temps, *.s) for the DPP read hazard around inline-assembly
-v_fmac_f64_dpp / v_mov_b64_dpp instructions (csrc/sweep_kernels.hpp: fmac_bcast, mov_bcast).
+v_fmac_f64_dpp / v_mov_b64_dpp instructions (csrc/epilogue_factor.hpp: fmac_bcast, mov_bcast).
 
 gfx9 rules: a DPP instruction must not read a VGPR that a VALU instruction wrote less than 2 wait
 states earlier, nor follow a VALU write of EXEC by less than 5; and (the matrix pipe's result hazard,

@@ -2,7 +2,7 @@
 """Static check of HAND-ISSUED vector-memory operations in a gfx950 ISA dump (hipcc -save-temps, *.s).
 
 The kernels issue some loads as inline assembly and wait for them with hand-counted
-`s_waitcnt vmcnt(n)` (csrc/sweep_multi_slim_kernel.hpp: the profile gathers; csrc/sweep_kernels.hpp:
+`s_waitcnt vmcnt(n)` (csrc/sweep_multi_slim_kernel.hpp: the profile gathers; csrc/sweep_primitives.hpp:
 the global -> LDS copies of glds16 / glds_quad).  The compiler's wait-count pass does not see such
 loads: nothing stops it from re-using a destination register while the load is in flight, and a
 miscounted wait reads a stale value without failing any test.  This checker follows every path of a

@@ -7,9 +7,9 @@ that k_profiles wrote:
     prof[((ql * 2 + kind) * S + i) * stride + p]          csrc/multi_kernels.hpp:37
     stride = ceil16(4 * ceil(max_pix / 4) + 4)             csrc/host_multi.hpp, multi_alloc
     allocation = nq_sub * 2 * S * stride doubles           (same place)
-    steps(q) = ceil(n_u(q) / 4),  n_u <= the quasar's pixel count      csrc/sweep_kernels.hpp:285
+    steps(q) = ceil(n_u(q) / 4),  n_u <= the quasar's pixel count      csrc/prepare_kernels.hpp:167
     shipped gather index:  p = min(4 * (rn + kAhead) + jj, 4 * steps + jj),  rn < steps, jj < 4
-                                                            csrc/sweep_multi_slim_kernel.hpp:123, 152, 210
+                                                            csrc/sweep_multi_slim_kernel.hpp:123, 144, 204
 
 This enumerates the largest byte offset any lane can request -- over quasars of a sub-batch, both
 kinds, every sample row, every K-step and jj -- for the SHIPPED (clamped) index and for the index of
