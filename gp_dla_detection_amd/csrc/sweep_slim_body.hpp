@@ -71,8 +71,8 @@ __global__ __launch_bounds__(kSlimWaves * 64, 2) void GPDLA_SWEEP_SLIM_KERNEL(GP
   const double *const my_rec0 = uniform_pointer(rec_base + (size_t)wave_s * kSlimRec);
   constexpr size_t kChunkDoubles = (size_t)CH * kSlimRec;
   uint32_t off_raw = 16u * (uint32_t)lane;
-  auto issue_chunk = [&](int c, const double *my_rec) {  // my_rec: this wave's record of chunk c
-    if (lane < kSlimRec / 2) glds16_at(my_rec, off_raw, raw_mine + (c & 1) * kSlimSweepBlock);
+  auto issue_chunk = [&](int parity, const double *my_rec) {  // my_rec: this wave's record of a chunk of that parity
+    if (lane < kSlimRec / 2) glds16_at(my_rec, off_raw, raw_mine + parity * kSlimSweepBlock);
   };
   // This wave's private copy of K-step `wave` of a chunk: its 4 M rows, each laid down twice
   // (lane 16 jj + p fetches doubles 2 (p & 7), 2 (p & 7) + 1 of pixel jj's row), and m[16..19] of
@@ -207,19 +207,28 @@ __global__ __launch_bounds__(kSlimWaves * 64, 2) void GPDLA_SWEEP_SLIM_KERNEL(GP
   // taps of the next K-step, carried across the chunk barrier too (the ring is this wave's own)
   double n0 = my_ring[0], n1 = my_ring[1], n2 = my_ring[2], n3 = my_ring[3], n4 = my_ring[4], n5 = my_ring[5], n6 = my_ring[6];
   const double *next_rec = my_rec0 + kChunkDoubles;  // this wave's record of chunk c + 1
-  for (int c = 0; c < nchunks; ++c, next_rec += kChunkDoubles) {
+  // The wavelength and the pixel row of the next K-step live across the chunk loop although K-step 0 reads neither:
+  // declared inside a chunk they were set to zero once per chunk, and once more on the path of a K-step that does not run.
+  double lam_next = 0.0;
+  double2 n01 = {0.0, 0.0}, n23 = {0.0, 0.0};                                    // its pixel row
+  // kE3, which the leading Horner step of the wing series takes from a vector register (wing_lead): held in one from
+  // here on.  Left to itself the compiler moves it there from a scalar pair in every K-step, behind the v_rcp_f64.
+  double e3v = kE3;
+  asm volatile("" : "+v"(e3v));
+  // One chunk, of the parity given.  A callable, and the parity an argument, on purpose: the same K-step written
+  // straight into the loop below has the same vector instructions, but the compiler then interleaves the exp series
+  // with the weights less well (137.6 against 136.6 ms per launch; LABBOOK, "Bookkeeping instructions of the K-step").
+  auto chunk = [&](const int c, const int parity) __attribute__((always_inline)) {
     // vmcnt(0): nothing of ours is in flight (see k_sweep).  lgkmcnt(0): no LDS request is open behind the chunk
     // barrier either, but the compiler cannot know that no scalar load of the prologue is (they return out of order),
     // and would make K-step 0's first use of LDS data wait for ALL of that step's requests
     __builtin_amdgcn_s_waitcnt(0x0070);
-    if (c + 1 < nchunks) issue_chunk(c + 1, next_rec);
-    const int par = (c & 1) * kSlimSweepBlock;
+    if (c + 1 < nchunks) issue_chunk(1 - parity, next_rec);
+    const int par = parity * kSlimSweepBlock;
     const double *tbuf = pinned(tb0 + par);
     const double *mine0 = pinned(mb0 + par);
     const double *ubuf = pinned(ub0 + par);
     double *xdst = pinned(xd1 - par);
-    double lam_next = 0.0;
-    double2 n01 = {0.0, 0.0}, n23 = {0.0, 0.0};                                    // its pixel row
 #pragma unroll
     for (int tt = 0; tt < CH; ++tt) {
       const int rn = c * CH + tt;
@@ -267,7 +276,7 @@ __global__ __launch_bounds__(kSlimWaves * 64, 2) void GPDLA_SWEEP_SLIM_KERNEL(GP
         if constexpr (LINES == 3) {
           if (tt > 0) wf = wing3_front(lamP, ms_r[0], ms_r[1], ms_r[2], cs, &near);
           WingLines3 wl;
-          total = wing3_back_rcp4(wf, d, &inv_d, &wl);
+          total = wing3_back_rcp4(wf, d, e3v, &inv_d, &wl);
           if (__builtin_expect(__any(near), 0)) total = near_lines3(lamP, mult_r[0], mult_r[1], mult_r[2], wl);
         } else {
           total = optical_sum(lamP);
@@ -338,7 +347,9 @@ __global__ __launch_bounds__(kSlimWaves * 64, 2) void GPDLA_SWEEP_SLIM_KERNEL(GP
     }
     glds_wait();      // the prefetched raw chunk and this wave's next rows have landed ...
     __syncthreads();  // ... everyone's tiles of the next chunk are written; this chunk's buffers are free
-  }
+    next_rec += kChunkDoubles;
+  };
+  for (int c = 0; c < nchunks; ++c) chunk(c, c & 1);
 
   double logd_sum = log(dprod) + (double)dexp * 0.6931471805599453;
   quad_sum += __shfl_xor(quad_sum, 16);

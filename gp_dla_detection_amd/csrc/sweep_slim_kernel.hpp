@@ -175,7 +175,8 @@ __device__ __forceinline__ double exp_series_scaled(const ExpState &e) {
 __device__ __forceinline__ double exp_finish_scaled(const ExpState &e, double p) { return ldexp(e.tabv * p, e.ni >> 6); }
 
 // wing_sum3_rcp4 in two pieces (the same operations on the same operands): the part that needs the
-// wavelength alone -- velocities, s_j, the near vote, the prefix products -- and the part that takes d.
+// wavelength alone -- velocities, s_j, the near vote, the prefix products -- and the part that takes d (e3v: kE3 in
+// a vector register, which the caller holds there across its loop).
 struct WingFront {
   double sa, sb, sc, pab, pabc;
 };
@@ -187,13 +188,12 @@ __device__ __forceinline__ WingFront wing3_front(double lamP, double msa, double
   f.pab = f.sa * f.sb, f.pabc = f.pab * f.sc;
   return f;
 }
-__device__ __forceinline__ double wing3_back_rcp4(const WingFront &f, double d, double *inv_d, WingLines3 *lines) {
+__device__ __forceinline__ double wing3_back_rcp4(const WingFront &f, double d, double e3v, double *inv_d, WingLines3 *lines) {
   const double rinv = fast_rcp(f.pabc * d);
   *inv_d = rinv * f.pabc;
   const double r3 = rinv * d;
   const double rc = r3 * f.pab, r2 = r3 * f.sc;
   const double ra = r2 * f.sb, rb = r2 * f.sa;
-  const double e3v = kE3;
   double ta = wing_lead(ra, e3v), tb = wing_lead(rb, e3v), tc = wing_lead(rc, e3v);
   ta = fma(ta, ra, g_lines.t2[0]); tb = fma(tb, rb, g_lines.t2[1]); tc = fma(tc, rc, g_lines.t2[2]);
   ta = fma(ta, ra, kE1); tb = fma(tb, rb, kE1); tc = fma(tc, rc, kE1);
