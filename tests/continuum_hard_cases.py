@@ -156,9 +156,10 @@ def restatement_samples(inp, tables, form: str, nu=None) -> dict:
     return out
 
 
-def restatement_products(inp, per_sample, rows_by_table, p, sample_coefficients=False) -> dict:
+def restatement_products(inp, per_sample, rows_by_table, p, sample_coefficients=False, components=MR.COMPONENTS) -> dict:
     """The seven marginal-continuum and five predictive-flux products of one (row, mixture) in fp64, with the sums in
-    the order of ``MR.sampled_component`` / ``PR.component`` and the mixing of ``MR.mix`` / ``PR.mix``."""
+    the order of ``MR.sampled_component`` / ``PR.component`` and the mixing of ``MR.mix`` / ``PR.mix``.  ``components``:
+    the names behind ``p``, "null" first; a sampled one has ``inp["profiles_" + name]``, a row and per-sample results."""
     p = np.asarray(p, dtype=np.float64)
     p = p / p.sum()
     kept, n_u = inp["kept"], inp["kept"].size
@@ -166,7 +167,7 @@ def restatement_products(inp, per_sample, rows_by_table, p, sample_coefficients=
     omega2, nu = np.full(n_u, np.nan), np.full(n_u, np.nan)
     omega2[kept], nu[kept] = inp["omega2"], per_sample["nu"]
     mc_parts, pf_parts, ci = [], [], None
-    for name, pm in zip(MR.COMPONENTS, p):
+    for name, pm in zip(components, p):
         if not pm > 0:
             mc_parts.append(None)
             pf_parts.append(None)
@@ -259,9 +260,10 @@ def exact_weights(row, dps: int = DPS):
         return live, [x / total for x in e]
 
 
-def exact_products(per_sample, rows_by_table, p, mu_all, M_all, dps: int = DPS, raw: bool = False) -> dict:
+def exact_products(per_sample, rows_by_table, p, mu_all, M_all, dps: int = DPS, raw: bool = False,
+                   components=MR.COMPONENTS) -> dict:
     """The products of one (row, mixture) from ``exact_sample`` results ({"null": [one], table: {index: result}}),
-    rounded to fp64 at the very end (``raw``: the mpf lists themselves)."""
+    rounded to fp64 at the very end (``raw``: the mpf lists themselves).  ``components``: the names behind ``p``."""
     import mpmath as mp
     with mp.workdps(dps):
         total = mp.fsum(mp.mpf(float(x)) for x in p)
@@ -272,7 +274,7 @@ def exact_products(per_sample, rows_by_table, p, mu_all, M_all, dps: int = DPS, 
         c, W, S2 = [zero] * k, [zero] * nb, [zero] * nb
         F1, F2, FW, FD = [zero] * n_u, [zero] * n_u, [zero] * n_u, [zero] * n_u
         masked = None
-        for name, pm in zip(MR.COMPONENTS, pm_all):
+        for name, pm in zip(components, pm_all):
             if not pm > 0:
                 continue
             if name == "null":
