@@ -291,6 +291,7 @@ SPECTRA_MAX_ABSORBERS = 8                                   # GPDLA_SPECTRA_MAX_
 MAX_FIXED_ABSORBERS = 8                                     # GPDLA_MAX_FIXED_ABSORBERS
 SPECTRA_MAP, SPECTRA_MOMENTS, SPECTRA_CONTINUUM = 1, 2, 4   # GPDLA_SPECTRA_* product bits
 SPECTRA_WEIGHTS_NONE, SPECTRA_WEIGHTS_RESIDENT, SPECTRA_WEIGHTS_HOST = 0, 1, 2
+SPECTRA_WEIGHTS_REFINED, SPECTRA_NOT_REFINED = 3, 16        # GPDLA_SPECTRA_WEIGHTS_REFINED; the status bit GPDLA_SPECTRA_NOT_REFINED
 SPECTRA_MULTI_MODELS, SPECTRA_MULTI_AVERAGE = 1, 2            # GPDLA_SPECTRA_MULTI_* product bits
 SPECTRA_AVERAGE_UNDEFINED, SPECTRA_MULTI_FLAG_LLS = 8, 0x40000000   # status bit; model_flags bit of the sub-DLA model
 

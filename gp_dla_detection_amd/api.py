@@ -445,6 +445,10 @@ class Batch:
         ``weights``: ``"resident"`` -- the batch's own sample log-likelihoods after :meth:`process` /
         :meth:`process_multi` (multi: model DLA(1), or the sub-DLA table with ``sub_dla``) -- or a
         host array ``[nsel, S]`` of them (a processed file needs no second sweep); None: no moments.
+        ``"refined"``: the batch's refined table after :meth:`refine` -- the S' refine points mapped through each
+        quasar's last box, weighted by its refined sample log-posteriors.  Posterior mass outside
+        the last box is ignored, as by ``parameter_summaries(refined=True)``; not with ``sub_dla``; a quasar the
+        refine pass did not take (or found unusable) gets NaN rows and ``SPECTRA_NOT_REFINED`` in ``status``.
         ``meanflux``: prepared rows of the mean-flux model (default: on for a multi-DLA batch).
         ``products``: any of ``"map"`` (``map_absorption``), ``"moments"`` (``mean_absorption``,
         ``var_absorption``), ``"continuum"`` (``continuum``, ``model_flux``: the posterior mean of the
@@ -463,9 +467,9 @@ class Batch:
         products = [p for p in products if not (p == "moments" and weights is None)]
         rq.products = int(sum(bits[p] for p in set(products)))
         if isinstance(weights, str):
-            if weights != "resident":
-                raise ValueError("weights: 'resident', an array [nsel, S] or None")
-            rq.weights_source = _lib.SPECTRA_WEIGHTS_RESIDENT
+            if weights not in ("resident", "refined"):
+                raise ValueError("weights: 'resident', 'refined', an array [nsel, S] or None")
+            rq.weights_source = _lib.SPECTRA_WEIGHTS_RESIDENT if weights == "resident" else _lib.SPECTRA_WEIGHTS_REFINED
         elif weights is not None:
             w = np.ascontiguousarray(weights, dtype=np.float64)
             if w.shape != (nsel, self.num_samples):
@@ -593,9 +597,9 @@ class Batch:
         rq.model_weights = pw.ctypes.data_as(_dp)
         keep = [sel, pw]
         if isinstance(weights, str):
-            if weights != "resident":
-                raise ValueError("weights: 'resident', an array [nsel, S], a dict of them or None")
-            rq.weights_source = _lib.SPECTRA_WEIGHTS_RESIDENT
+            if weights not in ("resident", "refined"):
+                raise ValueError("weights: 'resident', 'refined', an array [nsel, S], a dict of them or None")
+            rq.weights_source = _lib.SPECTRA_WEIGHTS_RESIDENT if weights == "resident" else _lib.SPECTRA_WEIGHTS_REFINED
         elif weights is not None:
             if not isinstance(weights, dict):
                 sampled = [c for c in components if c != "null"]
@@ -613,6 +617,19 @@ class Batch:
         rq.meanflux = int(bool(self.max_dlas) if meanflux is None else bool(meanflux))
         return sel, keep
 
+    @staticmethod
+    def _coefficient_samples(weights_source: int, model_weights, num_samples: int, num_refine_points) -> int:
+        """Rows per quasar of ``sample_coefficients``, by the library's own rule: the S' refine points where the request
+        runs the DLA component on the refined table -- the refined source AND some row of the model weights (columns of
+        unlisted components already zeroed) weighs the DLA column -- and the batch's S otherwise.  A refined source whose
+        DLA column is 0 everywhere is evaluated on the first pass's tables, so its rows are S long."""
+        pw = np.asarray(model_weights, dtype=np.float64)
+        if weights_source == _lib.SPECTRA_WEIGHTS_REFINED and bool((pw[:, 2] > 0).any()):
+            if num_refine_points is None:
+                raise _lib.GpdlaError(_lib.ERR_INVALID_ARGUMENT, "the batch has not been refined")
+            return int(num_refine_points)
+        return int(num_samples)
+
     def marginal_continuum(self, selection=None, weights="resident", components=("dla",), model_weights=None,
                            meanflux: bool | None = None, sample_coefficients: bool = False) -> dict:
         """The GP continuum of the selected quasars averaged over the absorber posterior instead of
@@ -628,7 +645,12 @@ class Batch:
         evaluated.
         ``weights``: ``"resident"`` (the batch's tables after :meth:`process` / :meth:`process_multi`), a host
         array ``[nsel, S]`` of sample log-likelihoods when one sampled component is listed, or a dict
-        ``{"dla": ..., "sub_dla": ...}`` of them.
+        ``{"dla": ..., "sub_dla": ...}`` of them.  ``"refined"``: the DLA component runs on the batch's refined table
+        after :meth:`refine` -- the S' refine points mapped through each quasar's last box, weighted by its refined
+        sample log-posteriors; the null and the sub-DLA component are unchanged (the sub-DLA table keeps
+        its S samples).  Posterior mass outside the last box is ignored, as by ``parameter_summaries(refined=True)``.  A
+        quasar whose DLA component carries weight and that the refine pass did not take (or found unusable) gets NaN rows
+        and status ``SPECTRA_NOT_REFINED``; ``sample_coefficients`` is then ``[nsel, S', k]``.
         ``meanflux``: prepared rows of the mean-flux model (default: on for a multi-DLA batch).
         ``sample_coefficients``: also ``sample_coefficients [nsel, S, k]``, the coefficient mean of every
         sample of the ONE sampled component, NaN rows for samples of weight 0.
@@ -639,7 +661,9 @@ class Batch:
         unmeasured pixel and is left out, as in ``continuum`` of :meth:`model_spectra`."""
         rq = _lib.MarginalContinuumRequest()
         sel, keep = self._mixture_request(rq, selection, weights, components, model_weights, meanflux)
-        nsel, S, k = sel.size, self.num_samples, self.ctx.k
+        nsel, k = sel.size, self.ctx.k
+        S = self._coefficient_samples(rq.weights_source, keep[1], self.num_samples,
+                                      None if self.ctx.refine_points is None else int(self.ctx.refine_points[0].size))
         rq.sample_coefficients = int(bool(sample_coefficients))
         nb = k * (k + 1) // 2
         rows = {"coef_mean": (nsel, k), "coef_cov_within": (nsel, nb), "coef_cov_between": (nsel, nb)}
@@ -676,7 +700,8 @@ class Batch:
         curve to lay over the observed spectrum, with its error band; it is NOT the product of ``mean_absorption``
         and ``continuum_mean``, because the continuum coefficients move with the absorber.
 
-        ``selection``, ``weights``, ``components``, ``model_weights``, ``meanflux``: as :meth:`marginal_continuum`.
+        ``selection``, ``weights``, ``components``, ``model_weights``, ``meanflux``: as :meth:`marginal_continuum`
+        (``weights="refined"`` included: the DLA component on the refined table, mass outside the last box ignored).
         Returns ``offsets``, ``status`` and the flat per-pixel ``flux_mean``, ``flux_var`` (within + between),
         ``flux_var_within`` (the GP's spread given the absorber), ``flux_var_between`` (the spread over absorbers
         and models) and ``noise_var`` (NaN on masked pixels).  ``flux_var`` is the variance of the low-rank,
@@ -1541,11 +1566,12 @@ def _block_size(max_quasars_per_batch, spectra, idx, model: dict, samples: dict)
                                                            np.asarray(samples["offset_samples"]).size, 1))
 
 
-def _resident_blocks(model: dict, samples: dict, spectra, idx, params: Parameters, device: int, per: int):
+def _resident_blocks(model: dict, samples: dict, spectra, idx, params: Parameters, device: int, per: int, refined=None):
     """Generator over the quasars ``idx`` of ``spectra`` in blocks of ``per``, each resident in turn in ONE batch of a
     context of its own (uploaded, then reloaded; placeholder priors, since nothing is swept): yields
     ``(lo, hi, idx[lo:hi], batch)``.  Batch and context are closed when the generator is (``contextlib.closing``
-    around the loop makes that every exit path)."""
+    around the loop makes that every exit path).  ``refined``: what :func:`_refined_options` returns -- the blocks are
+    uploaded with the run's own priors and the context gets the refine points, for :func:`_refine_block`."""
     if not len(idx):
         return
     multi = isinstance(params, MultiParameters)
@@ -1555,11 +1581,19 @@ def _resident_blocks(model: dict, samples: dict, spectra, idx, params: Parameter
     try:
         ctx.set_model(model)
         ctx.set_samples(samples)
+        if refined is not None:
+            pts = refined["points"]
+            if pts is None or np.ndim(pts) == 0:
+                ctx.set_refine_points(num=None if pts is None else int(pts))
+            else:
+                ctx.set_refine_points(*pts)
         for lo, hi in batch_blocks(len(idx), per):
             block = idx[lo:hi]
             n = hi - lo
             args = ([spectra[i] for i in block], np.zeros(n), np.zeros((n, md)) if multi else np.zeros(n),
                     np.zeros(n) if multi else None)
+            if refined is not None:
+                args = (args[0], refined["log_priors"][0][block], refined["log_priors"][1][block], None)
             if batch is None:
                 batch = ctx.upload(*args)
             else:
@@ -1569,6 +1603,60 @@ def _resident_blocks(model: dict, samples: dict, spectra, idx, params: Parameter
         if batch is not None:
             batch.close()
         ctx.close()
+
+
+REFINED_KEYS = ("levels", "delta", "pad", "points", "prior")
+
+
+def _refined_options(refined, results, params):
+    """The ``refined=`` argument of :func:`model_spectra`, :func:`marginal_continuum` and :func:`predictive_flux` checked and
+    completed: None, or a dict with ``levels``, ``delta``, ``pad``, ``prior`` (:meth:`Batch.refine`), ``points`` ((u, v), a
+    number of default points, or None: as many as there are DLA samples) and the run's ``log_priors``."""
+    if refined is None:
+        return None
+    from . import refine as _refine
+    if isinstance(params, MultiParameters):
+        raise ValueError("refined: a multi-DLA batch cannot be refined (DESIGN.md 4.18)")
+    unknown = set(refined) - set(REFINED_KEYS)
+    if unknown:
+        raise ValueError(f"refined: unknown keys {sorted(unknown)}; known: {REFINED_KEYS}")
+    if results is None or "log_priors_no_dla" not in results or "log_priors_dla" not in results:
+        raise ValueError("refined needs results with log_priors_no_dla and log_priors_dla: the selected quasars are processed again")
+    opts = dict(levels=_refine.DEFAULT_LEVELS, delta=_refine.DEFAULT_DELTA, pad=_refine.DEFAULT_PAD, points=None, prior=None)
+    opts.update({k: v for k, v in refined.items() if v is not None})
+    pts = opts["points"]
+    _refine.validate(opts["levels"], opts["delta"], opts["pad"], opts["prior"], *((None, None) if pts is None or np.ndim(pts) == 0 else pts))
+    opts["log_priors"] = (np.asarray(results["log_priors_no_dla"], dtype=np.float64).reshape(-1),
+                          np.asarray(results["log_priors_dla"], dtype=np.float64).reshape(-1))
+    return opts
+
+
+def _refine_block(batch: "Batch", opts: dict) -> dict:
+    """The first pass and the refine pass of a resident block (the way :func:`refine_absorbers` works); returns the boxes
+    and the refine status of its quasars."""
+    batch.process()
+    return batch.refine(None, opts["levels"], opts["delta"], opts["pad"], opts["prior"], with_samples=False)
+
+
+def _refined_model_weights(batch: "Batch", components) -> np.ndarray:
+    """``[n, 3]`` as (p_no_dlas, 0, p_dlas) of :meth:`Batch.refined_posteriors`, with the fall-back of
+    :func:`_mixture_inputs` for a quasar whose listed posteriors are all 0 or NaN."""
+    rp = batch.refined_posteriors()
+    mw = np.stack([rp["p_no_dlas_refined"], np.zeros(rp["p_dlas_refined"].size), rp["p_dlas_refined"]], axis=1)
+    mw = np.maximum(np.nan_to_num(mw, nan=0.0), 0.0)
+    listed = np.array([c in components for c in ("null", "sub_dla", "dla")])
+    empty = ~(mw[:, listed].sum(axis=1) > 0)
+    mw[np.ix_(empty, listed)] = 1.0
+    return mw
+
+
+def _stitch_refined(out: dict, lo: int, hi: int, n: int, ref: dict):
+    """The boxes used and the refine status of block ``[lo, hi)`` into ``boxes [n, levels, 4]`` and ``refine_status [n]``."""
+    if "boxes" not in out:
+        out["boxes"] = np.full((n,) + ref["boxes"].shape[1:], np.nan)
+        out["refine_status"] = np.full(n, -1, dtype=np.int32)
+    out["boxes"][lo:hi] = ref["boxes"]
+    out["refine_status"][lo:hi] = ref["status"]
 
 
 def _stitch(out: dict, lo: int, hi: int, res: dict):
@@ -1581,7 +1669,7 @@ def model_spectra(model: dict, samples: dict, spectra, results: dict | None = No
                   params: Parameters | None = None, selection=None, absorbers="map", sub_dla: bool | None = None,
                   moments_sub_dla: bool = False, products=("map", "moments", "continuum"), sample_rows=None,
                   device: int = 0, max_quasars_per_batch: int | None = None, multi_models: bool = False,
-                  model_weights=None, multi_rows=None) -> dict:
+                  model_weights=None, multi_rows=None, refined: dict | None = None) -> dict:
     """Model spectra of the selected quasars of a processed run, batched like :func:`process_qsos`:
     the selected spectra are uploaded block by block and nothing is swept again -- the posterior
     weights come from the saved sample log-likelihoods.
@@ -1600,10 +1688,18 @@ def model_spectra(model: dict, samples: dict, spectra, results: dict | None = No
     -- or ``multi_rows(idx)`` returns the dict of those three for quasars ``idx`` -- and ``model_weights``
     ``[nq, 2 + max_dlas]`` over ALL quasars weighs the models (default: ``results["model_posteriors"]``;
     :func:`renormalised_model_posteriors` includes the quasars of the reference's early exit).
+    ``refined``: None, or ``dict(levels=, delta=, pad=, points=, prior=)`` (any may be left out): per resident block the
+    selected quasars are processed and refined (:meth:`Batch.process`, :meth:`Batch.refine`, the way
+    :func:`refine_absorbers` works; ``results`` supplies the priors) and the moments come from the refined table
+    (``weights="refined"``: posterior mass outside the last box is ignored).  The result gains ``boxes`` and
+    ``refine_status``.  Single-DLA runs only.
     Returns ``selection``, ``offsets``, ``status`` and the flat per-pixel arrays of
     :meth:`Batch.model_spectra`, in selection order; results do not depend on the batching."""
     p = params or Parameters()
     multi = isinstance(p, MultiParameters)
+    refined = _refined_options(refined, results, p)
+    if refined is not None and moments_sub_dla:
+        raise ValueError("refined: the refined table is the DLA table (no moments_sub_dla)")
     spectra = list(spectra)
     sel = np.arange(len(spectra), dtype=np.int64) if selection is None else np.asarray(selection, dtype=np.int64).reshape(-1)
     products = tuple(products)
@@ -1613,7 +1709,7 @@ def model_spectra(model: dict, samples: dict, spectra, results: dict | None = No
         if results is None:
             raise ValueError("absorbers='map' needs results")
         absorbers = map_absorbers(results, sub_dla=multi if sub_dla is None else sub_dla)
-    if "moments" in products and sample_rows is None:
+    if "moments" in products and sample_rows is None and refined is None:
         if results is None:
             raise ValueError("moments need results or sample_rows")
         table = np.asarray(results["sample_log_likelihoods_lls" if moments_sub_dla else "sample_log_likelihoods_dla"])
@@ -1632,11 +1728,15 @@ def model_spectra(model: dict, samples: dict, spectra, results: dict | None = No
     per = _block_size(max_quasars_per_batch, spectra, sel, model, samples)
     out = {"selection": sel, "offsets": np.zeros(sel.size + 1, dtype=np.int64), "status": np.zeros(sel.size, dtype=np.int32)}
     parts = {}
-    with closing(_resident_blocks(model, samples, spectra, sel, p, device, per)) as blocks:
+    with closing(_resident_blocks(model, samples, spectra, sel, p, device, per, refined)) as blocks:
         for lo, hi, idx, batch in blocks:
+            if refined is not None:
+                _stitch_refined(out, lo, hi, sel.size, _refine_block(batch, refined))
+                weights = "refined" if "moments" in products else None
+            else:
+                weights = np.asarray(sample_rows(idx), dtype=np.float64) if "moments" in products else None
             res = batch.model_spectra(absorbers=None if absorbers is None else _take_absorbers(absorbers, idx),
-                                      weights=np.asarray(sample_rows(idx), dtype=np.float64) if "moments" in products else None,
-                                      sub_dla=moments_sub_dla, products=products)
+                                      weights=weights, sub_dla=moments_sub_dla, products=products)
             _stitch(out, lo, hi, res)
             for name in MODEL_SPECTRA_ARRAYS:
                 if name in res:
@@ -1735,10 +1835,43 @@ def _mixture_multi(method: str, flat, rows, model, samples, spectra, results, p,
     return out
 
 
+def _mixture_refined(method: str, flat, rows, model, samples, spectra, p, sel, components, model_weights, refined, device,
+                     max_quasars_per_batch, multi_models, **kw) -> dict:
+    """:func:`marginal_continuum` / :func:`predictive_flux` with ``refined``: per resident block :func:`_refine_block`, then
+    ``Batch.<method>(weights="refined")``; ``flat`` per-pixel arrays and ``rows`` per-quasar arrays stitched in selection
+    order, with the boxes used and the refine status."""
+    if multi_models:
+        raise ValueError("refined: not with multi_models (a multi-DLA batch cannot be refined)")
+    components = tuple(components)
+    if "sub_dla" in components:
+        raise ValueError("refined: a single-DLA run has no sub-DLA table; components are 'null' and 'dla'")
+    by_posteriors = isinstance(model_weights, str)
+    if by_posteriors and model_weights != "posteriors":
+        raise ValueError("model_weights: 'posteriors', an array [nq, 3] or None")
+    if model_weights is not None and not by_posteriors:
+        model_weights = np.asarray(model_weights, dtype=np.float64)
+    per = _block_size(max_quasars_per_batch, spectra, sel, model, samples)
+    out = {"selection": sel, "offsets": np.zeros(sel.size + 1, dtype=np.int64), "status": np.zeros(sel.size, dtype=np.int32)}
+    parts = {}
+    with closing(_resident_blocks(model, samples, spectra, sel, p, device, per, refined)) as blocks:
+        for lo, hi, idx, batch in blocks:
+            _stitch_refined(out, lo, hi, sel.size, _refine_block(batch, refined))
+            mw = _refined_model_weights(batch, components) if by_posteriors else None if model_weights is None else model_weights[idx]
+            res = getattr(batch, method)(weights="refined", components=components, model_weights=mw, **kw)
+            _stitch(out, lo, hi, res)
+            for name in tuple(flat) + tuple(rows):
+                if name in res:
+                    parts.setdefault(name, []).append(res[name])
+    for name, ps in parts.items():
+        out[name] = np.concatenate(ps, axis=0)
+    return out
+
+
 def marginal_continuum(model: dict, samples: dict, spectra, results: dict | None = None,
                        params: Parameters | None = None, selection=None, components=("dla",), model_weights=None,
                        sample_coefficients: bool = False, sample_rows=None, device: int = 0,
-                       max_quasars_per_batch: int | None = None, multi_models: bool = False, multi_rows=None) -> dict:
+                       max_quasars_per_batch: int | None = None, multi_models: bool = False, multi_rows=None,
+                       refined: dict | None = None) -> dict:
     """The marginal continuum (:meth:`Batch.marginal_continuum`) of the selected quasars of a processed run,
     batched like :func:`model_spectra`: nothing is swept again, the posterior weights come from the saved
     sample log-likelihoods.
@@ -1758,10 +1891,22 @@ def marginal_continuum(model: dict, samples: dict, spectra, results: dict | None
     ``sample_log_likelihoods_dla`` and ``sample_log_likelihoods_lls`` -- or ``multi_rows(idx)`` returns the dict of those
     three for quasars ``idx`` -- and ``model_weights`` is ``[nq, 2 + max_dlas]`` over ALL quasars (default and
     ``"posteriors"``: ``results["model_posteriors"]``; :func:`renormalised_model_posteriors` includes the quasars of the
-    reference's early exit).  The result also carries ``model_flags``; ``sample_coefficients`` are not offered."""
+    reference's early exit).  The result also carries ``model_flags``; ``sample_coefficients`` are not offered.
+
+    ``refined``: None, or ``dict(levels=, delta=, pad=, points=, prior=)`` (any may be left out): per resident block the
+    selected quasars are processed and refined (:meth:`Batch.process`, :meth:`Batch.refine`, the way
+    :func:`refine_absorbers` works; ``results`` supplies the priors) and the DLA component runs on the refined table
+    (``weights="refined"``: posterior mass outside the last box is ignored); ``model_weights="posteriors"`` then mixes by
+    :meth:`Batch.refined_posteriors`.  Components ``"null"`` and ``"dla"`` of single-DLA runs only.  The result gains
+    ``boxes`` and ``refine_status``; ``sample_coefficients`` are ``[n, S', k]``."""
     p = params or Parameters()
     spectra = list(spectra)
     sel = np.arange(len(spectra), dtype=np.int64) if selection is None else np.asarray(selection, dtype=np.int64).reshape(-1)
+    refined = _refined_options(refined, results, p)
+    if refined is not None:
+        return _mixture_refined("marginal_continuum", MARGINAL_CONTINUUM_ARRAYS, MARGINAL_CONTINUUM_ROWS, model, samples, spectra,
+                                p, sel, components, model_weights, refined, device, max_quasars_per_batch, multi_models,
+                                sample_coefficients=sample_coefficients)
     if multi_models:
         if sample_coefficients:
             raise ValueError("sample_coefficients are not offered with multi_models")
@@ -1820,17 +1965,24 @@ def predictive_residuals(pf: dict, flux, kept) -> dict:
 def predictive_flux(model: dict, samples: dict, spectra, results: dict | None = None,
                     params: Parameters | None = None, selection=None, components=("dla",), model_weights=None,
                     residuals: bool = False, sample_rows=None, device: int = 0,
-                    max_quasars_per_batch: int | None = None, multi_models: bool = False, multi_rows=None) -> dict:
+                    max_quasars_per_batch: int | None = None, multi_models: bool = False, multi_rows=None,
+                    refined: dict | None = None) -> dict:
     """The posterior predictive flux (:meth:`Batch.predictive_flux`) of the selected quasars of a processed run,
     batched like :func:`marginal_continuum`, whose arguments these are: nothing is swept again, the posterior weights
     come from the saved sample log-likelihoods; ``model_weights="posteriors"`` mixes by
     :func:`posterior_model_weights`.  ``residuals``: also the in-sample replicate ``residual`` per pixel and
     ``chi2``, ``num_kept`` per quasar (conservative; not leave-one-out).  Returns ``selection``, ``offsets``,
     ``status`` and the arrays of :meth:`Batch.predictive_flux` in selection order; results do not depend on the
-    batching.  ``multi_models``, ``multi_rows``: as :func:`marginal_continuum` (:meth:`Batch.predictive_flux_multi`)."""
+    batching.  ``multi_models``, ``multi_rows``, ``refined``: as :func:`marginal_continuum` (:meth:`Batch.predictive_flux_multi`;
+    with ``refined`` the DLA component runs on the refined table, posterior mass outside the last box ignored)."""
     p = params or Parameters()
     spectra = list(spectra)
     sel = np.arange(len(spectra), dtype=np.int64) if selection is None else np.asarray(selection, dtype=np.int64).reshape(-1)
+    refined = _refined_options(refined, results, p)
+    if refined is not None:
+        names = PREDICTIVE_FLUX_ARRAYS + (PREDICTIVE_FLUX_RESIDUALS if residuals else ())
+        return _mixture_refined("predictive_flux", names, PREDICTIVE_FLUX_ROWS if residuals else (), model, samples, spectra, p, sel,
+                                components, model_weights, refined, device, max_quasars_per_batch, multi_models, residuals=residuals)
     if multi_models:
         names = PREDICTIVE_FLUX_ARRAYS + (PREDICTIVE_FLUX_RESIDUALS if residuals else ())
         return _mixture_multi("predictive_flux_multi", names, PREDICTIVE_FLUX_ROWS if residuals else (), model, samples, spectra,

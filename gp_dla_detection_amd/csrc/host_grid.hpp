@@ -103,6 +103,20 @@ int launch_sample_weights(Staging &sg, const gpdla_batch *b, const GridSelection
   return launch_sample_weights(table, d_rows, S, nsel, d_w, d_flag, sg.st);
 }
 
+// The refined source of the DLA component (GPDLA_SPECTRA_WEIGHTS_REFINED): the resident tables of the batch's
+// last gpdla_batch_refine -- S' unit points, the lambda rows [nq][S'], the refine's copy of the metadata, every quasar's last
+// box -- and the refine status of every quasar, read once per call.  refined_table (host_refine.hpp) makes the checks of
+// the refined summaries and fills it.
+struct RefinedTable {
+  int64_t Sr = 0;
+  const double *lam = nullptr;        // [nq][Sr]
+  const QuasarMeta *rmeta = nullptr;  // [nq]
+  const double *box = nullptr;        // quasar q's last box at box + q * kRefineBoxStride
+  const int32_t *d_status = nullptr;  // [nq]
+  std::vector<int32_t> status;        // [nq] on the host
+};
+int refined_table(gpdla_context *c, gpdla_batch *b, RefinedTable *out);
+
 // bytes of per-sample [vech(B) | v] rows k_mc_contract may have in flight: the selected quasars are taken in
 // groups that fit (results do not depend on the grouping: every quasar is reduced on its own)
 constexpr size_t kMcScratchBytes = (size_t)512 << 20;
@@ -127,6 +141,17 @@ int launch_mc_contract(const McContractMultiArgs &ma, int64_t n, int64_t S, hipS
   const dim3 grid((unsigned)(n * args.c.chunks));
   if (args.nslots >= 2) hipLaunchKernelGGL((k_mc_contract_multi<RT, CPW, PT>), grid, dim3(256), 0, st, args);
   else hipLaunchKernelGGL((k_mc_contract<RT, CPW, PT>), grid, dim3(256), 0, st, args.c);
+  HIP_TRY(hipGetLastError());
+  return GPDLA_OK;
+}
+
+// k_mc_contract_boxed on the refine points (ba.c.S of them)
+template <int RT, int CPW, int PT>
+int launch_mc_contract_boxed(const McContractBoxedArgs &ba, int64_t n, hipStream_t st) {
+  McContractBoxedArgs args = ba;
+  args.c.chunks = (int32_t)((args.c.S + 16 * RT - 1) / (16 * RT));
+  if (n * args.c.chunks > 2147483647LL) return fail(GPDLA_ERR_UNSUPPORTED, "selection too large for one launch");
+  hipLaunchKernelGGL((k_mc_contract_boxed<RT, CPW, PT>), dim3((unsigned)(n * args.c.chunks)), dim3(256), 0, st, args);
   HIP_TRY(hipGetLastError());
   return GPDLA_OK;
 }
@@ -169,8 +194,9 @@ int validate_mixture(const MixtureRequest &rq, int64_t nq, int64_t S, bool has_l
     }
   }
   if (tables) {
-    if (rq.weights_source != GPDLA_SPECTRA_WEIGHTS_RESIDENT && rq.weights_source != GPDLA_SPECTRA_WEIGHTS_HOST)
-      return fail(GPDLA_ERR_INVALID_ARGUMENT, "a sampled component needs a weights source (resident table or host table)");
+    if (rq.weights_source != GPDLA_SPECTRA_WEIGHTS_RESIDENT && rq.weights_source != GPDLA_SPECTRA_WEIGHTS_HOST &&
+        rq.weights_source != GPDLA_SPECTRA_WEIGHTS_REFINED)
+      return fail(GPDLA_ERR_INVALID_ARGUMENT, "a sampled component needs a weights source (resident, host or refined table)");
     if (rq.weights_source == GPDLA_SPECTRA_WEIGHTS_HOST) {
       if ((tables & 2) && !rq.sample_log_likelihoods_dla)
         return fail(GPDLA_ERR_INVALID_ARGUMENT, "weights source is the host table but sample_log_likelihoods_dla is null");
@@ -200,11 +226,13 @@ struct MixtureSpec {
   const double *posteriors;         // gathered by entry, or (nullptr as well) the row (0, .., 0, 1)
   bool meanflux;
   int64_t capacity;
+  const RefinedTable *refined;      // md = 1: DLA(1) runs on the refined table with its own S' samples; nullptr: on `dla`
 };
 
 // of a single-DLA entry; `tables` as validate_mixture gave them (no table is looked up for a mixture that reaches none)
-MixtureSpec mixture_spec(const gpdla_batch *b, const MixtureRequest &rq, int tables) {
+MixtureSpec mixture_spec(const gpdla_batch *b, const MixtureRequest &rq, int tables, const RefinedTable *refined = nullptr) {
   MixtureSpec sp = {};
+  sp.refined = refined;
   sp.num_selected = rq.num_selected;
   sp.selection = rq.selection;
   sp.md = 1;
@@ -231,6 +259,11 @@ MixtureSpec mixture_spec(const gpdla_batch *b, const MixtureRequest &rq, int tab
 // Everything a kernel of a group indexes by entry is handed to it from the group's first entry on, so the weights and
 // the staged slice are the group's own, as in host_spectra_multi.hpp.  The scratch table is ONE group-sized buffer,
 // reused component after component.  Host buffers first, the Staging last (its rule).
+// A component has a sample count of its own, samples(comp): S, or the S' refine points of DLA(1) on a refined table
+// (sp.refined).  What is sized per group -- the scratch rows, the weights, the chunk flags -- is sized by the larger of the
+// counts, Smax; a component's rows of weights and of scratch are packed at its own count.  chunks counts the
+// kMcSolveChunk-blocks of Smax: the solve kernels run that many blocks for every component (a block past a component's
+// last sample writes zero partials and a clear flag), so the finish kernels read one chunk count.
 struct MixturePlan {
   gpdla_context *c;
   gpdla_batch *b;
@@ -238,7 +271,7 @@ struct MixturePlan {
   hipStream_t st = nullptr;
   int md = 0, ncomp = 0;              // ncomp = 1 + md sampled components
   unsigned reach = 0;                 // bit comp: some row weighs the component
-  int64_t nsel = 0, S = 0, nsub = 0;  // nsub: quasars a launch group
+  int64_t nsel = 0, S = 0, Smax = 0, nsub = 0;  // nsub: quasars a launch group
   int k = 0, nb = 0, ncol = 0;        // nb: packed triangle of B; ncol: a scratch row, [vech(B) | v]
   int chunks = 0;                     // kMcSolveChunk samples each
   size_t tot = 1;                     // max(gs.total, 1)
@@ -247,6 +280,7 @@ struct MixturePlan {
   std::vector<double> pw, pcol, post;  // [nsel][2 + md] normalised; [ncomp][nsel] columns, 0 for an undefined row
   std::vector<int64_t> rows_dla, rows_lls, rows_base;
   std::vector<int32_t> status, flags;
+  std::vector<uint8_t> not_refined;    // [nsel] refined source: the DLA component weighs, the quasar has no refined row
   Staging sg;
   double *d_pw = nullptr, *d_pcol = nullptr, *d_w = nullptr, *d_scratch = nullptr, *d_tab_dla = nullptr, *d_tab_lls = nullptr;
   uint32_t *d_tab_base = nullptr;
@@ -257,7 +291,10 @@ struct MixturePlan {
 
   MixturePlan(gpdla_context *ctx, gpdla_batch *batch, const MixtureSpec &spec) : c(ctx), b(batch), sp(spec), sg(ctx->stream) {}
   bool reaches(int comp) const { return (reach >> comp) & 1u; }
-  double *w(int comp) const { return d_w + (size_t)comp * nsub * S; }                  // [ncomp][nsub][S]
+  bool boxed(int comp) const { return comp == 1 && sp.refined; }
+  int64_t samples(int comp) const { return boxed(comp) ? sp.refined->Sr : S; }
+  const int32_t *perm(int comp) const { return boxed(comp) ? c->d_rperm : c->d_perm; }
+  double *w(int comp) const { return d_w + (size_t)comp * nsub * Smax; }               // [ncomp][nsub][samples(comp)], Smax apart
   const double *pm(int comp, int64_t s0) const { return d_pcol + (size_t)comp * nsel + s0; }
   int32_t *notpd(int comp) const { return d_notpd + (size_t)comp * nsub * chunks; }  // [ncomp][nsub][chunks]
   const double *nhi(int comp) const { return comp == 0 ? c->d_lls_nhi : c->d_nhi; }
@@ -267,6 +304,7 @@ struct MixturePlan {
     int rc;
     md = sp.md, ncomp = 1 + md;
     nsel = sp.num_selected, S = b->S;
+    Smax = std::max(S, samples(1));
     k = c->model.k, nb = k * (k + 1) / 2, ncol = nb + k;
     if (k > GPDLA_MAX_K) return fail(GPDLA_ERR_UNSUPPORTED, "k = %d > %d", k, GPDLA_MAX_K);
     HIP_TRY(hipSetDevice(c->device_id));
@@ -304,20 +342,28 @@ struct MixturePlan {
         if (p[1 + comp] > 0.0) reach |= 1u << comp;
       }
     }
+    // refined source: a quasar without a refined row is not evaluated (its lambda row is NaN: the finish kernels write NaN rows)
+    not_refined.assign((size_t)nsel, 0);
+    if (sp.refined)
+      for (int64_t s = 0; s < nsel; ++s)
+        if (pcol[(size_t)nsel + s] > 0.0 && sp.refined->status[(size_t)gs.sel[(size_t)s]] != 0) {
+          pcol[(size_t)nsel + s] = 0.0;
+          not_refined[(size_t)s] = 1;
+        }
     if ((reach & 1u) && !c->d_lls_nhi) return fail(GPDLA_ERR_INVALID_ARGUMENT, "the sub-DLA component needs lls_nhi_samples in the context's samples");
     status.resize((size_t)nsel);
     flags.assign((size_t)ncomp * nsel, 0);
     if ((rc = sg.put(&d_pw, pw.data(), pw.size())) || (rc = sg.put(&d_pcol, pcol.data(), pcol.size()))) return rc;
 
     // launch groups: the scratch rows of a group's quasars fit the budget
-    chunks = (int)((S + kMcSolveChunk - 1) / kMcSolveChunk);
+    chunks = (int)((Smax + kMcSolveChunk - 1) / kMcSolveChunk);
     nsub = nsel;
     if (reach) {
-      const size_t per_q = (size_t)S * ncol * sizeof(double);
+      const size_t per_q = (size_t)Smax * ncol * sizeof(double);
       nsub = std::min<int64_t>(nsel, std::max<int64_t>(1, (int64_t)(mc_scratch_bytes() / per_q)));
       if (nsub * chunks > 2147483647LL) return fail(GPDLA_ERR_UNSUPPORTED, "selection too large for one launch");
-      if ((rc = sg.tmp.alloc(&d_scratch, (size_t)nsub * S * ncol)) || (rc = sg.tmp.alloc(&d_notpd, (size_t)ncomp * nsub * chunks)) ||
-          (rc = sg.tmp.alloc(&d_w, (size_t)ncomp * nsub * S)))
+      if ((rc = sg.tmp.alloc(&d_scratch, (size_t)nsub * Smax * ncol)) || (rc = sg.tmp.alloc(&d_notpd, (size_t)ncomp * nsub * chunks)) ||
+          (rc = sg.tmp.alloc(&d_w, (size_t)ncomp * nsub * Smax)))
         return rc;
     }
     if ((rc = sg.tmp.alloc(&d_flag, (size_t)ncomp * nsel))) return rc;
@@ -329,7 +375,7 @@ struct MixturePlan {
     rows_dla.resize((size_t)nsel), rows_lls.resize((size_t)nsel), rows_base.resize(need_base ? (size_t)nsel : 0);
     for (int64_t s = 0; s < nsel; ++s) {
       const int64_t r = sp.resident ? gs.sel[(size_t)s] : s % nsub;
-      rows_dla[(size_t)s] = r * sp.dla_stride;
+      rows_dla[(size_t)s] = r * (sp.refined ? sp.refined->Sr : sp.dla_stride);
       rows_lls[(size_t)s] = r * sp.lls_stride;
       if (need_base) rows_base[(size_t)s] = r * (md - 1) * S;
     }
@@ -340,7 +386,7 @@ struct MixturePlan {
                          (need_lls && (rc = sg.tmp.alloc(&d_tab_lls, (size_t)nsub * sp.lls_stride))) ||
                          (need_base && (rc = sg.tmp.alloc(&d_tab_base, (size_t)nsub * (md - 1) * S)))))
       return rc;
-    tab_dla = sp.resident ? sp.dla : d_tab_dla;
+    tab_dla = sp.refined ? sp.refined->lam : sp.resident ? sp.dla : d_tab_dla;
     tab_lls = sp.resident ? sp.lls : d_tab_lls;
     tab_base = sp.resident ? sp.base : d_tab_base;
     return GPDLA_OK;
@@ -362,8 +408,8 @@ struct MixturePlan {
                                hipMemcpyHostToDevice, st));
     }
     if (reaches(0) && (rc = launch_sample_weights(tab_lls, d_rows_lls + s0, S, n, w(0), d_flag + s0, st))) return rc;
-    // DLA(1): row 0 of the quasar's [md][S] table
-    if (reaches(1) && (rc = launch_sample_weights(tab_dla, d_rows_dla + s0, S, n, w(1), d_flag + nsel + s0, st))) return rc;
+    // DLA(1): row 0 of the quasar's [md][S] table, or its row of the refined table
+    if (reaches(1) && (rc = launch_sample_weights(tab_dla, d_rows_dla + s0, samples(1), n, w(1), d_flag + nsel + s0, st))) return rc;
     int n_lo = 0, n_hi = 0;
     for (int nn = 2; nn <= md; ++nn)
       if (reaches(nn)) {
@@ -397,13 +443,13 @@ struct MixturePlan {
     ca.pix = b->d_pix;
     ca.Mi = b->d_Mi;
     ca.lam_pad = b->d_lam;
-    ca.offset_samples = c->d_offset;
-    ca.nhi = nhi(comp);
-    ca.perm = c->d_perm;
+    ca.offset_samples = boxed(comp) ? c->d_ru : c->d_offset;
+    ca.nhi = boxed(comp) ? c->d_rv : nhi(comp);
+    ca.perm = perm(comp);
     ca.sel = gs.d_sel + s0;
     ca.w = w(comp);
     ca.pm = pm(comp, s0);
-    ca.S = S;
+    ca.S = samples(comp);
     ca.num_lines = c->cfg.num_lines;
     ca.k = k;
     ca.s0 = 0;
@@ -413,17 +459,25 @@ struct MixturePlan {
     ma.base_start = d_rows_base + s0;
     ma.nslots = comp;  // (0, 1: one profile a sample, k_mc_contract itself)
     // k <= 20: 16 column tiles, 64 samples a block; k <= 40: 55 column tiles, 16 samples a block
+    if (boxed(comp)) {
+      McContractBoxedArgs ba;
+      ba.c = ca;
+      ba.rmeta = sp.refined->rmeta;
+      ba.box = sp.refined->box;
+      ba.rstatus = sp.refined->d_status;
+      return k <= 20 ? launch_mc_contract_boxed<4, 4, 32>(ba, n, st) : launch_mc_contract_boxed<1, 14, 64>(ba, n, st);
+    }
     return k <= 20 ? launch_mc_contract<4, 4, 32>(ma, n, S, st) : launch_mc_contract<1, 14, 64>(ma, n, S, st);
   }
 
   McSolveArgs solve_args(int comp, int64_t s0) const {
     McSolveArgs sa;
     sa.meta = b->d_meta;
-    sa.perm = c->d_perm;
+    sa.perm = perm(comp);
     sa.sel = gs.d_sel + s0;
     sa.w = w(comp);
     sa.pm = pm(comp, s0);
-    sa.S = S;
+    sa.S = samples(comp);
     sa.k = k;
     sa.chunks = chunks;
     sa.scratch = d_scratch;
@@ -436,17 +490,17 @@ struct MixturePlan {
   PfLiveArgs live_args(int comp, int64_t s0, int32_t *d_list, int32_t *d_count) const {
     PfLiveArgs la;
     la.meta = b->d_meta;
-    la.perm = c->d_perm;
+    la.perm = perm(comp);
     la.sel = gs.d_sel + s0;
     la.w = w(comp);
     la.pm = pm(comp, s0);
-    la.S = S;
+    la.S = samples(comp);
     la.list = d_list;
     la.count = d_count;
     return la;
   }
 
-  // (.p alone for k_pf_pixels: comp < 2)
+  // (.p alone for k_pf_pixels: comp < 2; boxed(comp): pixels_boxed_args)
   PfPixelsMultiArgs pixels_args(int comp, int64_t s0, int64_t tiles, const int32_t *d_list, const int32_t *d_count, double *d_sums) const {
     PfPixelsMultiArgs ma;
     PfPixelsArgs &pa = ma.p;
@@ -454,15 +508,15 @@ struct MixturePlan {
     pa.pix = b->d_pix;
     pa.lam_pad = b->d_lam;
     pa.z_qsos = b->d_z;
-    pa.offset_samples = c->d_offset;
-    pa.nhi = nhi(comp);
-    pa.perm = c->d_perm;
+    pa.offset_samples = boxed(comp) ? c->d_ru : c->d_offset;
+    pa.nhi = boxed(comp) ? c->d_rv : nhi(comp);
+    pa.perm = perm(comp);
     pa.sel = gs.d_sel + s0;
     pa.out_off = gs.d_off + s0;
     pa.w = w(comp);
     pa.pm = pm(comp, s0);
     pa.g = g;
-    pa.S = S;
+    pa.S = samples(comp);
     pa.num_lines = c->cfg.num_lines;
     pa.s0 = 0;
     pa.tiles = (int32_t)tiles;
@@ -474,6 +528,15 @@ struct MixturePlan {
     ma.base_start = d_rows_base + s0;
     ma.nslots = comp;
     return ma;
+  }
+
+  PfPixelsBoxedArgs pixels_boxed_args(const PfPixelsArgs &pa) const {
+    PfPixelsBoxedArgs ba;
+    ba.p = pa;
+    ba.rmeta = sp.refined->rmeta;
+    ba.box = sp.refined->box;
+    ba.rstatus = sp.refined->d_status;
+    return ba;
   }
 
   MixtureArgs mixture_args(int64_t s0) const {
@@ -493,6 +556,9 @@ struct MixturePlan {
     int rc;
     if ((rc = sg.fetch(status.data(), d_status, (size_t)nsel)) || (rc = sg.fetch(flags.data(), d_flag, flags.size()))) return rc;
     HIP_TRY(hipStreamSynchronize(st));
+    // (a prepare status, or an undefined row, keeps its own value: those rows are NaN for that reason)
+    for (int64_t s = 0; s < nsel; ++s)
+      if (not_refined[(size_t)s] && status[(size_t)s] == 0) status[(size_t)s] = GPDLA_SPECTRA_NOT_REFINED;
     if (status_out) std::memcpy(status_out, status.data(), (size_t)nsel * sizeof(int32_t));
     if (flags_out)
       for (int64_t s = 0; s < nsel; ++s) {

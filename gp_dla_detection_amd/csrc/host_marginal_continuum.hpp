@@ -18,13 +18,15 @@ int validate_marginal_continuum(const gpdla_marginal_continuum_request *rq, int6
 }
 
 // The product of an opened plan into the caller's arrays (out.offsets are written already; any other may be null).
-// sample_coefficients: [nsel][S][k] of the ONE sampled component the plan reaches, or nullptr.
+// sample_coefficients: [nsel][S][k] of the ONE sampled component the model weights reach, or nullptr.  S is decided by the
+// REQUEST, as the caller sized its array: S' where the plan runs the DLA component on a refined table (the validated request
+// then reaches the DLA table alone), the batch's S otherwise -- never by which rows survive the normalisation.
 int run_marginal_continuum(MixturePlan &plan, const gpdla_marginal_continuum_multi &out, double *sample_coefficients) {
   gpdla_context *c = plan.c;
   const gpdla_batch *b = plan.b;
   Staging &sg = plan.sg;
   hipStream_t st = plan.st;
-  const int64_t nsel = plan.nsel, S = plan.S, nsub = plan.nsub, total = plan.gs.total;
+  const int64_t nsel = plan.nsel, S = sample_coefficients && plan.sp.refined ? plan.sp.refined->Sr : plan.S, nsub = plan.nsub, total = plan.gs.total;
   const int k = plan.k, nb = plan.nb, plen = k + 2 * nb, chunks = plan.chunks;
   const size_t tot = plan.tot, part_stride = (size_t)nsub * chunks * plen;
   int rc;
@@ -99,9 +101,12 @@ int gpdla_batch_marginal_continuum(gpdla_context *c, gpdla_batch *b, const gpdla
   int tables = 0;
   if (rc || (rc = check_unconditioned(b, "marginal continuum")) ||
       (rc = validate_marginal_continuum(rq, b->nq, b->S, c->d_lls_nhi != nullptr, &tables)) || (rc = check_unchanged(c, b, true)) ||
-      (tables && rq->weights_source == GPDLA_SPECTRA_WEIGHTS_RESIDENT && (rc = check_processed(b, "resident weights: "))))
+      (tables && rq->weights_source != GPDLA_SPECTRA_WEIGHTS_HOST && (rc = check_processed(b, "resident weights: "))))
     return rc;
-  MixturePlan plan(c, b, mixture_spec(b, MixtureRequest(*rq), tables));
+  RefinedTable refined;  // (before the plan: the plan reads its host copy of the refine status)
+  const bool use_refined = (tables & 2) && rq->weights_source == GPDLA_SPECTRA_WEIGHTS_REFINED;
+  if (use_refined && (rc = refined_table(c, b, &refined))) return rc;
+  MixturePlan plan(c, b, mixture_spec(b, MixtureRequest(*rq), tables, use_refined ? &refined : nullptr));
   if ((rc = plan.open(out->offsets)) || plan.nsel == 0) return rc;
   const gpdla_marginal_continuum_multi arrays = {out->offsets, out->continuum_mean, out->continuum_var, out->continuum_var_between,
                                                  out->coef_mean, out->coef_cov_within, out->coef_cov_between, out->status, nullptr};

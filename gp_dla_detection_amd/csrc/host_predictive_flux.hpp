@@ -17,7 +17,7 @@ int run_predictive_flux(MixturePlan &plan, const gpdla_predictive_flux_multi &ou
   const gpdla_batch *b = plan.b;
   Staging &sg = plan.sg;
   hipStream_t st = plan.st;
-  const int64_t nsel = plan.nsel, S = plan.S, nsub = plan.nsub, total = plan.gs.total;
+  const int64_t nsel = plan.nsel, nsub = plan.nsub, total = plan.gs.total;
   const int chunks = plan.chunks;
   const size_t tot = plan.tot;
   int rc;
@@ -28,7 +28,7 @@ int run_predictive_flux(MixturePlan &plan, const gpdla_predictive_flux_multi &ou
   for (int j = 0; j < 5; ++j)
     if ((rc = sg.tmp.alloc(&d_out[j], tot))) return rc;
   if ((rc = sg.tmp.alloc(&d_status, (size_t)nsel))) return rc;
-  if (plan.reach && ((rc = sg.tmp.alloc(&d_sums, (size_t)plan.ncomp * tot * 4)) || (rc = sg.tmp.alloc(&d_list, (size_t)nsub * S)) ||
+  if (plan.reach && ((rc = sg.tmp.alloc(&d_sums, (size_t)plan.ncomp * tot * 4)) || (rc = sg.tmp.alloc(&d_list, (size_t)nsub * plan.Smax)) ||
                      (rc = sg.tmp.alloc(&d_count, (size_t)nsub))))
     return rc;
   // (gpdla_context_set_timing: the kernels of this loop are what gpdla_context_last_sweep_ms reports)
@@ -48,7 +48,8 @@ int run_predictive_flux(MixturePlan &plan, const gpdla_predictive_flux_multi &ou
       hipLaunchKernelGGL(k_pf_live, dim3((unsigned)n), dim3(256), 0, st, plan.live_args(comp, s0, d_list, d_count));
       HIP_TRY(hipGetLastError());
       const PfPixelsMultiArgs pa = plan.pixels_args(comp, s0, tiles, d_list, d_count, d_sums + (size_t)comp * tot * 4);
-      if (comp < 2) hipLaunchKernelGGL(k_pf_pixels, dim3((unsigned)(n * tiles)), dim3(256), 0, st, pa.p);
+      if (plan.boxed(comp)) hipLaunchKernelGGL(k_pf_pixels_boxed, dim3((unsigned)(n * tiles)), dim3(256), 0, st, plan.pixels_boxed_args(pa.p));
+      else if (comp < 2) hipLaunchKernelGGL(k_pf_pixels, dim3((unsigned)(n * tiles)), dim3(256), 0, st, pa.p);
       else hipLaunchKernelGGL(k_pf_pixels_multi, dim3((unsigned)(n * tiles)), dim3(256), 0, st, pa);
       HIP_TRY(hipGetLastError());
     }
@@ -102,9 +103,12 @@ int gpdla_batch_predictive_flux(gpdla_context *c, gpdla_batch *b, const gpdla_pr
   int tables = 0;
   if (rc || (rc = check_unconditioned(b, "predictive flux")) ||
       (rc = validate_predictive_flux(rq, b->nq, b->S, c->d_lls_nhi != nullptr, &tables)) || (rc = check_unchanged(c, b, true)) ||
-      (tables && rq->weights_source == GPDLA_SPECTRA_WEIGHTS_RESIDENT && (rc = check_processed(b, "resident weights: "))))
+      (tables && rq->weights_source != GPDLA_SPECTRA_WEIGHTS_HOST && (rc = check_processed(b, "resident weights: "))))
     return rc;
-  MixturePlan plan(c, b, mixture_spec(b, MixtureRequest(*rq), tables));
+  RefinedTable refined;  // (before the plan: the plan reads its host copy of the refine status)
+  const bool use_refined = (tables & 2) && rq->weights_source == GPDLA_SPECTRA_WEIGHTS_REFINED;
+  if (use_refined && (rc = refined_table(c, b, &refined))) return rc;
+  MixturePlan plan(c, b, mixture_spec(b, MixtureRequest(*rq), tables, use_refined ? &refined : nullptr));
   if ((rc = plan.open(out->offsets)) || plan.nsel == 0) return rc;
   const gpdla_predictive_flux_multi arrays = {out->offsets, out->flux_mean, out->flux_var, out->flux_var_within, out->flux_var_between,
                                               out->noise_var, out->status, nullptr};

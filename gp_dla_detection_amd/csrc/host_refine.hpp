@@ -94,6 +94,31 @@ int check_refinable(gpdla_context *c, gpdla_batch *b) {
   return GPDLA_OK;
 }
 
+// The refined source of the per-pixel products (host_grid.hpp): the checks of the refined summaries
+// -- the batch has been refined, on the context's present refine points -- then the resident tables, every quasar's
+// LAST box and the refine status of every quasar, downloaded once.
+int refined_table(gpdla_context *c, gpdla_batch *b, RefinedTable *out) {
+  int rc = check_refinable(c, b);
+  if (rc) return rc;
+  RefineBuffers *rf = b->rf;
+  if (!rf || rf->levels < 1 || rf->nq != b->nq) return fail(GPDLA_ERR_INVALID_ARGUMENT, "the batch has not been refined");
+  if (rf->Sr != c->Sr || rf->points_gen != c->refine_points_gen)
+    return fail(GPDLA_ERR_INVALID_ARGUMENT, "the refine points changed after the batch was refined");
+  HIP_TRY(hipSetDevice(c->device_id));
+  out->Sr = rf->Sr;
+  out->lam = rf->lam;
+  out->rmeta = rf->rmeta;
+  out->box = rf->box + 4 * (rf->levels - 1);
+  out->d_status = rf->status;
+  out->status.resize((size_t)b->nq);
+  hipStream_t st = c->stream;
+  StreamDrain drain{st};
+  HIP_TRY(hipStreamWaitEvent(st, b->ev_done, 0));
+  HIP_TRY(hipMemcpyAsync(out->status.data(), rf->status, (size_t)b->nq * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return GPDLA_OK;
+}
+
 }  // namespace
 
 extern "C" {

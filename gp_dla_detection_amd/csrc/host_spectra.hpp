@@ -32,8 +32,11 @@ int validate_model_spectra(const gpdla_model_spectra_request *rq, int64_t nq, in
     return fail(GPDLA_ERR_INVALID_ARGUMENT, "products = %d: a non-empty set of GPDLA_SPECTRA_MAP | _MOMENTS | _CONTINUUM", rq->products);
   if ((rc = validate_absorbers(rq->num_selected, rq->absorber_offsets, rq->absorber_z, rq->absorber_nhi))) return rc;
   if (rq->products & GPDLA_SPECTRA_MOMENTS) {
-    if (rq->weights_source != GPDLA_SPECTRA_WEIGHTS_RESIDENT && rq->weights_source != GPDLA_SPECTRA_WEIGHTS_HOST)
-      return fail(GPDLA_ERR_INVALID_ARGUMENT, "mean / var absorption need a weights source (resident table or host table)");
+    if (rq->weights_source != GPDLA_SPECTRA_WEIGHTS_RESIDENT && rq->weights_source != GPDLA_SPECTRA_WEIGHTS_HOST &&
+        rq->weights_source != GPDLA_SPECTRA_WEIGHTS_REFINED)
+      return fail(GPDLA_ERR_INVALID_ARGUMENT, "mean / var absorption need a weights source (resident, host or refined table)");
+    if (rq->weights_source == GPDLA_SPECTRA_WEIGHTS_REFINED && rq->sub_dla)
+      return fail(GPDLA_ERR_INVALID_ARGUMENT, "the refined table is the DLA table: sub_dla has no refined source");
     if (rq->weights_source == GPDLA_SPECTRA_WEIGHTS_HOST && !rq->sample_log_likelihoods)
       return fail(GPDLA_ERR_INVALID_ARGUMENT, "weights source is the host table but sample_log_likelihoods is null");
     if (rq->sub_dla && !has_lls)
@@ -70,7 +73,10 @@ int gpdla_batch_model_spectra(gpdla_context *c, gpdla_batch *b, const gpdla_mode
   const bool want_map = (rq->products & GPDLA_SPECTRA_MAP) && out->map_absorption;
   const bool want_mom = (rq->products & GPDLA_SPECTRA_MOMENTS) && (out->mean_absorption || out->var_absorption);
   const bool want_cont = (rq->products & GPDLA_SPECTRA_CONTINUUM) && (out->continuum || out->model_flux);
-  if (want_mom && rq->weights_source == GPDLA_SPECTRA_WEIGHTS_RESIDENT && (rc = check_processed(b, "resident weights: "))) return rc;
+  if (want_mom && rq->weights_source != GPDLA_SPECTRA_WEIGHTS_HOST && (rc = check_processed(b, "resident weights: "))) return rc;
+  const bool use_refined = want_mom && rq->weights_source == GPDLA_SPECTRA_WEIGHTS_REFINED;
+  RefinedTable refined;
+  if (use_refined && (rc = refined_table(c, b, &refined))) return rc;
   const int64_t nsel = rq->num_selected;
   HIP_TRY(hipSetDevice(c->device_id));
   hipStream_t st = c->stream;
@@ -95,14 +101,22 @@ int gpdla_batch_model_spectra(gpdla_context *c, gpdla_batch *b, const gpdla_mode
 
   // P2
   if (want_mom) {
-    const int64_t S = b->S;
+    const int64_t S = use_refined ? refined.Sr : b->S;  // (refined: the S' refine points)
     double *d_w = nullptr, *d_mean = nullptr, *d_var = nullptr, *d_part = nullptr;
     int32_t *d_flag = nullptr;
     if ((rc = sg.tmp.alloc(&d_w, (size_t)nsel * S)) || (rc = sg.tmp.alloc(&d_flag, (size_t)nsel)) ||
-        (rc = sg.tmp.alloc(&d_mean, tot)) || (rc = sg.tmp.alloc(&d_var, tot)) ||
-        (rc = launch_sample_weights(sg, b, gs, rq->weights_source == GPDLA_SPECTRA_WEIGHTS_HOST ? rq->sample_log_likelihoods : nullptr,
-                                    rq->sub_dla != 0, rows, d_w, d_flag)))
+        (rc = sg.tmp.alloc(&d_mean, tot)) || (rc = sg.tmp.alloc(&d_var, tot)))
       return rc;
+    if (use_refined) {  // the rows of the resident lambda table, S' apart (a quasar that was not refined has a NaN row)
+      int64_t *d_rows = nullptr;
+      rows.resize((size_t)nsel);
+      for (int64_t s = 0; s < nsel; ++s) rows[(size_t)s] = sel[(size_t)s] * S;
+      if ((rc = sg.put(&d_rows, rows.data(), (size_t)nsel)) || (rc = launch_sample_weights(refined.lam, d_rows, S, nsel, d_w, d_flag, st)))
+        return rc;
+    } else if ((rc = launch_sample_weights(sg, b, gs, rq->weights_source == GPDLA_SPECTRA_WEIGHTS_HOST ? rq->sample_log_likelihoods : nullptr,
+                                           rq->sub_dla != 0, rows, d_w, d_flag))) {
+      return rc;
+    }
 
     const int chunks = (int)((S + kMomWaves * 64 - 1) / (kMomWaves * 64));
     const int64_t stride = ((std::max<int64_t>(b->max_pix, 1) + 15) / 16) * 16;  // n_u <= stored pixels
@@ -117,9 +131,9 @@ int gpdla_batch_model_spectra(gpdla_context *c, gpdla_batch *b, const gpdla_mode
       SpectraMomentsArgs pa;
       pa.meta = b->d_meta;
       pa.lam_pad = b->d_lam;
-      pa.offset_samples = c->d_offset;
-      pa.nhi = rq->sub_dla ? c->d_lls_nhi : c->d_nhi;
-      pa.perm = c->d_perm;
+      pa.offset_samples = use_refined ? c->d_ru : c->d_offset;
+      pa.nhi = use_refined ? c->d_rv : rq->sub_dla ? c->d_lls_nhi : c->d_nhi;
+      pa.perm = use_refined ? c->d_rperm : c->d_perm;
       pa.sel = d_sel;
       pa.w = d_w;
       pa.S = S;
@@ -128,7 +142,16 @@ int gpdla_batch_model_spectra(gpdla_context *c, gpdla_batch *b, const gpdla_mode
       pa.chunks = chunks;
       pa.stride = stride;
       pa.part = d_part;
-      hipLaunchKernelGGL(k_spectra_moments, dim3((unsigned)(n * chunks)), dim3(kMomWaves * 64), 0, st, pa);
+      if (use_refined) {
+        SpectraMomentsBoxedArgs ba;
+        ba.m = pa;
+        ba.rmeta = refined.rmeta;
+        ba.box = refined.box;
+        ba.rstatus = refined.d_status;
+        hipLaunchKernelGGL(k_spectra_moments_boxed, dim3((unsigned)(n * chunks)), dim3(kMomWaves * 64), 0, st, ba);
+      } else {
+        hipLaunchKernelGGL(k_spectra_moments, dim3((unsigned)(n * chunks)), dim3(kMomWaves * 64), 0, st, pa);
+      }
       HIP_TRY(hipGetLastError());
       SpectraCombineArgs ca;
       ca.meta = b->d_meta;
@@ -150,6 +173,11 @@ int gpdla_batch_model_spectra(gpdla_context *c, gpdla_batch *b, const gpdla_mode
 
   // P3
   for (int64_t s = 0; s < nsel; ++s) status[(size_t)s] = gs.meta[(size_t)sel[(size_t)s]].status;
+  // refined moments of a quasar without a refined row: NaN rows (its lambda row is NaN) and the status bit
+  std::vector<uint8_t> not_refined((size_t)nsel, 0);
+  if (use_refined)
+    for (int64_t s = 0; s < nsel; ++s)
+      not_refined[(size_t)s] = status[(size_t)s] == 0 && refined.status[(size_t)sel[(size_t)s]] != 0;
   if (want_cont) {
     double *d_cont = nullptr, *d_flux = nullptr;
     int32_t *d_status = nullptr;
@@ -174,6 +202,8 @@ int gpdla_batch_model_spectra(gpdla_context *c, gpdla_batch *b, const gpdla_mode
       return rc;
   }
   HIP_TRY(hipStreamSynchronize(st));
+  for (int64_t s = 0; s < nsel; ++s)
+    if (not_refined[(size_t)s]) status[(size_t)s] |= GPDLA_SPECTRA_NOT_REFINED;
   if (out->status) std::memcpy(out->status, status.data(), (size_t)nsel * sizeof(int32_t));
   return GPDLA_OK;
 } GPDLA_NO_THROW

@@ -106,6 +106,29 @@ __global__ __launch_bounds__(256) void k_mc_contract_multi(McContractMultiArgs a
 }
 
 // ------------------------------------------------------------------------------------------
+// k_mc_contract_boxed<RT, CPW, PT>: k_mc_contract over the refine points of a refined batch, as
+// k_spectra_moments_boxed is k_spectra_moments: c.offset_samples = u, c.nhi = v, c.perm the order of u, c.S = S', c.w the
+// weights of the resident lambda rows; z' from the refine's copy of the metadata, N' = exp10(n_lo + (n_hi - n_lo) v) from the
+// quasar's last box.  The decomposition, the contraction and the scratch layout are k_mc_contract's, on S' samples.
+// ------------------------------------------------------------------------------------------
+struct McContractBoxedArgs {
+  McContractArgs c;
+  const QuasarMeta *rmeta;  // [nq]
+  const double *box;        // quasar q's LAST box at box + q * kRefineBoxStride
+  const int32_t *rstatus;   // [nq] refine status
+};
+
+template <int RT, int CPW, int PT>
+__global__ __launch_bounds__(256) void k_mc_contract_boxed(McContractBoxedArgs bx) {
+  const McContractArgs &a = bx.c;
+#define GPDLA_MC_CONTRACT_MULTI 0
+#define GPDLA_MC_CONTRACT_BOXED
+#include "mc_contract_body.hpp"
+#undef GPDLA_MC_CONTRACT_BOXED
+#undef GPDLA_MC_CONTRACT_MULTI
+}
+
+// ------------------------------------------------------------------------------------------
 // k_mc_solve: 256 threads, the 64 consecutive z_DLA positions `chunk` of one selected quasar.  Wave 0 lists
 // the positions of weight > 0 in index order; the four waves take them round robin, a sample per
 // wave: L L' = B_i = I + scratch row (column by column, as continuum_null_solve), X = L^-1 (lane c solves

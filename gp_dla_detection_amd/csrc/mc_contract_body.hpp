@@ -7,6 +7,11 @@
 // column set-up, the Mi tile, the weights, the contraction and the result store stand once.  By inclusion and not as a
 // templated device function: that form moved the register allocation of both kernels and ran slower (DESIGN.md
 // 4.25 (c)); this one compiles to the instructions of two written-out kernels (4.26).
+// With GPDLA_MC_CONTRACT_BOXED defined (and the switch at 0) the file is k_mc_contract_boxed over the refine points
+// (DESIGN.md 4.28): `bx` is its McContractBoxedArgs and `a` its McContractArgs, whose offset_samples, nhi, perm and S are
+// the unit points u, v, their order and S'.  Two prologue lines differ: z' takes the range of the refine's copy of the
+// quasar's metadata and N' = exp10(n_lo + (n_hi - n_lo) v) the quasar's last box, both in the boxed sweep's own
+// expressions (sweep_slim_body.hpp); a quasar without a box returns at once.
   constexpr int NS = 16 * RT, NSUB = 256 / NS, PPS = PT / NSUB, KS = GPDLA_MAX_K + 2;
   static_assert(PPS >= 1 && PPS * NSUB == PT && PT % 4 == 0, "tile shape");
   __shared__ double s_exp[kExpTab];
@@ -20,6 +25,9 @@
   const int64_t s = a.s0 + sl;
   const QuasarMeta m = a.meta[a.sel[s]];
   if (m.status != 0 || a.pm[s] == 0.0) return;  // (the whole block)
+#ifdef GPDLA_MC_CONTRACT_BOXED
+  if (bx.rstatus[a.sel[s]] != 0) return;  // (not refined, or unusable: no box; the host gives it pm = 0 as well)
+#endif
   const int smp = tid % NS, sub = tid / NS;
   const int64_t pos = (int64_t)chunk * NS + smp;
   const bool live = pos < a.S;
@@ -41,7 +49,12 @@
   const uint32_t *base = am.base + am.base_start[s] + i;
 #else
   const int L = a.num_lines;
+#ifdef GPDLA_MC_CONTRACT_BOXED
+  const QuasarMeta rm = bx.rmeta[a.sel[s]];
+  const double z_dla = rm.min_z_dla + (rm.max_z_dla - rm.min_z_dla) * a.offset_samples[i];
+#else
   const double z_dla = m.min_z_dla + (m.max_z_dla - m.min_z_dla) * a.offset_samples[i];
+#endif
   const double c_light = g_lines.c, inv_s = g_lines.inv_sqrt2_sigma;
   double mult[3], ms[3];
 #pragma unroll
@@ -51,7 +64,12 @@
   }
   const double cs = c_light * inv_s;
   const double inv_opz = 1.0 / (1 + z_dla);
+#ifdef GPDLA_MC_CONTRACT_BOXED
+  const double *box = bx.box + a.sel[s] * kRefineBoxStride;
+  const double nscale = -exp10(box[2] + (box[3] - box[2]) * a.nhi[i]) * g_lines.inv_sqrt2pi_sigma * kInvSqrtPi * kExpScale;
+#else
   const double nscale = -a.nhi[i] * g_lines.inv_sqrt2pi_sigma * kInvSqrtPi * kExpScale;
+#endif
 #endif
   const double *lam = a.lam_pad + m.lam_off;
   const int n_pad = m.n_u + 6;

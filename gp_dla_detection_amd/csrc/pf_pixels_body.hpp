@@ -5,6 +5,11 @@
 // PfPixelsMultiArgs, lists).  Under the switch stand the head of the slot loop and what is done with a broadened value; the
 // tile set-up, the live list, the sample's multipliers, the contraction, the epilogue and the reduction stand once
 // (DESIGN.md 4.26).
+// With GPDLA_PF_PIXELS_BOXED defined (and the switch at 0) the file is k_pf_pixels_boxed over the refine points
+// (DESIGN.md 4.28): `bx` is its PfPixelsBoxedArgs and `a` its PfPixelsArgs, whose offset_samples, nhi, perm and S are the
+// unit points u, v, their order and S'.  Two lines of the sample's multipliers differ: z' takes the range of the refine's
+// copy of the quasar's metadata and N' = exp10(n_lo + (n_hi - n_lo) v) the quasar's last box, both in the boxed sweep's
+// own expressions (sweep_slim_body.hpp); a quasar without a box returns at once.
   constexpr int RT = kPfRowTiles, NS = kPfSamples, PT = kPfPixTile, PPS = PT / (256 / NS), KS = GPDLA_MAX_K + 2;
   static_assert(NS == 64 && PT == 64 && PPS * (256 / NS) == PT, "a lane is a sample, a wave a 16-pixel column tile");
   __shared__ double s_exp[kExpTab];
@@ -21,6 +26,11 @@
   const QuasarMeta m = a.meta[q];
   const int p0 = tile * PT;
   if (m.status != 0 || a.pm[s] == 0.0 || p0 >= m.n_u) return;  // (the whole block)
+#ifdef GPDLA_PF_PIXELS_BOXED
+  if (bx.rstatus[q] != 0) return;  // (not refined, or unusable: no box; the host gives it pm = 0 as well)
+  const QuasarMeta rm = bx.rmeta[q];
+  const double *box = bx.box + q * kRefineBoxStride;
+#endif
 
   const int k = a.g.model.k, nb = k * (k + 1) / 2, ncol = nb + k;
   const int nbp = (nb + kPfSlab - 1) & ~(kPfSlab - 1), kp = (k + kPfSlab - 1) & ~(kPfSlab - 1);
@@ -90,7 +100,11 @@
 #else
       const int64_t sj = i;  // (no scope of its own: the slot loop's closing brace stands under the switch too)
 #endif
+#ifdef GPDLA_PF_PIXELS_BOXED
+      const double z_dla = rm.min_z_dla + (rm.max_z_dla - rm.min_z_dla) * a.offset_samples[sj];
+#else
       const double z_dla = m.min_z_dla + (m.max_z_dla - m.min_z_dla) * a.offset_samples[sj];
+#endif
       double mult[3], ms[3];
 #pragma unroll
       for (int l = 0; l < 3; ++l) {
@@ -98,7 +112,11 @@
         ms[l] = mult[l] * inv_s;
       }
       const double inv_opz = 1.0 / (1 + z_dla);
+#ifdef GPDLA_PF_PIXELS_BOXED
+      const double nscale = -exp10(box[2] + (box[3] - box[2]) * a.nhi[sj]) * g_lines.inv_sqrt2pi_sigma * kInvSqrtPi * kExpScale;
+#else
       const double nscale = -a.nhi[sj] * g_lines.inv_sqrt2pi_sigma * kInvSqrtPi * kExpScale;
+#endif
       auto raw = [&](int P) -> double {  // sample sj at padded pixel P
         const double lamP = lam[min(P, n_pad - 1)];
         return exp_table_scaled(nscale * sampled_line_sum(lamP, mult, ms, cs, inv_opz, z_dla, L), s_exp);

@@ -149,6 +149,27 @@ __global__ __launch_bounds__(256) void k_pf_pixels_multi(PfPixelsMultiArgs am) {
 }
 
 // ------------------------------------------------------------------------------------------
+// k_pf_pixels_boxed: k_pf_pixels over the refine points of a refined batch, as k_mc_contract_boxed is
+// k_mc_contract: p.offset_samples = u, p.nhi = v, p.perm the order of u, p.S = S'; the live list, the scratch rows and the
+// weights are those of the S' refined samples.
+// ------------------------------------------------------------------------------------------
+struct PfPixelsBoxedArgs {
+  PfPixelsArgs p;
+  const QuasarMeta *rmeta;  // [nq]
+  const double *box;        // quasar q's LAST box at box + q * kRefineBoxStride
+  const int32_t *rstatus;   // [nq] refine status
+};
+
+__global__ __launch_bounds__(256) void k_pf_pixels_boxed(PfPixelsBoxedArgs bx) {
+  const PfPixelsArgs &a = bx.p;
+#define GPDLA_PF_PIXELS_MULTI 0
+#define GPDLA_PF_PIXELS_BOXED
+#include "pf_pixels_body.hpp"
+#undef GPDLA_PF_PIXELS_BOXED
+#undef GPDLA_PF_PIXELS_MULTI
+}
+
+// ------------------------------------------------------------------------------------------
 // k_pf_finish: one block per selected quasar of a launch group.
 //   The null component of weight p_0 > 0: c_0 from continuum_null_solve with a = 1 (the function k_mc_finish and
 //   k_spectra_continuum call), Sigma_0 = B_0^-1 through L^-1; per pixel (model_tile_rows) t_0 = mu + m' c_0,

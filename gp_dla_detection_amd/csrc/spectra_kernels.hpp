@@ -19,6 +19,7 @@
 #pragma once
 #include "continuum_solve.hpp"
 #include "sampled_profile.hpp"
+#include "sweep_primitives.hpp"  // kRefineBoxStride
 
 namespace gpdla {
 
@@ -148,6 +149,29 @@ constexpr int kMomWaves = 4;
 __global__ __launch_bounds__(kMomWaves * 64) void k_spectra_moments(SpectraMomentsArgs a) {
 #define GPDLA_SPECTRA_MOMENTS_MULTI 0
 #include "spectra_moments_body.hpp"
+#undef GPDLA_SPECTRA_MOMENTS_MULTI
+}
+
+// ------------------------------------------------------------------------------------------
+// k_spectra_moments_boxed: k_spectra_moments over the refine points of a refined batch.  The samples
+// are the context's S' unit points (m.offset_samples = u, m.nhi = v, m.perm the order of u, m.S = S', m.w the weights of the
+// resident lambda rows) mapped through the quasar's last box: z' = z_lo + (z_hi - z_lo) u with the range read from the
+// refine's copy of the metadata, N' = exp10(n_lo + (n_hi - n_lo) v) -- the boxed sweep's own two expressions.  Everything
+// after the prologue is k_spectra_moments; a quasar whose refine status is not 0 has no box and is not evaluated.
+// ------------------------------------------------------------------------------------------
+struct SpectraMomentsBoxedArgs {
+  SpectraMomentsArgs m;
+  const QuasarMeta *rmeta;  // [nq] the refine's copy: min_z_dla, max_z_dla are the last box's z_lo, z_hi
+  const double *box;        // quasar q's LAST box at box + q * kRefineBoxStride: (z_lo, z_hi, n_lo, n_hi)
+  const int32_t *rstatus;   // [nq] refine status: 0 = the quasar has a box and a lambda row
+};
+
+__global__ __launch_bounds__(kMomWaves * 64) void k_spectra_moments_boxed(SpectraMomentsBoxedArgs bx) {
+  const SpectraMomentsArgs &a = bx.m;
+#define GPDLA_SPECTRA_MOMENTS_MULTI 0
+#define GPDLA_SPECTRA_MOMENTS_BOXED
+#include "spectra_moments_body.hpp"
+#undef GPDLA_SPECTRA_MOMENTS_BOXED
 #undef GPDLA_SPECTRA_MOMENTS_MULTI
 }
 

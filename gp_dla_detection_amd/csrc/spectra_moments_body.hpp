@@ -8,6 +8,11 @@
 //   1  model DLA(n), n >= 2: the product over the n slots in the lane's own s_out row, slot by slot INSIDE the tile; the
 //      multipliers per slot, the six carried raw values recomputed per tile, the weights read from s_w every tile
 // The shared memory, the decomposition, the transpose, the reduction and the stores stand once.
+// With GPDLA_SPECTRA_MOMENTS_BOXED defined (and the switch at 0) the file is k_spectra_moments_boxed over the refine
+// points: `bx` is its SpectraMomentsBoxedArgs and `a` its SpectraMomentsArgs, whose offset_samples, nhi,
+// perm and S are the unit points u, v, their order and S'.  Two prologue lines differ: z' takes the range of the refine's
+// copy of the quasar's metadata and N' = exp10(n_lo + (n_hi - n_lo) v) the quasar's last box, both in the boxed sweep's
+// own expressions (sweep_slim_body.hpp); a quasar without a box returns at once.
   __shared__ double s_exp[kExpTab];
   __shared__ double s_out[kMomWaves][64][kProfTile + 1];
   __shared__ double s_w[kMomWaves][64];
@@ -30,6 +35,9 @@
   const int64_t s = a.s0 + sl;
   const QuasarMeta m = a.meta[a.sel[s]];
   if (m.status != 0) return;  // (the whole block: no sample redshifts; k_spectra_combine writes NaN)
+#ifdef GPDLA_SPECTRA_MOMENTS_BOXED
+  if (bx.rstatus[a.sel[s]] != 0) return;  // (not refined, or unusable: no box; its lambda row is NaN and so are its rows)
+#endif
 #endif
   const int L = a.num_lines;
   const int64_t pos = (int64_t)chunk * (kMomWaves * 64) + wave * 64 + lane;
@@ -46,7 +54,12 @@
   const double cs = c_light * inv_s;
   const uint32_t *base = a.base + a.base_start[sl] + i;
 #else
+#ifdef GPDLA_SPECTRA_MOMENTS_BOXED
+  const QuasarMeta rm = bx.rmeta[a.sel[s]];
+  const double z_dla = rm.min_z_dla + (rm.max_z_dla - rm.min_z_dla) * a.offset_samples[i];
+#else
   const double z_dla = m.min_z_dla + (m.max_z_dla - m.min_z_dla) * a.offset_samples[i];
+#endif
   const double c_light = g_lines.c, inv_s = g_lines.inv_sqrt2_sigma;
   double mult[3], ms[3];
 #pragma unroll
@@ -56,7 +69,12 @@
   }
   const double cs = c_light * inv_s;
   const double inv_opz = 1.0 / (1 + z_dla);
+#ifdef GPDLA_SPECTRA_MOMENTS_BOXED
+  const double *box = bx.box + a.sel[s] * kRefineBoxStride;
+  const double nscale = -exp10(box[2] + (box[3] - box[2]) * a.nhi[i]) * g_lines.inv_sqrt2pi_sigma * kInvSqrtPi * kExpScale;
+#else
   const double nscale = -a.nhi[i] * g_lines.inv_sqrt2pi_sigma * kInvSqrtPi * kExpScale;
+#endif
 #endif
   const double *lam = a.lam_pad + m.lam_off;
   const int n_pad = m.n_u + 6;

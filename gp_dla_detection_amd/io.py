@@ -847,6 +847,15 @@ MODEL_SPECTRA_MULTI_CELLS = ("mean_absorption_lls", "var_absorption_lls", "expec
 MODEL_SPECTRA_MULTI_PLANE_CELLS = ("mean_absorption_models", "var_absorption_models")
 
 
+def _put_refined(w, res: dict) -> None:
+    """The boxes a refined product was computed on (``refined=`` of the drivers in :mod:`api`): ``refine_boxes``
+    [N x 4 levels] with a quasar's level l in columns 4 l .. 4 l + 3 as (z_lo, z_hi, n_lo, n_hi), and ``refine_status``."""
+    if "boxes" in res:
+        b = np.asarray(res["boxes"], dtype=np.float64)
+        w.put("refine_boxes", np.ascontiguousarray(b.reshape(b.shape[0], -1)))
+        w.put("refine_status", np.asarray(res["refine_status"], dtype=np.float64))
+
+
 def save_model_spectra(path: str, spectra: dict, **run_metadata) -> None:
     """What :func:`api.model_spectra` returns as a ``-v7.3`` file: ``quasar_ind`` (the selection, 1-based
     like every MATLAB index), ``num_pixels`` and ``status`` as columns, the selected absorbers as the
@@ -866,6 +875,7 @@ def save_model_spectra(path: str, spectra: dict, **run_metadata) -> None:
         w.put("quasar_ind", np.asarray(spectra.get("selection", np.arange(nsel)), dtype=np.float64) + 1)
         w.put("num_pixels", np.diff(off).astype(np.float64))
         w.put("status", np.asarray(spectra.get("status", np.zeros(nsel)), dtype=np.float64))
+        _put_refined(w, spectra)
         if "absorber_offsets" in spectra:
             a = np.asarray(spectra["absorber_offsets"], dtype=np.int64)
             for name, key in (("map_z_dlas", "absorber_z_dlas"), ("map_log_nhis", "absorber_log_nhis")):
@@ -907,6 +917,7 @@ def save_marginal_continuum(path: str, mc: dict, **run_metadata) -> None:
         w.put("quasar_ind", np.asarray(mc.get("selection", np.arange(nsel)), dtype=np.float64) + 1)
         w.put("num_pixels", np.diff(off).astype(np.float64))
         w.put("status", np.asarray(mc.get("status", np.zeros(nsel)), dtype=np.float64))
+        _put_refined(w, mc)
         for name in MARGINAL_CONTINUUM_CELLS:
             if name in mc:
                 v = np.asarray(mc[name], dtype=np.float64)
@@ -943,6 +954,7 @@ def save_predictive_flux(path: str, pf: dict, **run_metadata) -> None:
         w.put("quasar_ind", np.asarray(pf.get("selection", np.arange(nsel)), dtype=np.float64) + 1)
         w.put("num_pixels", np.diff(off).astype(np.float64))
         w.put("status", np.asarray(pf.get("status", np.zeros(nsel)), dtype=np.float64))
+        _put_refined(w, pf)
         for name in PREDICTIVE_FLUX_CELLS:
             if name in pf:
                 v = np.asarray(pf[name], dtype=np.float64)

@@ -12,6 +12,11 @@ flux (:func:`gp_dla_detection_amd.api.model_spectra`).  Nothing is swept again: 
 are the rows of the processed file's sample table, streamed in blocks of selected quasars the way
 ``cddf.from_processed_file`` reads them.
 
+``--refined [--levels L] [--points N]`` (single-DLA files; the default products, ``--marginal-continuum`` and
+``--predictive-flux``): the selected quasars are processed again and refined block by block, and the sampled DLA
+profile is averaged over the refined table instead of the first pass's (posterior mass outside a quasar's
+last box is ignored).  The file gains ``refine_boxes`` and ``refine_status``.
+
 The module shares its name with :func:`gp_dla_detection_amd.api.model_spectra`, so it is callable:
 ``gp_dla_detection_amd.model_spectra(model, samples, spectra, results, ...)`` is that function.
 """
@@ -96,9 +101,9 @@ def select(results: dict, p_dla: float | None, indices) -> np.ndarray:
 def run(preloaded: str, catalog: str, model_file: str, samples_file: str, processed: str, out: str,
         p_dla: float | None = None, indices=None, products=("map", "moments", "continuum"), multi: bool | None = None,
         moments_sub_dla: bool = False, device: int = 0, max_quasars_per_batch: int | None = None,
-        multi_models: bool = False) -> dict:
+        multi_models: bool = False, refined: dict | None = None) -> dict:
     small = [k for k in ("model_posteriors", "p_dlas", "MAP_z_dlas", "MAP_log_nhis", "single_MAP_z_dlas",
-                         "single_MAP_log_nhis", "test_ind")]
+                         "single_MAP_log_nhis", "test_ind")] + (["log_priors_no_dla", "log_priors_dla"] if refined is not None else [])
     results = io.loadmat73(processed, small)
     results = {k[len("single_"):] if k.startswith("single_") else k: v for k, v in results.items()}
     mp = np.asarray(results["model_posteriors"], dtype=np.float64)
@@ -117,21 +122,25 @@ def run(preloaded: str, catalog: str, model_file: str, samples_file: str, proces
     model, samples = io.load_learned_model(model_file), io.load_dla_samples(samples_file)
     if multi_models and not is_multi:
         raise ValueError("--multi-models needs a multi-DLA processed file")
-    rows, close = sample_row_reader(processed, sub_dla=moments_sub_dla)
+    # (refined: the weights are the refined table's, so the file's sample tables are neither needed nor opened)
+    rows, close = sample_row_reader(processed, sub_dla=moments_sub_dla) if refined is None else (None, lambda: None)
     multi_rows, close_multi = multi_row_reader(processed) if multi_models else (None, lambda: None)
+    priors = None if refined is None else {k: np.asarray(results[k], dtype=np.float64).reshape(-1)[sel]
+                                           for k in ("log_priors_no_dla", "log_priors_dla")}
     try:  # the loaded list holds the selected quasars only: positions 0 .. len(sel) - 1 map to sel
-        res = api.model_spectra(model, samples, spectra_sel, None, params=MultiParameters() if is_multi else Parameters(),
+        res = api.model_spectra(model, samples, spectra_sel, priors, params=MultiParameters() if is_multi else Parameters(),
                                 absorbers=absorbers_sel, moments_sub_dla=moments_sub_dla, products=products,
-                                sample_rows=lambda idx: rows(sel[idx]), device=device,
+                                sample_rows=None if rows is None else (lambda idx: rows(sel[idx])), device=device,
                                 max_quasars_per_batch=max_quasars_per_batch, multi_models=multi_models,
                                 model_weights=mp[sel] if multi_models else None,
-                                multi_rows=(lambda idx: multi_rows(sel[idx])) if multi_models else None)
+                                multi_rows=(lambda idx: multi_rows(sel[idx])) if multi_models else None, refined=refined)
     finally:
         close()
         close_multi()
     res["selection"] = sel
     res["absorber_offsets"], res["absorber_z_dlas"], res["absorber_log_nhis"] = absorbers_sel
-    io.save_model_spectra(out, res, processed_file=str(processed), multi_dla=np.float64(is_multi))
+    io.save_model_spectra(out, res, processed_file=str(processed), multi_dla=np.float64(is_multi),
+                          **({"refined": np.float64(1)} if refined is not None else {}))
     return res
 
 
@@ -140,8 +149,9 @@ def _run_mixture(call, preloaded, catalog, model_file, samples_file, processed, 
     """What ``--marginal-continuum`` and ``--predictive-flux`` share: the selection of a processed file, its spectra,
     its sample tables streamed like the moments' rows, and ``call`` (:func:`api.marginal_continuum` or
     :func:`api.predictive_flux`) on them.  Returns ``(result with its selection, is_multi, components)``."""
-    small = ["model_posteriors", "p_dlas", "p_no_dlas", "p_lls", "test_ind"]
-    results = {k: np.asarray(v, dtype=np.float64).reshape(-1) if k.startswith("p_") else v
+    small = ["model_posteriors", "p_dlas", "p_no_dlas", "p_lls", "test_ind"] + (
+        ["log_priors_no_dla", "log_priors_dla"] if more.get("refined") is not None else [])
+    results = {k: np.asarray(v, dtype=np.float64).reshape(-1) if k.startswith(("p_", "log_priors_")) else v
                for k, v in io.loadmat73(processed, small).items()}
     is_multi = np.asarray(results["model_posteriors"]).shape[1] > 2 if multi is None else bool(multi)
     sel = select(results, p_dla, indices)
@@ -151,8 +161,9 @@ def _run_mixture(call, preloaded, catalog, model_file, samples_file, processed, 
     spectra_sel = io.load_preloaded_qsos(preloaded, z_qsos, run_pos[sel])
     model, samples = io.load_learned_model(model_file), io.load_dla_samples(samples_file)
     components = tuple(components)
-    readers = {name: sample_row_reader(processed, sub_dla=name == "sub_dla") for name in components if name != "null"}
-    res_sel = {k: v[sel] for k, v in results.items() if k.startswith("p_")}
+    readers = {} if more.get("refined") is not None else {
+        name: sample_row_reader(processed, sub_dla=name == "sub_dla") for name in components if name != "null"}
+    res_sel = {k: v[sel] for k, v in results.items() if k.startswith(("p_", "log_priors_"))}
     try:  # the loaded list holds the selected quasars only: positions 0 .. len(sel) - 1 map to sel
         res = call(model, samples, spectra_sel, res_sel, params=MultiParameters() if is_multi else Parameters(),
                    components=components, model_weights="posteriors" if model_weights == "posteriors" else None,
@@ -198,31 +209,38 @@ def _run_mixture_multi(call, preloaded, catalog, model_file, samples_file, proce
 def run_marginal_continuum(preloaded: str, catalog: str, model_file: str, samples_file: str, processed: str, out: str,
                            p_dla: float | None = None, indices=None, components=("dla",), model_weights="posteriors",
                            multi: bool | None = None, device: int = 0, max_quasars_per_batch: int | None = None,
-                           multi_models: bool = False) -> dict:
+                           multi_models: bool = False, refined: dict | None = None) -> dict:
     """``--marginal-continuum``: :func:`api.marginal_continuum` of the selected quasars of a processed file, its
     sample tables streamed like the moments' rows, written by :func:`io.save_marginal_continuum`.
     ``model_weights``: ``"posteriors"`` (p_no_dlas, p_lls or 0, p_dlas of the file) or ``"equal"``.
     ``multi_models`` (``--multi-models``): the mixture over all models of a multi-DLA file (DESIGN.md 4.25);
-    ``components`` is ignored, ``model_weights`` is the file's ``model_posteriors`` or equal over all of them."""
+    ``components`` is ignored, ``model_weights`` is the file's ``model_posteriors`` or equal over all of them.
+    ``refined`` (``--refined``): ``refined=`` of :func:`api.marginal_continuum`; ``"posteriors"`` are then the refined ones."""
+    if multi_models and refined is not None:
+        raise ValueError("--refined: not with --multi-models (a multi-DLA batch cannot be refined)")
     if multi_models:
         res = _run_mixture_multi(api.marginal_continuum, preloaded, catalog, model_file, samples_file, processed, p_dla, indices,
                                  model_weights, device, max_quasars_per_batch)
         io.save_marginal_continuum(out, res, processed_file=str(processed), multi_dla=np.float64(1), multi_models=np.float64(1))
         return res
     res, is_multi, components = _run_mixture(api.marginal_continuum, preloaded, catalog, model_file, samples_file, processed,
-                                             p_dla, indices, components, model_weights, multi, device, max_quasars_per_batch)
+                                             p_dla, indices, components, model_weights, multi, device, max_quasars_per_batch,
+                                             **({"refined": refined} if refined is not None else {}))
     io.save_marginal_continuum(out, res, processed_file=str(processed), multi_dla=np.float64(is_multi),
-                               components=",".join(components))
+                               components=",".join(components), **({"refined": np.float64(1)} if refined is not None else {}))
     return res
 
 
 def run_predictive_flux(preloaded: str, catalog: str, model_file: str, samples_file: str, processed: str, out: str,
                         p_dla: float | None = None, indices=None, components=("dla",), model_weights="posteriors",
                         residuals: bool = False, multi: bool | None = None, device: int = 0,
-                        max_quasars_per_batch: int | None = None, multi_models: bool = False) -> dict:
+                        max_quasars_per_batch: int | None = None, multi_models: bool = False,
+                        refined: dict | None = None) -> dict:
     """``--predictive-flux``: :func:`api.predictive_flux` of the selected quasars of a processed file, its sample
     tables streamed like the moments' rows, written by :func:`io.save_predictive_flux`.  The arguments are those of
     :func:`run_marginal_continuum`; ``residuals``: also the in-sample replicate residuals (``--residuals``)."""
+    if multi_models and refined is not None:
+        raise ValueError("--refined: not with --multi-models (a multi-DLA batch cannot be refined)")
     if multi_models:
         res = _run_mixture_multi(api.predictive_flux, preloaded, catalog, model_file, samples_file, processed, p_dla, indices,
                                  model_weights, device, max_quasars_per_batch, residuals=residuals)
@@ -230,9 +248,9 @@ def run_predictive_flux(preloaded: str, catalog: str, model_file: str, samples_f
         return res
     res, is_multi, components = _run_mixture(api.predictive_flux, preloaded, catalog, model_file, samples_file, processed,
                                              p_dla, indices, components, model_weights, multi, device, max_quasars_per_batch,
-                                             residuals=residuals)
+                                             residuals=residuals, **({"refined": refined} if refined is not None else {}))
     io.save_predictive_flux(out, res, processed_file=str(processed), multi_dla=np.float64(is_multi),
-                            components=",".join(components))
+                            components=",".join(components), **({"refined": np.float64(1)} if refined is not None else {}))
     return res
 
 
@@ -262,26 +280,35 @@ def main(argv=None) -> int:
     ap.add_argument("--model-weights", choices=("posteriors", "equal"), default="posteriors",
                     help="--marginal-continuum, --predictive-flux: mix the components by the file's posteriors, or equally "
                          "(--multi-models: model_posteriors, or equal over all 2 + max_dlas components)")
+    ap.add_argument("--refined", action="store_true",
+                    help="a single-DLA file: process and refine the selected quasars again and average over the refined "
+                         "table (DESIGN.md 4.28); the default products, --marginal-continuum and --predictive-flux")
+    ap.add_argument("--levels", type=int, default=None, help="--refined: refine levels (default 2)")
+    ap.add_argument("--points", type=int, default=None, help="--refined: number of refine points (default: the DLA samples)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--max-quasars-per-batch", type=int, default=None)
     a = ap.parse_args(argv)
     idx = None if a.indices is None else [int(x) for x in a.indices.split(",") if x]
+    if (a.levels is not None or a.points is not None) and not a.refined:
+        ap.error("--levels and --points go with --refined")
+    refined = dict(levels=a.levels, points=a.points) if a.refined else None
     if a.predictive_flux:
         res = run_predictive_flux(a.preloaded, a.catalog, a.model, a.samples, a.processed, a.out, p_dla=a.p_dla, indices=idx,
                                   components=tuple(x for x in a.components.split(",") if x), model_weights=a.model_weights,
                                   residuals=a.residuals, device=a.device, max_quasars_per_batch=a.max_quasars_per_batch,
-                                  multi_models=a.multi_models)
+                                  multi_models=a.multi_models, refined=refined)
         print(f"wrote {a.out}: {res['selection'].size} quasars, {int(res['offsets'][-1])} grid pixels")
         return 0
     if a.marginal_continuum:
         res = run_marginal_continuum(a.preloaded, a.catalog, a.model, a.samples, a.processed, a.out, p_dla=a.p_dla, indices=idx,
                                      components=tuple(x for x in a.components.split(",") if x), model_weights=a.model_weights,
-                                     device=a.device, max_quasars_per_batch=a.max_quasars_per_batch, multi_models=a.multi_models)
+                                     device=a.device, max_quasars_per_batch=a.max_quasars_per_batch, multi_models=a.multi_models,
+                                     refined=refined)
         print(f"wrote {a.out}: {res['selection'].size} quasars, {int(res['offsets'][-1])} grid pixels")
         return 0
     res = run(a.preloaded, a.catalog, a.model, a.samples, a.processed, a.out, p_dla=a.p_dla, indices=idx,
               products=tuple(a.products.split(",")), moments_sub_dla=a.moments_sub_dla, device=a.device,
-              max_quasars_per_batch=a.max_quasars_per_batch, multi_models=a.multi_models)
+              max_quasars_per_batch=a.max_quasars_per_batch, multi_models=a.multi_models, refined=refined)
     print(f"wrote {a.out}: {res['selection'].size} quasars, {int(res['offsets'][-1])} grid pixels")
     return 0
 

@@ -613,6 +613,19 @@ int gpdla_stats_bootstrap_sums(int64_t num_rows, int num_columns, const double *
  * Sums run in a fixed order without atomics: outputs are bit-identical from run to run, for any
  * selection order and any batching, and for the resident and the host form of the same table.
  * The call returns when the outputs are in the caller's arrays.
+ *
+ * THE REFINED SOURCE (GPDLA_SPECTRA_WEIGHTS_REFINED; additive, GPDLA_ABI_VERSION unchanged).  After
+ * gpdla_batch_refine with L levels on the context's S' refine points (u_j, v_j), a quasar q of refine status 0 has its
+ * last box (z_lo, z_hi, n_lo, n_hi) = boxes[q][L-1] and the resident table lambda_j =
+ * sample_log_posteriors_refined[q][j].  Its refined sample j is z'_j = z_lo + (z_hi - z_lo) u_j, N'_j =
+ * exp10(n_lo + (n_hi - n_lo) v_j), in the arithmetic of the boxed sweep that produced l'_j.  With the refined source,
+ * mean_absorption and var_absorption are their definitions above with (S, offset_i, N_i, l, min_z_dla, max_z_dla) replaced
+ * by (S', u, N', lambda, z_lo, z_hi): the weights are exp(lambda_j - max) / Sum, a NaN weighs 0, an entry the separation
+ * mask set to -inf weighs 0.  Posterior mass outside the last box is ignored -- the convention of the refined parameter
+ * summaries.  The refined table is the DLA table: sub_dla != 0 is refused with it.  The call returns
+ * GPDLA_ERR_INVALID_ARGUMENT when the batch has not been refined or the context's refine points changed since.  A selected
+ * quasar whose refine status is not 0 (outside the refine's selection, or unusable) gets NaN rows and the status bit
+ * GPDLA_SPECTRA_NOT_REFINED.  The promise of fixed-order sums holds as above.
  * ------------------------------------------------------------------------------------------- */
 #define GPDLA_SPECTRA_MAX_ABSORBERS 8
 #define GPDLA_SPECTRA_MAP 1        /* products bit: map_absorption */
@@ -621,6 +634,8 @@ int gpdla_stats_bootstrap_sums(int64_t num_rows, int num_columns, const double *
 #define GPDLA_SPECTRA_WEIGHTS_NONE 0
 #define GPDLA_SPECTRA_WEIGHTS_RESIDENT 1
 #define GPDLA_SPECTRA_WEIGHTS_HOST 2
+#define GPDLA_SPECTRA_WEIGHTS_REFINED 3  /* the resident refined table of gpdla_batch_refine (the DLA table only) */
+#define GPDLA_SPECTRA_NOT_REFINED 16     /* status bit: refined source, the quasar has no refined table (NaN rows) */
 typedef struct {
   int64_t num_selected;
   const int64_t *selection;          /* [num_selected] quasars of the batch; NULL = 0 .. num_selected-1 */
@@ -1295,11 +1310,24 @@ int64_t gpdla_debug_last_maps_launches(void);
  * gives NaN rows and status 0.  For a multi-DLA batch the resident tables are model DLA(1) and the sub-DLA
  * table.  A conditioned batch is refused.  Sums run in a fixed order without atomics: outputs are bit-identical
  * for any selection order and launch grouping and for the resident and the host form of a table.
+ *
+ * THE REFINED SOURCE (GPDLA_SPECTRA_WEIGHTS_REFINED): the DLA component is its definition above with
+ * (S, offset_i, N_i, l, min_z_dla, max_z_dla) replaced by (S', u, N', lambda, z_lo, z_hi) of the batch's refine pass, as
+ * defined for mean_absorption under "THE REFINED SOURCE": the samples are the S' refine points mapped through the quasar's
+ * last box, the weights those of its resident lambda row.  Everything else is unchanged -- the profile, the broadening,
+ * d_i, B_i, c_i, Sigma_i, the reductions and the mixture; the null component is unchanged; the sub-DLA component keeps the
+ * first-pass sub-DLA table and its own S samples, so a mixture may hold components of different sample counts.  Posterior
+ * mass outside the last box is ignored (the convention of the refined parameter summaries).  sample_coefficients is
+ * [num_selected][S'][k] when the one component is the refined DLA table.  GPDLA_ERR_INVALID_ARGUMENT when some row weighs the
+ * DLA component and the batch has not been refined, or the context's refine points changed since the refine.  A selected
+ * quasar whose DLA component carries weight and whose refine status is not 0 (outside the refine's selection, or unusable)
+ * gets NaN rows and status GPDLA_SPECTRA_NOT_REFINED; where the DLA component weighs exactly 0 the quasar is evaluated as
+ * before.  The bit-identity promise holds.
  * ------------------------------------------------------------------------------------------- */
 typedef struct {
   int64_t num_selected;
   const int64_t *selection;          /* [num_selected] quasars of the batch; NULL = 0 .. num_selected-1 */
-  int32_t weights_source;            /* GPDLA_SPECTRA_WEIGHTS_RESIDENT or _HOST (_NONE: null component only) */
+  int32_t weights_source;            /* GPDLA_SPECTRA_WEIGHTS_RESIDENT, _HOST or _REFINED (_NONE: null component only) */
   const double *sample_log_likelihoods_dla; /* [num_selected][S], _HOST, where a row weighs the DLA table */
   const double *sample_log_likelihoods_lls; /* [num_selected][S], _HOST, where a row weighs the sub-DLA table */
   const double *model_weights;       /* [num_selected][3] (null, sub-DLA, DLA), or NULL = (0, 0, 1) */
@@ -1366,11 +1394,16 @@ int gpdla_batch_marginal_continuum(gpdla_context *ctx, gpdla_batch *batch, const
  * resident tables are model DLA(1) and the sub-DLA table.  A conditioned batch is refused.  Sums run in a fixed
  * order without atomics: outputs are bit-identical for any selection order and launch grouping and for the
  * resident and the host form of a table.
+ *
+ * THE REFINED SOURCE (GPDLA_SPECTRA_WEIGHTS_REFINED): exactly as for gpdla_batch_marginal_continuum above --
+ * the DLA component runs on the S' refine points mapped through the quasar's last box, weighted by its resident lambda row;
+ * the null and the sub-DLA component are unchanged; mass outside the last box is ignored; the same refusals and the same
+ * NaN rows with status GPDLA_SPECTRA_NOT_REFINED.
  * ------------------------------------------------------------------------------------------- */
 typedef struct {
   int64_t num_selected;
   const int64_t *selection;          /* [num_selected] quasars of the batch; NULL = 0 .. num_selected-1 */
-  int32_t weights_source;            /* GPDLA_SPECTRA_WEIGHTS_RESIDENT or _HOST (_NONE: null component only) */
+  int32_t weights_source;            /* GPDLA_SPECTRA_WEIGHTS_RESIDENT, _HOST or _REFINED (_NONE: null component only) */
   const double *sample_log_likelihoods_dla; /* [num_selected][S], _HOST, where a row weighs the DLA table */
   const double *sample_log_likelihoods_lls; /* [num_selected][S], _HOST, where a row weighs the sub-DLA table */
   const double *model_weights;       /* [num_selected][3] (null, sub-DLA, DLA), or NULL = (0, 0, 1) */
