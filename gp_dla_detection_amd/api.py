@@ -25,7 +25,7 @@ from types import SimpleNamespace
 
 import numpy as np
 
-from . import _lib
+from . import _lib, grid_fields
 from .parameters import MultiParameters, Parameters
 
 _dp = C.POINTER(C.c_double)
@@ -434,6 +434,15 @@ class Batch:
         _lib.check(getattr(lib, f"gpdla_batch_{name}")(self.ctx._h, self._h, C.byref(rq), C.byref(st)))
         return out
 
+    def _grid_product_multi(self, name: str, rq, sel, st, shapes) -> dict:
+        """:meth:`_grid_product` for the three ``*_multi`` entries: their validate entries also take the batch's ``max_dlas`` and
+        whether it was processed, and their output structs carry ``model_flags [nsel]`` (uint32), returned last."""
+        flags = np.zeros(sel.size, dtype=np.uint32)
+        st.model_flags = flags.ctypes.data_as(C.POINTER(C.c_uint32))
+        out = self._grid_product(name, rq, sel, st, shapes, self.max_dlas, int(self._multi_processed))
+        out["model_flags"] = flags
+        return out
+
     def model_spectra(self, selection=None, absorbers=None, weights=None, sub_dla: bool = False,
                       meanflux: bool | None = None, products=("map", "moments", "continuum")) -> dict:
         """What the fitted model looks like on the selected quasars (gpdla_batch_model_spectra), per
@@ -466,22 +475,29 @@ class Batch:
         bits = {"map": _lib.SPECTRA_MAP, "moments": _lib.SPECTRA_MOMENTS, "continuum": _lib.SPECTRA_CONTINUUM}
         products = [p for p in products if not (p == "moments" and weights is None)]
         rq.products = int(sum(bits[p] for p in set(products)))
-        if isinstance(weights, str):
-            if weights not in ("resident", "refined"):
-                raise ValueError("weights: 'resident', 'refined', an array [nsel, S] or None")
-            rq.weights_source = _lib.SPECTRA_WEIGHTS_RESIDENT if weights == "resident" else _lib.SPECTRA_WEIGHTS_REFINED
-        elif weights is not None:
-            w = np.ascontiguousarray(weights, dtype=np.float64)
-            if w.shape != (nsel, self.num_samples):
-                raise _lib.GpdlaError(-1, f"weights must be [nsel, S] = {(nsel, self.num_samples)}, got {w.shape}")
-            keep.append(w)
-            rq.weights_source, rq.sample_log_likelihoods = _lib.SPECTRA_WEIGHTS_HOST, w.ctypes.data_as(_dp)
+        self._weights_source(rq, weights, "an array [nsel, S]", [("weights", "sample_log_likelihoods", weights)], nsel, keep)
         rq.sub_dla = int(bool(sub_dla))
         rq.meanflux = int(bool(self.max_dlas) if meanflux is None else bool(meanflux))
-        names = {"map": ("map_absorption",), "moments": ("mean_absorption", "var_absorption"),
-                 "continuum": ("continuum", "model_flux")}
-        return self._grid_product("model_spectra", rq, sel, _lib.ModelSpectra(),
-                                  lambda total: {name: total for p in set(products) for name in names[p]})
+        return self._grid_product("model_spectra", rq, sel, _lib.ModelSpectra(), lambda total: {
+            name: total for p in set(products) for name in grid_fields.names("model_spectra", options=(p,))})
+
+    def _weights_source(self, rq, weights, forms: str, tables, nsel: int, keep: list):
+        """``weights`` of a grid product into ``rq.weights_source``: ``"resident"``, ``"refined"``, None (no source), or host
+        tables -- ``tables`` lists them as (what the error text calls it, field of the request, ``[nsel, S]`` or None); the
+        arrays the request points into are appended to ``keep``.  ``forms``: the host forms the call takes, for the error text."""
+        if isinstance(weights, str):
+            if weights not in ("resident", "refined"):
+                raise ValueError(f"weights: 'resident', 'refined', {forms} or None")
+            rq.weights_source = _lib.SPECTRA_WEIGHTS_RESIDENT if weights == "resident" else _lib.SPECTRA_WEIGHTS_REFINED
+        elif weights is not None:
+            rq.weights_source = _lib.SPECTRA_WEIGHTS_HOST
+            for what, field, w in tables:
+                if w is not None:
+                    w = np.ascontiguousarray(w, dtype=np.float64)
+                    if w.shape != (nsel, self.num_samples):
+                        raise _lib.GpdlaError(-1, f"{what} must be [nsel, S] = {(nsel, self.num_samples)}, got {w.shape}")
+                    keep.append(w)
+                    setattr(rq, field, w.ctypes.data_as(_dp))
 
     def _multi_tables(self, rq, tables, nsel: int, keep: list) -> int:
         """Fill ``tables_source`` and the three table pointers of a multi-model request from ``tables`` ("resident" or a
@@ -533,30 +549,14 @@ class Batch:
         (``expected_absorption``, ``expected_var_absorption``).
         Returns those with ``offsets [nsel + 1]``, ``status [nsel]`` and ``model_flags [nsel]`` (bit n-1: model
         DLA(n) has no weight; bit 30: the sub-DLA model)."""
-        sel = self._selection(selection)
-        nsel = sel.size
         rq = _lib.ModelSpectraMultiRequest()
-        rq.num_selected = nsel
-        rq.selection = sel.ctypes.data_as(_i64p)
-        keep = [sel]
-        md = self._multi_tables(rq, tables, nsel, keep)
-        rq.max_dlas = md
+        sel, md, keep = self._mixture_multi_request(rq, selection, tables, model_weights, meanflux)
         first, last = (1, md) if models is None else ((int(models), int(models)) if np.isscalar(models) else
                                                       (int(models[0]), int(models[-1])))
         rq.first_model, rq.last_model = first, last
-        if model_weights is not None:
-            w = np.ascontiguousarray(model_weights, dtype=np.float64)
-            if w.shape != (nsel, 2 + md):
-                raise _lib.GpdlaError(-1, f"model_weights must be [nsel, 2 + max_dlas] = {(nsel, 2 + md)}, got {w.shape}")
-            keep.append(w)
-            rq.model_weights = w.ctypes.data_as(_dp)
         bits = {"models": _lib.SPECTRA_MULTI_MODELS, "average": _lib.SPECTRA_MULTI_AVERAGE}
         products = set(products)
         rq.products = int(sum(bits[p] for p in products))
-        rq.meanflux = int(bool(self.max_dlas) if meanflux is None else bool(meanflux))
-        flags = np.zeros(nsel, dtype=np.uint32)
-        ms = _lib.ModelSpectraMulti()
-        ms.model_flags = flags.ctypes.data_as(C.POINTER(C.c_uint32))
 
         def shapes(total):
             shapes = {}
@@ -567,8 +567,7 @@ class Batch:
             if "average" in products:
                 shapes.update(expected_absorption=(total,), expected_var_absorption=(total,))
             return shapes
-        out = self._grid_product("model_spectra_multi", rq, sel, ms, shapes, self.max_dlas, int(self._multi_processed))
-        out["model_flags"] = flags
+        out = self._grid_product_multi("model_spectra_multi", rq, sel, _lib.ModelSpectraMulti(), shapes)
         del keep
         return out
 
@@ -596,24 +595,15 @@ class Batch:
         rq.selection = sel.ctypes.data_as(_i64p)
         rq.model_weights = pw.ctypes.data_as(_dp)
         keep = [sel, pw]
-        if isinstance(weights, str):
-            if weights not in ("resident", "refined"):
-                raise ValueError("weights: 'resident', 'refined', an array [nsel, S], a dict of them or None")
-            rq.weights_source = _lib.SPECTRA_WEIGHTS_RESIDENT if weights == "resident" else _lib.SPECTRA_WEIGHTS_REFINED
-        elif weights is not None:
-            if not isinstance(weights, dict):
-                sampled = [c for c in components if c != "null"]
-                if len(sampled) != 1:
-                    raise ValueError("weights: one array serves one sampled component; pass {'dla': ..., 'sub_dla': ...}")
-                weights = {sampled[0]: weights}
-            rq.weights_source = _lib.SPECTRA_WEIGHTS_HOST
-            for name, field in (("dla", "sample_log_likelihoods_dla"), ("sub_dla", "sample_log_likelihoods_lls")):
-                if weights.get(name) is not None:
-                    w = np.ascontiguousarray(weights[name], dtype=np.float64)
-                    if w.shape != (nsel, S):
-                        raise _lib.GpdlaError(-1, f"weights[{name!r}] must be [nsel, S] = {(nsel, S)}, got {w.shape}")
-                    keep.append(w)
-                    setattr(rq, field, w.ctypes.data_as(_dp))
+        if weights is not None and not isinstance(weights, (str, dict)):
+            sampled = [c for c in components if c != "null"]
+            if len(sampled) != 1:
+                raise ValueError("weights: one array serves one sampled component; pass {'dla': ..., 'sub_dla': ...}")
+            weights = {sampled[0]: weights}
+        tables = weights if isinstance(weights, dict) else {}
+        self._weights_source(rq, weights, "an array [nsel, S], a dict of them",
+                             [(f"weights[{name!r}]", field, tables.get(name)) for name, field in
+                              (("dla", "sample_log_likelihoods_dla"), ("sub_dla", "sample_log_likelihoods_lls"))], nsel, keep)
         rq.meanflux = int(bool(self.max_dlas) if meanflux is None else bool(meanflux))
         return sel, keep
 
@@ -726,7 +716,8 @@ class Batch:
     # ---- marginal continuum and predictive flux over all models of a multi-DLA run ----
 
     def _mixture_multi_request(self, rq, selection, tables, model_weights, meanflux):
-        """Fill a multi-model mixture request; returns (selection, max_dlas, the arrays the request points into)."""
+        """Fill what the three multi-model requests (:meth:`model_spectra_multi` and the two mixtures) share: selection, tables,
+        ``max_dlas``, model weights and ``meanflux``; returns (selection, max_dlas, the arrays the request points into)."""
         sel = self._selection(selection)
         nsel = sel.size
         rq.num_selected = nsel
@@ -762,13 +753,8 @@ class Batch:
         nsel, k = sel.size, self.ctx.k
         nb = k * (k + 1) // 2
         rows = {"coef_mean": (nsel, k), "coef_cov_within": (nsel, nb), "coef_cov_between": (nsel, nb)}
-        flags = np.zeros(nsel, dtype=np.uint32)
-        st = _lib.MarginalContinuumMulti()
-        st.model_flags = flags.ctypes.data_as(C.POINTER(C.c_uint32))
-        out = self._grid_product("marginal_continuum_multi", rq, sel, st,
-                                 lambda total: {**{name: total for name in MARGINAL_CONTINUUM_ARRAYS}, **rows},
-                                 self.max_dlas, int(self._multi_processed))
-        out["model_flags"] = flags
+        out = self._grid_product_multi("marginal_continuum_multi", rq, sel, _lib.MarginalContinuumMulti(),
+                                       lambda total: {**{name: total for name in MARGINAL_CONTINUUM_ARRAYS}, **rows})
         del keep
         return out
 
@@ -779,12 +765,8 @@ class Batch:
         ``residuals`` of :meth:`predictive_flux`."""
         rq = _lib.PredictiveFluxMultiRequest()
         sel, _md, keep = self._mixture_multi_request(rq, selection, tables, model_weights, meanflux)
-        flags = np.zeros(sel.size, dtype=np.uint32)
-        st = _lib.PredictiveFluxMulti()
-        st.model_flags = flags.ctypes.data_as(C.POINTER(C.c_uint32))
-        out = self._grid_product("predictive_flux_multi", rq, sel, st, lambda total: {name: total for name in PREDICTIVE_FLUX_ARRAYS},
-                                 self.max_dlas, int(self._multi_processed))
-        out["model_flags"] = flags
+        out = self._grid_product_multi("predictive_flux_multi", rq, sel, _lib.PredictiveFluxMulti(),
+                                       lambda total: {name: total for name in PREDICTIVE_FLUX_ARRAYS})
         del keep
         if residuals:
             y, kept = self.grid_flux(sel)
@@ -1483,10 +1465,16 @@ def process_qsos_multiple_dlas_meanflux(model: dict, samples: dict, spectra, log
 # model spectra
 # ----------------------------------------------------------------------------------------------
 
-MODEL_SPECTRA_ARRAYS = ("map_absorption", "mean_absorption", "var_absorption", "continuum", "model_flux")
+#: the names of :mod:`grid_fields`, by product and kind
+MODEL_SPECTRA_ARRAYS = grid_fields.names("model_spectra")
 #: what ``multi_models`` adds: flat per-pixel arrays, and per-model planes [max_dlas, total]
-MODEL_SPECTRA_MULTI_ARRAYS = ("mean_absorption_lls", "var_absorption_lls", "expected_absorption", "expected_var_absorption")
-MODEL_SPECTRA_MULTI_PLANES = ("mean_absorption_models", "var_absorption_models")
+MODEL_SPECTRA_MULTI_ARRAYS = grid_fields.names("model_spectra_multi", "pixel")
+MODEL_SPECTRA_MULTI_PLANES = grid_fields.names("model_spectra_multi", "plane")
+MARGINAL_CONTINUUM_ARRAYS = grid_fields.names("marginal_continuum", "pixel")
+MARGINAL_CONTINUUM_ROWS = grid_fields.names("marginal_continuum", "row", (None, "sample_coefficients"))
+PREDICTIVE_FLUX_ARRAYS = grid_fields.names("predictive_flux", "pixel", (None,))
+PREDICTIVE_FLUX_RESIDUALS = grid_fields.names("predictive_flux", "pixel", ("residuals",))
+PREDICTIVE_FLUX_ROWS = grid_fields.names("predictive_flux", "column")
 
 
 def renormalised_model_posteriors(results: dict) -> np.ndarray:
@@ -1566,14 +1554,16 @@ def _block_size(max_quasars_per_batch, spectra, idx, model: dict, samples: dict)
                                                            np.asarray(samples["offset_samples"]).size, 1))
 
 
-def _resident_blocks(model: dict, samples: dict, spectra, idx, params: Parameters, device: int, per: int, refined=None):
-    """Generator over the quasars ``idx`` of ``spectra`` in blocks of ``per``, each resident in turn in ONE batch of a
-    context of its own (uploaded, then reloaded; placeholder priors, since nothing is swept): yields
+def _resident_blocks(model: dict, samples: dict, spectra, idx, params: Parameters, device: int, max_quasars_per_batch, refined=None):
+    """Generator over the quasars ``idx`` of ``spectra`` in blocks of :func:`_block_size`, each resident in turn in ONE batch
+    of a context of its own (uploaded, then reloaded; placeholder priors, since nothing is swept): yields
     ``(lo, hi, idx[lo:hi], batch)``.  Batch and context are closed when the generator is (``contextlib.closing``
-    around the loop makes that every exit path).  ``refined``: what :func:`_refined_options` returns -- the blocks are
-    uploaded with the run's own priors and the context gets the refine points, for :func:`_refine_block`."""
+    around the loop makes that every exit path).  An empty ``idx`` yields nothing and loads nothing.  ``refined``: what
+    :func:`_refined_options` returns -- the blocks are uploaded with the run's own priors and the context gets the refine
+    points, for :func:`_refine_block`."""
     if not len(idx):
         return
+    per = _block_size(max_quasars_per_batch, spectra, idx, model, samples)
     multi = isinstance(params, MultiParameters)
     md = params.max_dlas if multi else 0
     ctx = Context(device, params)
@@ -1638,11 +1628,10 @@ def _refine_block(batch: "Batch", opts: dict) -> dict:
     return batch.refine(None, opts["levels"], opts["delta"], opts["pad"], opts["prior"], with_samples=False)
 
 
-def _refined_model_weights(batch: "Batch", components) -> np.ndarray:
-    """``[n, 3]`` as (p_no_dlas, 0, p_dlas) of :meth:`Batch.refined_posteriors`, with the fall-back of
-    :func:`_mixture_inputs` for a quasar whose listed posteriors are all 0 or NaN."""
-    rp = batch.refined_posteriors()
-    mw = np.stack([rp["p_no_dlas_refined"], np.zeros(rp["p_dlas_refined"].size), rp["p_dlas_refined"]], axis=1)
+def _posterior_weights(mw: np.ndarray, components) -> np.ndarray:
+    """Model posteriors ``[n, 3]`` as (null, sub-DLA, DLA) made into the weights of ``model_weights="posteriors"``: a NaN or
+    negative probability weighs 0 (p_dlas is a difference of probabilities and can round to -1e-166), and a quasar whose
+    listed posteriors are then all 0 falls back to equal weights over the listed components."""
     mw = np.maximum(np.nan_to_num(mw, nan=0.0), 0.0)
     listed = np.array([c in components for c in ("null", "sub_dla", "dla")])
     empty = ~(mw[:, listed].sum(axis=1) > 0)
@@ -1650,19 +1639,68 @@ def _refined_model_weights(batch: "Batch", components) -> np.ndarray:
     return mw
 
 
-def _stitch_refined(out: dict, lo: int, hi: int, n: int, ref: dict):
-    """The boxes used and the refine status of block ``[lo, hi)`` into ``boxes [n, levels, 4]`` and ``refine_status [n]``."""
-    if "boxes" not in out:
-        out["boxes"] = np.full((n,) + ref["boxes"].shape[1:], np.nan)
+def stitch_blocks(blocks, n: int, per_block, expect, dims: dict, refined: dict | None = None) -> dict:
+    """THE block loop of the grid products: ``blocks`` iterates ``(lo, hi, idx, batch)`` over a selection of ``n`` quasars
+    (:func:`_resident_blocks`; any iterator will do), ``per_block(batch, idx, lo, hi)`` returns what one or several
+    ``Batch`` methods returned for the block (a dict, or a sequence of dicts), and the result is ``offsets [n + 1]`` and
+    ``status [n]`` (the OR over the block's dicts) followed by the fields ``expect`` (of :mod:`grid_fields`, which knows each
+    one's axis and dtype), stitched in selection order.  ``refined``: what :func:`_refined_options` returns -- each block is
+    processed and refined (:func:`_refine_block`) before ``per_block`` sees it, and ``boxes [n, levels, 4]`` and
+    ``refine_status [n]`` follow ``status``.  An empty selection returns the same keys with no extent
+    (:func:`grid_fields.empty` by ``dims``)."""
+    out = {"offsets": np.zeros(n + 1, dtype=np.int64), "status": np.zeros(n, dtype=np.int32)}
+    if refined is not None:
+        out["boxes"] = np.full((n, int(refined["levels"]), 4), np.nan)
         out["refine_status"] = np.full(n, -1, dtype=np.int32)
-    out["boxes"][lo:hi] = ref["boxes"]
-    out["refine_status"][lo:hi] = ref["status"]
+    parts = {f.name: [] for f in expect}
+    for lo, hi, idx, batch in blocks:
+        if refined is not None:
+            ref = _refine_block(batch, refined)
+            out["boxes"][lo:hi], out["refine_status"][lo:hi] = ref["boxes"], ref["status"]
+        results = per_block(batch, idx, lo, hi)
+        results = [results] if isinstance(results, dict) else list(results)
+        out["offsets"][lo + 1:hi + 1] = out["offsets"][lo] + results[0]["offsets"][1:]
+        for res in results:
+            out["status"][lo:hi] |= res["status"]
+            for name in parts:
+                if name in res:
+                    parts[name].append(res[name])
+    for f in expect:
+        out[f.name] = grid_fields.join(f, parts[f.name]) if n else grid_fields.empty(f, dims)
+    return out
 
 
-def _stitch(out: dict, lo: int, hi: int, res: dict):
-    """Offsets and status of block ``[lo, hi)`` into those of the whole selection."""
-    out["offsets"][lo + 1:hi + 1] = out["offsets"][lo] + res["offsets"][1:]
-    out["status"][lo:hi] = res["status"]
+def _drive(model: dict, samples: dict, spectra, sel, params, device: int, max_quasars_per_batch, per_block, expect,
+           refined: dict | None = None) -> dict:
+    """:func:`stitch_blocks` over :func:`_resident_blocks` of the selected quasars, with ``selection`` in front."""
+    S = np.asarray(samples["offset_samples"]).size
+    if refined is not None and refined["points"] is not None:    # S': the refine points the options name
+        S = int(refined["points"]) if np.ndim(refined["points"]) == 0 else np.asarray(refined["points"][0]).size
+    dims = dict(k=np.asarray(model["M"]).shape[1], samples=S, max_dlas=int(getattr(params, "max_dlas", 0)))
+    with closing(_resident_blocks(model, samples, spectra, sel, params, device, max_quasars_per_batch, refined)) as blocks:
+        return {"selection": sel, **stitch_blocks(blocks, sel.size, per_block, expect, dims, refined)}
+
+
+def _selected(spectra, selection) -> np.ndarray:
+    return np.arange(len(spectra), dtype=np.int64) if selection is None else np.asarray(selection, dtype=np.int64).reshape(-1)
+
+
+def _multi_inputs(results, model_weights, multi_rows, posteriors_by_name: bool):
+    """``(model_weights [nq, 2 + max_dlas], multi_rows)`` of a ``multi_models`` call: the three tables of ``results`` behind
+    ``multi_rows`` when none is given, ``results["model_posteriors"]`` for no weights (and, ``posteriors_by_name``, for
+    ``"posteriors"``)."""
+    if multi_rows is None:
+        if results is None or "base_sample_inds" not in results or np.asarray(results["sample_log_likelihoods_dla"]).ndim != 3:
+            raise ValueError("multi_models needs results with base_sample_inds and sample_log_likelihoods_dla [nq, max_dlas, S]")
+        multi_rows = lambda idx: {name: np.asarray(results[name])[idx] for name in  # noqa: E731
+                                  ("sample_log_likelihoods_dla", "base_sample_inds", "sample_log_likelihoods_lls")}
+    if model_weights is None or (posteriors_by_name and isinstance(model_weights, str) and model_weights == "posteriors"):
+        if results is None:
+            raise ValueError("multi_models needs model_weights or results")
+        model_weights = results["model_posteriors"]
+    elif posteriors_by_name and isinstance(model_weights, str):
+        raise ValueError("model_weights: 'posteriors', an array [nq, 2 + max_dlas] or None")
+    return np.asarray(model_weights, dtype=np.float64), multi_rows
 
 
 def model_spectra(model: dict, samples: dict, spectra, results: dict | None = None,
@@ -1694,14 +1732,15 @@ def model_spectra(model: dict, samples: dict, spectra, results: dict | None = No
     (``weights="refined"``: posterior mass outside the last box is ignored).  The result gains ``boxes`` and
     ``refine_status``.  Single-DLA runs only.
     Returns ``selection``, ``offsets``, ``status`` and the flat per-pixel arrays of
-    :meth:`Batch.model_spectra`, in selection order; results do not depend on the batching."""
+    :meth:`Batch.model_spectra`, in selection order; results do not depend on the batching.  An empty selection returns
+    every key the same call returns for a non-empty one, each with no extent (:func:`grid_fields.empty`)."""
     p = params or Parameters()
     multi = isinstance(p, MultiParameters)
     refined = _refined_options(refined, results, p)
     if refined is not None and moments_sub_dla:
         raise ValueError("refined: the refined table is the DLA table (no moments_sub_dla)")
     spectra = list(spectra)
-    sel = np.arange(len(spectra), dtype=np.int64) if selection is None else np.asarray(selection, dtype=np.int64).reshape(-1)
+    sel = _selected(spectra, selection)
     products = tuple(products)
     if isinstance(absorbers, str):
         if absorbers != "map":
@@ -1714,46 +1753,22 @@ def model_spectra(model: dict, samples: dict, spectra, results: dict | None = No
             raise ValueError("moments need results or sample_rows")
         table = np.asarray(results["sample_log_likelihoods_lls" if moments_sub_dla else "sample_log_likelihoods_dla"])
         sample_rows = (lambda idx: table[idx]) if table.ndim == 2 else (lambda idx: table[idx, 0, :])
+    expect = grid_fields.requested("model_spectra", products)
     if multi_models:
-        if multi_rows is None:
-            if results is None or "base_sample_inds" not in results or np.asarray(results["sample_log_likelihoods_dla"]).ndim != 3:
-                raise ValueError("multi_models needs results with base_sample_inds and sample_log_likelihoods_dla [nq, max_dlas, S]")
-            multi_rows = lambda idx: {name: np.asarray(results[name])[idx] for name in  # noqa: E731
-                                      ("sample_log_likelihoods_dla", "base_sample_inds", "sample_log_likelihoods_lls")}
-        if model_weights is None:
-            if results is None:
-                raise ValueError("multi_models needs model_weights or results")
-            model_weights = results["model_posteriors"]
-        model_weights = np.asarray(model_weights, dtype=np.float64)
-    per = _block_size(max_quasars_per_batch, spectra, sel, model, samples)
-    out = {"selection": sel, "offsets": np.zeros(sel.size + 1, dtype=np.int64), "status": np.zeros(sel.size, dtype=np.int32)}
-    parts = {}
-    with closing(_resident_blocks(model, samples, spectra, sel, p, device, per, refined)) as blocks:
-        for lo, hi, idx, batch in blocks:
-            if refined is not None:
-                _stitch_refined(out, lo, hi, sel.size, _refine_block(batch, refined))
-                weights = "refined" if "moments" in products else None
-            else:
-                weights = np.asarray(sample_rows(idx), dtype=np.float64) if "moments" in products else None
-            res = batch.model_spectra(absorbers=None if absorbers is None else _take_absorbers(absorbers, idx),
-                                      weights=weights, sub_dla=moments_sub_dla, products=products)
-            _stitch(out, lo, hi, res)
-            for name in MODEL_SPECTRA_ARRAYS:
-                if name in res:
-                    parts.setdefault(name, []).append(res[name])
-            if multi_models:
-                more = batch.model_spectra_multi(tables=multi_rows(idx), model_weights=model_weights[idx])
-                out.setdefault("model_flags", np.zeros(sel.size, dtype=np.uint32))[lo:hi] = more["model_flags"]
-                out["status"][lo:hi] |= more["status"]
-                for name in MODEL_SPECTRA_MULTI_ARRAYS + MODEL_SPECTRA_MULTI_PLANES:
-                    parts.setdefault(name, []).append(more[name])
-    for name, ps in parts.items():
-        out[name] = np.concatenate(ps, axis=-1)   # (the per-model planes are [max_dlas, pixels])
-    return out
+        model_weights, multi_rows = _multi_inputs(results, model_weights, multi_rows, posteriors_by_name=False)
+        expect = grid_fields.requested("multi_models") + expect + grid_fields.requested("model_spectra_multi")
 
-
-MARGINAL_CONTINUUM_ARRAYS = ("continuum_mean", "continuum_var", "continuum_var_between")
-MARGINAL_CONTINUUM_ROWS = ("coef_mean", "coef_cov_within", "coef_cov_between", "sample_coefficients")
+    def per_block(batch, idx, lo, hi):
+        if "moments" not in products:
+            weights = None
+        else:
+            weights = "refined" if refined is not None else np.asarray(sample_rows(idx), dtype=np.float64)
+        res = [batch.model_spectra(absorbers=None if absorbers is None else _take_absorbers(absorbers, idx),
+                                   weights=weights, sub_dla=moments_sub_dla, products=products)]
+        if multi_models:
+            res.append(batch.model_spectra_multi(tables=multi_rows(idx), model_weights=model_weights[idx]))
+        return res
+    return _drive(model, samples, spectra, sel, p, device, max_quasars_per_batch, per_block, expect, refined)
 
 
 def posterior_model_weights(results: dict) -> np.ndarray:
@@ -1777,10 +1792,7 @@ def _mixture_inputs(results, components, model_weights, sample_rows):
             raise ValueError("model_weights: 'posteriors', an array [nq, 3] or None")
         if results is None:
             raise ValueError("model_weights='posteriors' needs results")
-        model_weights = posterior_model_weights(results)
-        listed = np.array([c in components for c in ("null", "sub_dla", "dla")])
-        empty = ~(model_weights[:, listed].sum(axis=1) > 0)
-        model_weights[np.ix_(empty, listed)] = 1.0
+        model_weights = _posterior_weights(posterior_model_weights(results), components)
     elif model_weights is not None:
         model_weights = np.asarray(model_weights, dtype=np.float64)
     if sampled and sample_rows is None:
@@ -1795,76 +1807,53 @@ def _mixture_inputs(results, components, model_weights, sample_rows):
     return components, sampled, model_weights, sample_rows
 
 
-def _mixture_multi(method: str, flat, rows, model, samples, spectra, results, p, sel, model_weights, multi_rows, device,
-                   max_quasars_per_batch, **kw) -> dict:
-    """:func:`marginal_continuum` / :func:`predictive_flux` with ``multi_models``: ``Batch.<method>`` block by block on the
-    three tables of the selected quasars (``multi_rows(idx)``, default: those of ``results``), ``flat`` per-pixel arrays and
-    ``rows`` per-quasar arrays stitched in selection order."""
-    if not isinstance(p, MultiParameters):
-        raise ValueError("multi_models needs MultiParameters (a multi-DLA run)")
-    if multi_rows is None:
-        if results is None or "base_sample_inds" not in results or np.asarray(results["sample_log_likelihoods_dla"]).ndim != 3:
-            raise ValueError("multi_models needs results with base_sample_inds and sample_log_likelihoods_dla [nq, max_dlas, S]")
-        multi_rows = lambda idx: {name: np.asarray(results[name])[idx] for name in  # noqa: E731
-                                  ("sample_log_likelihoods_dla", "base_sample_inds", "sample_log_likelihoods_lls")}
-    if model_weights is None or (isinstance(model_weights, str) and model_weights == "posteriors"):
-        if results is None:
-            raise ValueError("multi_models needs model_weights or results")
-        model_weights = results["model_posteriors"]
-    elif isinstance(model_weights, str):
-        raise ValueError("model_weights: 'posteriors', an array [nq, 2 + max_dlas] or None")
-    model_weights = np.asarray(model_weights, dtype=np.float64)
-    per = _block_size(max_quasars_per_batch, spectra, sel, model, samples)
-    out = {"selection": sel, "offsets": np.zeros(sel.size + 1, dtype=np.int64), "status": np.zeros(sel.size, dtype=np.int32),
-           "model_flags": np.zeros(sel.size, dtype=np.uint32)}
-    parts = {name: [] for name in tuple(flat) + tuple(rows)}
-    with closing(_resident_blocks(model, samples, spectra, sel, p, device, per)) as blocks:
-        for lo, hi, idx, batch in blocks:
-            res = getattr(batch, method)(tables=multi_rows(idx), model_weights=model_weights[idx], **kw)
-            _stitch(out, lo, hi, res)
-            out["model_flags"][lo:hi] = res["model_flags"]
-            for name in parts:
-                parts[name].append(res[name])
-    k = np.asarray(model["M"]).shape[1]
-    empty = {"coef_mean": (0, k), "coef_cov_within": (0, k * (k + 1) // 2), "coef_cov_between": (0, k * (k + 1) // 2)}
-    for name in parts:
-        if parts[name]:
-            out[name] = np.concatenate(parts[name], axis=0)
-        else:
-            out[name] = np.zeros(empty.get(name, 0), dtype=np.int64 if name == "num_kept" else np.float64)
-    return out
+def _mixture(product: str, kw: dict, model, samples, spectra, results, params, selection, components, model_weights, sample_rows,
+             device, max_quasars_per_batch, multi_models, multi_rows, refined) -> dict:
+    """What :func:`marginal_continuum` and :func:`predictive_flux` are: ``Batch.<product>(**kw)`` block by block through
+    :func:`_drive` -- on the refined table (``refined``), over all models of a multi-DLA run (``multi_models``:
+    ``Batch.<product>_multi`` with the switches of ``kw`` that are on) or on the saved tables."""
+    p = params or Parameters()
+    spectra = list(spectra)
+    sel = _selected(spectra, selection)
+    refined = _refined_options(refined, results, p)
+    on = {name: v for name, v in kw.items() if v}
+    expect = grid_fields.requested(product, on)
+    if refined is not None:
+        if multi_models:
+            raise ValueError("refined: not with multi_models (a multi-DLA batch cannot be refined)")
+        components = tuple(components)
+        if "sub_dla" in components:
+            raise ValueError("refined: a single-DLA run has no sub-DLA table; components are 'null' and 'dla'")
+        by_posteriors = isinstance(model_weights, str)
+        if by_posteriors and model_weights != "posteriors":
+            raise ValueError("model_weights: 'posteriors', an array [nq, 3] or None")
+        if model_weights is not None and not by_posteriors:
+            model_weights = np.asarray(model_weights, dtype=np.float64)
 
+        def per_block(batch, idx, lo, hi):
+            if by_posteriors:   # (p_no_dlas, 0, p_dlas) of the refine pass this block has just had
+                rp = batch.refined_posteriors()
+                mw = _posterior_weights(np.stack([rp["p_no_dlas_refined"], np.zeros(rp["p_dlas_refined"].size),
+                                                  rp["p_dlas_refined"]], axis=1), components)
+            else:
+                mw = None if model_weights is None else model_weights[idx]
+            return getattr(batch, product)(weights="refined", components=components, model_weights=mw, **kw)
+    elif multi_models:
+        if not isinstance(p, MultiParameters):
+            raise ValueError("multi_models needs MultiParameters (a multi-DLA run)")
+        model_weights, multi_rows = _multi_inputs(results, model_weights, multi_rows, posteriors_by_name=True)
+        expect = grid_fields.requested("multi_models") + expect
 
-def _mixture_refined(method: str, flat, rows, model, samples, spectra, p, sel, components, model_weights, refined, device,
-                     max_quasars_per_batch, multi_models, **kw) -> dict:
-    """:func:`marginal_continuum` / :func:`predictive_flux` with ``refined``: per resident block :func:`_refine_block`, then
-    ``Batch.<method>(weights="refined")``; ``flat`` per-pixel arrays and ``rows`` per-quasar arrays stitched in selection
-    order, with the boxes used and the refine status."""
-    if multi_models:
-        raise ValueError("refined: not with multi_models (a multi-DLA batch cannot be refined)")
-    components = tuple(components)
-    if "sub_dla" in components:
-        raise ValueError("refined: a single-DLA run has no sub-DLA table; components are 'null' and 'dla'")
-    by_posteriors = isinstance(model_weights, str)
-    if by_posteriors and model_weights != "posteriors":
-        raise ValueError("model_weights: 'posteriors', an array [nq, 3] or None")
-    if model_weights is not None and not by_posteriors:
-        model_weights = np.asarray(model_weights, dtype=np.float64)
-    per = _block_size(max_quasars_per_batch, spectra, sel, model, samples)
-    out = {"selection": sel, "offsets": np.zeros(sel.size + 1, dtype=np.int64), "status": np.zeros(sel.size, dtype=np.int32)}
-    parts = {}
-    with closing(_resident_blocks(model, samples, spectra, sel, p, device, per, refined)) as blocks:
-        for lo, hi, idx, batch in blocks:
-            _stitch_refined(out, lo, hi, sel.size, _refine_block(batch, refined))
-            mw = _refined_model_weights(batch, components) if by_posteriors else None if model_weights is None else model_weights[idx]
-            res = getattr(batch, method)(weights="refined", components=components, model_weights=mw, **kw)
-            _stitch(out, lo, hi, res)
-            for name in tuple(flat) + tuple(rows):
-                if name in res:
-                    parts.setdefault(name, []).append(res[name])
-    for name, ps in parts.items():
-        out[name] = np.concatenate(ps, axis=0)
-    return out
+        def per_block(batch, idx, lo, hi):
+            return getattr(batch, product + "_multi")(tables=multi_rows(idx), model_weights=model_weights[idx], **on)
+    else:
+        components, sampled, model_weights, sample_rows = _mixture_inputs(results, components, model_weights, sample_rows)
+
+        def per_block(batch, idx, lo, hi):
+            return getattr(batch, product)(weights={c: np.asarray(sample_rows(idx, c), dtype=np.float64) for c in sampled} or None,
+                                           components=components, model_weights=None if model_weights is None else model_weights[idx],
+                                           **kw)
+    return _drive(model, samples, spectra, sel, p, device, max_quasars_per_batch, per_block, expect, refined)
 
 
 def marginal_continuum(model: dict, samples: dict, spectra, results: dict | None = None,
@@ -1884,7 +1873,8 @@ def marginal_continuum(model: dict, samples: dict, spectra, results: dict | None
     model DLA(1) of ``[nq, max_dlas, S]``) and ``sample_log_likelihoods_lls`` of ``results``;
     ``sample_rows(idx, name) -> [len(idx), S]`` (``name`` ``"dla"`` or ``"sub_dla"``) supplies the rows
     instead (a file streamed block by block).  Returns ``selection``, ``offsets``, ``status`` and the arrays of
-    :meth:`Batch.marginal_continuum` in selection order; results do not depend on the batching.
+    :meth:`Batch.marginal_continuum` in selection order; results do not depend on the batching.  An empty selection returns
+    every key the same call returns for a non-empty one, each with no extent (``refined`` and ``multi_models`` included).
 
     ``multi_models``: the mixture over ALL models of a multi-DLA run instead (:meth:`Batch.marginal_continuum_multi`):
     ``components`` and ``sample_rows`` are ignored, ``results`` must carry ``base_sample_inds``, the 3-D
@@ -1899,50 +1889,10 @@ def marginal_continuum(model: dict, samples: dict, spectra, results: dict | None
     (``weights="refined"``: posterior mass outside the last box is ignored); ``model_weights="posteriors"`` then mixes by
     :meth:`Batch.refined_posteriors`.  Components ``"null"`` and ``"dla"`` of single-DLA runs only.  The result gains
     ``boxes`` and ``refine_status``; ``sample_coefficients`` are ``[n, S', k]``."""
-    p = params or Parameters()
-    spectra = list(spectra)
-    sel = np.arange(len(spectra), dtype=np.int64) if selection is None else np.asarray(selection, dtype=np.int64).reshape(-1)
-    refined = _refined_options(refined, results, p)
-    if refined is not None:
-        return _mixture_refined("marginal_continuum", MARGINAL_CONTINUUM_ARRAYS, MARGINAL_CONTINUUM_ROWS, model, samples, spectra,
-                                p, sel, components, model_weights, refined, device, max_quasars_per_batch, multi_models,
-                                sample_coefficients=sample_coefficients)
-    if multi_models:
-        if sample_coefficients:
-            raise ValueError("sample_coefficients are not offered with multi_models")
-        return _mixture_multi("marginal_continuum_multi", MARGINAL_CONTINUUM_ARRAYS, MARGINAL_CONTINUUM_ROWS[:3], model, samples,
-                              spectra, results, p, sel, model_weights, multi_rows, device, max_quasars_per_batch)
-    components, sampled, model_weights, sample_rows = _mixture_inputs(results, components, model_weights, sample_rows)
-    S = np.asarray(samples["offset_samples"]).size
-    k = np.asarray(model["M"]).shape[1]
-    per = _block_size(max_quasars_per_batch, spectra, sel, model, samples)
-    out = {"selection": sel, "offsets": np.zeros(sel.size + 1, dtype=np.int64), "status": np.zeros(sel.size, dtype=np.int32)}
-    parts = {}
-    with closing(_resident_blocks(model, samples, spectra, sel, p, device, per)) as blocks:
-        for lo, hi, idx, batch in blocks:
-            res = batch.marginal_continuum(weights={c: np.asarray(sample_rows(idx, c), dtype=np.float64) for c in sampled} or None,
-                                           components=components,
-                                           model_weights=None if model_weights is None else model_weights[idx],
-                                           sample_coefficients=sample_coefficients)
-            _stitch(out, lo, hi, res)
-            for name in MARGINAL_CONTINUUM_ARRAYS + MARGINAL_CONTINUUM_ROWS:
-                if name in res:
-                    parts.setdefault(name, []).append(res[name])
-    nb = k * (k + 1) // 2
-    shapes = {"coef_mean": (0, k), "coef_cov_within": (0, nb), "coef_cov_between": (0, nb), "sample_coefficients": (0, S, k)}
-    for name in MARGINAL_CONTINUUM_ARRAYS:
-        out[name] = np.concatenate(parts[name]) if name in parts else np.zeros(0)
-    for name in MARGINAL_CONTINUUM_ROWS:
-        if name in parts:
-            out[name] = np.concatenate(parts[name], axis=0)
-        elif name != "sample_coefficients" or sample_coefficients:
-            out[name] = np.zeros(shapes[name])
-    return out
-
-
-PREDICTIVE_FLUX_ARRAYS = ("flux_mean", "flux_var", "flux_var_within", "flux_var_between", "noise_var")
-PREDICTIVE_FLUX_RESIDUALS = ("residual",)
-PREDICTIVE_FLUX_ROWS = ("chi2", "num_kept")
+    if multi_models and sample_coefficients and refined is None:
+        raise ValueError("sample_coefficients are not offered with multi_models")
+    return _mixture("marginal_continuum", dict(sample_coefficients=sample_coefficients), model, samples, spectra, results, params,
+                    selection, components, model_weights, sample_rows, device, max_quasars_per_batch, multi_models, multi_rows, refined)
 
 
 def predictive_residuals(pf: dict, flux, kept) -> dict:
@@ -1973,37 +1923,10 @@ def predictive_flux(model: dict, samples: dict, spectra, results: dict | None = 
     :func:`posterior_model_weights`.  ``residuals``: also the in-sample replicate ``residual`` per pixel and
     ``chi2``, ``num_kept`` per quasar (conservative; not leave-one-out).  Returns ``selection``, ``offsets``,
     ``status`` and the arrays of :meth:`Batch.predictive_flux` in selection order; results do not depend on the
-    batching.  ``multi_models``, ``multi_rows``, ``refined``: as :func:`marginal_continuum` (:meth:`Batch.predictive_flux_multi`;
+    batching, and an empty selection returns the same keys with no extent.  ``multi_models``, ``multi_rows``, ``refined``: as :func:`marginal_continuum` (:meth:`Batch.predictive_flux_multi`;
     with ``refined`` the DLA component runs on the refined table, posterior mass outside the last box ignored)."""
-    p = params or Parameters()
-    spectra = list(spectra)
-    sel = np.arange(len(spectra), dtype=np.int64) if selection is None else np.asarray(selection, dtype=np.int64).reshape(-1)
-    refined = _refined_options(refined, results, p)
-    if refined is not None:
-        names = PREDICTIVE_FLUX_ARRAYS + (PREDICTIVE_FLUX_RESIDUALS if residuals else ())
-        return _mixture_refined("predictive_flux", names, PREDICTIVE_FLUX_ROWS if residuals else (), model, samples, spectra, p, sel,
-                                components, model_weights, refined, device, max_quasars_per_batch, multi_models, residuals=residuals)
-    if multi_models:
-        names = PREDICTIVE_FLUX_ARRAYS + (PREDICTIVE_FLUX_RESIDUALS if residuals else ())
-        return _mixture_multi("predictive_flux_multi", names, PREDICTIVE_FLUX_ROWS if residuals else (), model, samples, spectra,
-                              results, p, sel, model_weights, multi_rows, device, max_quasars_per_batch, residuals=residuals)
-    components, sampled, model_weights, sample_rows = _mixture_inputs(results, components, model_weights, sample_rows)
-    per = _block_size(max_quasars_per_batch, spectra, sel, model, samples)
-    out = {"selection": sel, "offsets": np.zeros(sel.size + 1, dtype=np.int64), "status": np.zeros(sel.size, dtype=np.int32)}
-    names = PREDICTIVE_FLUX_ARRAYS + ((PREDICTIVE_FLUX_RESIDUALS + PREDICTIVE_FLUX_ROWS) if residuals else ())
-    parts = {name: [] for name in names}
-    with closing(_resident_blocks(model, samples, spectra, sel, p, device, per)) as blocks:
-        for lo, hi, idx, batch in blocks:
-            res = batch.predictive_flux(weights={c: np.asarray(sample_rows(idx, c), dtype=np.float64) for c in sampled} or None,
-                                        components=components,
-                                        model_weights=None if model_weights is None else model_weights[idx],
-                                        residuals=residuals)
-            _stitch(out, lo, hi, res)
-            for name in names:
-                parts[name].append(res[name])
-    for name in names:
-        out[name] = np.concatenate(parts[name]) if parts[name] else np.zeros(0, dtype=np.int64 if name == "num_kept" else np.float64)
-    return out
+    return _mixture("predictive_flux", dict(residuals=residuals), model, samples, spectra, results, params, selection, components,
+                    model_weights, sample_rows, device, max_quasars_per_batch, multi_models, multi_rows, refined)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -2029,11 +1952,10 @@ def draw_mock_spectra(model: dict, samples: dict, templates, truth=None, params:
     templates = list(templates)
     nq = len(templates)
     k = np.asarray(model["M"]).shape[1]
-    per = _block_size(max_quasars_per_batch, templates, range(nq), model, samples)
     out = {"flux": [], "status": np.zeros(nq, dtype=np.int32)}
     for name in components:
         out[name] = np.empty((nq, k)) if name == "latents" else []
-    with closing(_resident_blocks(model, samples, templates, range(nq), p, device, per)) as blocks:
+    with closing(_resident_blocks(model, samples, templates, range(nq), p, device, max_quasars_per_batch)) as blocks:
         for lo, hi, idx, batch in blocks:
             batch.ctx.set_first_quasar_index(first_quasar_index + lo)
             res = batch.draw_mocks(absorbers=None if truth is None else _take_absorbers(truth, idx),

@@ -27,7 +27,7 @@ import os
 
 import numpy as np
 
-from . import hdf5
+from . import grid_fields, hdf5
 
 MATLAB_HEADER_TEXT = "MATLAB 7.3 MAT-file, Platform: GLNXA64, Created on: {date} HDF5 schema 1.00 ."
 
@@ -841,19 +841,53 @@ def load_processed_qsos(path: str) -> dict:
 # model spectra
 # ---------------------------------------------------------------------------------------------
 
-MODEL_SPECTRA_CELLS = ("map_absorption", "mean_absorption", "var_absorption", "continuum", "model_flux")
-#: the products of a multi-DLA run's models: per-pixel cells, and cells of [pixels x max_dlas]
-MODEL_SPECTRA_MULTI_CELLS = ("mean_absorption_lls", "var_absorption_lls", "expected_absorption", "expected_var_absorption")
-MODEL_SPECTRA_MULTI_PLANE_CELLS = ("mean_absorption_models", "var_absorption_models")
+#: the names of :mod:`grid_fields` by the form they take in a file: per-pixel cells; cells of [pixels x max_dlas];
+#: [n x columns] matrices; columns
+MODEL_SPECTRA_CELLS = grid_fields.names("model_spectra")
+MODEL_SPECTRA_MULTI_CELLS = grid_fields.names("model_spectra_multi", "pixel")
+MODEL_SPECTRA_MULTI_PLANE_CELLS = grid_fields.names("model_spectra_multi", "plane")
+MARGINAL_CONTINUUM_CELLS = grid_fields.names("marginal_continuum", "pixel")
+MARGINAL_CONTINUUM_MATRICES = grid_fields.names("marginal_continuum", "row", (None, "caller"))
+PREDICTIVE_FLUX_CELLS = grid_fields.names("predictive_flux", "pixel")
+PREDICTIVE_FLUX_COLUMNS = grid_fields.names("predictive_flux", "column")
 
 
-def _put_refined(w, res: dict) -> None:
-    """The boxes a refined product was computed on (``refined=`` of the drivers in :mod:`api`): ``refine_boxes``
-    [N x 4 levels] with a quasar's level l in columns 4 l .. 4 l + 3 as (z_lo, z_hi, n_lo, n_hi), and ``refine_status``."""
-    if "boxes" in res:
-        b = np.asarray(res["boxes"], dtype=np.float64)
-        w.put("refine_boxes", np.ascontiguousarray(b.reshape(b.shape[0], -1)))
-        w.put("refine_status", np.asarray(res["refine_status"], dtype=np.float64))
+def _save_grid_product(path: str, res: dict, products, run_metadata: dict) -> None:
+    """THE saver of the grid products: ``run_metadata`` as given, ``quasar_ind`` (the selection, 1-based like every MATLAB
+    index), ``num_pixels`` and ``status`` as columns; of a refined product (``refined=`` of the drivers in :mod:`api`)
+    ``refine_boxes`` [N x 4 levels] with a quasar's level l in columns 4 l .. 4 l + 3 as (z_lo, z_hi, n_lo, n_hi) and
+    ``refine_status``; of the model spectra the selected absorbers as the cells ``map_z_dlas`` / ``map_log_nhis`` (when
+    ``absorber_offsets``, ``absorber_z_dlas`` and ``absorber_log_nhis`` are present); then every field of ``products`` that ``res`` holds, in the
+    order and the form :mod:`grid_fields` declares."""
+    off = np.asarray(res["offsets"], dtype=np.int64)
+    nsel = off.size - 1
+    w = _MatWriter(path)
+    try:
+        for k, v in run_metadata.items():
+            w.put(k, v)
+        w.put("quasar_ind", np.asarray(res.get("selection", np.arange(nsel)), dtype=np.float64) + 1)
+        w.put("num_pixels", np.diff(off).astype(np.float64))
+        w.put("status", np.asarray(res.get("status", np.zeros(nsel)), dtype=np.float64))
+        if "boxes" in res:
+            b = np.asarray(res["boxes"], dtype=np.float64)
+            w.put("refine_boxes", np.ascontiguousarray(b.reshape(b.shape[0], -1)))
+            w.put("refine_status", np.asarray(res["refine_status"], dtype=np.float64))
+        if "absorber_offsets" in res and "model_spectra" in products:
+            a = np.asarray(res["absorber_offsets"], dtype=np.int64)
+            for name, key in (("map_z_dlas", "absorber_z_dlas"), ("map_log_nhis", "absorber_log_nhis")):
+                v = np.asarray(res[key], dtype=np.float64)
+                w.put(name, [v[a[i]:a[i + 1]].reshape(-1, 1) for i in range(nsel)])
+        for f in (f for product in products for f in grid_fields.fields(product) if f.name in res):
+            v = np.ascontiguousarray(res[f.name], dtype=np.float64)
+            if f.kind == "pixel":
+                v = [v[off[i]:off[i + 1]].reshape(-1, 1) for i in range(nsel)]
+            elif f.kind == "plane":   # [max_dlas, total]: one [pixels x max_dlas] matrix per quasar
+                v = [np.ascontiguousarray(v[:, off[i]:off[i + 1]].T) for i in range(nsel)]
+            elif f.kind == "row" and len(f.trailing or ()) == 2:   # sample_coefficients: one [S x k] matrix per quasar
+                v = [np.ascontiguousarray(v[i]) for i in range(nsel)]
+            w.put(f.name, v)
+    finally:
+        w.close()
 
 
 def save_model_spectra(path: str, spectra: dict, **run_metadata) -> None:
@@ -866,38 +900,7 @@ def save_model_spectra(path: str, spectra: dict, **run_metadata) -> None:
     when present: the sub-DLA and expected rows as such cells, ``mean_absorption_models`` /
     ``var_absorption_models`` as cells of [pixels x max_dlas] matrices, ``model_flags`` as a column.
     ``run_metadata``: scalars and strings, as given."""
-    off = np.asarray(spectra["offsets"], dtype=np.int64)
-    nsel = off.size - 1
-    w = _MatWriter(path)
-    try:
-        for k, v in run_metadata.items():
-            w.put(k, v)
-        w.put("quasar_ind", np.asarray(spectra.get("selection", np.arange(nsel)), dtype=np.float64) + 1)
-        w.put("num_pixels", np.diff(off).astype(np.float64))
-        w.put("status", np.asarray(spectra.get("status", np.zeros(nsel)), dtype=np.float64))
-        _put_refined(w, spectra)
-        if "absorber_offsets" in spectra:
-            a = np.asarray(spectra["absorber_offsets"], dtype=np.int64)
-            for name, key in (("map_z_dlas", "absorber_z_dlas"), ("map_log_nhis", "absorber_log_nhis")):
-                v = np.asarray(spectra[key], dtype=np.float64)
-                w.put(name, [v[a[i]:a[i + 1]].reshape(-1, 1) for i in range(nsel)])
-        for name in MODEL_SPECTRA_CELLS + MODEL_SPECTRA_MULTI_CELLS:
-            if name in spectra:
-                v = np.asarray(spectra[name], dtype=np.float64)
-                w.put(name, [v[off[i]:off[i + 1]].reshape(-1, 1) for i in range(nsel)])
-        for name in MODEL_SPECTRA_MULTI_PLANE_CELLS:   # [max_dlas, total]: one [pixels x max_dlas] matrix per quasar
-            if name in spectra:
-                v = np.asarray(spectra[name], dtype=np.float64)
-                w.put(name, [np.ascontiguousarray(v[:, off[i]:off[i + 1]].T) for i in range(nsel)])
-        if "model_flags" in spectra:
-            w.put("model_flags", np.asarray(spectra["model_flags"], dtype=np.float64))
-    finally:
-        w.close()
-
-
-#: the marginal continuum (DESIGN.md 4.23): per-pixel cells, and [n x columns] matrices
-MARGINAL_CONTINUUM_CELLS = ("continuum_mean", "continuum_var", "continuum_var_between")
-MARGINAL_CONTINUUM_MATRICES = ("coef_mean", "coef_cov_within", "coef_cov_between", "model_weights")
+    _save_grid_product(path, spectra, ("model_spectra", "model_spectra_multi", "multi_models"), run_metadata)
 
 
 def save_marginal_continuum(path: str, mc: dict, **run_metadata) -> None:
@@ -908,35 +911,7 @@ def save_marginal_continuum(path: str, mc: dict, **run_metadata) -> None:
     ``model_weights`` [N x 3] as matrices and ``sample_coefficients`` as a cell of [S x k] matrices.  With
     ``multi_models`` the same cells hold the mixture over all models, ``model_weights`` is [N x (2 + max_dlas)] and
     ``model_flags`` is an extra column.  :func:`load_model_spectra` reads it."""
-    off = np.asarray(mc["offsets"], dtype=np.int64)
-    nsel = off.size - 1
-    w = _MatWriter(path)
-    try:
-        for k, v in run_metadata.items():
-            w.put(k, v)
-        w.put("quasar_ind", np.asarray(mc.get("selection", np.arange(nsel)), dtype=np.float64) + 1)
-        w.put("num_pixels", np.diff(off).astype(np.float64))
-        w.put("status", np.asarray(mc.get("status", np.zeros(nsel)), dtype=np.float64))
-        _put_refined(w, mc)
-        for name in MARGINAL_CONTINUUM_CELLS:
-            if name in mc:
-                v = np.asarray(mc[name], dtype=np.float64)
-                w.put(name, [v[off[i]:off[i + 1]].reshape(-1, 1) for i in range(nsel)])
-        for name in MARGINAL_CONTINUUM_MATRICES:
-            if name in mc:
-                w.put(name, np.ascontiguousarray(mc[name], dtype=np.float64))
-        if "sample_coefficients" in mc:
-            v = np.asarray(mc["sample_coefficients"], dtype=np.float64)
-            w.put("sample_coefficients", [np.ascontiguousarray(v[i]) for i in range(nsel)])
-        if "model_flags" in mc:     # multi_models (DESIGN.md 4.25)
-            w.put("model_flags", np.asarray(mc["model_flags"], dtype=np.float64))
-    finally:
-        w.close()
-
-
-#: the posterior predictive flux (DESIGN.md 4.24): per-pixel cells, and columns / matrices
-PREDICTIVE_FLUX_CELLS = ("flux_mean", "flux_var", "flux_var_within", "flux_var_between", "noise_var", "residual")
-PREDICTIVE_FLUX_COLUMNS = ("chi2", "num_kept")
+    _save_grid_product(path, mc, ("marginal_continuum", "multi_models"), run_metadata)
 
 
 def save_predictive_flux(path: str, pf: dict, **run_metadata) -> None:
@@ -945,29 +920,7 @@ def save_predictive_flux(path: str, pf: dict, **run_metadata) -> None:
     when present) as ragged N x 1 cell arrays, ``chi2`` and ``num_kept`` as columns and ``model_weights`` [N x 3] as a
     matrix when present ([N x (2 + max_dlas)], with ``model_flags`` as an extra column, for ``multi_models``).
     :func:`load_predictive_flux` reads it."""
-    off = np.asarray(pf["offsets"], dtype=np.int64)
-    nsel = off.size - 1
-    w = _MatWriter(path)
-    try:
-        for k, v in run_metadata.items():
-            w.put(k, v)
-        w.put("quasar_ind", np.asarray(pf.get("selection", np.arange(nsel)), dtype=np.float64) + 1)
-        w.put("num_pixels", np.diff(off).astype(np.float64))
-        w.put("status", np.asarray(pf.get("status", np.zeros(nsel)), dtype=np.float64))
-        _put_refined(w, pf)
-        for name in PREDICTIVE_FLUX_CELLS:
-            if name in pf:
-                v = np.asarray(pf[name], dtype=np.float64)
-                w.put(name, [v[off[i]:off[i + 1]].reshape(-1, 1) for i in range(nsel)])
-        for name in PREDICTIVE_FLUX_COLUMNS:
-            if name in pf:
-                w.put(name, np.asarray(pf[name], dtype=np.float64))
-        if "model_weights" in pf:
-            w.put("model_weights", np.ascontiguousarray(pf["model_weights"], dtype=np.float64))
-        if "model_flags" in pf:     # multi_models (DESIGN.md 4.25)
-            w.put("model_flags", np.asarray(pf["model_flags"], dtype=np.float64))
-    finally:
-        w.close()
+    _save_grid_product(path, pf, ("predictive_flux", "multi_models"), run_metadata)
 
 
 def load_predictive_flux(path: str) -> dict:

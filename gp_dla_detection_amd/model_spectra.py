@@ -98,35 +98,44 @@ def select(results: dict, p_dla: float | None, indices) -> np.ndarray:
     return np.flatnonzero(p >= (0.0 if p_dla is None else p_dla))
 
 
-def run(preloaded: str, catalog: str, model_file: str, samples_file: str, processed: str, out: str,
-        p_dla: float | None = None, indices=None, products=("map", "moments", "continuum"), multi: bool | None = None,
-        moments_sub_dla: bool = False, device: int = 0, max_quasars_per_batch: int | None = None,
-        multi_models: bool = False, refined: dict | None = None) -> dict:
-    small = [k for k in ("model_posteriors", "p_dlas", "MAP_z_dlas", "MAP_log_nhis", "single_MAP_z_dlas",
-                         "single_MAP_log_nhis", "test_ind")] + (["log_priors_no_dla", "log_priors_dla"] if refined is not None else [])
-    results = io.loadmat73(processed, small)
-    results = {k[len("single_"):] if k.startswith("single_") else k: v for k, v in results.items()}
-    mp = np.asarray(results["model_posteriors"], dtype=np.float64)
-    is_multi = mp.shape[1] > 2 if multi is None else bool(multi)
-    for k in ("MAP_z_dlas", "MAP_log_nhis"):
-        v = np.asarray(results[k], dtype=np.float64)
-        results[k] = v.reshape(-1) if not is_multi else v  # MATLAB [nq x model x slot] is this package's order
-    results["p_dlas"] = np.asarray(results["p_dlas"], dtype=np.float64).reshape(-1)
+def _open_run(preloaded, catalog, model_file, samples_file, processed, small, p_dla, indices, refined=None):
+    """What every run opens of a processed run: the ``small`` variables of the processed file (and ``test_ind``; ``refined``:
+    the priors too) with the ``single_`` prefixes dropped and the probabilities and priors flat, the selection, the spectra
+    of the selected quasars alone (positions 0 .. len(sel) - 1 of the list map to ``sel``), the model and the samples.
+    Returns ``(results, sel, spectra_sel, model, samples)``."""
+    small = list(small) + ["test_ind"] + (["log_priors_no_dla", "log_priors_dla"] if refined is not None else [])
+    results = {}
+    for k, v in io.loadmat73(processed, small).items():
+        k = k[len("single_"):] if k.startswith("single_") else k
+        results[k] = np.asarray(v, dtype=np.float64).reshape(-1) if k.startswith(("p_", "log_priors_")) else v
     sel = select(results, p_dla, indices)
     z_qsos = np.asarray(io.load_catalog(catalog, ("z_qsos",))["z_qsos"], dtype=np.float64)
     test_ind = np.asarray(results["test_ind"]).reshape(-1).astype(bool) if "test_ind" in results else None
     run_pos = np.flatnonzero(test_ind) if test_ind is not None else np.arange(z_qsos.size)
     spectra_sel = io.load_preloaded_qsos(preloaded, z_qsos, run_pos[sel])
+    return results, sel, spectra_sel, io.load_learned_model(model_file), io.load_dla_samples(samples_file)
+
+
+def run(preloaded: str, catalog: str, model_file: str, samples_file: str, processed: str, out: str,
+        p_dla: float | None = None, indices=None, products=("map", "moments", "continuum"), multi: bool | None = None,
+        moments_sub_dla: bool = False, device: int = 0, max_quasars_per_batch: int | None = None,
+        multi_models: bool = False, refined: dict | None = None) -> dict:
+    small = ["model_posteriors", "p_dlas", "MAP_z_dlas", "MAP_log_nhis", "single_MAP_z_dlas", "single_MAP_log_nhis"]
+    results, sel, spectra_sel, model, samples = _open_run(preloaded, catalog, model_file, samples_file, processed, small,
+                                                          p_dla, indices, refined)
+    mp = np.asarray(results["model_posteriors"], dtype=np.float64)
+    is_multi = mp.shape[1] > 2 if multi is None else bool(multi)
+    for k in ("MAP_z_dlas", "MAP_log_nhis"):
+        v = np.asarray(results[k], dtype=np.float64)
+        results[k] = v.reshape(-1) if not is_multi else v  # MATLAB [nq x model x slot] is this package's order
     absorbers = api.map_absorbers(results, sub_dla=is_multi)
     absorbers_sel = api._take_absorbers(absorbers, sel)
-    model, samples = io.load_learned_model(model_file), io.load_dla_samples(samples_file)
     if multi_models and not is_multi:
         raise ValueError("--multi-models needs a multi-DLA processed file")
     # (refined: the weights are the refined table's, so the file's sample tables are neither needed nor opened)
     rows, close = sample_row_reader(processed, sub_dla=moments_sub_dla) if refined is None else (None, lambda: None)
     multi_rows, close_multi = multi_row_reader(processed) if multi_models else (None, lambda: None)
-    priors = None if refined is None else {k: np.asarray(results[k], dtype=np.float64).reshape(-1)[sel]
-                                           for k in ("log_priors_no_dla", "log_priors_dla")}
+    priors = None if refined is None else {k: results[k][sel] for k in ("log_priors_no_dla", "log_priors_dla")}
     try:  # the loaded list holds the selected quasars only: positions 0 .. len(sel) - 1 map to sel
         res = api.model_spectra(model, samples, spectra_sel, priors, params=MultiParameters() if is_multi else Parameters(),
                                 absorbers=absorbers_sel, moments_sub_dla=moments_sub_dla, products=products,
@@ -149,17 +158,10 @@ def _run_mixture(call, preloaded, catalog, model_file, samples_file, processed, 
     """What ``--marginal-continuum`` and ``--predictive-flux`` share: the selection of a processed file, its spectra,
     its sample tables streamed like the moments' rows, and ``call`` (:func:`api.marginal_continuum` or
     :func:`api.predictive_flux`) on them.  Returns ``(result with its selection, is_multi, components)``."""
-    small = ["model_posteriors", "p_dlas", "p_no_dlas", "p_lls", "test_ind"] + (
-        ["log_priors_no_dla", "log_priors_dla"] if more.get("refined") is not None else [])
-    results = {k: np.asarray(v, dtype=np.float64).reshape(-1) if k.startswith(("p_", "log_priors_")) else v
-               for k, v in io.loadmat73(processed, small).items()}
+    results, sel, spectra_sel, model, samples = _open_run(preloaded, catalog, model_file, samples_file, processed,
+                                                          ["model_posteriors", "p_dlas", "p_no_dlas", "p_lls"], p_dla, indices,
+                                                          more.get("refined"))
     is_multi = np.asarray(results["model_posteriors"]).shape[1] > 2 if multi is None else bool(multi)
-    sel = select(results, p_dla, indices)
-    z_qsos = np.asarray(io.load_catalog(catalog, ("z_qsos",))["z_qsos"], dtype=np.float64)
-    test_ind = np.asarray(results["test_ind"]).reshape(-1).astype(bool) if "test_ind" in results else None
-    run_pos = np.flatnonzero(test_ind) if test_ind is not None else np.arange(z_qsos.size)
-    spectra_sel = io.load_preloaded_qsos(preloaded, z_qsos, run_pos[sel])
-    model, samples = io.load_learned_model(model_file), io.load_dla_samples(samples_file)
     components = tuple(components)
     readers = {} if more.get("refined") is not None else {
         name: sample_row_reader(processed, sub_dla=name == "sub_dla") for name in components if name != "null"}
@@ -182,17 +184,11 @@ def _run_mixture_multi(call, preloaded, catalog, model_file, samples_file, proce
     its spectra, its three tables streamed by :func:`multi_row_reader` (as ``--multi-models`` of the moments streams them)
     and ``call(..., multi_models=True)``.  ``model_weights``: ``"posteriors"`` (the file's ``model_posteriors``) or
     ``"equal"`` (equal over all ``2 + max_dlas`` components).  Returns the result with its selection and model_weights."""
-    results = {k: np.asarray(v, dtype=np.float64).reshape(-1) if k.startswith("p_") else v
-               for k, v in io.loadmat73(processed, ["model_posteriors", "p_dlas", "test_ind"]).items()}
+    results, sel, spectra_sel, model, samples = _open_run(preloaded, catalog, model_file, samples_file, processed,
+                                                          ["model_posteriors", "p_dlas"], p_dla, indices)
     mp = np.asarray(results["model_posteriors"], dtype=np.float64)
     if mp.shape[1] <= 2:
         raise ValueError("--multi-models needs a multi-DLA processed file")
-    sel = select(results, p_dla, indices)
-    z_qsos = np.asarray(io.load_catalog(catalog, ("z_qsos",))["z_qsos"], dtype=np.float64)
-    test_ind = np.asarray(results["test_ind"]).reshape(-1).astype(bool) if "test_ind" in results else None
-    run_pos = np.flatnonzero(test_ind) if test_ind is not None else np.arange(z_qsos.size)
-    spectra_sel = io.load_preloaded_qsos(preloaded, z_qsos, run_pos[sel])
-    model, samples = io.load_learned_model(model_file), io.load_dla_samples(samples_file)
     weights = mp[sel] if model_weights == "posteriors" else np.ones((sel.size, mp.shape[1]))
     multi_rows, close = multi_row_reader(processed)
     try:  # the loaded list holds the selected quasars only: positions 0 .. len(sel) - 1 map to sel
