@@ -208,6 +208,32 @@ class PredictiveFluxMulti(C.Structure):
                 ("flux_var_between", _dp), ("noise_var", _dp), ("status", _i32p), ("model_flags", _u32p)]
 
 
+_DISTRIBUTION_FIELDS = [("num_thresholds", C.c_int32), ("thresholds", _dp), ("num_bins", C.c_int32), ("num_levels", C.c_int32),
+                        ("levels", _dp)]
+_DISTRIBUTION_ARRAYS = [("prob_below", _dp), ("absorption_min", _dp), ("absorption_max", _dp), ("histogram", _dp), ("quantiles", _dp)]
+DISTRIBUTION_MAX_THRESHOLDS, DISTRIBUTION_MAX_LEVELS, DISTRIBUTION_MIN_BINS, DISTRIBUTION_MAX_BINS = 4, 8, 8, 256
+
+
+class AbsorptionDistributionRequest(C.Structure):
+    """gpdla_absorption_distribution_request"""
+    _fields_ = list(PredictiveFluxRequest._fields_) + _DISTRIBUTION_FIELDS
+
+
+class AbsorptionDistribution(C.Structure):
+    """gpdla_absorption_distribution"""
+    _fields_ = [("offsets", _i64p)] + _DISTRIBUTION_ARRAYS + [("status", _i32p)]
+
+
+class AbsorptionDistributionMultiRequest(C.Structure):
+    """gpdla_absorption_distribution_multi_request"""
+    _fields_ = list(MarginalContinuumMultiRequest._fields_) + _DISTRIBUTION_FIELDS
+
+
+class AbsorptionDistributionMulti(C.Structure):
+    """gpdla_absorption_distribution_multi"""
+    _fields_ = [("offsets", _i64p)] + _DISTRIBUTION_ARRAYS + [("status", _i32p), ("model_flags", _u32p)]
+
+
 class MockRequest(C.Structure):
     """gpdla_mock_request"""
     _fields_ = [("seed", C.c_uint64), ("absorber_offsets", _i64p), ("absorber_z", _dp), ("absorber_nhi", _dp),
@@ -391,6 +417,13 @@ SYMBOLS = [
                                                     C.POINTER(PredictiveFluxMulti)]),
     ("gpdla_batch_predictive_flux", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(PredictiveFluxRequest),
                                               C.POINTER(PredictiveFlux)]),
+    ("gpdla_absorption_distribution_validate", C.c_int, [C.POINTER(AbsorptionDistributionRequest), C.c_int64, C.c_int64, C.c_int]),
+    ("gpdla_batch_absorption_distribution", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(AbsorptionDistributionRequest),
+                                                      C.POINTER(AbsorptionDistribution)]),
+    ("gpdla_absorption_distribution_multi_validate", C.c_int, [C.POINTER(AbsorptionDistributionMultiRequest), C.c_int64, C.c_int64,
+                                                               C.c_int, C.c_int, C.c_int]),
+    ("gpdla_batch_absorption_distribution_multi", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(AbsorptionDistributionMultiRequest),
+                                                            C.POINTER(AbsorptionDistributionMulti)]),
     ("gpdla_debug_profiles_ms", C.c_int, [C.c_void_p, C.c_void_p, _dp]),
     ("gpdla_model_mean", C.c_int, [C.POINTER(Model), C.c_int64, _dp, _i64p, _dp, _dp, C.c_int, C.c_int, C.c_int,
                                    C.c_double, C.c_double, _dp, C.c_int]),

@@ -773,6 +773,67 @@ class Batch:
             out.update(predictive_residuals(out, y, kept))
         return out
 
+    # ---- absorption distribution ----
+
+    @staticmethod
+    def _distribution_request(rq, thresholds, bins, levels, histogram, keep: list):
+        """Fill what the two absorption-distribution requests ask of the reduction; returns ``shapes(total)`` of the arrays
+        the call returns.  The arrays the request points into are appended to ``keep``."""
+        thr = np.ascontiguousarray(() if thresholds is None else thresholds, dtype=np.float64).reshape(-1)
+        lev = np.ascontiguousarray(() if levels is None else levels, dtype=np.float64).reshape(-1)
+        keep += [thr, lev]
+        rq.num_thresholds, rq.thresholds = thr.size, thr.ctypes.data_as(_dp)
+        rq.num_levels, rq.levels = lev.size, lev.ctypes.data_as(_dp)
+        rq.num_bins = int(bins) if (histogram or lev.size) else 0
+        B = rq.num_bins
+
+        def shapes(total):
+            out = {"prob_below": (thr.size, total), "absorption_min": (total,), "absorption_max": (total,)}
+            if lev.size:
+                out["quantiles"] = (lev.size, total)
+            if histogram:
+                out["histogram"] = (B, total)
+            return out
+        return shapes
+
+    def absorption_distribution(self, selection=None, weights="resident", components=("dla",), model_weights=None,
+                                thresholds=(0.8,), bins: int = 64, levels=None, histogram: bool = False,
+                                meanflux: bool | None = None) -> dict:
+        """The per-pixel DISTRIBUTION of the absorption of the selected quasars over the absorber posterior and the models
+        (gpdla_batch_absorption_distribution; the definitions are in include/gpdla.h), where ``mean_absorption`` and
+        ``var_absorption`` stop at two moments: with abar the broadened profile clamped to [0, 1],
+
+        ``prob_below [T, total]``: the posterior probability that abar <= ``thresholds[j]`` (1 to 4 thresholds strictly inside
+        (0, 1)) -- what a forest mask is cut from (:func:`forest_mask`);
+        ``absorption_min``, ``absorption_max``: the extremes of abar over the samples and models of positive weight;
+        ``quantiles [Q, total]`` (``levels``: 1 to 8 strictly inside (0, 1)): the credible bands of the absorber profile, read off
+        a histogram of ``bins`` (8 .. 256) equal bins -- exact where the pixel is unabsorbed (1) or saturated (0), within one
+        bin width elsewhere;
+        ``histogram [bins, total]`` (``histogram=True``): the masses of the bins themselves.
+
+        ``selection``, ``weights``, ``components``, ``model_weights``, ``meanflux``: as :meth:`marginal_continuum`
+        (``weights="refined"`` included: the DLA component on the refined table; ``weights=None`` with ``components=("null",)``
+        is the unabsorbed answer).  A call without ``levels`` and ``histogram`` runs the kernel without bins.
+        Returns those with ``offsets [nsel + 1]`` and ``status [nsel]`` in the CSR layout of :meth:`model_spectra`."""
+        rq = _lib.AbsorptionDistributionRequest()
+        sel, keep = self._mixture_request(rq, selection, weights, components, model_weights, meanflux)
+        shapes = self._distribution_request(rq, thresholds, bins, levels, histogram, keep)
+        out = self._grid_product("absorption_distribution", rq, sel, _lib.AbsorptionDistribution(), shapes)
+        del keep
+        return out
+
+    def absorption_distribution_multi(self, selection=None, tables="resident", model_weights=None, thresholds=(0.8,),
+                                      bins: int = 64, levels=None, histogram: bool = False, meanflux: bool | None = None) -> dict:
+        """:meth:`absorption_distribution` over ALL models of a multi-DLA run (gpdla_batch_absorption_distribution_multi): the
+        components, ``tables``, ``model_weights`` and ``model_flags`` of :meth:`marginal_continuum_multi` -- sample i of model
+        DLA(n) absorbs with the product of the n profiles of its slots."""
+        rq = _lib.AbsorptionDistributionMultiRequest()
+        sel, _md, keep = self._mixture_multi_request(rq, selection, tables, model_weights, meanflux)
+        shapes = self._distribution_request(rq, thresholds, bins, levels, histogram, keep)
+        out = self._grid_product_multi("absorption_distribution_multi", rq, sel, _lib.AbsorptionDistributionMulti(), shapes)
+        del keep
+        return out
+
     # ---- refined posteriors (DESIGN.md 4.18) ----
 
     def _selection(self, selection):
@@ -1671,12 +1732,13 @@ def stitch_blocks(blocks, n: int, per_block, expect, dims: dict, refined: dict |
 
 
 def _drive(model: dict, samples: dict, spectra, sel, params, device: int, max_quasars_per_batch, per_block, expect,
-           refined: dict | None = None) -> dict:
-    """:func:`stitch_blocks` over :func:`_resident_blocks` of the selected quasars, with ``selection`` in front."""
+           refined: dict | None = None, plane_dims: dict | None = None) -> dict:
+    """:func:`stitch_blocks` over :func:`_resident_blocks` of the selected quasars, with ``selection`` in front.
+    ``plane_dims``: the named leading dimensions of the product's planes (:mod:`grid_fields`)."""
     S = np.asarray(samples["offset_samples"]).size
     if refined is not None and refined["points"] is not None:    # S': the refine points the options name
         S = int(refined["points"]) if np.ndim(refined["points"]) == 0 else np.asarray(refined["points"][0]).size
-    dims = dict(k=np.asarray(model["M"]).shape[1], samples=S, max_dlas=int(getattr(params, "max_dlas", 0)))
+    dims = dict(k=np.asarray(model["M"]).shape[1], samples=S, max_dlas=int(getattr(params, "max_dlas", 0)), **(plane_dims or {}))
     with closing(_resident_blocks(model, samples, spectra, sel, params, device, max_quasars_per_batch, refined)) as blocks:
         return {"selection": sel, **stitch_blocks(blocks, sel.size, per_block, expect, dims, refined)}
 
@@ -1808,8 +1870,8 @@ def _mixture_inputs(results, components, model_weights, sample_rows):
 
 
 def _mixture(product: str, kw: dict, model, samples, spectra, results, params, selection, components, model_weights, sample_rows,
-             device, max_quasars_per_batch, multi_models, multi_rows, refined) -> dict:
-    """What :func:`marginal_continuum` and :func:`predictive_flux` are: ``Batch.<product>(**kw)`` block by block through
+             device, max_quasars_per_batch, multi_models, multi_rows, refined, plane_dims: dict | None = None) -> dict:
+    """What :func:`marginal_continuum`, :func:`predictive_flux` and :func:`absorption_distribution` are: ``Batch.<product>(**kw)`` block by block through
     :func:`_drive` -- on the refined table (``refined``), over all models of a multi-DLA run (``multi_models``:
     ``Batch.<product>_multi`` with the switches of ``kw`` that are on) or on the saved tables."""
     p = params or Parameters()
@@ -1817,6 +1879,8 @@ def _mixture(product: str, kw: dict, model, samples, spectra, results, params, s
     sel = _selected(spectra, selection)
     refined = _refined_options(refined, results, p)
     on = {name: v for name, v in kw.items() if v}
+    # (the multi forms take the switches that are on; an argument that is no switch of a field goes through as given)
+    on_multi = {name: v for name, v in kw.items() if v or name in ("thresholds", "bins", "levels")}
     expect = grid_fields.requested(product, on)
     if refined is not None:
         if multi_models:
@@ -1845,7 +1909,7 @@ def _mixture(product: str, kw: dict, model, samples, spectra, results, params, s
         expect = grid_fields.requested("multi_models") + expect
 
         def per_block(batch, idx, lo, hi):
-            return getattr(batch, product + "_multi")(tables=multi_rows(idx), model_weights=model_weights[idx], **on)
+            return getattr(batch, product + "_multi")(tables=multi_rows(idx), model_weights=model_weights[idx], **on_multi)
     else:
         components, sampled, model_weights, sample_rows = _mixture_inputs(results, components, model_weights, sample_rows)
 
@@ -1853,7 +1917,7 @@ def _mixture(product: str, kw: dict, model, samples, spectra, results, params, s
             return getattr(batch, product)(weights={c: np.asarray(sample_rows(idx, c), dtype=np.float64) for c in sampled} or None,
                                            components=components, model_weights=None if model_weights is None else model_weights[idx],
                                            **kw)
-    return _drive(model, samples, spectra, sel, p, device, max_quasars_per_batch, per_block, expect, refined)
+    return _drive(model, samples, spectra, sel, p, device, max_quasars_per_batch, per_block, expect, refined, plane_dims)
 
 
 def marginal_continuum(model: dict, samples: dict, spectra, results: dict | None = None,
@@ -1927,6 +1991,39 @@ def predictive_flux(model: dict, samples: dict, spectra, results: dict | None = 
     with ``refined`` the DLA component runs on the refined table, posterior mass outside the last box ignored)."""
     return _mixture("predictive_flux", dict(residuals=residuals), model, samples, spectra, results, params, selection, components,
                     model_weights, sample_rows, device, max_quasars_per_batch, multi_models, multi_rows, refined)
+
+
+def absorption_distribution(model: dict, samples: dict, spectra, results: dict | None = None,
+                            params: Parameters | None = None, selection=None, components=("dla",), model_weights="posteriors",
+                            thresholds=(0.8,), bins: int = 64, levels=None, histogram: bool = False, sample_rows=None,
+                            device: int = 0, max_quasars_per_batch: int | None = None, multi_models: bool = False,
+                            multi_rows=None, refined: dict | None = None) -> dict:
+    """The per-pixel distribution of the absorption (:meth:`Batch.absorption_distribution`) of the selected quasars of a
+    processed run, block by block like :func:`predictive_flux`, whose shared arguments mean the same here: nothing is
+    swept again, the posterior weights come from the saved sample log-likelihoods, ``model_weights="posteriors"`` (the
+    default: a mask is a statement about the sightline, not about the DLA model alone) mixes by
+    :func:`posterior_model_weights` -- list the components to mix, ``("null", "dla")`` or all three -- and
+    ``multi_models`` / ``multi_rows`` / ``refined`` select :meth:`Batch.absorption_distribution_multi` or the refined table.
+    ``thresholds``, ``bins``, ``levels``, ``histogram``: as :meth:`Batch.absorption_distribution`.  Returns ``selection``,
+    ``offsets``, ``status`` and its arrays in selection order; results do not depend on the batching, and an empty selection
+    returns the same keys with no extent.  :func:`forest_mask` cuts the mask."""
+    thr = () if thresholds is None else tuple(np.asarray(thresholds, dtype=np.float64).reshape(-1))
+    lev = None if levels is None or np.size(levels) == 0 else tuple(np.asarray(levels, dtype=np.float64).reshape(-1))
+    kw = dict(thresholds=thr, bins=int(bins), levels=lev, histogram=bool(histogram))
+    return _mixture("absorption_distribution", kw, model, samples, spectra, results, params, selection, components, model_weights,
+                    sample_rows, device, max_quasars_per_batch, multi_models, multi_rows, refined,
+                    plane_dims=dict(thresholds=len(thr), levels=len(lev or ()), bins=int(bins)))
+
+
+def forest_mask(result: dict, threshold_index: int = 0, probability: float = 0.5) -> np.ndarray:
+    """The per-pixel boolean mask ``prob_below[threshold_index] >= probability`` of what
+    :func:`absorption_distribution` (or the :class:`Batch` methods) returns: the pixels whose transmission is at or below the
+    threshold with at least that posterior probability.  A NaN pixel (a quasar that was not evaluated) is not masked.
+    The wings outside the mask are corrected by the caller's division of the flux by ``expected_absorption`` or
+    ``mean_absorption`` of :func:`model_spectra`; this function only cuts the mask."""
+    p = np.asarray(result["prob_below"], dtype=np.float64)[threshold_index]
+    with np.errstate(invalid="ignore"):
+        return np.where(np.isnan(p), False, p >= probability)
 
 
 # ----------------------------------------------------------------------------------------------

@@ -41,6 +41,7 @@
 #include "spectra_multi_kernels.hpp"
 #include "marginal_continuum_kernels.hpp"
 #include "predictive_flux_kernels.hpp"
+#include "absorption_distribution_kernels.hpp"
 #include "mock_kernels.hpp"
 #include "sample_kernels.hpp"
 #include "preload_kernels.hpp"
@@ -68,6 +69,7 @@ using namespace gpdla;
 #include "host_marginal_continuum.hpp"
 #include "host_predictive_flux.hpp"
 #include "host_mixture_multi.hpp"
+#include "host_absorption_distribution.hpp"
 #include "host_mock.hpp"
 #include "host_samples.hpp"
 #include "host_preload.hpp"

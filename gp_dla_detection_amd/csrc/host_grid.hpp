@@ -227,6 +227,7 @@ struct MixtureSpec {
   bool meanflux;
   int64_t capacity;
   const RefinedTable *refined;      // md = 1: DLA(1) runs on the refined table with its own S' samples; nullptr: on `dla`
+  bool no_scratch;                  // the product runs no k_mc_contract: no scratch rows, no chunk flags; a group is sized by its weights
 };
 
 // of a single-DLA entry; `tables` as validate_mixture gave them (no table is looked up for a mixture that reaches none)
@@ -359,12 +360,13 @@ struct MixturePlan {
     chunks = (int)((Smax + kMcSolveChunk - 1) / kMcSolveChunk);
     nsub = nsel;
     if (reach) {
-      const size_t per_q = (size_t)Smax * ncol * sizeof(double);
+      const size_t per_q = (size_t)Smax * (sp.no_scratch ? ncomp : ncol) * sizeof(double);
       nsub = std::min<int64_t>(nsel, std::max<int64_t>(1, (int64_t)(mc_scratch_bytes() / per_q)));
       if (nsub * chunks > 2147483647LL) return fail(GPDLA_ERR_UNSUPPORTED, "selection too large for one launch");
-      if ((rc = sg.tmp.alloc(&d_scratch, (size_t)nsub * Smax * ncol)) || (rc = sg.tmp.alloc(&d_notpd, (size_t)ncomp * nsub * chunks)) ||
-          (rc = sg.tmp.alloc(&d_w, (size_t)ncomp * nsub * Smax)))
+      if (!sp.no_scratch &&
+          ((rc = sg.tmp.alloc(&d_scratch, (size_t)nsub * Smax * ncol)) || (rc = sg.tmp.alloc(&d_notpd, (size_t)ncomp * nsub * chunks))))
         return rc;
+      if ((rc = sg.tmp.alloc(&d_w, (size_t)ncomp * nsub * Smax))) return rc;
     }
     if ((rc = sg.tmp.alloc(&d_flag, (size_t)ncomp * nsel))) return rc;
     HIP_TRY(hipMemsetAsync(d_flag, 0, (size_t)ncomp * nsel * sizeof(int32_t), st));

@@ -1,5 +1,5 @@
-"""The fields of the grid products -- model spectra, marginal continuum, predictive flux (DESIGN.md 4.12, 4.21, 4.23-4.25,
-4.28) -- declared once: the drivers of :mod:`api` stitch their blocks by this table and the savers of :mod:`io` write their
+"""The fields of the grid products -- model spectra, marginal continuum, predictive flux, absorption distribution (DESIGN.md
+4.12, 4.21, 4.23-4.25, 4.28, 4.29) -- declared once: the drivers of :mod:`api` stitch their blocks by this table and the savers of :mod:`io` write their
 files by it, so a field is returned and saved, or neither.  No package imports: both modules import it.
 
 A result holds ``offsets [n + 1]`` and ``status [n]`` (and, refined, ``boxes`` and ``refine_status``), then these fields.
@@ -9,11 +9,13 @@ Quasar s of the selection owns pixels ``[offsets[s], offsets[s + 1])`` of its ``
 kind       shape                                      in a file
 =========  =========================================  ==========================================================
 ``pixel``  ``[total]``, joined along the last axis     a cell of column vectors
-``plane``  ``[max_dlas, total]``, last axis            a cell of ``[pixels x max_dlas]`` matrices
+``plane``  ``[D, total]``, last axis                   a cell of ``[pixels x D]`` matrices
 ``row``    ``[n, *trailing]``, joined along axis 0     a matrix; a cell of matrices for two trailing dimensions
 ``column`` ``[n]`` of ``dtype``                        a column
 =========  =========================================  ==========================================================
 
+``leading`` names the first dimension D of a plane: ``thresholds``, ``levels``, ``bins`` (the absorption distribution's, what
+the call asked for); a plane without a name has ``max_dlas`` rows.
 ``trailing`` names the dimensions of a row after the first: ``k`` (the rank), ``tri`` (k (k + 1) / 2, a packed lower
 triangle), ``samples`` (S, or the S' refine points where the DLA component runs on the refined table); None: the caller's.
 ``option``: the switch of the call that asks for the field (None: always); ``"caller"``: no driver returns it, the
@@ -25,11 +27,11 @@ from collections import namedtuple
 
 import numpy as np
 
-Field = namedtuple("Field", "product name kind dtype trailing option")
+Field = namedtuple("Field", "product name kind dtype trailing option leading", defaults=(None,))
 
 
-def _f(product, name, kind, dtype=np.float64, trailing=None, option=None):
-    return Field(product, name, kind, np.dtype(dtype), trailing, option)
+def _f(product, name, kind, dtype=np.float64, trailing=None, option=None, leading=None):
+    return Field(product, name, kind, np.dtype(dtype), trailing, option, leading)
 
 
 FIELDS = (
@@ -62,6 +64,13 @@ FIELDS = (
     _f("predictive_flux", "chi2", "column", option="residuals"),
     _f("predictive_flux", "num_kept", "column", np.int64, option="residuals"),
     _f("predictive_flux", "model_weights", "row", option="caller"),
+    # the absorption distribution
+    _f("absorption_distribution", "prob_below", "plane", leading="thresholds"),
+    _f("absorption_distribution", "absorption_min", "pixel"),
+    _f("absorption_distribution", "absorption_max", "pixel"),
+    _f("absorption_distribution", "quantiles", "plane", option="levels", leading="levels"),
+    _f("absorption_distribution", "histogram", "plane", option="histogram", leading="bins"),
+    _f("absorption_distribution", "model_weights", "row", option="caller"),
     # every multi_models form: a result carries it right after ``status``, a file holds it last
     _f("multi_models", "model_flags", "column", np.uint32),
 )
@@ -88,8 +97,9 @@ def join(field: Field, parts: list) -> np.ndarray:
 
 
 def empty(field: Field, dims: dict) -> np.ndarray:
-    """``field`` of an empty selection; ``dims``: ``k``, ``samples`` and ``max_dlas``."""
+    """``field`` of an empty selection; ``dims``: ``k``, ``samples`` and ``max_dlas`` (and the named leading dimension of a
+    plane that has one)."""
     sizes = dict(dims, tri=dims["k"] * (dims["k"] + 1) // 2)
-    shape = {"pixel": (0,), "column": (0,), "plane": (dims["max_dlas"], 0),
+    shape = {"pixel": (0,), "column": (0,), "plane": (dims[field.leading or "max_dlas"], 0),
              "row": (0,) + tuple(sizes[d] for d in field.trailing or ())}[field.kind]
     return np.zeros(shape, dtype=field.dtype)

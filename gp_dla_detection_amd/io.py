@@ -914,6 +914,16 @@ def save_marginal_continuum(path: str, mc: dict, **run_metadata) -> None:
     _save_grid_product(path, mc, ("marginal_continuum", "multi_models"), run_metadata)
 
 
+def save_absorption_distribution(path: str, dist: dict, thresholds=(), levels=(), num_bins: int = 0, **run_metadata) -> None:
+    """What :func:`api.absorption_distribution` returns as a ``-v7.3`` file, in the layout of :func:`save_marginal_continuum`:
+    ``prob_below``, ``quantiles`` and ``histogram`` as cells of ``[pixels x D]`` matrices (D thresholds, levels, bins),
+    ``absorption_min`` / ``absorption_max`` as cells of column vectors, and the ``thresholds``, ``levels`` and ``num_bins`` the
+    call was made with, so that the file explains its own columns."""
+    meta = dict(run_metadata, thresholds=np.asarray(thresholds, dtype=np.float64).reshape(-1),
+                levels=np.asarray(() if levels is None else levels, dtype=np.float64).reshape(-1), num_bins=np.float64(num_bins))
+    _save_grid_product(path, dist, ("absorption_distribution", "multi_models"), meta)
+
+
 def save_predictive_flux(path: str, pf: dict, **run_metadata) -> None:
     """What :func:`api.predictive_flux` returns as a ``-v7.3`` file, in the layout of :func:`save_marginal_continuum`:
     ``quasar_ind`` (1-based), ``num_pixels`` and ``status`` as columns, the five per-pixel arrays (and ``residual``

@@ -17,6 +17,10 @@ are the rows of the processed file's sample table, streamed in blocks of selecte
 profile is averaged over the refined table instead of the first pass's (posterior mass outside a quasar's
 last box is ignored).  The file gains ``refine_boxes`` and ``refine_status``.
 
+``--absorption-distribution [--thresholds 0.8,0.5] [--bins 64] [--quantile-levels 0.025,0.16,0.5,0.84,0.975] [--histogram]``
+writes the per-pixel distribution of the absorption instead; it combines with ``--multi-models``,
+``--components``, ``--model-weights`` and ``--refined`` as ``--predictive-flux`` does.
+
 The module shares its name with :func:`gp_dla_detection_amd.api.model_spectra`, so it is callable:
 ``gp_dla_detection_amd.model_spectra(model, samples, spectra, results, ...)`` is that function.
 """
@@ -250,6 +254,34 @@ def run_predictive_flux(preloaded: str, catalog: str, model_file: str, samples_f
     return res
 
 
+def run_absorption_distribution(preloaded: str, catalog: str, model_file: str, samples_file: str, processed: str, out: str,
+                                p_dla: float | None = None, indices=None, components=("dla",), model_weights="posteriors",
+                                thresholds=(0.8,), bins: int = 64, levels=None, histogram: bool = False,
+                                multi: bool | None = None, device: int = 0, max_quasars_per_batch: int | None = None,
+                                multi_models: bool = False, refined: dict | None = None) -> dict:
+    """``--absorption-distribution``: :func:`api.absorption_distribution` of the selected quasars of a processed file, its
+    sample tables streamed like the moments' rows, written by :func:`io.save_absorption_distribution`.  ``thresholds``,
+    ``bins``, ``levels`` (``--quantile-levels``), ``histogram``: as :meth:`api.Batch.absorption_distribution`; the other
+    arguments are those of :func:`run_marginal_continuum`."""
+    if multi_models and refined is not None:
+        raise ValueError("--refined: not with --multi-models (a multi-DLA batch cannot be refined)")
+    dist = dict(thresholds=tuple(thresholds), bins=int(bins), levels=None if not levels else tuple(levels), histogram=bool(histogram))
+    request = dict(thresholds=dist["thresholds"], levels=dist["levels"] or (), num_bins=dist["bins"] if (histogram or levels) else 0)
+    if multi_models:
+        res = _run_mixture_multi(api.absorption_distribution, preloaded, catalog, model_file, samples_file, processed, p_dla,
+                                 indices, model_weights, device, max_quasars_per_batch, **dist)
+        io.save_absorption_distribution(out, res, processed_file=str(processed), multi_dla=np.float64(1), multi_models=np.float64(1),
+                                        **request)
+        return res
+    res, is_multi, components = _run_mixture(api.absorption_distribution, preloaded, catalog, model_file, samples_file, processed,
+                                             p_dla, indices, components, model_weights, multi, device, max_quasars_per_batch,
+                                             **dist, **({"refined": refined} if refined is not None else {}))
+    io.save_absorption_distribution(out, res, processed_file=str(processed), multi_dla=np.float64(is_multi),
+                                    components=",".join(components), **request,
+                                    **({"refined": np.float64(1)} if refined is not None else {}))
+    return res
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     for name in ("preloaded", "catalog", "model", "samples", "processed", "out"):
@@ -268,6 +300,15 @@ def main(argv=None) -> int:
     ap.add_argument("--predictive-flux", action="store_true",
                     help="write the posterior predictive flux instead (DESIGN.md 4.24): per-pixel mean and variance of "
                          "absorption times continuum over the sample tables and the models")
+    ap.add_argument("--absorption-distribution", action="store_true",
+                    help="write the per-pixel distribution of the absorption instead (DESIGN.md 4.29): the probability of a "
+                         "transmission at or below each threshold, the extremes and, with --quantile-levels / --histogram, "
+                         "the quantiles and the histogram; combines with --multi-models, --components, --model-weights, --refined")
+    ap.add_argument("--thresholds", type=str, default="0.8", help="--absorption-distribution: up to 4 thresholds inside (0, 1)")
+    ap.add_argument("--bins", type=int, default=64, help="--absorption-distribution: bins of the histogram, 8 .. 256")
+    ap.add_argument("--quantile-levels", type=str, default=None,
+                    help="--absorption-distribution: up to 8 quantile levels inside (0, 1), e.g. 0.025,0.16,0.5,0.84,0.975")
+    ap.add_argument("--histogram", action="store_true", help="--absorption-distribution: also the histogram itself")
     ap.add_argument("--residuals", action="store_true",
                     help="--predictive-flux: also the in-sample replicate residuals, chi2 and num_kept")
     ap.add_argument("--components", type=str, default="dla",
@@ -288,6 +329,16 @@ def main(argv=None) -> int:
     if (a.levels is not None or a.points is not None) and not a.refined:
         ap.error("--levels and --points go with --refined")
     refined = dict(levels=a.levels, points=a.points) if a.refined else None
+    if a.absorption_distribution:
+        res = run_absorption_distribution(a.preloaded, a.catalog, a.model, a.samples, a.processed, a.out, p_dla=a.p_dla, indices=idx,
+                                          components=tuple(x for x in a.components.split(",") if x), model_weights=a.model_weights,
+                                          thresholds=tuple(float(x) for x in a.thresholds.split(",") if x), bins=a.bins,
+                                          levels=None if a.quantile_levels is None else
+                                          tuple(float(x) for x in a.quantile_levels.split(",") if x),
+                                          histogram=a.histogram, device=a.device, max_quasars_per_batch=a.max_quasars_per_batch,
+                                          multi_models=a.multi_models, refined=refined)
+        print(f"wrote {a.out}: {res['selection'].size} quasars, {int(res['offsets'][-1])} grid pixels")
+        return 0
     if a.predictive_flux:
         res = run_predictive_flux(a.preloaded, a.catalog, a.model, a.samples, a.processed, a.out, p_dla=a.p_dla, indices=idx,
                                   components=tuple(x for x in a.components.split(",") if x), model_weights=a.model_weights,

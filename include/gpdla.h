@@ -1526,6 +1526,127 @@ int gpdla_batch_predictive_flux_multi(gpdla_context *ctx, gpdla_batch *batch,
                                       const gpdla_predictive_flux_multi_request *request,
                                       gpdla_predictive_flux_multi *out);
 
+/* ---------------------------------------------------------------------------------------------
+ * Absorption distribution: per pixel, the DISTRIBUTION of the absorption over the sample tables and over the models
+ *  -- the posterior probability that the transmission is at or below a threshold (forest masks), the
+ * support, a histogram and its quantiles (credible bands of the absorber profile).  Additive: GPDLA_ABI_VERSION is
+ * unchanged.  fp64 throughout; tests/absorption_distribution_restatement.py states the same in NumPy.
+ *
+ * Everything lives on the unmasked-range grid of a selected quasar (n_u pixels, CSR offsets), as for
+ * gpdla_batch_model_spectra.
+ * Components.  The components m and their per-quasar model weights p_m are those of gpdla_batch_marginal_continuum
+ *   (null, the sub-DLA table, the DLA table; model_weights NULL: (0, 0, 1)), for the _multi entry those of
+ *   gpdla_batch_marginal_continuum_multi (null, sub-DLA, DLA(1) .. DLA(max_dlas); model_weights NULL: the resident
+ *   model_posteriors).  Rows are non-negative, finite, of positive sum, and normalised by their sum.
+ * Samples.  Sample i of component m has the broadened profile a_{m,i}(p) of mean_absorption; for DLA(n), n >= 2, the
+ *   product of the n gathered profiles in slot order, as mean_absorption_models defines it.  The weights w_{m,i} are
+ *   those of mean_absorption: exp(l - max l) / Sum, NaN -> 0.  Write abar = min(max(a, 0), 1).  The null component is
+ *   one atom at abar = 1.
+ * Exceedance.  F_p(t) = Sum_m p_m Sum_i w_{m,i} [abar_{m,i}(p) <= t].
+ * Support.  S_p: the atoms with p_m w_{m,i} > 0, the null atom included when p_null > 0.
+ *
+ * prob_below [num_thresholds][capacity] = F_p(t_j); the thresholds are finite and strictly inside (0, 1), at most 4.
+ *   The null atom never counts (t_j < 1).  The comparison is made on abar itself, not read off the histogram.  The
+ *   normalised weights add up to 1 within rounding only: the reported value is min(F, 1).
+ * absorption_min, absorption_max [capacity]: the minimum and maximum of abar over S_p.
+ * histogram [num_bins][capacity]: H_b(p) = the mass of the atoms with bin(abar) = b,
+ *   bin(x) = min(B - 1, (int)(x * (double)B)), B = num_bins in [8, 256]; the null atom falls in bin B - 1.
+ * quantiles [num_levels][capacity]: levels l_j strictly inside (0, 1), at most 8.  C_b = H_0 + .. + H_b, added in
+ *   ascending b, C_{-1} = 0; b* the first b with C_b >= l (none, by rounding: B - 1);
+ *   q = (b* + clamp((l - C_{b*-1}) / H_{b*}, 0, 1)) / B, then clamped to [absorption_min, absorption_max]: an unabsorbed
+ *   pixel reports 1, a saturated core 0; elsewhere the error is at most one bin width.  quantiles needs neither of the
+ *   other arrays to be requested.
+ * num_thresholds = 0: no prob_below.  num_bins = 0: no histogram (num_levels must be 0 then).  Both 0: refused.  A call
+ * whose histogram and quantiles pointers are NULL runs the kernel variant without bins whatever num_bins says.
+ *
+ * Special rows follow the siblings.  A quasar of sweep status 1 or 3 (no kept pixel; unusable noise) gets NaN rows and
+ * that status.  A component of positive model weight whose row has no weights gets NaN rows and status 0 (_multi: named in
+ * model_flags).  A component of weight exactly 0 is not evaluated; a sample of weight exactly 0 enters nothing.  With
+ * GPDLA_SPECTRA_WEIGHTS_REFINED (single-DLA entry only) the DLA component runs on the S' refine points of the quasar's last
+ * box, as defined under "THE REFINED SOURCE" above: a selected quasar without a refined table gets NaN rows and
+ * GPDLA_SPECTRA_NOT_REFINED, a stale or missing refine pass is GPDLA_ERR_INVALID_ARGUMENT, the sub-DLA component keeps its
+ * first-pass table.  A conditioned batch is refused.  weights_source NONE with a null-only mixture is legal: prob_below 0,
+ * all mass in bin B - 1, minimum = maximum = quantiles = 1.  _multi: a row of model weights with a NaN gives NaN rows and
+ * GPDLA_SPECTRA_AVERAGE_UNDEFINED.
+ *
+ * Sums run in a fixed order without floating-point atomics (samples in z_DLA order within a wave's 64-sample groups, the
+ * groups of a wave in order, the waves in wave order, the components in component order, the null atom last): outputs are
+ * bit-identical from run to run, for any selection order and launch grouping, and for the resident and the host form of a
+ * table.
+ * ------------------------------------------------------------------------------------------- */
+#define GPDLA_DISTRIBUTION_MAX_THRESHOLDS 4
+#define GPDLA_DISTRIBUTION_MAX_LEVELS 8
+#define GPDLA_DISTRIBUTION_MIN_BINS 8
+#define GPDLA_DISTRIBUTION_MAX_BINS 256
+typedef struct {
+  int64_t num_selected;
+  const int64_t *selection;          /* [num_selected] quasars of the batch; NULL = 0 .. num_selected-1 */
+  int32_t weights_source;            /* GPDLA_SPECTRA_WEIGHTS_RESIDENT, _HOST or _REFINED (_NONE: null component only) */
+  const double *sample_log_likelihoods_dla; /* [num_selected][S], _HOST, where a row weighs the DLA table */
+  const double *sample_log_likelihoods_lls; /* [num_selected][S], _HOST, where a row weighs the sub-DLA table */
+  const double *model_weights;       /* [num_selected][3] (null, sub-DLA, DLA), or NULL = (0, 0, 1) */
+  int32_t meanflux;                  /* != 0: the grid of the mean-flux model's prepared rows (the same pixels) */
+  int64_t capacity;                  /* entries of each plane of the per-pixel output arrays */
+  int32_t num_thresholds;            /* 0 .. 4 */
+  const double *thresholds;          /* [num_thresholds], strictly inside (0, 1) */
+  int32_t num_bins;                  /* 0, or 8 .. 256 */
+  int32_t num_levels;                /* 0 .. 8; > 0 needs num_bins */
+  const double *levels;              /* [num_levels], strictly inside (0, 1) */
+} gpdla_absorption_distribution_request;
+typedef struct {
+  int64_t *offsets;                  /* [num_selected + 1]; required */
+  double *prob_below;                /* [num_thresholds][capacity] or NULL */
+  double *absorption_min, *absorption_max; /* [capacity] or NULL */
+  double *histogram;                 /* [num_bins][capacity] or NULL */
+  double *quantiles;                 /* [num_levels][capacity] or NULL */
+  int32_t *status;                   /* [num_selected] or NULL */
+} gpdla_absorption_distribution;
+/* The checks of gpdla_marginal_continuum_validate, then this product's: more than 4 thresholds or 8 levels (or a negative
+ * count), a count without its array, a threshold or a level that is NaN or not strictly inside (0, 1), num_bins neither 0
+ * nor in [8, 256], levels without bins, nothing requested (no thresholds and no bins).  Returns GPDLA_OK or
+ * GPDLA_ERR_INVALID_ARGUMENT.  Needs no GPU. */
+int gpdla_absorption_distribution_validate(const gpdla_absorption_distribution_request *request, int64_t num_quasars,
+                                           int64_t num_samples, int has_lls_nhi_samples);
+/* With gpdla_context_set_timing enabled, gpdla_context_last_sweep_ms reports the launch groups of the call:
+ * k_absorption_init, per group the staging of a host table's slice, k_spectra_weights and k_absorption_dist per
+ * component, and k_absorption_combine. */
+int gpdla_batch_absorption_distribution(gpdla_context *ctx, gpdla_batch *batch,
+                                        const gpdla_absorption_distribution_request *request,
+                                        gpdla_absorption_distribution *out);
+typedef struct {
+  int64_t num_selected;
+  const int64_t *selection;
+  int32_t max_dlas;
+  int32_t tables_source;
+  const double *sample_log_likelihoods_dla;
+  const uint32_t *base_sample_inds;
+  const double *sample_log_likelihoods_lls;
+  const double *model_weights;
+  int32_t meanflux;
+  int64_t capacity;                  /* the fields of gpdla_marginal_continuum_multi_request up to here */
+  int32_t num_thresholds;
+  const double *thresholds;
+  int32_t num_bins;
+  int32_t num_levels;
+  const double *levels;
+} gpdla_absorption_distribution_multi_request;
+typedef struct {
+  int64_t *offsets;                  /* [num_selected + 1]; required */
+  double *prob_below;
+  double *absorption_min, *absorption_max;
+  double *histogram;
+  double *quantiles;
+  int32_t *status;                   /* [num_selected] or NULL */
+  uint32_t *model_flags;             /* [num_selected] or NULL */
+} gpdla_absorption_distribution_multi;
+/* The checks of gpdla_marginal_continuum_multi_validate, then those of gpdla_absorption_distribution_validate. */
+int gpdla_absorption_distribution_multi_validate(const gpdla_absorption_distribution_multi_request *request,
+                                                 int64_t num_quasars, int64_t num_samples, int has_lls_nhi_samples,
+                                                 int batch_max_dlas, int batch_processed);
+int gpdla_batch_absorption_distribution_multi(gpdla_context *ctx, gpdla_batch *batch,
+                                              const gpdla_absorption_distribution_multi_request *request,
+                                              gpdla_absorption_distribution_multi *out);
+
 #ifdef __cplusplus
 }
 #endif
