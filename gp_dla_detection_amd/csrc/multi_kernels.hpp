@@ -425,7 +425,13 @@ __global__ void k_multi_posteriors(MultiPostArgs a) {
   if (!any) mx = NAN;
   double e[2 + 8], sum = 0.0;
   for (int j = 0; j < nm; ++j) {
-    e[j] = exp(lp[j] - mx);  // :485-488
+    // :485-488.  lp[j] - mx rounds by up to |lp[j] - mx| 2^-53, which exp() turns into a relative error of that
+    // size -- 64 ulp on a posterior of 1e-80.  The rounding error of the difference is recovered exactly (two-sum;
+    // the build has no fast-math and no contraction) and applied to first order: exp(d + r) = exp(d) (1 + r).
+    const double d = lp[j] - mx, bv = d - lp[j];
+    const double r = (lp[j] - (d - bv)) - (mx + bv);
+    const double ed = exp(d);
+    e[j] = r == r ? ed + ed * r : ed;  // (r is NaN where d is infinite or NaN: keep exp(d))
     sum += e[j];             // NaN entries propagate, as sum() does (:491)
   }
   for (int j = 0; j < nm; ++j) a.post[q * nm + j] = e[j] * (1.0 / sum);

@@ -50,6 +50,8 @@ def config4():
 
 
 def test_config4_full_size_properties(config4):
+    """The size-independent properties of the module docstring, at the workload's shape and NumPy's precision
+    (the evidences and posteriors against 50-digit values: tests/test_gpu_multi_epilogue.py)."""
     p, model, samples, spectra, lp, out = config4
     S, md = 10000, p.max_dlas
     log_S = np.log(S)
@@ -218,7 +220,8 @@ def test_resampling_follows_the_weights():
     drawn indices must be distributed as W = exp(ll - max) / sum.  Chi-square over ~40 bins of
     (nearly) equal probability mass along the sample axis (S draws; bins expecting <= 5 draws are
     left out; 99.99 % quantile), for the first resampling step of 4 quasars; plus independence of
-    the stream across quasars."""
+    the stream across quasars.  (Every single draw is restated exactly, at small shapes, in
+    tests/test_gpu_multi_epilogue.py.)"""
     from scipy.stats import chi2
     p = MultiParameters(max_dlas=2)
     model = synthetic.make_model(20)
